@@ -3,7 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W
                     [--workload c2|c3|c4|c5] [--size WxH] [--spp S] [--scaling weak|strong]
-                    [--arith rocm-opencl|rocm-opencl-nocontract|ieee]
+                    [--arith rocm-opencl|rocm-opencl-nocontract|ieee] [--dump-outputs DIR]
 
 Metric (BASELINE.json): Msamples/s (pixel-samples = camera paths per second) and the % of the HBM roofline; the
 roofline that actually binds (VALU issue) rides along.  One *step* = one pass of the hot path over one frame: clear,
@@ -268,7 +268,7 @@ def parity_leg(rt, np, tracer, wl, workload, spp, arith, table, note):
         out["real_opencl"] = {"skipped": "t_textured materials need an OpenCL image object, which a HIP process cannot create "
                                          "(raytracer.cl:105-107 stays unpinned; tests/test_gpu_ref950.py compares the untextured scene)"}
     elif not orc_mod.ReferenceGfx950.available(hs):
-        out["real_opencl"] = {"skipped": "oracle/_ref_gfx950 (the reference built by ROCm's OpenCL tool chain) is not on this machine"}
+        out["real_opencl"] = {"skipped": "oracle/_ref/gfx950 (the reference built by ROCm's OpenCL tool chain) is not on this machine"}
     else:
         note("parity: against the reference's gfx950 OpenCL build (%s)" % os.path.basename(hs))
         ref = orc_mod.ReferenceGfx950(hs)
@@ -286,7 +286,7 @@ def parity_leg(rt, np, tracer, wl, workload, spp, arith, table, note):
         b = timed_linear[:gh, :gw]
         rel = np.abs(a - b) / np.maximum(np.maximum(np.abs(a), np.abs(b)), 1e-6)
         out["real_opencl"] = {
-            "checker": "oracle/_ref_gfx950/" + os.path.basename(hs) + " (kernels/raytracer.cl built by ROCm's OpenCL tool chain, ROCm's builtin library)",
+            "checker": "oracle/_ref/gfx950/" + os.path.basename(hs) + " (kernels/raytracer.cl built by ROCm's OpenCL tool chain, ROCm's builtin library)",
             "region": "whole frame" if not grid else "corner %dx%d of the frame" % (gw, gh),
             "pixel_samples_bit_identical_samples_0_1": same,
             "timed_frame_max_rel_dev": float(rel.max()), "timed_frame_pixels_within_1e-4": float((rel <= 1e-4).mean()),
@@ -318,6 +318,25 @@ def parity_leg(rt, np, tracer, wl, workload, spp, arith, table, note):
     return out
 
 
+DUMP_LIMIT_BYTES = 63 << 20     # all dumped files together stay under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, note):
+    """--dump-outputs: each array as DIR/<name>.npy in float32.  An array above the size limit is replaced by a fixed
+    sample of its pixels (seeded, sorted, the same for every run of the same frame size), shape (n, channels)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > DUMP_LIMIT_BYTES // len(arrays):
+            px = a.reshape(-1, a.shape[-1])
+            n = DUMP_LIMIT_BYTES // len(arrays) // (px.shape[1] * 4)
+            idx = np.sort(np.random.RandomState(0).choice(px.shape[0], n, replace=False))
+            note("dump: %s %s is above the limit: %d of its %d pixels (seed 0)" % (name, a.shape, n, px.shape[0]))
+            a = px[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -340,7 +359,11 @@ def main():
     ap.add_argument("--no-single-gpu-reference", action="store_true")
     ap.add_argument("--no-arith-variants", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for the baseline leg (N > 1: a quarter)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame the last timed step produced (rank 0's gamma RGBA image) as DIR/image.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup not negative")
 
     # a plain `python bench.py --gpus N`: start the ranks as a child BEFORE anything touches torch or HIP
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -414,6 +437,8 @@ def main():
         step()
     fence()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": renderer.image()}, note)
     # per-launch kernel durations over the timed region: the library records HIP events on the launch stream
     # around every fused call and between its two stages; they are only read back here
     calls = min(args.steps * (spp // chunk), 64)

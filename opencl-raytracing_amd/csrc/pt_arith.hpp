@@ -22,7 +22,7 @@
 //               (the last two come from compiling this translation unit with -fno-hip-fp32-correctly-rounded-divide-sqrt:
 //               clang then attaches the same !fpmath metadata as under -x cl, and the same backend expands them),
 //               the kernel's OWN expressions not contracted (-ffp-contract=off).  Bit for bit what
-//               oracle/_ref_gfx950/ref950_nocontract.hsaco computes — that code object is the checker
+//               oracle/_ref/gfx950/ref950_nocontract.hsaco computes — that code object is the checker
 //               (tests/test_gpu_ref950.py), no host can restate v_rsq_f32 / v_rcp_f32 / v_sqrt_f32.
 //   PT_ARITH 2  RT_ARITH_ROCM_OCL            the same, plus the contractions clang performs on the reference's own
 //               expressions under OpenCL's default -ffp-contract=on: an a*b that is a direct operand of + or − in ONE
@@ -34,7 +34,7 @@
 //                   rayRefract :381,:385 / rayRefractDielectric :424,:428   1 - k²(1 - cai²) = fma(-(k·k), fma(-cai, cai, 1), 1);
 //                                        k·dir − n·(k·cai + sqrt) = fma(k, dir, −(n · fma(k, cai, sqrt)))
 //                   schlick :404        fma(1 − r0, pow, r0)
-//               Bit for bit what oracle/_ref_gfx950/ref950.hsaco — the reference as ROCm's OpenCL builds it by default
+//               Bit for bit what oracle/_ref/gfx950/ref950.hsaco — the reference as ROCm's OpenCL builds it by default
 //               — computes.
 //
 // The acceleration structures' CULLING arithmetic (pt_device.hpp hit_spheres_bvh, pt_mesh_bvh.hpp) is ours in every

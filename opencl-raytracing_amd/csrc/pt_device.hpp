@@ -7,7 +7,7 @@
 // translation unit's ARITHMETIC POLICY defines them (pt_arith.hpp): policy 0 is bit-identical per
 // pixel-sample to the reference compiled without FMA contraction and with plain IEEE builtins (the CPU
 // oracle's pin), policies 1 and 2 to the reference as ROCm's own OpenCL tool chain builds it for gfx950
-// (oracle/_ref_gfx950/*.hsaco).  Compile with -ffp-contract=off and without any fast-math flag.
+// (oracle/_ref/gfx950/*.hsaco).  Compile with -ffp-contract=off and without any fast-math flag.
 //
 // Mapping to the hardware:
 //   * the 64 lanes of a wave are 64 samples of one pixel (or 64/g pixels × g

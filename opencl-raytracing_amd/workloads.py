@@ -255,7 +255,7 @@ def shipped_like(width=1200, height=800, spp=16):
 
 def untextured(wl):
     """The same workload with every t_textured material turned into t_diffuse and no texture array: the reference's
-    real OpenCL build (oracle/_ref_gfx950) can only be driven without an OpenCL image object, and everything but the
+    real OpenCL build (oracle/_ref/gfx950) can only be driven without an OpenCL image object, and everything but the
     texel fetch (raytracer.cl:105-107) — lenses, small meshes by face scan, uv interpolation — is still exercised."""
     wl.scene.materials["type"][wl.scene.materials["type"] == _abi.T_TEXTURED] = _abi.T_DIFFUSE
     wl.scene.textures = None

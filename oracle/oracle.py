@@ -7,10 +7,10 @@ this module; the product package never does.
                after `make -C oracle` / __graft_entry__.build().
   Reference()  _ref/libref.so — the unmodified reference kernel compiled for
                x86-64 and linked with the IEEE-plain builtin stand-ins of
-               ref_shim.cpp (build container only: .gpurunignore keeps it off the
-               GPU box).  "Parity unpinned" in the sense of the build rules — see
+               ref_shim.cpp (built only where the reference tree is present; the
+               files under _ref/ then travel with the working tree).  "Parity unpinned" in the sense of the build rules — see
                the header of pt_oracle.c.
-  ReferenceGfx950()  _ref_gfx950/ — the same kernel file built for gfx950 with ROCm's REAL OpenCL
+  ReferenceGfx950()  _ref/gfx950/ — the same kernel file built for gfx950 with ROCm's REAL OpenCL
                builtin library and run on the GPU through the HIP module API (GPU box only;
                measurement tool of DESIGN.md §3, no pass/fail parity test depends on it).
 All take the product's host-side scene object (anything with .desc() and
@@ -26,9 +26,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "liboracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libref.so")
-REF950_SO = os.path.join(HERE, "_ref_gfx950", "libref950.so")
-REF950_HSACO = os.path.join(HERE, "_ref_gfx950", "ref950.hsaco")
-REF950_HSACO_NOCONTRACT = os.path.join(HERE, "_ref_gfx950", "ref950_nocontract.hsaco")
+REF950_SO = os.path.join(HERE, "_ref", "gfx950", "libref950.so")
+REF950_HSACO = os.path.join(HERE, "_ref", "gfx950", "ref950.hsaco")
+REF950_HSACO_NOCONTRACT = os.path.join(HERE, "_ref", "gfx950", "ref950_nocontract.hsaco")
 
 COUNTER_FIELDS = ("samples", "bounces", "t_sphere", "t_plane", "t_lens", "t_model", "t_mesh", "t_tri", "h_tri",
                   "h_bounce", "n_scatter", "n_dielectric", "n_texfetch", "image_reads")

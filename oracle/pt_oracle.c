@@ -21,7 +21,7 @@
  * IEEE-754 formula of each builtin.  So the pin is "reference source + IEEE-plain
  * builtins, no FMA", not an execution of the reference under a real OpenCL runtime.
  * A real one exists for the GPU: ROCm's own OpenCL tool chain builds the same file
- * for gfx950 with its real builtin library (oracle/_ref_gfx950); its dot() is an
+ * for gfx950 with its real builtin library (oracle/_ref/gfx950); its dot() is an
  * fma chain, its normalize() rsq-based, its '/' rcp-based
  * (profiles/r02_ref_gfx950_builtins.md), so it cannot agree bit for bit; the
  * measured distance on the MI355X — 97.7 % of C2's pixel-samples identical, frame

@@ -1,5 +1,5 @@
 // ref_gfx950_host.cpp — TEST INFRASTRUCTURE: runs the gfx950 build of the reference's kernel file
-// (oracle/_ref_gfx950/ref950.hsaco: kernels/raytracer.cl compiled by ROCm's OpenCL tool chain with ROCm's
+// (oracle/_ref/gfx950/ref950.hsaco: kernels/raytracer.cl compiled by ROCm's OpenCL tool chain with ROCm's
 // real OpenCL builtin library, see ref_gfx950_wrap.cl and oracle/Makefile) on the GPU through the HIP
 // module API.  It answers one question: how far is the arithmetic contract the oracle is
 // pinned to — "reference source + IEEE-plain builtins, no FMA" — from what the reference computes when AMD's
@@ -11,7 +11,7 @@
 // createScene kernel (:541-558) stashes the pointers, and ref950_sample_frame (our wrapper) calls the
 // reference's genInitRay + getCol once per pixel for one sample.
 //
-//   hipcc -O2 -fPIC -shared oracle/ref_gfx950_host.cpp -o oracle/_ref_gfx950/libref950.so
+//   hipcc -O2 -fPIC -shared oracle/ref_gfx950_host.cpp -o oracle/_ref/gfx950/libref950.so
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

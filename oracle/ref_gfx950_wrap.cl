@@ -10,7 +10,7 @@
 // by t_textured materials (raytracer.cl:105-107, :474-477): scenes without them pass a null handle.
 // The reference's createScene kernel (:541-558) is used as it is.
 //
-// Build recipe: oracle/Makefile, target ref_gfx950 → oracle/_ref_gfx950/ref950.hsaco (git-ignored).
+// Build recipe: oracle/Makefile, target ref_gfx950 → oracle/_ref/gfx950/ref950.hsaco (git-ignored).
 #include "kernels/raytracer.cl"
 
 __kernel void ref950_sample_frame(__global float4* out, int width, int height,

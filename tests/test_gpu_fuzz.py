@@ -93,7 +93,7 @@ _HSACO = {1: orc.REF950_HSACO_NOCONTRACT, 2: orc.REF950_HSACO}
 
 
 @pytest.mark.skipif(not (orc.ReferenceGfx950.available() and orc.ReferenceGfx950.available(orc.REF950_HSACO_NOCONTRACT)),
-                    reason="oracle/_ref_gfx950 (gfx950 builds of the reference) not present")
+                    reason="oracle/_ref/gfx950 (gfx950 builds of the reference) not present")
 @pytest.mark.parametrize("seed", list(range(201, 217)))
 def test_random_scene_bit_exact_against_the_rocm_opencl_build(seed):
     """Arbitrary scenes (spheres below and above the BVH threshold, planes, lenses, meshes below and above theirs, every

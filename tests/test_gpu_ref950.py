@@ -1,4 +1,4 @@
-"""GPU (-m gpu), where oracle/_ref_gfx950/ travelled: the HIP path against the reference's kernel file as ROCm's OWN
+"""GPU (-m gpu), where oracle/_ref/gfx950/ travelled: the HIP path against the reference's kernel file as ROCm's OWN
 OpenCL tool chain builds it for this chip (real ROCm builtin library — no stand-ins; oracle/Makefile ref_gfx950),
 executed through the HIP module API.  This is the pin of parity to a REAL OpenCL build of the reference:
 
@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.join(cases.ROOT, "oracle"))
 import oracle as orc  # noqa: E402
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not (orc.ReferenceGfx950.available() and orc.ReferenceGfx950.available(orc.REF950_HSACO_NOCONTRACT)),
-                                                  reason="oracle/_ref_gfx950 (gfx950 builds of the reference) not present")]
+                                                  reason="oracle/_ref/gfx950 (gfx950 builds of the reference) not present")]
 rt = cases.rt
 HSACO = {1: orc.REF950_HSACO_NOCONTRACT, 2: orc.REF950_HSACO}
 BUILTINS = ["dot", "cross", "normalize", "divide", "sqrt", "mix", "min", "sign", "pow5", "hash"]

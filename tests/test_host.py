@@ -206,9 +206,8 @@ def test_default_scene_is_the_references_path_and_the_repositorys_own_file():
     s.loadTextures()
     assert (len(s.materials), len(s.spheres), len(s.planes), len(s.lenses), len(s.models)) == (10, 10, 1, 1, 2)
     assert s.textures.shape[0] == 2 and list(s.meshes["face_count"]) == [12, 12]
-    ref = "/root/reference/assets/scenes/scene.scene"
-    if os.path.isfile(ref):     # authored here, not the reference's file
-        assert open(ref).read() != open(rt.RayTracer.REPO_DEFAULT_SCENE).read()
+    ref = os.path.join(ROOT, "tests", "golden", "reference_tree", "assets", "scenes", "scene.scene")
+    assert open(ref).read() != open(rt.RayTracer.REPO_DEFAULT_SCENE).read()     # authored here, not the reference's file
 
 
 def test_c1_and_c5_come_from_scene_and_obj_files():

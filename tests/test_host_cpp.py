@@ -65,16 +65,15 @@ def test_cpp_scene_arrays_match_python(built, scene, tmp_path):
         assert np.array_equal(tex.view(np.uint32), s.textures.view(np.uint32))
 
 
-REF = "/root/reference"
+# the reference's assets/ data (scene file, OBJ/MTL cubes, RGBA PNGs), stored byte for byte
+REF = os.path.join(ROOT, "tests", "golden", "reference_tree")
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "assets", "scenes", "scene.scene")),
-                    reason="the reference tree exists in the build container only")
 def test_reference_scene_tree_loads_unchanged(built, tmp_path):
-    """The reference's own scene file, OBJ/MTL cubes and RGBA PNGs, read where they lie with the working
-    directory at the reference's root (its `load:` paths are CWD-relative, src/scene.cpp:355 → :195; its .mtl
-    files name an absolute path on the author's machine, assets/cube/cube.mtl:13): both mirrors must accept
-    the tree as it is and produce byte-identical arrays.  Nothing is copied into the repo."""
+    """The reference's own scene file, OBJ/MTL cubes and RGBA PNGs, read with the working directory at the
+    root of that tree (its `load:` paths are CWD-relative, src/scene.cpp:355 → :195; its .mtl files name an
+    absolute path on the author's machine, assets/cube/cube.mtl:13): both mirrors must accept the tree as it
+    is and produce byte-identical arrays."""
     out = str(tmp_path / "ref.bin")
     subprocess.run([CLI, "--scene", "assets/scenes/scene.scene", "--dump-scene", out, "--size", "1200x800"],
                    check=True, cwd=REF)

@@ -1,5 +1,5 @@
-"""CPU, build container only: the reference's kernel file as ROCm's own OpenCL tool chain builds it for gfx950
-(oracle/_ref_gfx950/, real ROCm builtin library) — which arithmetic does it contain, and is that the IEEE-plain
+"""CPU, wherever build() compiled the reference (oracle/_ref/): the reference's kernel file as ROCm's own OpenCL tool chain builds it for gfx950
+(oracle/_ref/gfx950/, real ROCm builtin library) — which arithmetic does it contain, and is that the IEEE-plain
 contract the oracle is pinned to (oracle/ref_shim.cpp)?  It is not: this test records the fact (DESIGN.md §3,
 profiles/r02_ref_gfx950_builtins.md, profiles/r02_ref_distance.json measure the consequences on the GPU)."""
 import os
@@ -7,12 +7,14 @@ import re
 import subprocess
 
 import pytest
+from oracle import Reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HSACO = os.path.join(ROOT, "oracle", "_ref_gfx950", "ref950.hsaco")
-HSACO_NC = os.path.join(ROOT, "oracle", "_ref_gfx950", "ref950_nocontract.hsaco")
+HSACO = os.path.join(ROOT, "oracle", "_ref", "gfx950", "ref950.hsaco")
+HSACO_NC = os.path.join(ROOT, "oracle", "_ref", "gfx950", "ref950_nocontract.hsaco")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree exists in the build container only")
+# oracle/Makefile builds _ref/libref.so and _ref/gfx950/ under the same condition: where one exists, so must the other
+pytestmark = pytest.mark.skipif(not Reference.available(), reason="oracle/_ref (builds of the reference) not present")
 
 
 def ops(path, symbol):
@@ -30,7 +32,7 @@ def test_gfx950_reference_build_exists_and_exports_the_kernels(built):
     assert notes.count(".value_kind:     image") >= 4
 
 
-@pytest.mark.parametrize("path", [HSACO, HSACO_NC])
+@pytest.mark.parametrize("path", [HSACO, HSACO_NC], ids=os.path.basename)   # ids independent of where the tree lies
 def test_real_rocm_builtins_are_not_the_ieee_plain_contract(built, path):
     o = ops(path, "ref950_sample_frame")
     assert len(o) > 1000

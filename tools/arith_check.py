@@ -2,7 +2,7 @@
 """tools/arith_check.py [--policies 1,2] [--workloads ...] [--out FILE] — GPU box.
 
 Bit-for-bit distance between the HIP kernels' arithmetic policies (RT_OPT_ARITH 1 / 2, csrc/pt_arith.hpp) and the
-reference's kernel file as ROCm's own OpenCL tool chain builds it for gfx950 (oracle/_ref_gfx950/ref950_nocontract.hsaco
+reference's kernel file as ROCm's own OpenCL tool chain builds it for gfx950 (oracle/_ref/gfx950/ref950_nocontract.hsaco
 for policy 1, ref950.hsaco for policy 2): per builtin on random operands, then per pixel-sample on the workloads.
 Prints one JSON object; `identical` must be 1.0 everywhere."""
 import argparse

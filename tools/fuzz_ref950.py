@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/fuzz_ref950.py <first seed> <last seed> — the random scenes of tests/test_gpu_fuzz.py (policies 1 and 2 alternating)
-against the reference kernel file as ROCm's OpenCL tool chain builds it for gfx950 (oracle/_ref_gfx950/*.hsaco): samples 0-2
+against the reference kernel file as ROCm's OpenCL tool chain builds it for gfx950 (oracle/_ref/gfx950/*.hsaco): samples 0-2
 of every pixel bit for bit with the acceleration structures on and off, the fused frame within 1e-4.  GPU box only."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -2,7 +2,7 @@
 """tools/ref_builtins_table.py — build container only (needs /root/reference).
 
 What do the OpenCL builtins the reference kernel calls become when ROCm's OWN OpenCL tool chain builds
-kernels/raytracer.cl for gfx950 (oracle/_ref_gfx950/, oracle/Makefile), and is that the IEEE-plain
+kernels/raytracer.cl for gfx950 (oracle/_ref/gfx950/, oracle/Makefile), and is that the IEEE-plain
 sequence the oracle's pin assumes (oracle/ref_shim.cpp)?  Each builtin is compiled in a one-line OpenCL
 kernel of its own, with the flags of the reference build and with -ffp-contract=off, and the ISA is
 inspected.  Prints a markdown table (profiles/r02_ref_gfx950_builtins.md)."""

@@ -4,7 +4,7 @@
 How far is the arithmetic contract this build is pinned to ("reference source + IEEE-plain builtins,
 no FMA": oracle/ref_shim.cpp = oracle/pt_oracle.c = the HIP kernels, bit for bit) from what the
 reference computes when ROCm's own OpenCL tool chain builds kernels/raytracer.cl for gfx950 with its
-real builtin library (oracle/_ref_gfx950/, see oracle/Makefile)?  Same scene arrays, camera block and
+real builtin library (oracle/_ref/gfx950/, see oracle/Makefile)?  Same scene arrays, camera block and
 random table go to both; per pixel-sample the two either agree bit for bit or take different paths
 (the table index is a hash of the ray direction, raytracer.cl:113-125).
 
