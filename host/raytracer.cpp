@@ -74,6 +74,19 @@ const float *RayTracer::renderFrame(const Camera *camera, uint32_t spp) {
     return transferImage();
 }
 
+rt_adaptive_stats RayTracer::renderAdaptive(const Camera *camera, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive(ctx, camera->transferData(), &params, &st));
+    transferImage();
+    return st;
+}
+
+std::vector<uint32_t> RayTracer::sampleCounts() {
+    std::vector<uint32_t> c((size_t)width * height);
+    check(rt_read_sample_counts(ctx, c.data(), c.size() * sizeof(uint32_t)));
+    return c;
+}
+
 uint32_t RayTracer::sampleCounter() const {
     uint32_t v = 0;
     rt_sample_counter(ctx, &v);

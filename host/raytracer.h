@@ -57,6 +57,10 @@ public:
     // native additions
     void renderSamples(const Camera *camera, uint32_t first_sample, uint32_t n_samples);  // fused, asynchronous
     const float *renderFrame(const Camera *camera, uint32_t spp);  // clear + fused + resolve + read back
+    // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
+    rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
+    std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major
+    const float *lastImage() const { return pixels.data(); }  // what the last read-back returned
     uint32_t sampleCounter() const;
     rt_context *context() { return ctx; }
     SceneCreator &sceneCreator() { return scene; }

@@ -3,8 +3,13 @@
 //   rt_cli --scene assets/scenes/c2_cornell.scene --size 1920x1080 --spp 64
 //          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive]
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
+//          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
-// per sample); the default is the fused path (all samples in one launch).
+// per sample); the default is the fused path (all samples in one launch).  --adaptive renders
+// rounds of --batch samples (default 64) until every 8x8 block's error is below THRESHOLD, with
+// at least --min-spp (default 2 x batch) and at most --spp (default 1024 here) samples per pixel; --counts writes the
+// per-pixel sample counts (16-bit PGM for a .pgm name, raw uint32 otherwise).
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -13,13 +18,42 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "raytracer.h"
 
 static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
-                 "[--seed N] [--progressive] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N]\n";
+                 "[--seed N] [--progressive] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
+                 "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]\n";
     std::exit(2);
+}
+
+// a whole decimal number in [lo, hi], or usage()
+static long parse_int(const char *v, long lo, long hi) {
+    char *end = nullptr;
+    long x = std::strtol(v, &end, 10);
+    if (!*v || *end || x < lo || x > hi) usage();
+    return x;
+}
+
+static void write_counts(const std::string &path, const std::vector<uint32_t> &c, int w, int h) {
+    std::ofstream f(path, std::ios::binary);
+    if (path.size() >= 4 && path.compare(path.size() - 4, 4, ".pgm") == 0) {
+        // binary 16-bit PGM: big-endian samples, top row first (image row 0 is the bottom of the picture)
+        f << "P5\n" << w << " " << h << "\n65535\n";
+        std::string row((size_t)w * 2, '\0');
+        for (int y = h - 1; y >= 0; y--) {
+            for (int x = 0; x < w; x++) {
+                uint32_t v = std::min<uint32_t>(c[(size_t)y * w + x], 65535u);
+                row[2 * x] = (char)(v >> 8);
+                row[2 * x + 1] = (char)(v & 0xFF);
+            }
+            f.write(row.data(), row.size());
+        }
+    } else {
+        f.write((const char *)c.data(), c.size() * sizeof(uint32_t));
+    }
 }
 
 int main(int argc, char **argv) {
@@ -29,6 +63,10 @@ int main(int argc, char **argv) {
     float cam[5] = {0, 0, 0, 0, 0};
     unsigned long long seed = 0xC0FFEE;
     bool progressive = false;
+    bool adaptive = false, spp_given = false;
+    float threshold = 0.0f;
+    long batch = 0, min_spp = 0;
+    std::string out_counts;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -40,7 +78,7 @@ int main(int argc, char **argv) {
         const char *v;
         if ((v = val("--scene"))) scene_path = v;
         else if ((v = val("--size"))) { if (std::sscanf(v, "%dx%d", &w, &h) != 2) usage(); }
-        else if ((v = val("--spp"))) spp = std::atoi(v);
+        else if ((v = val("--spp"))) { spp = std::atoi(v); spp_given = true; }
         else if ((v = val("--camera"))) { if (std::sscanf(v, "%f,%f,%f,%f,%f", cam, cam + 1, cam + 2, cam + 3, cam + 4) != 5) usage(); }
         else if ((v = val("--fov"))) fov = std::atoi(v);
         else if ((v = val("--seed"))) seed = std::strtoull(v, nullptr, 0);
@@ -49,10 +87,27 @@ int main(int argc, char **argv) {
         else if ((v = val("--raw"))) out_raw = v;
         else if ((v = val("--device"))) device = std::atoi(v);
         else if ((v = val("--dump-scene"))) dump_scene = v;
+        else if ((v = val("--adaptive"))) {
+            char *end = nullptr;
+            threshold = std::strtof(v, &end);
+            if (!*v || *end || !(threshold >= 0.0f) || !std::isfinite(threshold)) usage();
+            adaptive = true;
+        }
+        else if ((v = val("--batch"))) batch = parse_int(v, 1, 512);
+        else if ((v = val("--min-spp"))) min_spp = parse_int(v, 1, (long)RT_MAX_SAMPLE + 1);
+        else if ((v = val("--counts"))) out_counts = v;
         else if (a == "--progressive") progressive = true;
         else usage();
     }
     if (spp < 1 || w < 1 || h < 1) usage();
+    if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
+    if (adaptive) {
+        if (progressive) usage();
+        if (!batch) batch = 64;
+        if (!min_spp) min_spp = 2 * batch;
+        if (!spp_given) spp = 1024;
+        if (min_spp < 2 * batch || min_spp % batch || spp < min_spp || spp > (long)RT_MAX_SAMPLE + 1) usage();
+    }
 
     Camera camera(fov, (float)w / (float)h, rth::vec3(cam[0], cam[1], cam[2]), cam[3], cam[4]);
     if (!dump_scene.empty()) {
@@ -89,7 +144,12 @@ int main(int argc, char **argv) {
 
     auto t0 = std::chrono::steady_clock::now();
     const float *img;
-    if (progressive) {
+    rt_adaptive_stats st{};
+    if (adaptive) {
+        rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
+        st = tracer.renderAdaptive(&camera, p);
+        img = tracer.lastImage();
+    } else if (progressive) {
         tracer.render(&camera);
         for (int s = 1; s < spp; s++) tracer.renderAgain(&camera);
         img = tracer.transferImage();
@@ -97,8 +157,16 @@ int main(int argc, char **argv) {
         img = tracer.renderFrame(&camera, (uint32_t)spp);
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : "fused") << ": " << sec * 1e3
-              << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
+    if (adaptive) {
+        std::cout << w << "x" << h << " adaptive threshold " << threshold << " batch " << batch << " spp " << min_spp
+                  << ".." << spp << ": " << st.rounds << " rounds, mean " << (double)st.pixel_samples / ((double)w * h)
+                  << " spp, " << st.blocks_at_max << " of " << st.blocks << " blocks at max, " << sec * 1e3
+                  << " ms incl. read-back" << std::endl;
+        if (!out_counts.empty()) write_counts(out_counts, tracer.sampleCounts(), w, h);
+    } else {
+        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : "fused") << ": " << sec * 1e3
+                  << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
+    }
 
     if (!out_raw.empty()) {
         std::ofstream f(out_raw, std::ios::binary);

@@ -281,6 +281,39 @@ int rt_clear(rt_context *ctx);
 int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample, uint32_t n_samples);
 int rt_resolve(rt_context *ctx);
 
+/*
+ * Adaptive sampling (new): render until every decision block of block_w x block_h pixels has converged.
+ * Round k (k = 0, 1, ...) traces samples k*batch .. k*batch+c-1, c = min(batch, max_spp - k*batch), of every pixel of
+ * a still-active block, so a pixel whose count is n holds exactly samples 0 .. n-1 and each round adds, bit for bit,
+ * what rt_render_spp(cam, k*batch, c) would have added to it.  From round 1 on, with I the linear mean of all of a
+ * pixel's samples and A the linear mean of its even rounds' samples (0, 2, 4, ...), the pixel's error is
+ * e = (|I.r-A.r| + |I.g-A.g| + |I.b-A.b|) / sqrt(I.r + I.g + I.b) (0 when the root is 0) and a block's error is the
+ * mean e of its in-frame pixels (Dammertz et al. 2010, computed in linear space).  A block stays active while its
+ * count < min_spp, or while its error >= threshold and its count < max_spp.  The call is a self-contained
+ * rt_clear + rounds + rt_resolve: the image and the linear accumulator (sample counts in its 4th channel) end in
+ * the state those calls leave.  Synchronous (one counter is read back per round).  Unsharded contexts only.
+ */
+typedef struct rt_adaptive_params {
+    uint32_t batch;      /* samples per pixel per round, 1 .. 512                                           */
+    uint32_t min_spp;    /* every pixel gets at least this many: >= 2*batch, a multiple of batch             */
+    uint32_t max_spp;    /* no pixel gets more: >= min_spp, <= RT_MAX_SAMPLE + 1                              */
+    float threshold;     /* a block stops when its error is < threshold; 0 = never stop early                */
+    uint32_t block_w, block_h; /* decision block: powers of two, 1 .. 256 (8 x 8 suggested)                  */
+} rt_adaptive_params;
+
+typedef struct rt_adaptive_stats {
+    uint32_t rounds;            /* launches of the sample pipeline                                           */
+    uint64_t pixel_samples;     /* sum of all per-pixel counts                                               */
+    uint32_t blocks, blocks_at_max; /* blocks in the frame; blocks that reached max_spp unconverged          */
+} rt_adaptive_stats;
+
+int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out);
+/* Per-pixel sample counts (accum.w) of the accumulator: W*H uint32, row-major; bytes = W*H*4. */
+int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes);
+/* Block errors of the last rt_render_adaptive call, ceil(W/block_w) * ceil(H/block_h) floats, row-major; a block
+ * holds its error after the last round it was traced in.  RT_ESTATE before the first call / after rt_resize. */
+int rt_read_block_error(rt_context *ctx, float *err, size_t bytes);
+
 /* Wait for everything queued on the context's stream (reference:
  * queue.finish(), src/raytracer.cpp:140).  rt_render/rt_render_again already
  * return synchronously; rt_render_spp/rt_resolve/rt_clear are asynchronous. */

@@ -65,6 +65,55 @@ class Counters(C.Structure):
                 64 * c.samples + 16 * c.image_reads)
 
 
+class AdaptiveParams(C.Structure):
+    """rt_adaptive_params"""
+    _fields_ = [("batch", C.c_uint32), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float),
+                ("block_w", C.c_uint32), ("block_h", C.c_uint32)]
+
+
+ADAPTIVE_STATS_FIELDS = ("rounds", "pixel_samples", "blocks", "blocks_at_max")
+
+
+class AdaptiveStats(C.Structure):
+    """rt_adaptive_stats"""
+    _fields_ = [("rounds", C.c_uint32), ("pixel_samples", C.c_uint64), ("blocks", C.c_uint32),
+                ("blocks_at_max", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n in ADAPTIVE_STATS_FIELDS}
+
+
+def adaptive_prototypes(lib):
+    """ctypes prototypes of the adaptive-sampling entry points (rt_render_adaptive & co.)."""
+    vp, sz = C.c_void_p, C.c_size_t
+    lib.rt_render_adaptive.argtypes = [vp, vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_read_sample_counts.argtypes = [vp, vp, sz]
+    lib.rt_read_block_error.argtypes = [vp, vp, sz]
+
+
+def block_error_reference(accum, half, block_w, block_h):
+    """Host restatement of the adaptive stopping rule's block error (rt_amd.h, rt_render_adaptive): `accum` and `half`
+    are H x W x 4 float32 linear sums (RGB, sample count) of all samples and of the even rounds' samples.  Per pixel,
+    in float32 and in the device's order, I = accum / count, A = half / count,
+    e = ((|I.r-A.r| + |I.g-A.g|) + |I.b-A.b|) / sqrt((I.r+I.g)+I.b), 0 where the root is 0 or the pixel has no samples;
+    per block the mean e over its in-frame pixels (in float64).  → ceil(H/bh) x ceil(W/bw) float64 array."""
+    accum = np.asarray(accum, dtype=np.float32)
+    half = np.asarray(half, dtype=np.float32)
+    h, w = accum.shape[:2]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        i = accum[..., :3] / accum[..., 3:4]
+        a = half[..., :3] / half[..., 3:4]
+        d = np.abs(i - a)
+        num = (d[..., 0] + d[..., 1]) + d[..., 2]
+        den = np.sqrt((i[..., 0] + i[..., 1]) + i[..., 2])
+        ok = den > 0
+        e = np.where(ok, num / np.where(ok, den, np.float32(1)), np.float32(0)).astype(np.float64)
+    by, bx = -(-h // block_h), -(-w // block_w)
+    pad = np.full((by * block_h, bx * block_w), np.nan)
+    pad[:h, :w] = e
+    return np.nanmean(pad.reshape(by, block_h, bx, block_w), axis=(1, 3))
+
+
 def ptr(a):
     """void* of a numpy array (None/empty → NULL)."""
     if a is None or a.size == 0:

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
     uint32_t slot = fp.slot_begin + (tid >> fp.group_log2);
     uint32_t lane = tid & (g - 1u);
     uint32_t x = 0, y = 0;
-    bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y);
+    bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y) && pixel_active(fp, x, y);
 
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     if (valid) {
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void pt_prefix(DeviceScene sc, FrameParams fp,
 
     uint32_t slot = fp.slot_begin + blockIdx.x * 256u + threadIdx.x;
     uint32_t x = 0, y = 0;
-    bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y);
+    bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y) && pixel_active(fp, x, y);
     bool is_live = false;
     PixelRec rec;
     rec.p_kind = rec.n_extra = rec.d = rec.out = rec.col = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1232,9 +1232,19 @@ __global__ __launch_bounds__(256) void pt_debug_div3(const float *__restrict__ i
 
 // Direct path (every sample from the camera): trace / retrace compat modes, and the
 // fused mode when prefix sharing is switched off.
+static void apply_mask(FrameParams &fp, const BlockMask *mask) {
+    if (!mask) return;
+    fp.block_active = mask->active;
+    fp.blk_w_log2 = mask->w_log2;
+    fp.blk_h_log2 = mask->h_log2;
+    fp.blocks_x = mask->blocks_x;
+}
+
 template <int MODE>
-int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2) {
+int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                  const BlockMask *mask) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
+    apply_mask(fp, mask);
     DeviceScene sc = device_scene(ctx);
     uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
@@ -1250,7 +1260,7 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
         uint64_t threads = (uint64_t)(fp.slot_end - fp.slot_begin) << glog2;
         dim3 grid((unsigned)((threads + 255) / 256)), block(256);
 #define PT_CALL(C, A) \
-    hipLaunchKernelGGL((pt_render<MODE, C, A>), grid, block, 0, ctx->stream, sc, fp, ctx->d_accum, ctx->d_image, ctx->d_counters)
+    hipLaunchKernelGGL((pt_render<MODE, C, A>), grid, block, 0, ctx->stream, sc, fp, accum, ctx->d_image, ctx->d_counters)
         PT_DISPATCH(ctx->count_enabled, scene_has_accel(sc), PT_CALL);
 #undef PT_CALL
     }
@@ -1261,8 +1271,10 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
 }
 
 // Fused path: pt_prefix (one work-item per pixel) + pt_samples (g lanes per live pixel).
-int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2) {
+int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                 const BlockMask *mask) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
+    apply_mask(fp, mask);
     DeviceScene sc = device_scene(ctx);
     uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
@@ -1324,7 +1336,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         bool queue = ctx->sample_queue && count <= QUEUE_SLOTS;
         size_t lds_q = static_f4 * sizeof(float4) + PT_Q_BLOCK_WAVES * (size_t)queue_wave_lds_bytes(ppw, count);
 #define PT_CALL_PREFIX(C, A) \
-    hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ctx->d_recs, ctx->d_live, live_count, ctx->d_accum, ctx->d_counters)
+    hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ctx->d_recs, ctx->d_live, live_count, accum, ctx->d_counters)
         bool accel_on = scene_has_accel(sc);
         PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
         if (fp.tree_cap) {
@@ -1356,7 +1368,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
             dim3 gridq((units(ppw) + PT_Q_BLOCK_WAVES - 1) / PT_Q_BLOCK_WAVES);
             dim3 grid2((unsigned)((((uint64_t)units(1u) << glog2) + 255) / 256));
 #define PT_CALL_QUEUE_W(C, A, G, W) \
-    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), gridq, blockq, lds_q, st, sc, fl, l_recs, l_live, l_count, ctx->d_accum, ctx->d_counters, ppw)
+    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), gridq, blockq, lds_q, st, sc, fl, l_recs, l_live, l_count, accum, ctx->d_counters, ppw)
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
         if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
@@ -1364,7 +1376,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
     } while (0)
 #define PT_CALL_FIXED(C, A) \
-    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, st, sc, fl, l_recs, l_live, l_count, ctx->d_accum, ctx->d_counters)
+    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, st, sc, fl, l_recs, l_live, l_count, accum, ctx->d_counters)
             if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled && !PT_LDS_SPHERES) {
                 // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
                 uint32_t ppw_w = queue_pixels_per_wave(count, ctx->walk_jobs.n == 1 ? PT_W_WAVES : PT_W_WAVES_MULTI, static_f4, PT_W_BLOCK_WAVES);
@@ -1373,14 +1385,14 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
                 dim3 gridw((units(ppw_w) + PT_W_BLOCK_WAVES - 1) / PT_W_BLOCK_WAVES), blockw(64 * PT_W_BLOCK_WAVES);
                 if (ctx->walk_jobs.n == 1)
                     hipLaunchKernelGGL(pt_samples_w<false>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
-                                       ctx->d_accum, ppw_w, ctx->walk_jobs.p, 1u
+                                       accum, ppw_w, ctx->walk_jobs.p, 1u
 #ifdef PT_WSTAT
                                        , ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8
 #endif
                                        );
                 else
                     hipLaunchKernelGGL(pt_samples_w<true>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
-                                       ctx->d_accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
+                                       accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
 #ifdef PT_WSTAT
                                        , ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8
 #endif
@@ -1438,11 +1450,12 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
 
 namespace {
 
-int ks_launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2) {
+int ks_launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
+                     float4 *accum, const BlockMask *mask) {
     switch (mode) {
-        case MODE_ACCUM: return launch_render<MODE_ACCUM>(ctx, cam, first, count, glog2);
-        case MODE_TRACE: return launch_render<MODE_TRACE>(ctx, cam, first, count, glog2);
-        case MODE_RETRACE: return launch_render<MODE_RETRACE>(ctx, cam, first, count, glog2);
+        case MODE_ACCUM: return launch_render<MODE_ACCUM>(ctx, cam, first, count, glog2, accum, mask);
+        case MODE_TRACE: return launch_render<MODE_TRACE>(ctx, cam, first, count, glog2, accum, mask);
+        case MODE_RETRACE: return launch_render<MODE_RETRACE>(ctx, cam, first, count, glog2, accum, mask);
         default: return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
     }
 }

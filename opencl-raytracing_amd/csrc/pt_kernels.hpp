@@ -10,9 +10,12 @@ struct KernelSet {
     int arith;             // RT_ARITH_* this set was compiled for
     const char *name;
     // direct path: MODE_ACCUM / MODE_TRACE / MODE_RETRACE (rt_render, rt_render_again, prefix sharing off)
-    int (*launch_render)(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2);
-    // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples
-    int (*launch_fused)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2);
+    // `accum`: the accumulator MODE_ACCUM adds to; `mask`: the pixels traced (NULL = every owned pixel)
+    int (*launch_render)(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
+                         float4 *accum, const BlockMask *mask);
+    // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples, adding to `accum`
+    int (*launch_fused)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
+                        float4 *accum, const BlockMask *mask);
     // rt_trace_samples: d_in = n x, n y, n sample (uint32), d_out = 3 n floats
     int (*launch_probe)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out);
     // unit probes (rt_debug_hit / rt_debug_material / rt_debug_div3)

@@ -149,6 +149,17 @@ struct FrameParams {
     uint32_t *tree_count;           // how many pt_prefix listed (tree i belongs to glass[i])
     uint32_t tree_cap;              // capacity of `trees` (0: trees off — RT_OPT_PREFIX_TREE, counting builds)
     uint32_t lds_face_f4;           // pt_samples_q: float4 of DeviceScene::faces staged in LDS after the static tables (0: none; see launch_fused)
+    // adaptive rounds (rt_render_adaptive): per decision block of (1 << blk_w_log2) x (1 << blk_h_log2) pixels, nonzero =
+    // the block is traced by this launch; NULL = every pixel.  pt_prefix / pt_render treat a masked-out pixel like an
+    // unowned slot, so it never reaches the live list and the later kernels see only active work.
+    const uint32_t *block_active;
+    uint32_t blk_w_log2, blk_h_log2, blocks_x;
+};
+
+// the decision-block mask of an adaptive round, as the launchers take it (NULL = every pixel)
+struct BlockMask {
+    const uint32_t *active;
+    uint32_t w_log2, h_log2, blocks_x;
 };
 
 // The live list (pixels that need per-sample work) can be kept in LIVE_SEGMENTS independent segments, workgroup b
@@ -181,6 +192,10 @@ PT_DEV bool slot_to_pixel(const FrameParams &fp, uint32_t slot, uint32_t &x, uin
     x = (tx << fp.tile_w_log2) + (in & ((1u << fp.tile_w_log2) - 1u));
     y = (ty << fp.tile_h_log2) + (in >> fp.tile_w_log2);
     return x < (uint32_t)fp.w && y < (uint32_t)fp.h;
+}
+
+PT_DEV bool pixel_active(const FrameParams &fp, uint32_t x, uint32_t y) {
+    return !fp.block_active || fp.block_active[(y >> fp.blk_h_log2) * fp.blocks_x + (x >> fp.blk_w_log2)] != 0u;
 }
 
 #define PT_MESH_BVH_NONE 0xFFFFFFFFu   // mesh_bvh_root[m]: mesh m has no BVH (face scan)

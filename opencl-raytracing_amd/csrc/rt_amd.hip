@@ -59,6 +59,82 @@ __global__ __launch_bounds__(256) void pt_resolve(const float4 *__restrict__ acc
     image[i] = o;
 }
 
+// Adaptive sampling (rt_render_adaptive), after each round: one wave per decision block, PT_MERGE_WAVES per workgroup.  A round has traced the active
+// blocks into `scratch`, which is zero everywhere else, so scratch = 0 + the launch's per-pixel sum exactly, and
+// accum + scratch is, bit for bit, what rt_render_spp of that launch would have made of accum.  Per pixel of an active
+// block: accum += scratch, half += scratch in even rounds, scratch = 0; from round 1 on the pixel error (rt_amd.h)
+// from I = accum / accum.w and A = half / half.w.  The block error is the mean over its in-frame pixels in a fixed
+// order (lane l sums pixels l, l + 64, ... in turn, then an xor butterfly), and lane 0 decides whether the block is
+// traced by the next round.  stats (PT_MERGE_REPLICAS rows, summed by the host): [0] blocks active next round,
+// [1] blocks stopped at max_spp unconverged, [2] pixel samples of the blocks that stopped.
+struct MergeParams {
+    uint32_t w, h;
+    uint32_t bw_log2, bh_log2, blocks_x, blocks;
+    uint32_t round;        // k
+    uint32_t count;        // samples every pixel of an active block holds after this round
+    uint32_t min_spp, max_spp;
+    float threshold;
+};
+
+#define PT_MERGE_WAVES 4u       // decision blocks (one wave each) per workgroup
+#define PT_MERGE_REPLICAS 64u    // rows of the stats counters, 128 bytes apart: one address took the whole frame's atomics
+#define PT_MERGE_STRIDE 16u      // (MI355X, C2 1080p: 190-395 us per round on one row, most of the merge's time)
+__global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge(MergeParams mp, float4 *__restrict__ accum, float4 *__restrict__ half,
+                                                        float4 *__restrict__ scratch, uint32_t *__restrict__ active,
+                                                        float *__restrict__ block_err, unsigned long long *__restrict__ stats) {
+    const uint32_t b = blockIdx.x * PT_MERGE_WAVES + (threadIdx.x >> 6);
+    if (b >= mp.blocks || active[b] == 0u) return;   // (uniform over the wave; no workgroup barrier follows)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t bw = 1u << mp.bw_log2, area = bw << mp.bh_log2;
+    const uint32_t x0 = (b % mp.blocks_x) << mp.bw_log2, y0 = (b / mp.blocks_x) << mp.bh_log2;
+    const bool even = (mp.round & 1u) == 0u;
+    float esum = 0.0f;
+    uint32_t npx = 0u;
+    for (uint32_t i = lane; i < area; i += 64u) {
+        const uint32_t x = x0 + (i & (bw - 1u)), y = y0 + (i >> mp.bw_log2);
+        if (x >= mp.w || y >= mp.h) continue;
+        const size_t p = (size_t)y * mp.w + x;
+        const float4 s = scratch[p];
+        float4 m = accum[p];
+        m.x += s.x; m.y += s.y; m.z += s.z; m.w += s.w;
+        accum[p] = m;
+        float4 a = half[p];
+        if (even) {
+            a.x += s.x; a.y += s.y; a.z += s.z; a.w += s.w;
+            half[p] = a;
+        }
+        scratch[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        npx++;
+        if (mp.round >= 1u) {
+            const float ix = m.x / m.w, iy = m.y / m.w, iz = m.z / m.w;
+            const float ax = a.x / a.w, ay = a.y / a.w, az = a.z / a.w;
+            const float den = sqrtf(ix + iy + iz);
+            if (den > 0.0f) esum += (fabsf(ix - ax) + fabsf(iy - ay) + fabsf(iz - az)) / den;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        esum += __shfl_xor(esum, off);
+        npx += __shfl_xor(npx, off);
+    }
+    if (lane != 0u) return;
+    float err = 0.0f;
+    if (mp.round >= 1u) {
+        err = esum / (float)npx;
+        block_err[b] = err;
+    }
+    const bool unconverged = mp.round == 0u || mp.threshold == 0.0f || !(err < mp.threshold);
+    const bool next = mp.count < mp.max_spp && (mp.count < mp.min_spp || unconverged);
+    active[b] = next ? 1u : 0u;
+    stats += (size_t)(b % PT_MERGE_REPLICAS) * PT_MERGE_STRIDE;
+    if (next) {
+        atomicAdd(&stats[0], 1ull);
+    } else {
+        if (mp.count >= mp.max_spp && unconverged) atomicAdd(&stats[1], 1ull);
+        atomicAdd(&stats[2], (unsigned long long)npx * mp.count);
+    }
+}
+
 // ================================== host side ==================================
 
 namespace {
@@ -297,7 +373,22 @@ int fail(rt_context *ctx, int code, const char *fmt, ...) {
 
 namespace {
 
+void free_adaptive(rt_context *ctx) {
+    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_half) (void)hipFree(ctx->d_half);
+    if (ctx->d_block_active) (void)hipFree(ctx->d_block_active);
+    if (ctx->d_block_err) (void)hipFree(ctx->d_block_err);
+    if (ctx->d_adaptive_stats) (void)hipFree(ctx->d_adaptive_stats);
+    ctx->d_scratch = ctx->d_half = nullptr;
+    ctx->d_block_active = nullptr;
+    ctx->d_block_err = nullptr;
+    ctx->d_adaptive_stats = nullptr;
+    ctx->adaptive_block_capacity = 0;
+    ctx->adaptive_blocks = 0;
+}
+
 int alloc_frame(rt_context *ctx, int w, int h) {
+    free_adaptive(ctx);
     if (ctx->d_image) (void)hipFree(ctx->d_image);
     if (ctx->d_accum) (void)hipFree(ctx->d_accum);
     ctx->d_image = ctx->d_accum = nullptr;
@@ -456,6 +547,7 @@ void rt_destroy(rt_context *ctx) {
     if (ctx->d_trees) (void)hipFree(ctx->d_trees);
     if (ctx->d_glass) (void)hipFree(ctx->d_glass);
     if (ctx->d_tree_work) (void)hipFree(ctx->d_tree_work);
+    free_adaptive(ctx);
     ctx->sph4.release();
     ctx->faces.release();
     ctx->mesh_face_base.release();
@@ -724,7 +816,7 @@ int rt_render(rt_context *ctx, const float camera[12]) {
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->sample_counter = 0;  // src/raytracer.cpp:128
-    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->d_accum, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // queue.finish(), src/raytracer.cpp:140
     return RT_OK;
 }
@@ -735,7 +827,7 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     if (ctx->sample_counter >= RT_MAX_SAMPLE) return fail(ctx, RT_EINVAL, "sample counter limit %u reached", RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->sample_counter++;  // src/raytracer.cpp:147
-    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->d_accum, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -766,8 +858,9 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
     // 18.4 ms where 512 take 10.2); the accumulator then is the sum of those launches' sums, on every path alike.
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c))
-                                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c));
+        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->d_accum, nullptr)
+                                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c),
+                                                          ctx->d_accum, nullptr);
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
@@ -787,6 +880,139 @@ int rt_resolve(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return resolve_into(ctx, 0);
+}
+
+// ---- adaptive sampling ----------------------------------------------------------------------------------------------
+
+extern "C++" {
+namespace {
+
+int ensure_adaptive(rt_context *ctx, size_t blocks) {
+    if (ctx->d_scratch && blocks <= ctx->adaptive_block_capacity) return RT_OK;
+    free_adaptive(ctx);
+    const size_t px = (size_t)ctx->width * ctx->height;
+    hipError_t e = hipMalloc((void **)&ctx->d_scratch, px * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_half, px * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_block_active, blocks * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_block_err, blocks * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_adaptive_stats, PT_MERGE_REPLICAS * PT_MERGE_STRIDE * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        free_adaptive(ctx);
+        return fail(ctx, RT_EHIP, "adaptive buffers: %s", hipGetErrorString(e));
+    }
+    ctx->adaptive_block_capacity = blocks;
+    return RT_OK;
+}
+
+int log2_pow2(uint32_t v) {
+    int l = 0;
+    while ((1u << l) < v && l < 31) l++;
+    return (1u << l) == v ? l : -1;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
+    int rc = check_ready(ctx, camera);
+    if (rc) return rc;
+    if (!p || !out) return fail(ctx, RT_EINVAL, "adaptive parameters / stats are NULL");
+    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "adaptive rendering of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
+    if (p->batch < 1 || p->batch > RT_SPP_PER_LAUNCH)
+        return fail(ctx, RT_EINVAL, "batch %u outside 1..%u", p->batch, RT_SPP_PER_LAUNCH);
+    if (p->min_spp < 2 * p->batch || p->min_spp % p->batch)
+        return fail(ctx, RT_EINVAL, "min_spp %u must be a multiple of batch %u and at least twice it", p->min_spp, p->batch);
+    if (p->max_spp < p->min_spp || p->max_spp > RT_MAX_SAMPLE + 1u)
+        return fail(ctx, RT_EINVAL, "max_spp %u outside min_spp %u .. %u", p->max_spp, p->min_spp, RT_MAX_SAMPLE + 1u);
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold))
+        return fail(ctx, RT_EINVAL, "threshold must be finite and >= 0");
+    const int bwl = log2_pow2(p->block_w), bhl = log2_pow2(p->block_h);
+    if (p->block_w < 1 || p->block_h < 1 || p->block_w > 256 || p->block_h > 256 || bwl < 0 || bhl < 0)
+        return fail(ctx, RT_EINVAL, "block %ux%u: sides must be powers of two in 1..256", p->block_w, p->block_h);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t bx = ((uint32_t)ctx->width + p->block_w - 1) >> bwl, by = ((uint32_t)ctx->height + p->block_h - 1) >> bhl;
+    const uint32_t blocks = bx * by;
+    if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
+    ctx->adaptive_blocks = 0;
+    const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_accum, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scratch, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_half, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_block_active, 0xFF, blocks * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_block_err, 0, blocks * sizeof(float), ctx->stream));
+    ctx->accum_count = 0;
+    const BlockMask mask{ctx->d_block_active, (uint32_t)bwl, (uint32_t)bhl, bx};
+    MergeParams mp;
+    mp.w = (uint32_t)ctx->width;
+    mp.h = (uint32_t)ctx->height;
+    mp.bw_log2 = (uint32_t)bwl;
+    mp.bh_log2 = (uint32_t)bhl;
+    mp.blocks_x = bx;
+    mp.blocks = blocks;
+    mp.min_spp = p->min_spp;
+    mp.max_spp = p->max_spp;
+    mp.threshold = p->threshold;
+    uint32_t rounds = 0;
+    uint64_t at_max = 0, pixel_samples = 0;
+    std::vector<unsigned long long> st(PT_MERGE_REPLICAS * PT_MERGE_STRIDE);
+    const size_t st_bytes = st.size() * sizeof(unsigned long long);
+    for (uint32_t k = 0;; k++) {
+        const uint32_t first = k * p->batch;
+        const uint32_t c = std::min(p->batch, p->max_spp - first);
+        rc = ctx->prefix_sharing
+                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), ctx->d_scratch, &mask)
+                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), ctx->d_scratch, &mask);
+        if (rc != RT_OK) return rc;
+        mp.round = k;
+        mp.count = first + c;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_adaptive_stats, 0, st_bytes, ctx->stream));
+        hipLaunchKernelGGL(pt_adaptive_merge, dim3((blocks + PT_MERGE_WAVES - 1) / PT_MERGE_WAVES), dim3(64 * PT_MERGE_WAVES), 0,
+                           ctx->stream, mp, ctx->d_accum, ctx->d_half, ctx->d_scratch, ctx->d_block_active, ctx->d_block_err,
+                           ctx->d_adaptive_stats);
+        HIP_TRY(ctx, hipGetLastError());
+        rounds++;
+        ctx->accum_count = first + c;
+        HIP_TRY(ctx, hipMemcpyAsync(st.data(), ctx->d_adaptive_stats, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        uint64_t still = 0;
+        for (uint32_t r = 0; r < PT_MERGE_REPLICAS; r++) {
+            still += st[r * PT_MERGE_STRIDE];
+            at_max += st[r * PT_MERGE_STRIDE + 1];
+            pixel_samples += st[r * PT_MERGE_STRIDE + 2];
+        }
+        if (still == 0) break;
+    }
+    if ((rc = resolve_into(ctx, 0)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->adaptive_blocks = blocks;
+    out->rounds = rounds;
+    out->pixel_samples = pixel_samples;
+    out->blocks = blocks;
+    out->blocks_at_max = (uint32_t)at_max;
+    return RT_OK;
+}
+
+int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const size_t n = (size_t)ctx->width * ctx->height;
+    if (!counts || bytes != n * sizeof(uint32_t)) return fail(ctx, RT_EINVAL, "count buffer must be %zu bytes", n * sizeof(uint32_t));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<float4> h(n);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d_accum, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) counts[i] = (uint32_t)h[i].w;
+    return RT_OK;
+}
+
+int rt_read_block_error(rt_context *ctx, float *err, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    if (!ctx->adaptive_blocks) return fail(ctx, RT_ESTATE, "no rt_render_adaptive call since the frame was (re)allocated");
+    const size_t need = (size_t)ctx->adaptive_blocks * sizeof(float);
+    if (!err || bytes != need) return fail(ctx, RT_EINVAL, "block error buffer must be %zu bytes", need);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(err, ctx->d_block_err, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 int rt_sync(rt_context *ctx) {

@@ -112,6 +112,15 @@ struct rt_context {
     uint32_t sample_counter = 0;
     bool count_enabled = false;
 
+    // adaptive sampling (rt_render_adaptive), allocated on its first call
+    float4 *d_scratch = nullptr;        // W x H: the current round's sums (zero outside it)
+    float4 *d_half = nullptr;           // W x H: the sums of the even rounds
+    uint32_t *d_block_active = nullptr; // per decision block: traced by the next round
+    float *d_block_err = nullptr;       // per decision block: its error after the last round it was traced in
+    unsigned long long *d_adaptive_stats = nullptr;   // pt_adaptive_merge's counter rows (rt_amd.hip)
+    size_t adaptive_block_capacity = 0;
+    uint32_t adaptive_blocks = 0;       // blocks of the last completed rt_render_adaptive call (0: none since the last resize)
+
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
 };
@@ -211,6 +220,9 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     fp.tree_count = nullptr;
     fp.tree_cap = 0;
     fp.lds_face_f4 = 0;
+    fp.block_active = nullptr;
+    fp.blk_w_log2 = fp.blk_h_log2 = 0;
+    fp.blocks_x = 0;
     {
         volatile float c = (float)count;
         volatile float q = 1.0f / c;

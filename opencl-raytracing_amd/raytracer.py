@@ -28,6 +28,7 @@ SYMBOLS = (
     "rt_enable_counters", "rt_reset_counters", "rt_get_counters", "rt_counters_bytes", "rt_last_kernel_ms",
     "rt_kernel_ms_history", "rt_stage_ms_history", "rt_debug_hit", "rt_debug_material", "rt_debug_div3", "rt_device_info", "rt_set_option", "rt_shard_slots", "rt_pack_accum", "rt_unpack_accum",
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
+    "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -109,6 +110,7 @@ def load_library(path=LIB_PATH):
     lib.rt_device_info.argtypes = [vp, C.c_char_p, sz, C.POINTER(C.c_int), C.c_char_p, sz]
     lib.rt_walk_overflow.argtypes = [vp, C.POINTER(u32)]
     lib.rt_debug_builtin.argtypes = [vp, C.c_int, vp, sz, vp]
+    _abi.adaptive_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -292,6 +294,29 @@ class RayTracer:
         self.clear()
         self.renderSamples(camera, 0, spp)
         self.resolve()
+
+    def renderAdaptive(self, camera, threshold, batch=64, min_spp=128, max_spp=1024, block=(8, 8)):
+        """Adaptive frame (rt_render_adaptive): rounds of `batch` samples per pixel until every block of block[0] x
+        block[1] pixels has converged (error < threshold, after at least min_spp samples) or holds max_spp samples.
+        The image and the linear accumulator are left resolved, as renderFrameOnDevice leaves them.  → stats dict."""
+        p = _abi.AdaptiveParams(int(batch), int(min_spp), int(max_spp), float(threshold), int(block[0]), int(block[1]))
+        st = _abi.AdaptiveStats()
+        self._check(self._lib.rt_render_adaptive(self._ctx, _cam_block(camera).ctypes.data, C.byref(p), C.byref(st)))
+        self._adaptive_block = (int(block[0]), int(block[1]))
+        return st.as_dict()
+
+    def sampleCounts(self):
+        """Per-pixel sample counts of the accumulator → (h, w) uint32."""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        self._check(self._lib.rt_read_sample_counts(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def blockError(self):
+        """Block errors of the last renderAdaptive call → (ceil(h/bh), ceil(w/bw)) float32."""
+        bw, bh = getattr(self, "_adaptive_block", (8, 8))
+        out = np.empty((-(-self.height // bh), -(-self.width // bw)), dtype=np.float32)
+        self._check(self._lib.rt_read_block_error(self._ctx, out.ctypes.data, out.nbytes))
+        return out
 
     def traceSamples(self, camera, xs, ys, samples):
         xs = np.ascontiguousarray(xs, dtype=np.uint32)
