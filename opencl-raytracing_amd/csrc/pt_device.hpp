@@ -744,6 +744,24 @@ PT_DEV bool hit_scene(const Ctx &c, const Ray &r, Hit &hit) {
 // ---- materials -------------------------------------------------------------------
 // :401-405
 PT_DEV float schlick(float cosine, float r0) { return mad(1.0f - r0, pow5(1.0f - cosine), r0); }   // r0 + (1 - r0) * pow(1 - cai, 5)
+// The reference's choice at a dielectric surface, `schlick(cosine, r0) < u` (:430-431).  The reflect probability is
+// used for nothing else, so where a cheap estimate settles the comparison the library's pow (about 150 instructions
+// under policies 1 and 2, run for every lane on glass) is not needed: x⁵ as three products is within 4 ulp of the
+// exact x⁵, and the library's pow within a few ulp of that too; below 2^-100 both are absolute 2^-100 apart at
+// most.  The margin allows 2^-10 of relative error, several thousand times more than either can have.  Only a lane
+// whose u lies within that margin of the probability (about 0.1 % of them) computes it exactly.  NaN or infinite
+// estimates fail both tests and take the exact path.  The decision is the reference's, bit for bit.
+PT_DEV bool schlick_below(float cosine, float r0, float u) {
+    if (PT_OCL) {
+        const float x = 1.0f - cosine, x2 = x * x;
+        const float q = (x2 * x2) * x;
+        const float p = mad(1.0f - r0, q, r0);
+        const float m = fabsf(1.0f - r0) * (fabsf(q) * 0x1p-10f + 0x1p-100f) + fabsf(p) * 0x1p-10f + 0x1p-100f;
+        if (u - p > m) return true;
+        if (p - u > m) return false;
+    }
+    return schlick(cosine, r0) < u;
+}
 
 // :105-107 with the bilinear definition of DESIGN.md (OpenCL 1.2 §8.2, edge clamp)
 PT_DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -830,8 +848,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
         bool want = true;
         if (type == RT_DIELECTRIC) {
             if (COUNT) c.cn->c[CN_N_DIELECTRIC]++;
-            float prob = schlick(-cai, g.r0);
-            want = prob < rnd.u;
+            want = schlick_below(-cai, g.r0, rnd.u);   // = schlick(-cai, g.r0) < rnd.u
         }
         float disc = glass_disc(g);
         if (want && disc > 0.0f) {

@@ -576,28 +576,27 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
                     bits = __float_as_uint(q0.w);
                 }
                 if (COUNT) cn.c[CN_SAMPLES]++;
+                // the state of an idle lane is dead: it takes the record whatever its kind, so that the registers are
+                // written in place (a final colour's lane stays idle and its state is never read)
+                depth = (bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
+                hn = xyz(q1);
+                r.o = xyz(q0);
+                r.d = xyz(q2);
+                hmat = __float_as_uint(q2.w);
+                out = xyz(q3);
+                col = xyz(q4);
                 if ((bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
                     slot[3 * idx] = q3.x;
                     slot[3 * idx + 1] = q3.y;
                     slot[3 * idx + 2] = q3.z;
                 } else {
-                    depth = (bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
-                    hn = xyz(q1);
-                    r.o = xyz(q0);
-                    r.d = xyz(q2);
-                    hmat = __float_as_uint(q2.w);
-                    out = xyz(q3);
-                    col = xyz(q4);
                     if (PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
                     active = true;
                 }
             }
             next += (uint32_t)__popcll(m);
         }
-        if (!__any(active)) {
-            if (next >= total) break;
-            continue;  // every candidate was a final-colour pixel: keep draining the queue
-        }
+        if (!__any(active) && next >= total) break;
         PT_STAMP(c, 0);
 #ifdef PT_EXP_PAD  // timing experiment (tools/pad_experiment.sh): PT_EXP_PAD extra full-rate VALU instructions per iteration
                    // (v_or_b32 x, x, x on a live register: no new VGPR; PT_EXP_PAD_NOP: operand-free v_nop instead).  An
@@ -611,7 +610,7 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
 #endif
 #endif
 #ifdef PT_QSTAT  // diagnostic: lane-iterations used / offered (read through rt_get_debug_counters on a BVH-free scene)
-        if (COUNT) {
+        if (COUNT && __any(active)) {   // (an iteration that only refilled final colours is not offered)
             uint32_t na = (uint32_t)__popcll(__ballot(active));
             if (lane == 0) cn.c[CN_DBG_BVH_NODES] += na;
             if (lane == 0) cn.c[CN_DBG_BVH_TESTS] += 64u;
@@ -646,10 +645,7 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
             if (PT_RNG_PREFETCH == 1) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
             V3 res;
             bool done = false;
-            Hit h;
-            h.p = h.n = mk(0.0f, 0.0f, 0.0f);
-            h.u = h.v = 0.0f;
-            h.tex = h.mat = 0;
+            Hit h;   // (every field is written by hit_finish on a hit, and read only then)
             Nearest nb;
             hit_primitives<COUNT, ACCEL, GEOM != 0>(c, r, nb);
             if (GEOM != 0) hit_models<COUNT, GEOM == 2>(c, r, nb);
@@ -658,6 +654,11 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
                 done = true;
             } else {
                 if (COUNT) cn.c[CN_H_BOUNCE]++;
+                // the next interaction happens here (for a light the lane retires below and this state is dead):
+                // written in the branch that computed it, so that the registers are updated in place
+                r.o = h.p;
+                hn = h.n;
+                hmat = h.mat;
                 int type;
                 float extra;
                 load_material(c, h.mat, type, extra, col);
@@ -677,11 +678,6 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
             } else if (PT_RNG_PREFETCH == 2) {
                 // this lane WILL interact next iteration: its table reads fly during the refill step
                 rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-            }
-            if (!done) {   // the next interaction happens here
-                r.o = h.p;
-                hn = h.n;
-                hmat = h.mat;
             }
         }
         PT_STAMP(c, 4);
