@@ -87,6 +87,24 @@ std::vector<uint32_t> RayTracer::sampleCounts() {
     return c;
 }
 
+void RayTracer::renderFeatures(const Camera *camera) {
+    check(rt_render_features(ctx, camera->transferData()));
+}
+
+std::vector<rt_feature> RayTracer::features() {
+    std::vector<rt_feature> f((size_t)width * height);
+    check(rt_read_features(ctx, f.data(), f.size() * sizeof(rt_feature)));
+    return f;
+}
+
+const float *RayTracer::denoise(const Camera *camera, const rt_denoise_params &params) {
+    if (camera) renderFeatures(camera);
+    check(rt_denoise(ctx, &params));
+    pixels.resize((size_t)width * height * 4);
+    check(rt_read_denoised(ctx, pixels.data(), pixels.size() * sizeof(float)));
+    return pixels.data();
+}
+
 uint32_t RayTracer::sampleCounter() const {
     uint32_t v = 0;
     rt_sample_counter(ctx, &v);

@@ -61,6 +61,12 @@ public:
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
     std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major
     const float *lastImage() const { return pixels.data(); }  // what the last read-back returned
+    // first-hit feature records of every pixel (rt_render_features, asynchronous) and their read-back
+    void renderFeatures(const Camera *camera);
+    std::vector<rt_feature> features();
+    // features for `camera` (unless it is null: then the last ones) + rt_denoise + read back into the image that
+    // transferImage() / lastImage() return; the accumulator is left as it was
+    const float *denoise(const Camera *camera, const rt_denoise_params &params);
     uint32_t sampleCounter() const;
     rt_context *context() { return ctx; }
     SceneCreator &sceneCreator() { return scene; }

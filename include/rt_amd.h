@@ -314,6 +314,69 @@ int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes);
  * holds its error after the last round it was traced in.  RT_ESTATE before the first call / after rt_resize. */
 int rt_read_block_error(rt_context *ctx, float *err, size_t bytes);
 
+/*
+ * First-hit feature buffers (new; the reference has no such entry point).  One record per pixel of the frame,
+ * row-major W x H in the layout of rt_read_image: the pixel's primary ray (no jitter, raytracer.cl:500-505, so one
+ * first hit per pixel) through the same nearest-hit search and winner rebuild as the trace kernels, under the
+ * selected arithmetic policy — bit for bit what rt_debug_hit(kind 3) returns for (camera origin, dir).
+ * On a miss: t = +inf, pos / normal / albedo 0, object and material 0xFFFFFFFF, face 0xFFFFFFFF, u = v = tex = 0,
+ * flags 0; the direction is always written.  80 bytes, five 16-byte groups.
+ */
+typedef struct rt_feature {
+    float pos[3];       /* hit point                                                                          */
+    float t;            /* ray parameter of the nearest hit (+inf: miss)                                      */
+    float normal[3];    /* the hit routine's normal, unchanged (not turned to face the ray)                   */
+    uint32_t object;    /* kind in bits 31..30 (0 sphere, 1 plane, 2 lens, 3 mesh), index in bits 29..0      */
+    float albedo[3];    /* material colour; for RT_TEXTURED the bilinear texel the path fetches at (u, v)      */
+    uint32_t material;  /* mat_ID of the hit                                                                  */
+    float dir[3];       /* primary ray direction, as the selected policy computes it                          */
+    uint32_t face;      /* face index inside the mesh for a mesh hit, else 0xFFFFFFFF                         */
+    float u, v;         /* texture coordinates (mesh hits; 0 otherwise)                                       */
+    uint32_t tex;       /* texture id (mesh hits; 0 otherwise)                                                */
+    uint32_t flags;     /* RT_FEATURE_HIT                                                                     */
+} rt_feature;
+#define RT_FEATURE_HIT 1u
+
+/* Render the feature record of every pixel for `camera` (asynchronous on the context's stream; replaces the
+ * previous features).  Leaves the image, the accumulator and the sample counter untouched.  Unsharded contexts only.
+ * rt_read_features: bytes = W*H*80.  rt_device_features: the device address of the W x H records.  Both give
+ * RT_ESTATE until rt_render_features has run since the frame was (re)allocated. */
+int rt_render_features(rt_context *ctx, const float camera[12]);
+int rt_read_features(rt_context *ctx, rt_feature *out, size_t bytes);
+int rt_device_features(rt_context *ctx, void **d_features);
+
+/*
+ * Edge-avoiding à-trous denoiser (new; the reference has no such entry point): Dammertz et al. 2010, "Edge-Avoiding
+ * À-Trous Wavelet Transform for fast Global Illumination Filtering", over the linear accumulator, guided by the last
+ * rt_render_features call.  With c_p, n_p, x_p, a_p a pixel's colour, normal, position and albedo (the feature
+ * record's fp32 values):
+ *   c0_p = accum.rgb / accum.w, or 0 where accum.w == 0;
+ *   for i = 0 .. L-1, s = 2^i:  c(i+1)_p = sum_q w_pq c(i)_q / sum_q w_pq  over q = p + s*(dx, dy), dx, dy in -2..2
+ *     (dy outer, dx inner), taps outside the frame skipped;
+ *   w_pq = h[dx] h[dy] e(|c(i)_p - c(i)_q|^2 / (sigma_color 2^-i)^2) e(|n_p - n_q|^2 / sigma_normal^2)
+ *          e(|x_p - x_q|^2 / sigma_position^2) e(|a_p - a_q|^2 / sigma_albedo^2),
+ *     h = (1/16, 1/4, 3/8, 1/4, 1/16), e(z) = exp(-z); a sigma of +inf switches its term off;
+ *     w_pq = 0 when the hit flags of p and q differ, and with RT_DENOISE_SPLIT_OBJECTS also when their object ids
+ *     differ (the centre tap always has weight > 0);
+ *   output RGBA = (sqrt(c(L)_p), 1) where accum.w > 0, else 0 (as rt_resolve), into a buffer of its own.
+ * Asynchronous on the context's stream; one launch per iteration.  Leaves the image, the accumulator and the sample
+ * counter untouched.  RT_EINVAL: iterations outside 1..8, a sigma <= 0 or NaN, unknown flags, a NULL pointer, a
+ * sharded context; RT_ESTATE: no features since the frame was (re)allocated.
+ * rt_read_denoised: bytes = W*H*16.  rt_device_denoised: the device address of the W x H x 4 floats.  Both give
+ * RT_ESTATE until rt_denoise has run since the frame was (re)allocated.
+ */
+typedef struct rt_denoise_params {
+    uint32_t iterations;    /* L, 1 .. 8 (5 suggested)                                                       */
+    float sigma_color, sigma_normal, sigma_position, sigma_albedo;   /* > 0; +inf = term off                  */
+    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS                                                       */
+} rt_denoise_params;
+#define RT_DENOISE_SPLIT_OBJECTS 1u
+#define RT_DENOISE_MAX_ITERATIONS 8u
+
+int rt_denoise(rt_context *ctx, const rt_denoise_params *p);
+int rt_read_denoised(rt_context *ctx, float *rgba, size_t bytes);
+int rt_device_denoised(rt_context *ctx, void **d_rgba);
+
 /* Wait for everything queued on the context's stream (reference:
  * queue.finish(), src/raytracer.cpp:140).  rt_render/rt_render_again already
  * return synchronously; rt_render_spp/rt_resolve/rt_clear are asynchronous. */

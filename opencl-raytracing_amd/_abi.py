@@ -114,6 +114,47 @@ def block_error_reference(accum, half, block_w, block_h):
     return np.nanmean(pad.reshape(by, block_h, bx, block_w), axis=(1, 3))
 
 
+# rt_feature (rt_render_features): one first-hit record per pixel, 80 bytes in five 16-byte groups
+FEATURE = np.dtype([("pos", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("object", "<u4"),
+                    ("albedo", "<f4", (3,)), ("material", "<u4"), ("dir", "<f4", (3,)), ("face", "<u4"),
+                    ("u", "<f4"), ("v", "<f4"), ("tex", "<u4"), ("flags", "<u4")])
+assert FEATURE.itemsize == 80
+FEATURE_HIT = 1
+NO_ID = 0xFFFFFFFF          # object / material / face of a miss; face of a hit that is not a mesh's
+OBJECT_KINDS = ("sphere", "plane", "lens", "mesh")   # object id >> 30
+DENOISE_SPLIT_OBJECTS = 1
+DENOISE_MAX_ITERATIONS = 8
+# rt_denoise defaults of the Python and C++ surfaces (DESIGN.md "Feature buffers and denoising": the sweep that chose them)
+DENOISE_DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_position=2.0, sigma_albedo=0.2,
+                        split_objects=True)
+
+
+class DenoiseParams(C.Structure):
+    """rt_denoise_params"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
+
+
+def denoise_prototypes(lib):
+    """ctypes prototypes of the feature-buffer and denoiser entry points (rt_render_features & co.)."""
+    vp, sz = C.c_void_p, C.c_size_t
+    lib.rt_render_features.argtypes = [vp, vp]
+    lib.rt_read_features.argtypes = [vp, vp, sz]
+    lib.rt_device_features.argtypes = [vp, C.POINTER(vp)]
+    lib.rt_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+    lib.rt_read_denoised.argtypes = [vp, vp, sz]
+    lib.rt_device_denoised.argtypes = [vp, C.POINTER(vp)]
+
+
+def split_features(rec):
+    """(H, W) FEATURE records → dict of (H, W, ...) arrays (RayTracer.features())."""
+    return {"position": rec["pos"].copy(), "depth": rec["t"].copy(), "normal": rec["normal"].copy(),
+            "albedo": rec["albedo"].copy(), "object": rec["object"].copy(), "material": rec["material"].copy(),
+            "face": rec["face"].copy(), "direction": rec["dir"].copy(),
+            "uv": np.stack([rec["u"], rec["v"]], axis=-1), "texture": rec["tex"].copy(),
+            "hit": (rec["flags"] & FEATURE_HIT) != 0}
+
+
 def ptr(a):
     """void* of a numpy array (None/empty → NULL)."""
     if a is None or a.size == 0:

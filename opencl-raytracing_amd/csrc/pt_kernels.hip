@@ -1099,6 +1099,47 @@ __global__ __launch_bounds__(256) void pt_probe(DeviceScene sc, FrameParams fp, 
     out[3 * i + 2] = col.z;
 }
 
+// First-hit feature buffers (rt_render_features): one work-item per pixel of the whole frame.  The primary ray through
+// the nearest-hit search of the trace kernels (hit_primitives + hit_models + hit_finish, the parts of hit_scene, kept
+// apart for the winner's id and face), the material colour or the path's texel, into the public rt_feature record
+// (include/rt_amd.h) as five 16-byte stores.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features(DeviceScene sc, FrameParams fp, float4 *__restrict__ out) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
+    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
+    const Ray r = primary_ray(fp.cam, x, y, fp.w, fp.h);
+    Nearest nb;
+    hit_primitives<false, ACCEL>(c, r, nb);
+    hit_models<false, ACCEL>(c, r, nb);
+    Hit h;
+    float4 *o = out + 5 * (size_t)i;
+    if (hit_finish<false>(c, r, nb, h)) {
+        int type;
+        float extra;
+        V3 col;
+        load_material(c, h.mat, type, extra, col);
+        if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
+        const bool mesh = (nb.id & K_MASK) == K_MESH;
+        o[0] = make_float4(h.p.x, h.p.y, h.p.z, nb.t);
+        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
+        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
+        o[3] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
+        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(RT_FEATURE_HIT));
+    } else {
+        const float none = __uint_as_float(0xFFFFFFFFu);
+        o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+        o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
+        o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
+        o[3] = make_float4(r.d.x, r.d.y, r.d.z, none);
+        o[4] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
 // ---- unit probes of the device routines (tests only; rt_debug_hit / rt_debug_material / rt_debug_div3) -----------
 // One work-item per record; the routines are the very ones the trace kernels inline (hit_primitives' sphere_t /
 // plane_t / lens_t, triangle_t, hit_scene + hit_finish, scatter), so a unit vector that matches the oracle here
@@ -1466,6 +1507,17 @@ int ks_launch_probe(rt_context *ctx, const FrameParams &fp, const DeviceScene &s
     return RT_OK;
 }
 
+// (the ACCEL choice of launch_fused: the BVH walks are compiled in when the scene has a BVH)
+int ks_launch_features(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, rt_feature *d_out) {
+    const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
+    dim3 grid((n + 255u) / 256u), block(256);
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    if (scene_has_accel(sc)) hipLaunchKernelGGL(pt_features<true>, grid, block, 0, ctx->stream, sc, fp, o);
+    else hipLaunchKernelGGL(pt_features<false>, grid, block, 0, ctx->stream, sc, fp, o);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -1511,7 +1563,7 @@ const pt::KernelSet g_kernel_set = {
 #else
     "rocm-opencl",
 #endif
-    ks_launch_render, launch_fused, ks_launch_probe, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
+    ks_launch_render, launch_fused, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin};
 
 }  // namespace

@@ -18,6 +18,8 @@ struct KernelSet {
                         float4 *accum, const BlockMask *mask);
     // rt_trace_samples: d_in = n x, n y, n sample (uint32), d_out = 3 n floats
     int (*launch_probe)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out);
+    // rt_render_features: pt_features, one rt_feature per pixel of the fp.w x fp.h frame into d_out
+    int (*launch_features)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, rt_feature *d_out);
     // unit probes (rt_debug_hit / rt_debug_material / rt_debug_div3)
     int (*launch_debug_hit)(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                             const uint32_t *d_face, uint32_t n, float *d_out);

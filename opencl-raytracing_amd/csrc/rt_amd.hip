@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -133,6 +134,108 @@ __global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge(MergePa
         if (mp.count >= mp.max_spp && unconverged) atomicAdd(&stats[1], 1ull);
         atomicAdd(&stats[2], (unsigned long long)npx * mp.count);
     }
+}
+
+// Edge-avoiding à-trous denoiser (rt_denoise; the math is written out in rt_amd.h): one launch per iteration.  At step
+// s = 2^i the 5x5 stencil only ever couples pixels of one residue class (x mod s, y mod s), so a workgroup owns a
+// 16x16 tile of one class's sub-lattice {(rx + s i, ry + s j)}, stages the 20x20 lattice points of the tile and its
+// 2-point halo into LDS (colour + the guide's three 16-byte groups of the feature record: pos_t, normal_obj,
+// albedo_mat), and every tap is an LDS neighbour at distance <= 2 for every step; an iteration re-reads 400/256 =
+// 1.56x its input.  The hit flag is read as t < +inf (the same bit as RT_FEATURE_HIT by construction of pt_features).
+// A staged point carries a key: the object id (split objects) or the hit flag, and PT_DN_OFF for a point outside the
+// frame, whose data are zeros — a tap's weight is 0 unless its key equals the centre's (a select, no branch).
+// Workgroup ids are remapped so that the s classes of one tile row, which share cache lines, run on one XCD.
+#define PT_DN_TILE 16
+#define PT_DN_SIDE (PT_DN_TILE + 4)
+#define PT_DN_POINTS (PT_DN_SIDE * PT_DN_SIDE)
+#define PT_DN_OFF 0xFFFFFFFEu          // key of an out-of-frame point (never an object id: 2^30 - 2 meshes)
+#define PT_DN_XCDS 8u
+struct DenoiseStep {
+    uint32_t w, h;
+    uint32_t step_log2;                 // s = 1 << step_log2
+    uint32_t tiles_x;                   // 16x16 tiles across the widest sub-lattice
+    uint32_t groups;                    // s * s * tiles_x * tiles_y
+    float inv_c, inv_n, inv_x, inv_a;   // 1 / sigma^2 of this iteration (colour: 4^i / sigma_c^2); 0 = term off
+    uint32_t split;                     // RT_DENOISE_SPLIT_OBJECTS
+    uint32_t first, last;               // src is the accumulator (c0 = rgb / w) / dst gets (sqrt(c), 1) or 0
+};
+
+PT_DEV float dn_d2(float4 a, float4 b) {
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return dx * dx + dy * dy + dz * dz;
+}
+
+__global__ __launch_bounds__(256) void pt_atrous(DenoiseStep ds, const float4 *__restrict__ src,
+                                                 const float4 *__restrict__ feat, float4 *__restrict__ dst) {
+    __shared__ float4 s_col[PT_DN_POINTS], s_pos[PT_DN_POINTS], s_nrm[PT_DN_POINTS], s_alb[PT_DN_POINTS];
+    // XCD remap: consecutive logical groups (the residue classes rx of one tile) share an XCD
+    const uint32_t per_xcd = gridDim.x / PT_DN_XCDS;
+    const uint32_t g = (blockIdx.x % PT_DN_XCDS) * per_xcd + blockIdx.x / PT_DN_XCDS;
+    if (g >= ds.groups) return;
+    const uint32_t sl = ds.step_log2, s = 1u << sl;
+    const uint32_t rx = g & (s - 1u);
+    uint32_t rem = g >> sl;
+    const uint32_t tx = rem % ds.tiles_x;
+    rem /= ds.tiles_x;
+    const uint32_t ry = rem & (s - 1u), ty = rem >> sl;
+    const int i0 = (int)(tx * PT_DN_TILE), j0 = (int)(ty * PT_DN_TILE);
+    const int nx = (int)((ds.w - rx + s - 1u) >> sl), ny = (int)((ds.h - ry + s - 1u) >> sl);   // the class's lattice size
+    if (i0 >= nx || j0 >= ny) return;   // (uniform over the workgroup, before its barrier)
+    for (uint32_t k = threadIdx.x; k < PT_DN_POINTS; k += 256u) {
+        const int x = (int)rx + (i0 - 2 + (int)(k % PT_DN_SIDE)) * (int)s;
+        const int y = (int)ry + (j0 - 2 + (int)(k / PT_DN_SIDE)) * (int)s;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p = c, n = c, a = c;
+        uint32_t key = PT_DN_OFF;
+        if (x >= 0 && y >= 0 && x < (int)ds.w && y < (int)ds.h) {
+            const size_t q = (size_t)y * ds.w + (size_t)x;
+            c = src[q];
+            if (ds.first) {
+                const float cw = c.w;
+                c = cw > 0.0f ? make_float4(c.x / cw, c.y / cw, c.z / cw, cw) : make_float4(0.0f, 0.0f, 0.0f, cw);
+            }
+            const float4 *f = feat + 5 * q;
+            p = f[0];
+            n = f[1];
+            a = f[2];
+            const bool hit = p.w < INFINITY;
+            key = ds.split ? __float_as_uint(n.w) : (hit ? 0u : 1u);
+        }
+        p.w = __uint_as_float(key);
+        s_col[k] = c;
+        s_pos[k] = p;
+        s_nrm[k] = n;
+        s_alb[k] = a;
+    }
+    __syncthreads();
+    const uint32_t li = threadIdx.x & (PT_DN_TILE - 1u), lj = threadIdx.x / PT_DN_TILE;
+    const uint32_t x = rx + (((uint32_t)i0 + li) << sl), y = ry + (((uint32_t)j0 + lj) << sl);
+    if (x >= ds.w || y >= ds.h) return;
+    const uint32_t ci = (lj + 2u) * PT_DN_SIDE + li + 2u;
+    const float4 cp = s_col[ci], pp = s_pos[ci], np = s_nrm[ci], ap = s_alb[ci];
+    const uint32_t keyp = __float_as_uint(pp.w);
+    const float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+#pragma unroll
+    for (int dy = 0; dy < 5; dy++) {
+#pragma unroll
+        for (int dx = 0; dx < 5; dx++) {
+            const uint32_t q = ci + (uint32_t)((dy - 2) * PT_DN_SIDE + (dx - 2));
+            const float4 cq = s_col[q], pq = s_pos[q], nq = s_nrm[q], aq = s_alb[q];
+            const float z = ds.inv_c * dn_d2(cp, cq) + ds.inv_n * dn_d2(np, nq) + ds.inv_x * dn_d2(pp, pq) +
+                            ds.inv_a * dn_d2(ap, aq);
+            float wt = (hk[dx] * hk[dy]) * __expf(-z);
+            wt = __float_as_uint(pq.w) == keyp ? wt : 0.0f;
+            sw += wt;
+            sr += wt * cq.x;
+            sg += wt * cq.y;
+            sb += wt * cq.z;
+        }
+    }
+    const float r = sr / sw, gg = sg / sw, b = sb / sw;
+    float4 o;
+    if (ds.last) o = cp.w > 0.0f ? make_float4(sqrtf(r), sqrtf(gg), sqrtf(b), 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    else o = make_float4(r, gg, b, cp.w);
+    dst[(size_t)y * ds.w + x] = o;
 }
 
 // ================================== host side ==================================
@@ -387,8 +490,20 @@ void free_adaptive(rt_context *ctx) {
     ctx->adaptive_blocks = 0;
 }
 
+void free_denoise(rt_context *ctx) {
+    if (ctx->d_features) (void)hipFree(ctx->d_features);
+    if (ctx->d_dn[0]) (void)hipFree(ctx->d_dn[0]);
+    if (ctx->d_dn[1]) (void)hipFree(ctx->d_dn[1]);
+    if (ctx->d_denoised) (void)hipFree(ctx->d_denoised);
+    ctx->d_features = nullptr;
+    ctx->d_dn[0] = ctx->d_dn[1] = nullptr;
+    ctx->d_denoised = nullptr;
+    ctx->have_features = ctx->have_denoised = false;
+}
+
 int alloc_frame(rt_context *ctx, int w, int h) {
     free_adaptive(ctx);
+    free_denoise(ctx);
     if (ctx->d_image) (void)hipFree(ctx->d_image);
     if (ctx->d_accum) (void)hipFree(ctx->d_accum);
     ctx->d_image = ctx->d_accum = nullptr;
@@ -548,6 +663,7 @@ void rt_destroy(rt_context *ctx) {
     if (ctx->d_glass) (void)hipFree(ctx->d_glass);
     if (ctx->d_tree_work) (void)hipFree(ctx->d_tree_work);
     free_adaptive(ctx);
+    free_denoise(ctx);
     ctx->sph4.release();
     ctx->faces.release();
     ctx->mesh_face_base.release();
@@ -1012,6 +1128,116 @@ int rt_read_block_error(rt_context *ctx, float *err, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(err, ctx->d_block_err, need, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// ---- feature buffers and denoiser ------------------------------------------------------------------------------------
+
+int rt_render_features(rt_context *ctx, const float camera[12]) {
+    int rc = check_ready(ctx, camera);
+    if (rc) return rc;
+    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "features of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_features)
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_features, (size_t)ctx->width * ctx->height * sizeof(rt_feature)));
+    const FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
+    const DeviceScene sc = device_scene(ctx);
+    if ((rc = ctx->ks->launch_features(ctx, fp, sc, ctx->d_features)) != RT_OK) return rc;
+    ctx->have_features = true;
+    return RT_OK;
+}
+
+int rt_read_features(rt_context *ctx, rt_feature *out, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const size_t need = (size_t)ctx->width * ctx->height * sizeof(rt_feature);
+    if (!out || bytes != need) return fail(ctx, RT_EINVAL, "feature buffer must be %zu bytes", need);
+    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_features, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_device_features(rt_context *ctx, void **d_features) {
+    if (!ctx || !d_features) return RT_EINVAL;
+    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    *d_features = ctx->d_features;
+    return RT_OK;
+}
+
+int rt_denoise(rt_context *ctx, const rt_denoise_params *p) {
+    if (!ctx) return RT_EINVAL;
+    if (!p) return fail(ctx, RT_EINVAL, "denoise parameters are NULL");
+    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "denoising a sharded context (rank %d of %d)", ctx->rank, ctx->world);
+    if (p->iterations < 1 || p->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(ctx, RT_EINVAL, "iterations %u outside 1..%u", p->iterations, RT_DENOISE_MAX_ITERATIONS);
+    const float sig[4] = {p->sigma_color, p->sigma_normal, p->sigma_position, p->sigma_albedo};
+    for (float v : sig)
+        if (!(v > 0.0f)) return fail(ctx, RT_EINVAL, "every sigma must be > 0 (+inf switches its term off)");
+    if (p->flags & ~RT_DENOISE_SPLIT_OBJECTS) return fail(ctx, RT_EINVAL, "unknown denoise flags 0x%x", p->flags);
+    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
+    if (!ctx->d_denoised) {
+        hipError_t e = hipMalloc((void **)&ctx->d_dn[0], bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_dn[1], bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_denoised, bytes);
+        if (e != hipSuccess) {
+            free_denoise(ctx);
+            return fail(ctx, RT_EHIP, "denoise buffers: %s", hipGetErrorString(e));
+        }
+    }
+    // 1 / sigma^2 as the header's formula has it, (sigma 2^-i)^2 for the colour; +inf -> 0 (term off); a sigma so
+    // small that the reciprocal overflows is held at FLT_MAX (z = 0 still gives 0 at the centre, not inf * 0)
+    auto inv_sq = [](float sigma, int i) {
+        if (std::isinf(sigma)) return 0.0f;
+        const double sd = (double)sigma * std::ldexp(1.0, -i);
+        return (float)std::min(1.0 / (sd * sd), (double)FLT_MAX);
+    };
+    const uint32_t w = (uint32_t)ctx->width, h = (uint32_t)ctx->height;
+    for (uint32_t i = 0; i < p->iterations; i++) {
+        DenoiseStep ds;
+        ds.w = w;
+        ds.h = h;
+        ds.step_log2 = i;
+        const uint32_t s = 1u << i;
+        const uint32_t lat_w = (w + s - 1u) >> i, lat_h = (h + s - 1u) >> i;   // the widest / tallest class
+        ds.tiles_x = (lat_w + PT_DN_TILE - 1u) / PT_DN_TILE;
+        const uint32_t tiles_y = (lat_h + PT_DN_TILE - 1u) / PT_DN_TILE;
+        ds.groups = s * s * ds.tiles_x * tiles_y;
+        ds.inv_c = inv_sq(p->sigma_color, (int)i);
+        ds.inv_n = inv_sq(p->sigma_normal, 0);
+        ds.inv_x = inv_sq(p->sigma_position, 0);
+        ds.inv_a = inv_sq(p->sigma_albedo, 0);
+        ds.split = (p->flags & RT_DENOISE_SPLIT_OBJECTS) ? 1u : 0u;
+        ds.first = i == 0;
+        ds.last = i + 1 == p->iterations;
+        const float4 *src = i == 0 ? ctx->d_accum : ctx->d_dn[(i - 1) & 1u];
+        float4 *dst = ds.last ? ctx->d_denoised : ctx->d_dn[i & 1u];
+        const uint32_t grid = (ds.groups + PT_DN_XCDS - 1u) / PT_DN_XCDS * PT_DN_XCDS;
+        hipLaunchKernelGGL(pt_atrous, dim3(grid), dim3(256), 0, ctx->stream, ds, src,
+                           reinterpret_cast<const float4 *>(ctx->d_features), dst);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    ctx->have_denoised = true;
+    return RT_OK;
+}
+
+int rt_read_denoised(rt_context *ctx, float *rgba, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const size_t need = (size_t)ctx->width * ctx->height * sizeof(float4);
+    if (!rgba || bytes != need) return fail(ctx, RT_EINVAL, "image buffer must be %zu bytes", need);
+    if (!ctx->have_denoised) return fail(ctx, RT_ESTATE, "no rt_denoise call since the frame was (re)allocated");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(rgba, ctx->d_denoised, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_device_denoised(rt_context *ctx, void **d_rgba) {
+    if (!ctx || !d_rgba) return RT_EINVAL;
+    if (!ctx->have_denoised) return fail(ctx, RT_ESTATE, "no rt_denoise call since the frame was (re)allocated");
+    *d_rgba = ctx->d_denoised;
     return RT_OK;
 }
 

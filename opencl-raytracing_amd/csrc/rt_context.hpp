@@ -121,6 +121,12 @@ struct rt_context {
     size_t adaptive_block_capacity = 0;
     uint32_t adaptive_blocks = 0;       // blocks of the last completed rt_render_adaptive call (0: none since the last resize)
 
+    // feature buffers and denoiser (rt_render_features, rt_denoise), allocated on their first calls
+    rt_feature *d_features = nullptr;   // W x H first-hit records
+    float4 *d_dn[2] = {nullptr, nullptr};   // W x H: the à-trous iterations' ping-pong buffers (linear colour, count)
+    float4 *d_denoised = nullptr;       // W x H: the last rt_denoise result, gamma RGBA
+    bool have_features = false, have_denoised = false;   // made since the frame was (re)allocated
+
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
 };

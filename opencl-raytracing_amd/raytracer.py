@@ -29,6 +29,7 @@ SYMBOLS = (
     "rt_kernel_ms_history", "rt_stage_ms_history", "rt_debug_hit", "rt_debug_material", "rt_debug_div3", "rt_device_info", "rt_set_option", "rt_shard_slots", "rt_pack_accum", "rt_unpack_accum",
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
+    "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -111,6 +112,7 @@ def load_library(path=LIB_PATH):
     lib.rt_walk_overflow.argtypes = [vp, C.POINTER(u32)]
     lib.rt_debug_builtin.argtypes = [vp, C.c_int, vp, sz, vp]
     _abi.adaptive_prototypes(lib)
+    _abi.denoise_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -317,6 +319,60 @@ class RayTracer:
         out = np.empty((-(-self.height // bh), -(-self.width // bw)), dtype=np.float32)
         self._check(self._lib.rt_read_block_error(self._ctx, out.ctypes.data, out.nbytes))
         return out
+
+    def renderFeatures(self, camera):
+        """First-hit feature records of every pixel for `camera` (rt_render_features, asynchronous).  Leaves the image,
+        the accumulator and the sample counter untouched."""
+        self._check(self._lib.rt_render_features(self._ctx, _cam_block(camera).ctypes.data))
+
+    def featureRecords(self):
+        """The last renderFeatures call's records → (h, w) array of _abi.FEATURE."""
+        out = np.empty((self.height, self.width), dtype=_abi.FEATURE)
+        self._check(self._lib.rt_read_features(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def features(self):
+        """The last renderFeatures call's records as (h, w, ...) arrays: position, depth (t, +inf on a miss), normal,
+        albedo, object (kind << 30 | index), material, face, direction, uv, texture, hit."""
+        return _abi.split_features(self.featureRecords())
+
+    def denoise(self, camera=None, iterations=_abi.DENOISE_DEFAULTS["iterations"],
+                sigma_color=_abi.DENOISE_DEFAULTS["sigma_color"], sigma_normal=_abi.DENOISE_DEFAULTS["sigma_normal"],
+                sigma_position=_abi.DENOISE_DEFAULTS["sigma_position"],
+                sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """Edge-avoiding à-trous filter of the linear accumulator guided by the feature records (rt_denoise); renders
+        the features for `camera` first when one is given.  → the denoised gamma image (h, w, 4)."""
+        if camera is not None:
+            self.renderFeatures(camera)
+        self.denoiseOnDevice(iterations, sigma_color, sigma_normal, sigma_position, sigma_albedo, split_objects)
+        return self.denoisedImage()
+
+    def denoiseOnDevice(self, iterations=_abi.DENOISE_DEFAULTS["iterations"],
+                        sigma_color=_abi.DENOISE_DEFAULTS["sigma_color"],
+                        sigma_normal=_abi.DENOISE_DEFAULTS["sigma_normal"],
+                        sigma_position=_abi.DENOISE_DEFAULTS["sigma_position"],
+                        sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """rt_denoise enqueued, nothing read back."""
+        p = _abi.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
+                               float(sigma_albedo), _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+        self._check(self._lib.rt_denoise(self._ctx, C.byref(p)))
+
+    def denoisedImage(self):
+        """The last denoise result → gamma RGBA (h, w, 4)."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self._lib.rt_read_denoised(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def deviceFeatures(self):
+        """Device address of the W x H feature records (rt_device_features)."""
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_features(self._ctx, C.byref(p)))
+        return p.value
+
+    def deviceDenoised(self):
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_denoised(self._ctx, C.byref(p)))
+        return DeviceBuffer(p.value, self.height, self.width, self)
 
     def traceSamples(self, camera, xs, ys, samples):
         xs = np.ascontiguousarray(xs, dtype=np.uint32)

@@ -1,0 +1,150 @@
+"""Feature buffers + à-trous denoiser against fixed sample counts (DESIGN.md "Feature buffers and denoising").
+
+For each scene: a fixed 4096-spp frame is the ground truth.  For 1 / 4 / 16 / 64 spp it reports the gamma-space RMSE
+of the noisy frame and of the denoised frame (default sigmas), the device time of rt_render_features and of rt_denoise
+(events on the tracer's stream, median of --reps), and the smallest fixed spp (a power of two) whose noisy RMSE reaches
+the denoised 16-spp RMSE.  --sweep instead scores a grid of sigmas at 16 spp (the choice of the defaults).
+--profile-only runs just the denoise, --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
+such a run's kernel_trace.csv into per-iteration times.
+
+    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep]
+"""
+import argparse
+import csv
+import itertools
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import opencl_raytracing_amd as rt  # noqa: E402
+
+D = rt._abi.DENOISE_DEFAULTS
+
+
+def per_iteration(trace, iterations):
+    """Per-iteration pt_atrous times (us, median) from a rocprofv3 kernel_trace.csv of --profile-only runs."""
+    rows = [r for r in csv.DictReader(open(trace)) if "pt_atrous" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows]
+    us = us[len(us) % iterations:]
+    return [float(np.median(us[i::iterations])) for i in range(iterations)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", default="c2,c3,c5")
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--truth-spp", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--profile-only", action="store_true")
+    ap.add_argument("--trace", default=None)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if a.trace:
+        print(json.dumps({"pt_atrous_us_per_iteration": per_iteration(a.trace, D["iterations"])}))
+        return
+    import torch
+    w, h = (int(v) for v in a.size.split("x"))
+    rows, sweep = [], []
+    for name in a.scenes.split(","):
+        wl = rt.workloads.get(name, width=w, height=h)
+        t = rt.RayTracer(w, h, scene=wl.scene, seed=rt.workloads.SEED)
+        stream = torch.cuda.Stream()
+        t.setStream(stream.cuda_stream)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        def dev(buf):
+            return torch.as_tensor(buf, device="cuda")[..., :3].double()
+
+        t.renderFrameOnDevice(wl.camera, 16)   # warm-up (code objects, buffers)
+        t.renderFeatures(wl.camera)
+        t.denoiseOnDevice()
+        if a.profile_only:
+            for _ in range(a.reps):
+                t.denoiseOnDevice()
+            t.sync()
+            t.setStream(None)
+            t.close()
+            continue
+        t.renderFrameOnDevice(wl.camera, a.truth_spp)
+        t.sync()
+        truth = dev(t.deviceImage()).clone()
+
+        def rmse(buf):
+            t.sync()
+            return float(torch.sqrt(((dev(buf) - truth) ** 2).mean()))
+
+        if a.sweep:
+            t.renderFrameOnDevice(wl.camera, 16)
+            noisy = rmse(t.deviceImage())
+            grid = itertools.product((0.25, 0.5, 1.0, 2.0, np.inf), (0.1, 0.3, 0.5, 1.0), (0.1, 0.25, 0.5, 1.0, 2.0),
+                                     (0.05, 0.2, 0.5, np.inf))
+            for sc, sn, sx, sa in grid:
+                t.denoiseOnDevice(D["iterations"], sc, sn, sx, sa, True)
+                sweep.append(dict(scene=name, sigma=[sc, sn, sx, sa], rmse=rmse(t.deviceDenoised()), noisy=noisy))
+            t.setStream(None)
+            t.close()
+            continue
+        ms_f = float(np.median([timed(lambda: t.renderFeatures(wl.camera)) for _ in range(a.reps)]))
+        ms_d = float(np.median([timed(lambda: t.denoiseOnDevice()) for _ in range(a.reps)]))
+        den16 = None
+        for spp in (1, 4, 16, 64):
+            t.renderFrameOnDevice(wl.camera, spp)
+            noisy = rmse(t.deviceImage())
+            t.denoiseOnDevice()
+            den = rmse(t.deviceDenoised())
+            if spp == 16:
+                den16 = den
+            rows.append(dict(scene=name, spp=spp, rmse_noisy=noisy, rmse_denoised=den, ms_features=ms_f,
+                             ms_denoise=ms_d))
+        match = None
+        for spp in (32, 64, 128, 256, 512, 1024, 2048):
+            t.renderFrameOnDevice(wl.camera, spp)
+            if rmse(t.deviceImage()) <= den16:
+                match = spp
+                break
+        for r in rows:
+            if r["scene"] == name:
+                r["fixed_spp_matching_denoised_16"] = match
+        t.setStream(None)
+        t.close()
+    if a.profile_only:
+        return
+    if a.sweep:
+        by = {}
+        for r in sweep:
+            by.setdefault(tuple(r["sigma"]), []).append(r["rmse"] / r["noisy"])
+        ranked = sorted(by.items(), key=lambda kv: float(np.mean(kv[1])))
+        print("| sigma c, n, x, a | RMSE ratio denoised / noisy per scene (16 spp) | mean |")
+        print("|---|---|---:|")
+        for k, v in ranked[:12]:
+            print("| %s | %s | %.3f |" % (", ".join("%g" % x for x in k), ", ".join("%.3f" % x for x in v), np.mean(v)))
+        out = sweep
+    else:
+        print("| scene | spp | RMSE noisy | RMSE denoised | features ms | denoise ms | fixed spp matching denoised 16 |")
+        print("|---|---:|---:|---:|---:|---:|---:|")
+        for r in rows:
+            m = r["fixed_spp_matching_denoised_16"]
+            print("| %s | %d | %.5f | %.5f | %.3f | %.3f | %s |" % (r["scene"], r["spp"], r["rmse_noisy"], r["rmse_denoised"],
+                                                                 r["ms_features"], r["ms_denoise"], m if m else "> 2048"))
+        out = rows
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
