@@ -1297,7 +1297,7 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
         uint64_t threads = (uint64_t)(fp.slot_end - fp.slot_begin) << glog2;
         dim3 grid((unsigned)((threads + 255) / 256)), block(256);
 #define PT_CALL(C, A) \
-    hipLaunchKernelGGL((pt_render<MODE, C, A>), grid, block, 0, ctx->stream, sc, fp, accum, ctx->d_image, ctx->d_counters)
+    hipLaunchKernelGGL((pt_render<MODE, C, A>), grid, block, 0, ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p)
         PT_DISPATCH(ctx->count_enabled, scene_has_accel(sc), PT_CALL);
 #undef PT_CALL
     }
@@ -1317,7 +1317,8 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
     if (slots == 0) return RT_OK;
     int rc = ensure_slots(ctx, slots);
     if (rc) return rc;
-    uint32_t *live_count = ctx->d_live + ctx->slot_capacity + (size_t)LIVE_SEGMENTS * 256u;
+    const rt_context::Slots &ss = ctx->slots;
+    uint32_t *live_count = ss.live.p + ss.capacity + (size_t)LIVE_SEGMENTS * 256u;
     uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
     if (slots_per_launch == 0) slots_per_launch = 1;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
@@ -1328,14 +1329,14 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         uint32_t n = fp.slot_end - fp.slot_begin;
         HIP_TRY(ctx, hipMemsetAsync(live_count, 0, (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
-        fp.trees = ctx->d_trees;
-        fp.glass = ctx->d_glass;
+        fp.trees = ss.trees.p;
+        fp.glass = ss.glass.p;
         fp.tree_count = live_count + LIVE_TREE_COUNTER;
         // (and not for a handful of samples per call: tracing both continuations of a pixel costs more than the few samples
         // that would share them — C2 at 1 / 8 / 16 / 32 samples per call: 0.321 / 0.457 / 0.609 / 1.031 ms with trees,
         // 0.243 / 0.393 / 0.582 / 1.088 without)
         const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
-        fp.tree_cap = (tree_on && !ctx->count_enabled && ctx->d_trees && ctx->d_tree_work) ? (uint32_t)ctx->tree_capacity : 0u;
+        fp.tree_cap = (tree_on && !ctx->count_enabled) ? (uint32_t)ss.tree_capacity : 0u;   // (0 without the tree buffers)
         // workgroup b of pt_prefix appends to segment b mod LIVE_SEGMENTS: a segment holds at most seg_cap entries
         const uint32_t prefix_blocks = (n + 255) / 256;
         fp.seg_cap = ((prefix_blocks + LIVE_SEGMENTS - 1) / LIVE_SEGMENTS) * 256u;
@@ -1373,7 +1374,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         bool queue = ctx->sample_queue && count <= QUEUE_SLOTS;
         size_t lds_q = static_f4 * sizeof(float4) + PT_Q_BLOCK_WAVES * (size_t)queue_wave_lds_bytes(ppw, count);
 #define PT_CALL_PREFIX(C, A) \
-    hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ctx->d_recs, ctx->d_live, live_count, accum, ctx->d_counters)
+    hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
         bool accel_on = scene_has_accel(sc);
         PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
         if (fp.tree_cap) {
@@ -1384,15 +1385,15 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
             // the glass-first pixels in a list of their own, trees and a second launch of the sample kernel on a side
             // stream beside the main list's — a queue-kernel wave lives ~0.1 ms whatever the size of its launch.
             dim3 gridt(std::min<uint32_t>(768u, (2u * fp.tree_cap + 255u) / 256u));
-            const uint32_t q_cap = (uint32_t)ctx->tree_capacity;
-            TreeWork *q[2] = {ctx->d_tree_work, ctx->d_tree_work + ctx->tree_capacity};
+            const uint32_t q_cap = (uint32_t)ss.tree_capacity;
+            TreeWork *q[2] = {ss.tree_work.p, ss.tree_work.p + ss.tree_capacity};
             for (uint32_t level = 0; level < PT_TREE_LEVELS; level++) {
                 const TreeWork *in = level ? q[(level - 1u) & 1u] : nullptr;
                 const uint32_t *in_count = level ? fp.tree_count + level : nullptr;
                 TreeWork *out = q[level & 1u];
                 uint32_t *out_count = fp.tree_count + level + 1u;
-                if (accel_on) hipLaunchKernelGGL(pt_tree_pass<true>, gridt, block, 0, ctx->stream, sc, fp, ctx->d_recs, level, in, in_count, out, out_count, q_cap);
-                else hipLaunchKernelGGL(pt_tree_pass<false>, gridt, block, 0, ctx->stream, sc, fp, ctx->d_recs, level, in, in_count, out, out_count, q_cap);
+                if (accel_on) hipLaunchKernelGGL(pt_tree_pass<true>, gridt, block, 0, ctx->stream, sc, fp, ss.recs.p, level, in, in_count, out, out_count, q_cap);
+                else hipLaunchKernelGGL(pt_tree_pass<false>, gridt, block, 0, ctx->stream, sc, fp, ss.recs.p, level, in, in_count, out, out_count, q_cap);
             }
         }
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
@@ -1405,7 +1406,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
             dim3 gridq((units(ppw) + PT_Q_BLOCK_WAVES - 1) / PT_Q_BLOCK_WAVES);
             dim3 grid2((unsigned)((((uint64_t)units(1u) << glog2) + 255) / 256));
 #define PT_CALL_QUEUE_W(C, A, G, W) \
-    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), gridq, blockq, lds_q, st, sc, fl, l_recs, l_live, l_count, accum, ctx->d_counters, ppw)
+    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), gridq, blockq, lds_q, st, sc, fl, l_recs, l_live, l_count, accum, ctx->counters.p, ppw)
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
         if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
@@ -1413,7 +1414,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
     } while (0)
 #define PT_CALL_FIXED(C, A) \
-    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, st, sc, fl, l_recs, l_live, l_count, accum, ctx->d_counters)
+    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, st, sc, fl, l_recs, l_live, l_count, accum, ctx->counters.p)
             if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled && !PT_LDS_SPHERES) {
                 // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
                 uint32_t ppw_w = queue_pixels_per_wave(count, ctx->walk_jobs.n == 1 ? PT_W_WAVES : PT_W_WAVES_MULTI, static_f4, PT_W_BLOCK_WAVES);
@@ -1424,14 +1425,14 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
                     hipLaunchKernelGGL(pt_samples_w<false>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
                                        accum, ppw_w, ctx->walk_jobs.p, 1u
 #ifdef PT_WSTAT
-                                       , ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8
+                                       , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
 #endif
                                        );
                 else
                     hipLaunchKernelGGL(pt_samples_w<true>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
                                        accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
 #ifdef PT_WSTAT
-                                       , ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8
+                                       , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
 #endif
                                        );
             } else if (queue) PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_QUEUE);
@@ -1440,7 +1441,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
 #undef PT_CALL_QUEUE_W
 #undef PT_CALL_FIXED
         };
-        launch_samples(ctx->stream, ctx->d_recs, ctx->d_live, live_count, fp.seg_cap);
+        launch_samples(ctx->stream, ss.recs.p, ss.live.p, live_count, fp.seg_cap);
 #undef PT_CALL_PREFIX
     }
     HIP_TRY(ctx, hipGetLastError());

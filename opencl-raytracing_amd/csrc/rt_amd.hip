@@ -476,54 +476,17 @@ int fail(rt_context *ctx, int code, const char *fmt, ...) {
 
 namespace {
 
-void free_adaptive(rt_context *ctx) {
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_half) (void)hipFree(ctx->d_half);
-    if (ctx->d_block_active) (void)hipFree(ctx->d_block_active);
-    if (ctx->d_block_err) (void)hipFree(ctx->d_block_err);
-    if (ctx->d_adaptive_stats) (void)hipFree(ctx->d_adaptive_stats);
-    ctx->d_scratch = ctx->d_half = nullptr;
-    ctx->d_block_active = nullptr;
-    ctx->d_block_err = nullptr;
-    ctx->d_adaptive_stats = nullptr;
-    ctx->adaptive_block_capacity = 0;
-    ctx->adaptive_blocks = 0;
-}
-
-void free_denoise(rt_context *ctx) {
-    if (ctx->d_features) (void)hipFree(ctx->d_features);
-    if (ctx->d_dn[0]) (void)hipFree(ctx->d_dn[0]);
-    if (ctx->d_dn[1]) (void)hipFree(ctx->d_dn[1]);
-    if (ctx->d_denoised) (void)hipFree(ctx->d_denoised);
-    ctx->d_features = nullptr;
-    ctx->d_dn[0] = ctx->d_dn[1] = nullptr;
-    ctx->d_denoised = nullptr;
-    ctx->have_features = ctx->have_denoised = false;
-}
-
 int alloc_frame(rt_context *ctx, int w, int h) {
-    free_adaptive(ctx);
-    free_denoise(ctx);
-    if (ctx->d_image) (void)hipFree(ctx->d_image);
-    if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-    ctx->d_image = ctx->d_accum = nullptr;
-    if (ctx->d_recs) (void)hipFree(ctx->d_recs);
-    if (ctx->d_live) (void)hipFree(ctx->d_live);
-    if (ctx->d_trees) (void)hipFree(ctx->d_trees);
-    if (ctx->d_glass) (void)hipFree(ctx->d_glass);
-    if (ctx->d_tree_work) (void)hipFree(ctx->d_tree_work);
-    ctx->d_tree_work = nullptr;
-    ctx->d_recs = nullptr;
-    ctx->d_live = nullptr;
-    ctx->d_trees = nullptr;
-    ctx->d_glass = nullptr;
-    ctx->slot_capacity = 0;
-    ctx->tree_capacity = 0;
-    size_t bytes = (size_t)w * h * sizeof(float4);
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_image, bytes));
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_accum, bytes));
-    HIP_TRY(ctx, hipMemset(ctx->d_image, 0, bytes));
-    HIP_TRY(ctx, hipMemset(ctx->d_accum, 0, bytes));
+    // what was made for the old frame goes with it
+    ctx->slots = {};
+    ctx->adaptive = {};
+    ctx->features = {};
+    ctx->denoise = {};
+    const size_t px = (size_t)w * h;
+    HIP_TRY(ctx, ctx->image.alloc(px));
+    HIP_TRY(ctx, ctx->accum.alloc(px));
+    HIP_TRY(ctx, hipMemset(ctx->image.p, 0, px * sizeof(float4)));
+    HIP_TRY(ctx, hipMemset(ctx->accum.p, 0, px * sizeof(float4)));
     ctx->width = w;
     ctx->height = h;
     ctx->accum_count = 0;
@@ -538,6 +501,18 @@ int check_ready(rt_context *ctx, const float *cam) {
     if (ctx->scene_uses_textures && (ctx->tex_layers <= 0 || ctx->max_texture_id >= (uint32_t)ctx->tex_layers))
         return fail(ctx, RT_ERANGE, "scene has textured meshes (max texture id %u) but only %d texture layers are set",
                     ctx->max_texture_id, ctx->tex_layers);
+    return RT_OK;
+}
+
+// Copies the `need` bytes of device buffer `src` into the caller's `dst` of `bytes` bytes and waits for them: EINVAL
+// unless the sizes match, then ESTATE unless `src` is `ready` (written by a `producer` call since the frame was made).
+int read_back(rt_context *ctx, void *dst, size_t bytes, const void *src, size_t need, const char *what, bool ready = true,
+              const char *producer = nullptr) {
+    if (!dst || bytes != need) return fail(ctx, RT_EINVAL, "%s buffer must be %zu bytes", what, need);
+    if (!ready) return fail(ctx, RT_ESTATE, "no %s call since the frame was (re)allocated", producer);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 
@@ -634,9 +609,9 @@ int rt_create(int device, int width, int height, rt_context **out) {
     ctx->stream = ctx->own_stream;
     for (int i = 0; i < rt_context::EV_RING; i++)
         if (hipEventCreate(&ctx->ev[i][0]) != hipSuccess || hipEventCreate(&ctx->ev[i][1]) != hipSuccess || hipEventCreate(&ctx->ev[i][2]) != hipSuccess) { ctx->error = "hipEventCreate failed"; return bail(RT_EHIP); }
-    if (hipMalloc((void **)&ctx->d_counters, (COUNTER_REPLICAS * COUNTER_STRIDE + 32) * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(ctx->d_counters, 0, (COUNTER_REPLICAS * COUNTER_STRIDE + 32) * sizeof(unsigned long long)) != hipSuccess) { ctx->error = "counter allocation failed"; return bail(RT_EHIP); }
-    ctx->d_walk_overflow = reinterpret_cast<uint32_t *>(ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 24);
+    if (ctx->counters.alloc(COUNTER_REPLICAS * COUNTER_STRIDE + 32) != hipSuccess ||
+        hipMemset(ctx->counters.p, 0, (COUNTER_REPLICAS * COUNTER_STRIDE + 32) * sizeof(unsigned long long)) != hipSuccess) { ctx->error = "counter allocation failed"; return bail(RT_EHIP); }
+    ctx->d_walk_overflow = reinterpret_cast<uint32_t *>(ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 24);
 
     ctx->arith = RT_ARITH_IEEE;
     ctx->ks = kernel_set_a0();
@@ -651,31 +626,6 @@ void rt_destroy(rt_context *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-    ctx->materials.release(); ctx->spheres.release(); ctx->planes.release(); ctx->lenses.release();
-    ctx->vertices.release(); ctx->uvs.release(); ctx->indices.release(); ctx->meshes.release(); ctx->models.release();
-    ctx->table.release(); ctx->tex.release();
-    if (ctx->d_image) (void)hipFree(ctx->d_image);
-    if (ctx->d_accum) (void)hipFree(ctx->d_accum);
-    if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-    if (ctx->d_recs) (void)hipFree(ctx->d_recs);
-    if (ctx->d_live) (void)hipFree(ctx->d_live);
-    if (ctx->d_trees) (void)hipFree(ctx->d_trees);
-    if (ctx->d_glass) (void)hipFree(ctx->d_glass);
-    if (ctx->d_tree_work) (void)hipFree(ctx->d_tree_work);
-    free_adaptive(ctx);
-    free_denoise(ctx);
-    ctx->sph4.release();
-    ctx->faces.release();
-    ctx->mesh_face_base.release();
-    ctx->mbvh_nodes.release();
-    ctx->mbvh_faces.release();
-    ctx->mbvh_face_idx.release();
-    ctx->walk_jobs.release();
-    ctx->mesh_bvh_root.release();
-    ctx->bvh_nodes.release();
-    ctx->bvh_sph.release();
-    ctx->bvh_idx.release();
-    ctx->bvh_links.release();
     for (int i = 0; i < rt_context::EV_RING; i++)
         for (int k = 0; k < 3; k++)
             if (ctx->ev[i][k]) (void)hipEventDestroy(ctx->ev[i][k]);
@@ -932,7 +882,7 @@ int rt_render(rt_context *ctx, const float camera[12]) {
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->sample_counter = 0;  // src/raytracer.cpp:128
-    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->d_accum, nullptr)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // queue.finish(), src/raytracer.cpp:140
     return RT_OK;
 }
@@ -943,7 +893,7 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     if (ctx->sample_counter >= RT_MAX_SAMPLE) return fail(ctx, RT_EINVAL, "sample counter limit %u reached", RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->sample_counter++;  // src/raytracer.cpp:147
-    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->d_accum, nullptr)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -957,7 +907,7 @@ int rt_sample_counter(const rt_context *ctx, uint32_t *out) {
 int rt_clear(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_accum, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
     ctx->accum_count = 0;
     return RT_OK;
 }
@@ -974,9 +924,9 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
     // 18.4 ms where 512 take 10.2); the accumulator then is the sum of those launches' sums, on every path alike.
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->d_accum, nullptr)
+        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr)
                                  : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c),
-                                                          ctx->d_accum, nullptr);
+                                                          ctx->accum.p, nullptr);
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
@@ -986,7 +936,7 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
 
 static int resolve_into(rt_context *ctx, int linear_only) {
     uint32_t n = (uint32_t)ctx->width * ctx->height;
-    hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_accum, ctx->d_image, n,
+    hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->accum.p, ctx->image.p, n,
                        linear_only);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
@@ -1004,19 +954,20 @@ extern "C++" {
 namespace {
 
 int ensure_adaptive(rt_context *ctx, size_t blocks) {
-    if (ctx->d_scratch && blocks <= ctx->adaptive_block_capacity) return RT_OK;
-    free_adaptive(ctx);
+    rt_context::Adaptive &a = ctx->adaptive;
+    if (a.scratch.p && blocks <= a.block_capacity) return RT_OK;
+    a = {};
     const size_t px = (size_t)ctx->width * ctx->height;
-    hipError_t e = hipMalloc((void **)&ctx->d_scratch, px * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_half, px * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_block_active, blocks * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_block_err, blocks * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_adaptive_stats, PT_MERGE_REPLICAS * PT_MERGE_STRIDE * sizeof(unsigned long long));
+    hipError_t e = a.scratch.alloc(px);
+    if (e == hipSuccess) e = a.half.alloc(px);
+    if (e == hipSuccess) e = a.block_active.alloc(blocks);
+    if (e == hipSuccess) e = a.block_err.alloc(blocks);
+    if (e == hipSuccess) e = a.stats.alloc(PT_MERGE_REPLICAS * PT_MERGE_STRIDE);
     if (e != hipSuccess) {
-        free_adaptive(ctx);
+        a = {};
         return fail(ctx, RT_EHIP, "adaptive buffers: %s", hipGetErrorString(e));
     }
-    ctx->adaptive_block_capacity = blocks;
+    a.block_capacity = blocks;
     return RT_OK;
 }
 
@@ -1049,15 +1000,16 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     const uint32_t bx = ((uint32_t)ctx->width + p->block_w - 1) >> bwl, by = ((uint32_t)ctx->height + p->block_h - 1) >> bhl;
     const uint32_t blocks = bx * by;
     if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
-    ctx->adaptive_blocks = 0;
+    rt_context::Adaptive &a = ctx->adaptive;
+    a.blocks = 0;
     const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_accum, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_scratch, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_half, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_block_active, 0xFF, blocks * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_block_err, 0, blocks * sizeof(float), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.scratch.p, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.half.p, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.block_active.p, 0xFF, blocks * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.block_err.p, 0, blocks * sizeof(float), ctx->stream));
     ctx->accum_count = 0;
-    const BlockMask mask{ctx->d_block_active, (uint32_t)bwl, (uint32_t)bhl, bx};
+    const BlockMask mask{a.block_active.p, (uint32_t)bwl, (uint32_t)bhl, bx};
     MergeParams mp;
     mp.w = (uint32_t)ctx->width;
     mp.h = (uint32_t)ctx->height;
@@ -1076,19 +1028,18 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
         const uint32_t first = k * p->batch;
         const uint32_t c = std::min(p->batch, p->max_spp - first);
         rc = ctx->prefix_sharing
-                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), ctx->d_scratch, &mask)
-                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), ctx->d_scratch, &mask);
+                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), a.scratch.p, &mask)
+                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), a.scratch.p, &mask);
         if (rc != RT_OK) return rc;
         mp.round = k;
         mp.count = first + c;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_adaptive_stats, 0, st_bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(a.stats.p, 0, st_bytes, ctx->stream));
         hipLaunchKernelGGL(pt_adaptive_merge, dim3((blocks + PT_MERGE_WAVES - 1) / PT_MERGE_WAVES), dim3(64 * PT_MERGE_WAVES), 0,
-                           ctx->stream, mp, ctx->d_accum, ctx->d_half, ctx->d_scratch, ctx->d_block_active, ctx->d_block_err,
-                           ctx->d_adaptive_stats);
+                           ctx->stream, mp, ctx->accum.p, a.half.p, a.scratch.p, a.block_active.p, a.block_err.p, a.stats.p);
         HIP_TRY(ctx, hipGetLastError());
         rounds++;
         ctx->accum_count = first + c;
-        HIP_TRY(ctx, hipMemcpyAsync(st.data(), ctx->d_adaptive_stats, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(st.data(), a.stats.p, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         uint64_t still = 0;
         for (uint32_t r = 0; r < PT_MERGE_REPLICAS; r++) {
@@ -1100,7 +1051,7 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     }
     if ((rc = resolve_into(ctx, 0)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->adaptive_blocks = blocks;
+    a.blocks = blocks;
     out->rounds = rounds;
     out->pixel_samples = pixel_samples;
     out->blocks = blocks;
@@ -1114,7 +1065,7 @@ int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
     if (!counts || bytes != n * sizeof(uint32_t)) return fail(ctx, RT_EINVAL, "count buffer must be %zu bytes", n * sizeof(uint32_t));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<float4> h(n);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d_accum, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->accum.p, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n; i++) counts[i] = (uint32_t)h[i].w;
     return RT_OK;
@@ -1122,13 +1073,9 @@ int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
 
 int rt_read_block_error(rt_context *ctx, float *err, size_t bytes) {
     if (!ctx) return RT_EINVAL;
-    if (!ctx->adaptive_blocks) return fail(ctx, RT_ESTATE, "no rt_render_adaptive call since the frame was (re)allocated");
-    const size_t need = (size_t)ctx->adaptive_blocks * sizeof(float);
-    if (!err || bytes != need) return fail(ctx, RT_EINVAL, "block error buffer must be %zu bytes", need);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(err, ctx->d_block_err, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
+    const rt_context::Adaptive &a = ctx->adaptive;
+    if (!a.blocks) return fail(ctx, RT_ESTATE, "no rt_render_adaptive call since the frame was (re)allocated");
+    return read_back(ctx, err, bytes, a.block_err.p, a.blocks * sizeof(float), "block error");
 }
 
 // ---- feature buffers and denoiser ------------------------------------------------------------------------------------
@@ -1138,30 +1085,26 @@ int rt_render_features(rt_context *ctx, const float camera[12]) {
     if (rc) return rc;
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "features of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_features)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_features, (size_t)ctx->width * ctx->height * sizeof(rt_feature)));
+    rt_context::Features &f = ctx->features;
+    if (!f.records.p) HIP_TRY(ctx, f.records.alloc((size_t)ctx->width * ctx->height));
     const FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
     const DeviceScene sc = device_scene(ctx);
-    if ((rc = ctx->ks->launch_features(ctx, fp, sc, ctx->d_features)) != RT_OK) return rc;
-    ctx->have_features = true;
+    if ((rc = ctx->ks->launch_features(ctx, fp, sc, f.records.p)) != RT_OK) return rc;
+    f.ready = true;
     return RT_OK;
 }
 
 int rt_read_features(rt_context *ctx, rt_feature *out, size_t bytes) {
     if (!ctx) return RT_EINVAL;
-    const size_t need = (size_t)ctx->width * ctx->height * sizeof(rt_feature);
-    if (!out || bytes != need) return fail(ctx, RT_EINVAL, "feature buffer must be %zu bytes", need);
-    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_features, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
+    const rt_context::Features &f = ctx->features;
+    return read_back(ctx, out, bytes, f.records.p, (size_t)ctx->width * ctx->height * sizeof(rt_feature), "feature", f.ready,
+                     "rt_render_features");
 }
 
 int rt_device_features(rt_context *ctx, void **d_features) {
     if (!ctx || !d_features) return RT_EINVAL;
-    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
-    *d_features = ctx->d_features;
+    if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    *d_features = ctx->features.records.p;
     return RT_OK;
 }
 
@@ -1175,15 +1118,16 @@ int rt_denoise(rt_context *ctx, const rt_denoise_params *p) {
     for (float v : sig)
         if (!(v > 0.0f)) return fail(ctx, RT_EINVAL, "every sigma must be > 0 (+inf switches its term off)");
     if (p->flags & ~RT_DENOISE_SPLIT_OBJECTS) return fail(ctx, RT_EINVAL, "unknown denoise flags 0x%x", p->flags);
-    if (!ctx->have_features) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
-    if (!ctx->d_denoised) {
-        hipError_t e = hipMalloc((void **)&ctx->d_dn[0], bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_dn[1], bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_denoised, bytes);
+    rt_context::Denoise &d = ctx->denoise;
+    if (!d.out.p) {
+        const size_t px = (size_t)ctx->width * ctx->height;
+        hipError_t e = d.pingpong[0].alloc(px);
+        if (e == hipSuccess) e = d.pingpong[1].alloc(px);
+        if (e == hipSuccess) e = d.out.alloc(px);
         if (e != hipSuccess) {
-            free_denoise(ctx);
+            d = {};
             return fail(ctx, RT_EHIP, "denoise buffers: %s", hipGetErrorString(e));
         }
     }
@@ -1212,32 +1156,27 @@ int rt_denoise(rt_context *ctx, const rt_denoise_params *p) {
         ds.split = (p->flags & RT_DENOISE_SPLIT_OBJECTS) ? 1u : 0u;
         ds.first = i == 0;
         ds.last = i + 1 == p->iterations;
-        const float4 *src = i == 0 ? ctx->d_accum : ctx->d_dn[(i - 1) & 1u];
-        float4 *dst = ds.last ? ctx->d_denoised : ctx->d_dn[i & 1u];
+        const float4 *src = i == 0 ? ctx->accum.p : d.pingpong[(i - 1) & 1u].p;
+        float4 *dst = ds.last ? d.out.p : d.pingpong[i & 1u].p;
         const uint32_t grid = (ds.groups + PT_DN_XCDS - 1u) / PT_DN_XCDS * PT_DN_XCDS;
         hipLaunchKernelGGL(pt_atrous, dim3(grid), dim3(256), 0, ctx->stream, ds, src,
-                           reinterpret_cast<const float4 *>(ctx->d_features), dst);
+                           reinterpret_cast<const float4 *>(ctx->features.records.p), dst);
         HIP_TRY(ctx, hipGetLastError());
     }
-    ctx->have_denoised = true;
+    d.ready = true;
     return RT_OK;
 }
 
 int rt_read_denoised(rt_context *ctx, float *rgba, size_t bytes) {
     if (!ctx) return RT_EINVAL;
-    const size_t need = (size_t)ctx->width * ctx->height * sizeof(float4);
-    if (!rgba || bytes != need) return fail(ctx, RT_EINVAL, "image buffer must be %zu bytes", need);
-    if (!ctx->have_denoised) return fail(ctx, RT_ESTATE, "no rt_denoise call since the frame was (re)allocated");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(rgba, ctx->d_denoised, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
+    const rt_context::Denoise &d = ctx->denoise;
+    return read_back(ctx, rgba, bytes, d.out.p, (size_t)ctx->width * ctx->height * sizeof(float4), "image", d.ready, "rt_denoise");
 }
 
 int rt_device_denoised(rt_context *ctx, void **d_rgba) {
     if (!ctx || !d_rgba) return RT_EINVAL;
-    if (!ctx->have_denoised) return fail(ctx, RT_ESTATE, "no rt_denoise call since the frame was (re)allocated");
-    *d_rgba = ctx->d_denoised;
+    if (!ctx->denoise.ready) return fail(ctx, RT_ESTATE, "no rt_denoise call since the frame was (re)allocated");
+    *d_rgba = ctx->denoise.out.p;
     return RT_OK;
 }
 
@@ -1258,62 +1197,48 @@ int rt_trace_samples(rt_context *ctx, const float camera[12], const uint32_t *x,
         if (x[i] >= (uint32_t)ctx->width || y[i] >= (uint32_t)ctx->height || sample[i] > RT_MAX_SAMPLE)
             return fail(ctx, RT_EINVAL, "probe %zu (%u,%u,%u) outside the frame / sample range", i, x[i], y[i], sample[i]);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t *d_in = nullptr;
-    float *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_in, 3 * n * sizeof(uint32_t)));
-    if (hipMalloc((void **)&d_out, 3 * n * sizeof(float)) != hipSuccess) { (void)hipFree(d_in); return fail(ctx, RT_EHIP, "hipMalloc failed"); }
-    hipError_t e = hipMemcpyAsync(d_in, x, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in + n, y, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in + 2 * n, sample, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
-        DeviceScene sc = device_scene(ctx);
-        if (ctx->ks->launch_probe(ctx, fp, sc, d_in, (uint32_t)n, d_out) != RT_OK) e = hipErrorLaunchFailure;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, 3 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(ctx, RT_EHIP, "probe: %s", hipGetErrorString(e));
+    DevBuf<uint32_t> d_in;
+    DevBuf<float> d_out;
+    HIP_TRY(ctx, d_in.alloc(3 * n));
+    HIP_TRY(ctx, d_out.alloc(3 * n));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.p, x, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.p + n, y, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.p + 2 * n, sample, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    const FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
+    if ((rc = ctx->ks->launch_probe(ctx, fp, device_scene(ctx), d_in.p, (uint32_t)n, d_out.p)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, d_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 
 int rt_read_image(rt_context *ctx, float *rgba, size_t bytes) {
     if (!ctx) return RT_EINVAL;
-    size_t need = (size_t)ctx->width * ctx->height * sizeof(float4);
-    if (!rgba || bytes != need) return fail(ctx, RT_EINVAL, "image buffer must be %zu bytes", need);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpyAsync(rgba, ctx->d_image, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RT_OK;
+    return read_back(ctx, rgba, bytes, ctx->image.p, (size_t)ctx->width * ctx->height * sizeof(float4), "image");
 }
 
 int rt_read_linear(rt_context *ctx, float *rgba, size_t bytes) {
     if (!ctx) return RT_EINVAL;
-    size_t need = (size_t)ctx->width * ctx->height * sizeof(float4);
-    if (!rgba || bytes != need) return fail(ctx, RT_EINVAL, "image buffer must be %zu bytes", need);
+    const size_t n = (size_t)ctx->width * ctx->height;
+    if (!rgba || bytes != n * sizeof(float4)) return fail(ctx, RT_EINVAL, "image buffer must be %zu bytes", n * sizeof(float4));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float4 *tmp = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&tmp, need));
-    uint32_t n = (uint32_t)ctx->width * ctx->height;
-    hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_accum, tmp, n, 1);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(rgba, tmp, need, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(ctx, RT_EHIP, "read_linear: %s", hipGetErrorString(e));
+    DevBuf<float4> tmp;
+    HIP_TRY(ctx, tmp.alloc(n));
+    hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->accum.p, tmp.p, (uint32_t)n, 1);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(rgba, tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 
 int rt_device_image(rt_context *ctx, void **d_rgba) {
     if (!ctx || !d_rgba) return RT_EINVAL;
-    *d_rgba = ctx->d_image;
+    *d_rgba = ctx->image.p;
     return RT_OK;
 }
 
 int rt_device_accum(rt_context *ctx, void **d_rgba) {
     if (!ctx || !d_rgba) return RT_EINVAL;
-    *d_rgba = ctx->d_accum;
+    *d_rgba = ctx->accum.p;
     return RT_OK;
 }
 
@@ -1601,19 +1526,16 @@ int rt_debug_check_accel(const rt_scene_desc *d, uint64_t stats[8], char *err, s
 
 extern "C++" {
 namespace {
-// upload `bytes` of input, run `launch(d_in, d_out)`, download `out_bytes`
+// upload `bytes` of input, run `launch(d_in, d_out)` (an RT_* code), download `out_bytes`
 template <class F>
 int debug_roundtrip(rt_context *ctx, const void *in, size_t bytes, void *out, size_t out_bytes, F launch) {
-    void *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_in, bytes ? bytes : 16));
-    if (hipMalloc(&d_out, out_bytes ? out_bytes : 16) != hipSuccess) { (void)hipFree(d_in); return fail(ctx, RT_EHIP, "hipMalloc failed"); }
-    hipError_t e = hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) { launch(d_in, d_out); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(ctx, RT_EHIP, "debug probe: %s", hipGetErrorString(e));
+    DevBuf<uint8_t> d_in, d_out;
+    HIP_TRY(ctx, d_in.alloc(bytes ? bytes : 16));
+    HIP_TRY(ctx, d_out.alloc(out_bytes ? out_bytes : 16));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = launch(d_in.p, d_out.p)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 }  // namespace
@@ -1650,7 +1572,7 @@ int rt_debug_hit(rt_context *ctx, int kind, const float *rays, const uint32_t *p
     return debug_roundtrip(ctx, in.data(), in.size() * 4, out12, 12 * n * sizeof(float), [&](void *d_in, void *d_out) {
         const float *d_rays = (const float *)d_in;
         const uint32_t *d_prim = (const uint32_t *)d_in + 6 * n, *d_face = d_prim + n;
-        (void)ctx->ks->launch_debug_hit(ctx, sc, kind, d_rays, d_prim, d_face, (uint32_t)n, (float *)d_out);
+        return ctx->ks->launch_debug_hit(ctx, sc, kind, d_rays, d_prim, d_face, (uint32_t)n, (float *)d_out);
     });
 }
 
@@ -1669,7 +1591,7 @@ int rt_debug_material(rt_context *ctx, int routine, const float *in16, size_t n,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DeviceScene sc = device_scene(ctx);
     return debug_roundtrip(ctx, in16, 16 * n * sizeof(float), out9, 9 * n * sizeof(float), [&](void *d_in, void *d_out) {
-        (void)ctx->ks->launch_debug_material(ctx, sc, routine, (const float *)d_in, (uint32_t)n, (float *)d_out);
+        return ctx->ks->launch_debug_material(ctx, sc, routine, (const float *)d_in, (uint32_t)n, (float *)d_out);
     });
 }
 
@@ -1678,7 +1600,7 @@ int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6) {
     if (n == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return debug_roundtrip(ctx, in4, 4 * n * sizeof(float), out6, 6 * n * sizeof(float), [&](void *d_in, void *d_out) {
-        (void)ctx->ks->launch_debug_div3(ctx, (const float *)d_in, (uint32_t)n, (float *)d_out);
+        return ctx->ks->launch_debug_div3(ctx, (const float *)d_in, (uint32_t)n, (float *)d_out);
     });
 }
 
@@ -1698,7 +1620,7 @@ int rt_pack_accum(rt_context *ctx, void *d_packed, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float cam0[12] = {0};
     FrameParams fp = frame_params(ctx, cam0, 0, 0, 0);
-    hipLaunchKernelGGL(pt_pack, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fp, ctx->d_accum, (float4 *)d_packed, n);
+    hipLaunchKernelGGL(pt_pack, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fp, ctx->accum.p, (float4 *)d_packed, n);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1713,7 +1635,7 @@ int rt_unpack_accum(rt_context *ctx, const void *d_packed, size_t bytes, int src
     float cam0[12] = {0};
     FrameParams fp = frame_params(ctx, cam0, 0, 0, 0, src_rank, world);  // the SENDER's shard
     if (fp.slot_end)
-        hipLaunchKernelGGL(pt_unpack, dim3((fp.slot_end + 255) / 256), dim3(256), 0, ctx->stream, fp, (const float4 *)d_packed, ctx->d_accum);
+        hipLaunchKernelGGL(pt_unpack, dim3((fp.slot_end + 255) / 256), dim3(256), 0, ctx->stream, fp, (const float4 *)d_packed, ctx->accum.p);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1755,7 +1677,7 @@ int rt_set_option(rt_context *ctx, int option, int value) {
 int rt_reset_counters(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, COUNTER_REPLICAS * COUNTER_STRIDE * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, COUNTER_REPLICAS * COUNTER_STRIDE * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_walk_overflow, 0, sizeof(uint32_t), ctx->stream));
     return RT_OK;
 }
@@ -1764,7 +1686,7 @@ int rt_get_counters(rt_context *ctx, rt_counters *out) {
     if (!ctx || !out) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h(COUNTER_REPLICAS * COUNTER_STRIDE);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->counters.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t *o = (uint64_t *)out;
     for (int i = 0; i < 14; i++) {
@@ -1778,7 +1700,7 @@ int rt_get_debug_counters(rt_context *ctx, uint64_t out[2]) {
     if (!ctx || !out) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h(COUNTER_REPLICAS * COUNTER_STRIDE);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->d_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->counters.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     out[0] = out[1] = 0;
     for (int r = 0; r < COUNTER_REPLICAS; r++) {
@@ -1788,18 +1710,18 @@ int rt_get_debug_counters(rt_context *ctx, uint64_t out[2]) {
 #ifdef PT_WSTAT
     {   // diagnostic build: lane census of pt_samples_w (tools/wstat.py)
         unsigned long long v[12];
-        if (hipMemcpy(v, ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8, sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(v, ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8, sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
             const char *names[12] = {"outer iterations", "active lanes", "phase-0 lanes", "phase-1 lanes", "phase-2 lanes", "walk slices",
                                      "walk steps", "node-test lanes", "(unused)", "leaf phases", "leaf lanes", "finished (idle) lanes"};
             for (int k = 0; k < 12; k++) fprintf(stderr, "[wstat] %-24s %llu\n", names[k], v[k]);
-            (void)hipMemset(ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE + 8, 0, sizeof v);
+            (void)hipMemset(ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8, 0, sizeof v);
         }
     }
 #endif
 #if PT_STAMPS
     {   // diagnostic build: print the s_memtime shares of pt_samples_q's sections
         unsigned long long st[8];
-        if (hipMemcpy(st, ctx->d_counters + COUNTER_REPLICAS * COUNTER_STRIDE, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(st, ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
             const char *names[6] = {"refill", "scatter", "hit:spheres", "hit:planes/lenses/models", "hit:rebuild+material", "loop"};
             double tot = 0;
             for (int k = 0; k < 6; k++) tot += (double)st[k];
@@ -1823,7 +1745,7 @@ int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float 
     if (n == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return debug_roundtrip(ctx, in8, 8 * n * sizeof(float), out4, 4 * n * sizeof(float), [&](void *d_in, void *d_out) {
-        (void)ctx->ks->launch_debug_builtin(ctx, op, (const float *)d_in, (uint32_t)n, (float *)d_out);
+        return ctx->ks->launch_debug_builtin(ctx, op, (const float *)d_in, (uint32_t)n, (float *)d_out);
     });
 }
 

@@ -8,14 +8,35 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pt_types.hpp"
 
+// Owns one device array: freed by release(), by reassignment and on destruction.  A group of them is reset by
+// assigning {} to it.
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {   // (the old array dies with `o`: at once for `= {}`)
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // exactly `count` uninitialised elements
+    hipError_t alloc(size_t count) {
+        release();
+        hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; return e; }
+        n = count;
+        return e;
+    }
     hipError_t upload(const T *src, size_t count) {
         release();
         size_t alloc = count ? count : 1;  // empty arrays become 1-element dummies (src/scene.cpp:41-44)
@@ -90,17 +111,22 @@ struct rt_context {
     bool scene_uses_textures = false;
     uint32_t max_texture_id = 0;
 
-    float4 *d_image = nullptr;
-    float4 *d_accum = nullptr;
-    unsigned long long *d_counters = nullptr;
-    uint32_t *d_walk_overflow = nullptr;   // one word of sticky PT_OVF_* bits
-    pt::PixelRec *d_recs = nullptr;      // per owned pixel slot: shared path prefix (fused path)
-    uint32_t *d_live = nullptr;      // slots that need per-sample work + [capacity] = their count
-    size_t slot_capacity = 0;
-    pt::PixelTree *d_trees = nullptr;   // shared decision trees of dielectric-first pixels (pt_types.hpp), tree_capacity of them
-    uint32_t *d_glass = nullptr;        // live-list positions of those pixels (pt_prefix → pt_tree_pass)
-    pt::TreeWork *d_tree_work = nullptr;  // glass vertices waiting for the next level: two queues of tree_capacity entries
-    size_t tree_capacity = 0;
+    // frame: reallocated and zeroed by alloc_frame
+    DevBuf<float4> image, accum;
+    // counter block (COUNTER_REPLICAS rows, then 32 words): made once by rt_create, dies with the context
+    DevBuf<unsigned long long> counters;
+    uint32_t *d_walk_overflow = nullptr;   // one word of sticky PT_OVF_* bits, inside `counters`
+    // fused-path slot buffers, made whole by ensure_slots when the shard outgrows them: reset by alloc_frame
+    struct Slots {
+        DevBuf<pt::PixelRec> recs;      // per owned pixel slot: shared path prefix (fused path)
+        DevBuf<uint32_t> live;          // slots that need per-sample work + [capacity] = their count
+        size_t capacity = 0;
+        // shared decision trees of dielectric-first pixels (pt_types.hpp): all three or none (tree_capacity 0)
+        DevBuf<pt::PixelTree> trees;    // tree_capacity of them
+        DevBuf<uint32_t> glass;         // live-list positions of those pixels (pt_prefix → pt_tree_pass)
+        DevBuf<pt::TreeWork> tree_work; // glass vertices waiting for the next level: two queues of tree_capacity entries
+        size_t tree_capacity = 0;
+    } slots;
     bool wave_fill = true;              // RT_OPT_WAVE_FILL
     int prefix_tree = 1;                // RT_OPT_PREFIX_TREE: 0 off, 1 from PT_TREE_MIN_SAMPLES samples per call on, 2 always
     bool prefix_sharing = true;
@@ -112,20 +138,28 @@ struct rt_context {
     uint32_t sample_counter = 0;
     bool count_enabled = false;
 
-    // adaptive sampling (rt_render_adaptive), allocated on its first call
-    float4 *d_scratch = nullptr;        // W x H: the current round's sums (zero outside it)
-    float4 *d_half = nullptr;           // W x H: the sums of the even rounds
-    uint32_t *d_block_active = nullptr; // per decision block: traced by the next round
-    float *d_block_err = nullptr;       // per decision block: its error after the last round it was traced in
-    unsigned long long *d_adaptive_stats = nullptr;   // pt_adaptive_merge's counter rows (rt_amd.hip)
-    size_t adaptive_block_capacity = 0;
-    uint32_t adaptive_blocks = 0;       // blocks of the last completed rt_render_adaptive call (0: none since the last resize)
-
-    // feature buffers and denoiser (rt_render_features, rt_denoise), allocated on their first calls
-    rt_feature *d_features = nullptr;   // W x H first-hit records
-    float4 *d_dn[2] = {nullptr, nullptr};   // W x H: the à-trous iterations' ping-pong buffers (linear colour, count)
-    float4 *d_denoised = nullptr;       // W x H: the last rt_denoise result, gamma RGBA
-    bool have_features = false, have_denoised = false;   // made since the frame was (re)allocated
+    // adaptive sampling (rt_render_adaptive), made whole on its first call and when the blocks outgrow them: reset by
+    // alloc_frame and by a failed allocation
+    struct Adaptive {
+        DevBuf<float4> scratch;         // W x H: the current round's sums (zero outside it)
+        DevBuf<float4> half;            // W x H: the sums of the even rounds
+        DevBuf<uint32_t> block_active;  // per decision block: traced by the next round
+        DevBuf<float> block_err;        // per decision block: its error after the last round it was traced in
+        DevBuf<unsigned long long> stats;   // pt_adaptive_merge's counter rows (rt_amd.hip)
+        size_t block_capacity = 0;
+        uint32_t blocks = 0;            // blocks of the last completed rt_render_adaptive call (0: none)
+    } adaptive;
+    // first-hit features (rt_render_features), allocated on its first call: reset by alloc_frame
+    struct Features {
+        DevBuf<rt_feature> records;     // W x H
+        bool ready = false;             // written since the frame was (re)allocated
+    } features;
+    // denoiser (rt_denoise), allocated on its first call: reset by alloc_frame and by a failed allocation
+    struct Denoise {
+        DevBuf<float4> pingpong[2];     // W x H: the à-trous iterations' ping-pong buffers (linear colour, count)
+        DevBuf<float4> out;             // W x H: the last rt_denoise result, gamma RGBA
+        bool ready = false;             // written since the frame was (re)allocated
+    } denoise;
 
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
@@ -241,34 +275,24 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
 inline bool scene_has_accel(const DeviceScene &sc) { return sc.bvh_node_count != 0 || sc.mesh_bvh_root != nullptr; }
 
 inline int ensure_slots(rt_context *ctx, size_t slots) {
-    if (slots <= ctx->slot_capacity) return RT_OK;
-    if (ctx->d_recs) (void)hipFree(ctx->d_recs);
-    if (ctx->d_live) (void)hipFree(ctx->d_live);
-    if (ctx->d_trees) (void)hipFree(ctx->d_trees);
-    if (ctx->d_glass) (void)hipFree(ctx->d_glass);
-    if (ctx->d_tree_work) (void)hipFree(ctx->d_tree_work);
-    ctx->d_tree_work = nullptr;
-    ctx->d_recs = nullptr;
-    ctx->d_live = nullptr;
-    ctx->d_trees = nullptr;
-    ctx->d_glass = nullptr;
-    ctx->slot_capacity = 0;
-    ctx->tree_capacity = 0;
+    rt_context::Slots &s = ctx->slots;
+    if (slots <= s.capacity) return RT_OK;
+    s = {};
     // segmented live list: LIVE_SEGMENTS segments of whole workgroups' worth of entries, then the segment counters
     size_t entries = slots + (size_t)LIVE_SEGMENTS * 256u;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_recs, entries * sizeof(PixelRec)));
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_live, (entries + (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE) * sizeof(uint32_t)));
+    HIP_TRY(ctx, s.recs.alloc(entries));
+    HIP_TRY(ctx, s.live.alloc(entries + (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE));
     // decision trees for a quarter of the slots (a frame with more dielectric-first pixels keeps plain records for the rest)
-    ctx->tree_capacity = slots / 4 + 256;
-    if (hipMalloc((void **)&ctx->d_trees, ctx->tree_capacity * sizeof(PixelTree)) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_glass, ctx->tree_capacity * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_tree_work, 2 * ctx->tree_capacity * sizeof(TreeWork)) != hipSuccess) {
+    const size_t trees = slots / 4 + 256;
+    if (s.trees.alloc(trees) == hipSuccess && s.glass.alloc(trees) == hipSuccess && s.tree_work.alloc(2 * trees) == hipSuccess) {
+        s.tree_capacity = trees;
+    } else {   // not fatal: the frame renders without shared trees
         (void)hipGetLastError();
-        if (ctx->d_trees) (void)hipFree(ctx->d_trees);
-        ctx->d_trees = nullptr;       // not fatal: the frame renders without shared trees
-        ctx->tree_capacity = 0;
+        s.trees.release();
+        s.glass.release();
+        s.tree_work.release();
     }
-    ctx->slot_capacity = slots;
+    s.capacity = slots;
     return RT_OK;
 }
 
