@@ -1060,6 +1060,51 @@ PT_DEV PixelRec tree_branch(const Ctx &c, const PixelRec &rec, uint32_t which) {
     return trace_branch<false, ACCEL>(c, r, out, ((__float_as_uint(rec.p_kind.w) >> 8) & 0xFFu) + 1u, PT_TREE_STRETCH);
 }
 
+// One work-item of the tree builder (pt_prefix's tree phase): continuation `which` of the glass vertex that is to become
+// node `heap` of tree T (index `tree`).  Both work-items of a vertex settle it; the one with which = 0 writes the
+// decision node (or, when there is no decision after all, the leaf — at the root: the pixel's own record `root`, which
+// the samples then simply continue from).  A decision node at the root turns the pixel's record into REC_TREE + tree
+// index.  The continuation becomes a leaf, or — when it ends at another glass vertex and `last` is false — waits in
+// waits[2·heap + which − 2] to become that node of the next level (its parent's child link is written when it is
+// settled).  A waiting vertex is read from waits[heap − 2], the root from `root`.  Returns whether it waits.
+template <bool ACCEL>
+PT_DEV bool tree_step(const Ctx &c, PixelTree *T, uint32_t tree, uint32_t heap, uint32_t which, bool last, PixelRec *root,
+                      PixelRec *waits) {
+    PixelRec rec = heap == 1u ? *root : waits[heap - 2u];
+    float prob = 0.0f;
+    if (!tree_settle<ACCEL>(c, rec, prob)) {
+        if (which == 0u) {
+            if (heap == 1u) *root = rec;   // the pixel needs no tree: the prefix simply went on
+            else {
+                const uint32_t li = atomicAdd(&T->dec[0].hsh, 1u);
+                T->leaf[li] = rec;
+                T->dec[heap >> 1].child[heap & 1u] = (uint16_t)(0x8000u | li);
+            }
+        }
+        return false;
+    }
+    if (which == 0u) {
+        T->dec[heap].hsh = dir_hash(xyz(rec.d));
+        T->dec[heap].prob = prob;
+        T->dec[heap].depth = (__float_as_uint(rec.p_kind.w) >> 8) & 0xFFu;
+        if (heap == 1u) {
+            root->p_kind.w = __uint_as_float((uint32_t)REC_TREE);
+            root->col.w = __uint_as_float(tree);
+        } else {
+            T->dec[heap >> 1].child[heap & 1u] = (uint16_t)heap;
+        }
+    }
+    rec = tree_branch<ACCEL>(c, rec, which);
+    if (!last && is_glass_vertex(rec)) {
+        waits[2u * heap + which - 2u] = rec;
+        return true;
+    }
+    const uint32_t li = atomicAdd(&T->dec[0].hsh, 1u);
+    T->leaf[li] = rec;
+    T->dec[heap].child[which] = (uint16_t)(0x8000u | li);
+    return false;
+}
+
 // The leaf a sample continues from: walk the decisions with the sample's own table entries (random(), :120-125:
 // float 300000 + (hash + s_seed·2683 + gid0·3931 + gid1) mod 100000, s_seed = bounce index + sample; bu = the
 // sample's part of that sum, rnd_base_u).  → pointer to the leaf's five float4.

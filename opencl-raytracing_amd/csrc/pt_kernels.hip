@@ -151,8 +151,13 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
 // glass chains) is finished here: all its samples are equal, and their sum in the
 // order of stage 2 (k sequential adds per lane, then log2(g) doublings) is
 // computed in closed form.  Other pixels are appended to the live list.
-template <bool COUNT, bool ACCEL>
-__global__ __launch_bounds__(256) void pt_prefix(DeviceScene sc, FrameParams fp, PixelRec *__restrict__ recs,
+// TREES: the instantiation that also builds the shared decision trees (RT_OPT_PREFIX_TREE; never in counting builds).
+// The tree phase needs some 120 VGPRs against the prefix's 86: a frame without trees keeps the leaner kernel.
+#ifndef PT_PREFIX_WAVES
+#define PT_PREFIX_WAVES 4   // waves per SIMD pt_prefix is compiled for (profiles/r05_experiments.md)
+#endif
+template <bool COUNT, bool ACCEL, bool TREES = false>
+__global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(DeviceScene sc, FrameParams fp, PixelRec *__restrict__ recs,
                                                  uint32_t *__restrict__ live, uint32_t *__restrict__ live_count,
                                                  float4 *__restrict__ accum, unsigned long long *counters) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
@@ -225,13 +230,29 @@ __global__ __launch_bounds__(256) void pt_prefix(DeviceScene sc, FrameParams fp,
     // (bits 8..15: the vertex's bounce index = mirror / glass bounces before it; a final colour's: hits on its way)
     const bool lane_heavy = valid && (((kb >> 8) & 0xFFu) >= 2u || is_glass_vertex(rec));
     const bool wg_heavy = __syncthreads_or(lane_heavy ? 1 : 0) != 0;
-    __shared__ uint32_t s_wave_n[4], s_base;
+    // Pixels whose first random event is a dielectric surface get a shared decision tree (the tree phase below): their
+    // two continuations through the glass are traced once per pixel there instead of once per sample.  Their tree
+    // indices are reserved with the same one atomic per workgroup.
+    const bool glass = TREES && is_live && is_glass_vertex(rec);
+    __shared__ uint32_t s_wave_n[4], s_wave_g[4], s_base, s_tree0;
+    __shared__ uint32_t s_tpos[256];                                    // live position of the workgroup's tree j
+    __shared__ uint32_t s_wn[PT_TREE_LEVELS];                           // [L]: glass vertices waiting for level L
+    __shared__ uint16_t s_wait[PT_TREE_LEVELS > 2 ? 2 : 1][256u << (PT_TREE_LEVELS - 1)];   // (heap << 8 | j) of those, by level parity
     unsigned long long m = __ballot(is_live);
-    if (lane == 0) s_wave_n[wv] = (uint32_t)__popcll(m);
+    const unsigned long long gm = __ballot(glass);
+    if (lane == 0) {
+        s_wave_n[wv] = (uint32_t)__popcll(m);
+        if (TREES) s_wave_g[wv] = (uint32_t)__popcll(gm);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t total = s_wave_n[0] + s_wave_n[1] + s_wave_n[2] + s_wave_n[3];
         s_base = total ? atomicAdd(&live_count[wg_heavy ? LIVE_HEAVY_COUNTER : 0u], total) : 0u;
+        if (TREES) {
+            const uint32_t trees = s_wave_g[0] + s_wave_g[1] + s_wave_g[2] + s_wave_g[3];
+            s_tree0 = trees ? atomicAdd(fp.tree_count, trees) : 0u;
+            for (uint32_t l = 0; l < PT_TREE_LEVELS; l++) s_wn[l] = 0u;
+        }
     }
     __syncthreads();
     uint32_t pos = 0u;
@@ -243,108 +264,39 @@ __global__ __launch_bounds__(256) void pt_prefix(DeviceScene sc, FrameParams fp,
         live[pos] = slot;
         recs[pos] = rec;
     }
-    const uint32_t glass_pos = pos;
-    // Pixels whose first random event is a dielectric surface are listed for pt_tree_pass (one atomic per wave): their
-    // two continuations through the glass are traced once per pixel there instead of once per sample.
-    {
-        const bool glass = !COUNT && is_live && fp.tree_cap != 0u && is_glass_vertex(rec);
-        const unsigned long long gm = __ballot(glass);
-        if (gm) {
-            uint32_t base = 0u;
-            const int leader = __builtin_ctzll(gm);
-            if ((int)lane == leader) base = atomicAdd(fp.tree_count, (uint32_t)__popcll(gm));
-            base = (uint32_t)__shfl((int)base, leader);
-            const uint32_t gi = base + lanes_below(gm);
-            if (glass && gi < fp.tree_cap) {
-                fp.glass[gi] = glass_pos;
-                fp.trees[gi].dec[0].hsh = 0u;   // the tree's leaf counter
-            }
+    flush_counters<COUNT>(cn, counters, fp.count);  // the prefix stands for `count` samples' worth of work
+    if (!TREES) return;
+    // Tree phase (pt_types.hpp PixelTree): the trees of the workgroup's glass-first pixels, level by level, two
+    // work-items per waiting glass vertex (one per continuation: refracted / reflected ray), so that every work-item
+    // traces ONE stretch of path.  Tree j of the workgroup is tree s_tree0 + j; a pixel beyond the capacity gets none
+    // and continues per sample.  These work-items run in the gaps of the other workgroups' prefix waves: as launches
+    // of their own (until round 5), two levels cost 0.09 ms of a 1.43 ms C2 step, each lasting as long as its longest
+    // stretch of path with a few thousand waves in flight.
+    const uint32_t tree0 = s_tree0;
+    const uint32_t nt = tree0 < fp.tree_cap ? min(s_wave_g[0] + s_wave_g[1] + s_wave_g[2] + s_wave_g[3], fp.tree_cap - tree0) : 0u;
+    if (nt == 0u) return;   // (workgroup-uniform)
+    if (glass) {
+        uint32_t before = 0;
+        for (uint32_t k = 0; k < wv; k++) before += s_wave_g[k];
+        const uint32_t j = before + lanes_below(gm);
+        if (j < nt) {
+            s_tpos[j] = pos;
+            fp.trees[tree0 + j].dec[0].hsh = 0u;   // the tree's leaf counter
         }
     }
-    flush_counters<COUNT>(cn, counters, fp.count);  // the prefix stands for `count` samples' worth of work
-}
-
-// Fused path, stage 1b: the shared decision trees (pt_types.hpp PixelTree) of the pixels pt_prefix listed, one LEVEL per
-// launch.  Two work-items per waiting glass vertex — one per continuation (refracted / reflected ray) — so that every
-// work-item traces ONE stretch of path (grid-stride: the work's length is only known on the device).  Level 0 takes
-// the listed pixels' own records (the root, heap node 1) and rewrites them (REC_TREE + tree index; or the one record
-// every sample continues from, when the glass reflects totally); a continuation that ends at another glass vertex
-// waits in `out` for the next level, below the last level it becomes a leaf the samples continue from on their own.
-template <bool ACCEL>
-__global__ __launch_bounds__(256) void pt_tree_pass(DeviceScene sc, FrameParams fp, PixelRec *__restrict__ recs, uint32_t level,
-                                                   const TreeWork *__restrict__ in, const uint32_t *__restrict__ in_count,
-                                                   TreeWork *__restrict__ out, uint32_t *__restrict__ out_count, uint32_t q_cap) {
-    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
-    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
-    c.lwin = staged_winners(sc, s_mat);
-    c.lpln = staged_planes(sc, s_mat);
-    const uint32_t n = level == 0u ? min(*fp.tree_count, fp.tree_cap) : min(*in_count, q_cap);
-    const uint32_t lane = threadIdx.x & 63u;
-    // (wave-uniform loop: the appends to the next level's queue are one atomic per WAVE — one per work-item made a
-    // hundred thousand atomics queue on a single address, 0.2 ms of a 1.9 ms frame)
-    for (uint32_t t0 = blockIdx.x * 256u + (threadIdx.x & ~63u); t0 < 2u * n; t0 += gridDim.x * 256u) {
-        const uint32_t t = t0 + lane;
-        const bool live = t < 2u * n;
-        const uint32_t item = live ? t >> 1 : 0u, which = t & 1u;
-        uint32_t tree = item, heap = 1u, pos = 0u;
-        PixelRec rec;
-        rec.p_kind = rec.n_extra = rec.d = rec.out = rec.col = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (REC_FINAL: not a glass vertex)
-        if (live) {
-            if (level == 0u) {
-                pos = fp.glass[item];
-                rec = recs[pos];
-            } else {
-                rec = in[item].rec;
-                tree = in[item].tree;
-                heap = in[item].heap;
+    __syncthreads();   // (the records, the positions and the leaf counters are the other work-items')
+    for (uint32_t level = 0; level < PT_TREE_LEVELS; level++) {
+        const uint32_t items = 2u * (level ? s_wn[level] : nt);
+        for (uint32_t t = threadIdx.x; t < items; t += 256u) {
+            const uint32_t e = level ? (uint32_t)s_wait[(level - 1u) & 1u][t >> 1] : (1u << 8) | (t >> 1);
+            const uint32_t j = e & 0xFFu, heap = e >> 8, which = t & 1u, tree = tree0 + j;
+            if (tree_step<ACCEL>(c, fp.trees + tree, tree, heap, which, level + 1u == PT_TREE_LEVELS, recs + s_tpos[j],
+                                 fp.tree_wait + (size_t)tree * PT_TREE_WAITS)) {
+                const uint32_t k = atomicAdd(&s_wn[level + 1u], 1u);
+                s_wait[level & 1u][k] = (uint16_t)(((2u * heap + which) << 8) | j);
             }
         }
-        PixelTree *T = fp.trees + tree;
-        float prob = 0.0f;
-        const bool decision = tree_settle<ACCEL>(c, rec, prob) && live;
-        if (live && !decision && which == 0u) {
-            // no decision here after all (total internal reflection led to another kind of vertex): a leaf
-            if (heap == 1u) recs[pos] = rec;   // the pixel needs no tree: the prefix simply went on
-            else {
-                const uint32_t li = atomicAdd(&T->dec[0].hsh, 1u);
-                T->leaf[li] = rec;
-                T->dec[heap >> 1].child[heap & 1u] = (uint16_t)(0x8000u | li);
-            }
-        }
-        if (decision && which == 0u) {
-            T->dec[heap].hsh = dir_hash(xyz(rec.d));
-            T->dec[heap].prob = prob;
-            T->dec[heap].depth = (__float_as_uint(rec.p_kind.w) >> 8) & 0xFFu;
-            if (heap == 1u) {
-                recs[pos].p_kind.w = __uint_as_float((uint32_t)REC_TREE);
-                recs[pos].col.w = __uint_as_float(tree);
-            } else {
-                T->dec[heap >> 1].child[heap & 1u] = (uint16_t)heap;
-            }
-        }
-        PixelRec rb = rec;
-        if (decision) rb = tree_branch<ACCEL>(c, rec, which);
-        const bool wait = decision && is_glass_vertex(rb) && level + 1u < PT_TREE_LEVELS;
-        const unsigned long long wm = __ballot(wait);
-        bool queued = false;
-        if (wm) {
-            uint32_t base = 0u;
-            const int leader = __builtin_ctzll(wm);
-            if ((int)lane == leader) base = atomicAdd(out_count, (uint32_t)__popcll(wm));
-            base = (uint32_t)__shfl((int)base, leader);
-            const uint32_t qi = base + lanes_below(wm);
-            if (wait && qi < q_cap) {
-                out[qi].rec = rb;
-                out[qi].tree = tree;
-                out[qi].heap = 2u * heap + which;
-                queued = true;   // (its parent's child link is written when the vertex is settled, next level)
-            }
-        }
-        if (decision && !queued) {
-            const uint32_t li = atomicAdd(&T->dec[0].hsh, 1u);
-            T->leaf[li] = rb;
-            T->dec[heap].child[which] = (uint16_t)(0x8000u | li);
-        }
+        if (level + 1u < PT_TREE_LEVELS) __syncthreads();
     }
 }
 
@@ -1330,7 +1282,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         HIP_TRY(ctx, hipMemsetAsync(live_count, 0, (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
         fp.trees = ss.trees.p;
-        fp.glass = ss.glass.p;
+        fp.tree_wait = ss.tree_wait.p;
         fp.tree_count = live_count + LIVE_TREE_COUNTER;
         // (and not for a handful of samples per call: tracing both continuations of a pixel costs more than the few samples
         // that would share them — C2 at 1 / 8 / 16 / 32 samples per call: 0.321 / 0.457 / 0.609 / 1.031 ms with trees,
@@ -1376,26 +1328,10 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
 #define PT_CALL_PREFIX(C, A) \
     hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
         bool accel_on = scene_has_accel(sc);
-        PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
-        if (fp.tree_cap) {
-            // stage 1b: the decision trees of the glass-first pixels, level by level (grid-stride over device-side lists;
-            // a modest grid: 4096 workgroups that stage the materials and find next to nothing to do cost 0.06 ms each).
-            // These launches are latency-bound — each lasts as long as its longest stretch of path, 30-60 us with a few
-            // thousand waves in flight (PT_TREE_STRETCH bounds it).  Tried and measured slower (profiles/r03_experiments.md):
-            // the glass-first pixels in a list of their own, trees and a second launch of the sample kernel on a side
-            // stream beside the main list's — a queue-kernel wave lives ~0.1 ms whatever the size of its launch.
-            dim3 gridt(std::min<uint32_t>(768u, (2u * fp.tree_cap + 255u) / 256u));
-            const uint32_t q_cap = (uint32_t)ss.tree_capacity;
-            TreeWork *q[2] = {ss.tree_work.p, ss.tree_work.p + ss.tree_capacity};
-            for (uint32_t level = 0; level < PT_TREE_LEVELS; level++) {
-                const TreeWork *in = level ? q[(level - 1u) & 1u] : nullptr;
-                const uint32_t *in_count = level ? fp.tree_count + level : nullptr;
-                TreeWork *out = q[level & 1u];
-                uint32_t *out_count = fp.tree_count + level + 1u;
-                if (accel_on) hipLaunchKernelGGL(pt_tree_pass<true>, gridt, block, 0, ctx->stream, sc, fp, ss.recs.p, level, in, in_count, out, out_count, q_cap);
-                else hipLaunchKernelGGL(pt_tree_pass<false>, gridt, block, 0, ctx->stream, sc, fp, ss.recs.p, level, in, in_count, out, out_count, q_cap);
-            }
-        }
+        if (fp.tree_cap) {   // (never in counting builds)
+            if (accel_on) hipLaunchKernelGGL((pt_prefix<false, true, true>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
+            else hipLaunchKernelGGL((pt_prefix<false, false, true>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
+        } else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
         // the sample kernel over a list: (records, slots, its counter, its capacity)
         auto launch_samples = [&](hipStream_t st, const PixelRec *l_recs, const uint32_t *l_live, const uint32_t *l_count, uint32_t l_cap) {

@@ -110,9 +110,11 @@ enum { REC_FINAL = 0, REC_VERTEX = 1, REC_TREE = 2 };
 // from on their own).  The sample kernels walk the decisions per sample (one table read each) and start from the
 // chosen leaf: the nearest-hit searches behind the glass are done once per pixel instead of once per sample.  A record
 // of kind REC_TREE names its tree in col.w.  Bits are unchanged: the same operations, not repeated per sample.
-// Built level by level (pt_tree_pass): two work-items per waiting glass vertex, one per continuation.
+// Built level by level by the workgroup of pt_prefix that found the pixel: two work-items per waiting glass vertex, one
+// per continuation.
 #ifndef PT_TREE_LEVELS
 #define PT_TREE_LEVELS 2      // A/B on MI355X, whole fused call (profiles/r03_experiments.md): C2 off 1.927 ms, 1 level ?, 2 levels 1.822, 3 levels 1.867; C5 at 1080p x 512 spp 174.0 / 149.5 / 149.7
+                              // (built inside pt_prefix, round 5: 3 levels no faster, profiles/r05_experiments.md)
 #endif
 #define PT_TREE_DECISIONS ((1 << PT_TREE_LEVELS) - 1)
 #define PT_TREE_LEAVES (1 << PT_TREE_LEVELS)   // a binary tree with 2^L - 1 inner nodes has at most 2^L leaves
@@ -126,10 +128,9 @@ struct PixelTree {      // 8 x 16 + 8 x 80 = 768 bytes at 3 levels
     TreeDecision dec[PT_TREE_DECISIONS + 1];   // heap-indexed from 1
     PixelRec leaf[PT_TREE_LEAVES];
 };
-struct TreeWork {       // a glass vertex waiting to become node `heap` of tree `tree`
-    PixelRec rec;
-    uint32_t tree, heap, _pad[2];
-};
+// A glass vertex waiting for the next level to become node `heap` (2 … 2^L − 1) of tree t has a fixed place:
+// tree_wait[t · PT_TREE_WAITS + heap − 2].
+#define PT_TREE_WAITS (PT_TREE_LEAVES - 2)
 
 enum RenderMode { MODE_ACCUM = 0, MODE_TRACE = 1, MODE_RETRACE = 2 };
 
@@ -144,9 +145,9 @@ struct FrameParams {
     uint32_t group_log2;            // lanes per pixel = 1 << group_log2 (<= 64)
     uint32_t seg_cap;               // live list: entries per segment (see LIVE_SEGMENTS)
     float inv_count;                // 1 / count, the IEEE quotient computed on the host: a scalar operand of the queue kernels
-    PixelTree *trees;               // shared decision trees of this launch (pt_tree writes, the sample kernels read)
-    uint32_t *glass;                // live-list positions of the pixels whose first random event is a dielectric surface
-    uint32_t *tree_count;           // how many pt_prefix listed (tree i belongs to glass[i])
+    PixelTree *trees;               // shared decision trees of this launch (pt_prefix writes, the sample kernels read)
+    PixelRec *tree_wait;            // glass vertices waiting for the next level of their tree (PT_TREE_WAITS per tree)
+    uint32_t *tree_count;           // how many trees pt_prefix's workgroups reserved
     uint32_t tree_cap;              // capacity of `trees` (0: trees off — RT_OPT_PREFIX_TREE, counting builds)
     uint32_t lds_face_f4;           // pt_samples_q: float4 of DeviceScene::faces staged in LDS after the static tables (0: none; see launch_fused)
     // adaptive rounds (rt_render_adaptive): per decision block of (1 << blk_w_log2) x (1 << blk_h_log2) pixels, nonzero =
@@ -174,7 +175,7 @@ struct BlockMask {
 #endif
 #define LIVE_COUNT_STRIDE 32u   // counters 128 bytes apart: one L2 line each
 #define LIVE_HEAVY_COUNTER 24u   // word of the live-count block: how many HEAVY pixels pt_prefix stored from the end of the list downwards
-#define LIVE_TREE_COUNTER 16u   // words of the live-count block (zeroed with it): [16] glass-first pixels = trees, [17], [18] the work of levels 1, 2
+#define LIVE_TREE_COUNTER 16u   // words of the live-count block (zeroed with it): [16] glass-first pixels = trees
 
 // Counters are spread over COUNTER_REPLICAS rows (one per workgroup residue) so
 // that two million waves do not serialise on 14 addresses; the host sums the rows.

@@ -121,10 +121,9 @@ struct rt_context {
         DevBuf<pt::PixelRec> recs;      // per owned pixel slot: shared path prefix (fused path)
         DevBuf<uint32_t> live;          // slots that need per-sample work + [capacity] = their count
         size_t capacity = 0;
-        // shared decision trees of dielectric-first pixels (pt_types.hpp): all three or none (tree_capacity 0)
+        // shared decision trees of dielectric-first pixels (pt_types.hpp): both or none (tree_capacity 0)
         DevBuf<pt::PixelTree> trees;    // tree_capacity of them
-        DevBuf<uint32_t> glass;         // live-list positions of those pixels (pt_prefix → pt_tree_pass)
-        DevBuf<pt::TreeWork> tree_work; // glass vertices waiting for the next level: two queues of tree_capacity entries
+        DevBuf<pt::PixelRec> tree_wait; // glass vertices waiting for the next level: PT_TREE_WAITS per tree
         size_t tree_capacity = 0;
     } slots;
     bool wave_fill = true;              // RT_OPT_WAVE_FILL
@@ -256,7 +255,7 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     fp.group_log2 = glog2;
     fp.seg_cap = 0;
     fp.trees = nullptr;
-    fp.glass = nullptr;
+    fp.tree_wait = nullptr;
     fp.tree_count = nullptr;
     fp.tree_cap = 0;
     fp.lds_face_f4 = 0;
@@ -284,13 +283,12 @@ inline int ensure_slots(rt_context *ctx, size_t slots) {
     HIP_TRY(ctx, s.live.alloc(entries + (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE));
     // decision trees for a quarter of the slots (a frame with more dielectric-first pixels keeps plain records for the rest)
     const size_t trees = slots / 4 + 256;
-    if (s.trees.alloc(trees) == hipSuccess && s.glass.alloc(trees) == hipSuccess && s.tree_work.alloc(2 * trees) == hipSuccess) {
+    if (s.trees.alloc(trees) == hipSuccess && s.tree_wait.alloc(trees * PT_TREE_WAITS) == hipSuccess) {
         s.tree_capacity = trees;
     } else {   // not fatal: the frame renders without shared trees
         (void)hipGetLastError();
         s.trees.release();
-        s.glass.release();
-        s.tree_work.release();
+        s.tree_wait.release();
     }
     s.capacity = slots;
     return RT_OK;
