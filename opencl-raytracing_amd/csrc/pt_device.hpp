@@ -36,11 +36,6 @@ namespace PT_NS {
 #define PT_BEHIND_SKIP 1   // skip the square root for spheres behind the ray origin
 #endif
 
-#ifndef PT_LDS_SPHERES
-#define PT_LDS_SPHERES 0   // A/B switch: 1 = the brute-force sphere loop reads an LDS copy of the spheres
-#endif                     // (ds_read_b128 broadcast) instead of scalar loads; measured slower, DESIGN.md §5
-#define PT_LDS_SPHERE_CAP 256
-
 #ifndef PT_FACE_MASK
 #define PT_FACE_MASK 1  // face-scanned meshes of <= 32 faces: facing test first, per-lane candidate lists (hit_models)
 #endif
@@ -80,7 +75,6 @@ struct Ctx {
     const DeviceScene &sc;
     LdsV4 lmat;  // LDS: [2i] = (r,g,b,extra), [2i+1].x = type bits; nullptr → read global
     LaneCounters *cn;
-    const float4 *lsph = nullptr;  // PT_LDS_SPHERES: LDS copy of sph4 (or nullptr)
     LdsV4 lwin = nullptr;  // LDS winner records of small sphere sets (stage_materials), or nullptr
     LdsV4 lpln = nullptr;  // LDS (normal, mat) of small plane sets, or nullptr
     LdsV4 lfaces = nullptr;  // LDS copy of DeviceScene::faces (scenes of a few small meshes; pt_samples_q), or nullptr
@@ -131,15 +125,6 @@ PT_DEV LdsV4 staged_winners(const DeviceScene &sc, const float4 *lds) {
 }
 PT_DEV LdsV4 staged_planes(const DeviceScene &sc, const float4 *lds) {
     return lds_pln_n(sc.plane_count) ? lds_ptr(lds + lds_mat_n(sc.material_count) + lds_win_n(sc.sphere_count)) : (LdsV4) nullptr;
-}
-// PT_LDS_SPHERES experiment: stage the sphere test data of small scenes (after stage_materials' barrier
-// has been passed by every thread; contains its own barrier)
-PT_DEV const float4 *stage_spheres(const DeviceScene &sc, float4 *lds) {
-    uint32_t n = (sc.sphere_batches + 1u) * PT_SPHERE_BATCH;
-    if (!PT_LDS_SPHERES || n > PT_LDS_SPHERE_CAP) return nullptr;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) lds[i] = sc.sph4[i];
-    __syncthreads();
-    return lds;
 }
 
 PT_DEV void load_material(const Ctx &c, uint32_t id, int &type, float &extra, V3 &col) {
@@ -489,11 +474,12 @@ PT_DEV void hit_primitives(const Ctx &c, const Ray &r, Nearest &nb) {
         if (!brute) hit_spheres_bvh<COUNT>(sc, r, best_t, best_id, c.cn);
     }
     // brute force: wave-uniform index → scalar loads; a batch of 4 in flight while 4 are tested
+    // (an LDS copy of the spheres read with broadcast ds_read_b128 instead was measured slower)
 #ifndef PT_QSTAT
     if (COUNT && brute) c.cn->c[CN_DBG_BVH_TESTS] += sc.sphere_count;
 #endif
     if (brute && sc.sphere_batches) {
-        const float4 *sp = (PT_LDS_SPHERES && c.lsph) ? c.lsph : sc.sph4;
+        const float4 *sp = sc.sph4;
         float4 a0 = sp[0], a1 = sp[1], a2 = sp[2], a3 = sp[3];
         for (uint32_t b = 0; b < sc.sphere_batches; b++) {
             sp += PT_SPHERE_BATCH;  // the array ends with one dummy batch, so this prefetch is always in bounds

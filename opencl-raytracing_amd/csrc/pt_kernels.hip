@@ -41,14 +41,6 @@ PT_DEV uint32_t live_take(const FrameParams &fp, const uint32_t *__restrict__ li
     const unsigned long long start64 = (unsigned long long)(heavy ? unit : unit - units_h) * want;
     const uint32_t start = (uint32_t)min(start64, (unsigned long long)cnt);
     first = (heavy ? cap - cnt_h : 0u) + start;
-#ifdef PT_EXP_SKIP   // timing experiment (wrong image): leave out the last (1) / first (2) 3 % of the light list's chunks
-    {
-        const uint32_t nl = want ? (cnt_l + want - 1u) / want : 0u, c = unit - units_h;
-        if (!heavy && PT_EXP_SKIP == 1 && c >= nl - nl / 32u) return 0u;
-        if (!heavy && PT_EXP_SKIP == 2 && c < nl / 32u) return 0u;
-        if (!heavy && PT_EXP_SKIP == 3 && c >= nl / 2u && c < nl / 2u + nl / 32u) return 0u;
-    }
-#endif
     return min(want, cnt - start);
 }
 
@@ -166,10 +158,6 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
     Ctx c{sc, stage_materials(sc, s_mat), &cn};
     c.lwin = staged_winners(sc, s_mat);
     c.lpln = staged_planes(sc, s_mat);
-#if PT_LDS_SPHERES
-    __shared__ float4 s_sph[PT_LDS_SPHERE_CAP];
-    c.lsph = stage_spheres(sc, s_sph);
-#endif
 
     uint32_t slot = fp.slot_begin + blockIdx.x * 256u + threadIdx.x;
     uint32_t x = 0, y = 0;
@@ -326,12 +314,10 @@ __global__ __launch_bounds__(256) void pt_samples(DeviceScene sc, FrameParams fp
         uint32_t slot = live[entry];
         (void)slot_to_pixel(fp, slot, x, y);
         PixelRec rec = recs[entry];
-        bool final_px = (__float_as_uint(rec.p_kind.w) & 0xFFu) == REC_FINAL;
         for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
             if (COUNT) cn.c[CN_SAMPLES]++;
             sum = sum + radiance_from_rec<COUNT, ACCEL>(c, rec, s, x, y, fp.trees);
         }
-        (void)final_px;
     }
     sum = group_sum(sum, g);
     if (valid && lane == 0) accumulate(accum, (size_t)y * fp.w + x, sum, fp.count);
@@ -356,14 +342,26 @@ __global__ __launch_bounds__(256) void pt_samples(DeviceScene sc, FrameParams fp
 #ifndef QUEUE_MAX_PIXELS
 #define QUEUE_MAX_PIXELS 16
 #endif
-// dynamic LDS of pt_samples_q, per workgroup: materials, then per wave {records, coordinates, slots}
-__host__ __device__ inline uint32_t queue_wave_lds_bytes(uint32_t pixels_per_wave, uint32_t count) {
-    uint32_t b = pixels_per_wave * 5u * 16u + pixels_per_wave * 4u * 4u + pixels_per_wave * count * 3u * 4u;
-    return (b + 15u) & ~15u;
+// THE layout of a wave's queue in LDS — the one place that knows it.  The workgroup's dynamic LDS starts with the staged
+// tables and face records (queue_static_f4 float4), then the wave's three regions in this order:
+//   records      pixels_per_wave x QUEUE_REC_F4 float4   the pixels' PixelRec
+//   coordinates  pixels_per_wave x QUEUE_XY_F4 float4    (x, y, rnd_base_v(0, x, y), rnd_base_u(0, x, y))
+//   slots        pixels_per_wave x count x 3 floats      one sample's radiance each
+// queue_pixels_per_wave and the launcher size by these functions and queue_stage carves by them.
+#define QUEUE_REC_F4 5u
+#define QUEUE_XY_F4 1u
+static_assert(sizeof(PixelRec) == QUEUE_REC_F4 * sizeof(float4), "a queue record is a PixelRec");
+PT_HD uint32_t queue_pixel_bytes(uint32_t count) { return (QUEUE_REC_F4 + QUEUE_XY_F4) * 16u + count * 3u * 4u; }
+PT_HD uint32_t queue_xy_f4(uint32_t pixels_per_wave) { return pixels_per_wave * QUEUE_REC_F4; }                    // float4 from the wave's base
+PT_HD uint32_t queue_slot_f4(uint32_t pixels_per_wave) { return pixels_per_wave * (QUEUE_REC_F4 + QUEUE_XY_F4); }   // likewise
+PT_HD uint32_t queue_wave_lds_bytes(uint32_t pixels_per_wave, uint32_t count) {
+    return (pixels_per_wave * queue_pixel_bytes(count) + 15u) & ~15u;
 }
-#ifndef PT_UNIFORM_WAVE
-#define PT_UNIFORM_WAVE 1
-#endif
+// The static prefix of the dynamic LDS, in front of the wave's queue: stage_materials' tables, then — from float4
+// queue_faces_f4 on — the face_f4 float4 of face records of a scene of a few small meshes (fp.lds_face_f4, set by
+// launch_fused).  A kernel that cannot stage faces (GEOM == 0, pt_samples_w) passes 0 and never reads the field.
+PT_HD uint32_t queue_faces_f4(const DeviceScene &sc) { return lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count); }
+PT_HD uint32_t queue_static_f4(const DeviceScene &sc, uint32_t face_f4) { return queue_faces_f4(sc) + face_f4; }
 #ifndef PT_Q_WAVES
 #define PT_Q_WAVES 6  // waves per SIMD the register allocator must leave room for: 6 = 80 VGPRs (A/B on C2: 5 → 2.62 ms, 6 → 2.48)
 #endif
@@ -378,21 +376,21 @@ static_assert(QUEUE_SLOTS >= RT_SPP_PER_LAUNCH, "rt_render_spp's launches must f
 #ifndef QUEUE_MIN_SAMPLES
 #define QUEUE_MIN_SAMPLES 384u
 #endif
-// Pixels per wave: as many as the LDS of a CU allows with PT_Q_WAVES(_ACCEL) workgroups resident (6: 160 KB / 6 per
-// workgroup); when that leaves a wave fewer than 384 samples (256 spp and up: the queue's tail grows) the
-// budget of 5 resident workgroups is used instead — the kernel's 80 VGPRs fit either way.
+// Pixels per wave: as many as the LDS of a CU allows with PT_Q_WAVES(_ACCEL) one-wave workgroups resident per SIMD
+// (6: 160 KB / 24 per workgroup); when that leaves a wave fewer than 384 samples (256 spp and up: the queue's tail
+// grows) the budget of 5 per SIMD is used instead — the kernel's 80 VGPRs fit either way.
 #ifndef PT_LDS_GRANULE
 #define PT_LDS_GRANULE 1024u
 #endif
-__host__ inline uint32_t queue_pixels_per_wave(uint32_t count, uint32_t waves, uint32_t static_float4, uint32_t block_waves = 4u) {
+__host__ inline uint32_t queue_pixels_per_wave(uint32_t count, uint32_t waves, uint32_t static_float4) {
     auto fit = [&](uint32_t waves_per_simd) {
-        uint32_t workgroups = waves_per_simd * 4u / block_waves;  // resident workgroups per CU
+        uint32_t workgroups = waves_per_simd * 4u;  // resident workgroups per CU: one wave each
         // (LDS is handed out in blocks: a request of 6 584 bytes — 7 pixels of 64 samples — left fewer than 24 workgroups
         // resident although 24 × 6 584 < 160 KiB, and 6 pixels (5 728 bytes) are 4.5 % faster on C2; the budget is
         // therefore rounded DOWN to a multiple of PT_LDS_GRANULE)
         uint32_t budget = 163840u / workgroups / PT_LDS_GRANULE * PT_LDS_GRANULE;
-        uint32_t per_wave = (budget - static_float4 * (uint32_t)sizeof(float4)) / block_waves - 15u;
-        uint32_t p = per_wave / (5u * 16u + 4u * 4u + count * 3u * 4u);
+        uint32_t per_wave = budget - static_float4 * (uint32_t)sizeof(float4) - 15u;   // (15: queue_wave_lds_bytes rounds up)
+        uint32_t p = per_wave / queue_pixel_bytes(count);
         if (p * count > QUEUE_SLOTS) p = QUEUE_SLOTS / count;
         return p > QUEUE_MAX_PIXELS ? (uint32_t)QUEUE_MAX_PIXELS : p;
     };
@@ -412,16 +410,143 @@ __host__ inline uint32_t queue_pixels_per_wave(uint32_t count, uint32_t waves, u
 #ifndef PT_LDS_FACE_CAP
 #define PT_LDS_FACE_CAP 64u   // faces (48 bytes each) of a scene of small meshes that may be staged in LDS (launch_fused)
 #endif
-#ifndef PT_Q_BLOCK_WAVES
-#define PT_Q_BLOCK_WAVES 1  // waves per workgroup of pt_samples_q (they share only the staged materials): a wave that is through frees
-                            // its LDS and wave slot at once instead of waiting for three others (A/B on C2: 4 → 2.42 ms, 2 → 2.42, 1 → 2.34)
-#endif
+
+// ---- the wave's sample queue (pt_samples_q, pt_samples_w) -----------------------------------------------------------
+// One wave per workgroup: a wave that is through frees its LDS and wave slot at once instead of waiting for three others
+// (A/B on C2, waves per workgroup: 4 → 2.42 ms, 2 → 2.42, 1 → 2.34), and lane = threadIdx.x.
+// The three regions are carried as LDS-QUALIFIED pointers (like Ctx's staged tables, pt_device.hpp) and every access goes
+// through them: as generic pointers in a struct they lose their address space, and the record reads of a refill become
+// flat loads — vector-memory instructions, which these kernels are bound by as much as by ALU work.  The 16-byte
+// regions are plain aligned structs read and written member by member: the type carries the alignment (which does
+// not survive the address-space cast otherwise), and the compiler merges exactly the members a kernel uses into one
+// ds_read_b96 / b128, ds_read2_b32 or ds_write_b128.
+struct alignas(16) QueueF4 { float x, y, z, w; };
+struct alignas(16) QueueXY { uint32_t x, y, bv, bu; };   // bv, bu: rnd_base_v(0, x, y), rnd_base_u(0, x, y)
+typedef QueueF4 __attribute__((address_space(3))) *LdsQueueF4;
+typedef QueueXY __attribute__((address_space(3))) *LdsQueueXY;
+typedef float __attribute__((address_space(3))) *LdsF32;
+typedef v4f __attribute__((address_space(3))) *LdsV4Rw;
+struct WaveQueue {
+    LdsQueueF4 rec;     // [5 p + k]: part k of pixel p's record
+    LdsQueueXY xy;      // [p]: pixel p's coordinates and its part of the table index sums
+    LdsF32 slot;        // [3 (p count + j) + …]: the radiance of pixel p's sample first + j
+    uint32_t npix;      // live pixels this wave owns (<= pixels_per_wave)
+    uint32_t count;     // samples per pixel of this launch
+    uint32_t total;     // npix x count queue entries
+    uint32_t count_log2;  // log2(count) where count is a power of two, else 0xFF
+    float inv_count;
+};
+
+// Takes the wave's pixels off the live list and stages their records and coordinates; `lds` is the workgroup's dynamic
+// LDS and face_f4 the float4 of face records the kernel staged in it (queue_static_f4).  Every lane of the wave calls it (contains the wave's fence and barrier).
+PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const PixelRec *__restrict__ recs,
+                             const uint32_t *__restrict__ live, const uint32_t *__restrict__ live_count,
+                             uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
+    float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
+    WaveQueue q;
+    q.rec = (LdsQueueF4)wave_lds;
+    q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
+    q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
+    const uint32_t lane = threadIdx.x;
+    uint32_t pix0 = 0;
+    q.npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    q.count = fp.count;
+    q.total = q.npix * q.count;
+    for (uint32_t i = lane; i < q.npix * QUEUE_REC_F4; i += 64u) {
+        uint32_t p = i / QUEUE_REC_F4, part = i - p * QUEUE_REC_F4;
+        const float4 t = reinterpret_cast<const float4 *>(recs + pix0 + p)[part];
+        // The record part is written whole, through a vector-typed pointer to the same 16 aligned bytes that queue_fetch
+        // reads member by member.  The pun is intentional: written member by member, the loop vectoriser interleaves this
+        // loop two trips wide (a longer prologue for nothing).  It is safe: clang lets vector types alias their element
+        // type, and the wave's fence and barrier below stand between this store and every read.
+        *(LdsV4Rw)(q.rec + i) = v4f{t.x, t.y, t.z, t.w};
+    }
+    if (lane < q.npix) {
+        uint32_t x = 0, y = 0;
+        (void)slot_to_pixel(fp, live[pix0 + lane], x, y);
+        // (x, y, and the pixel's part of the two table index sums: rnd_base_v = (sample·2683 + x·3931 + y·2504)·3 and
+        // rnd_base_u = sample·2683 + x·3931 + y are linear in uint32 arithmetic, so a refill needs two multiplies, not five)
+        q.xy[lane].x = x;
+        q.xy[lane].y = y;
+        q.xy[lane].bv = rnd_base_v(0u, x, y);
+        q.xy[lane].bu = rnd_base_u(0u, x, y);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // (the two operands of queue_fetch's division, formed here, where the parent kernels formed them: before the staging
+    // loop they change the register allocation of every instantiation)
+    q.inv_count = fp.inv_count;
+    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    return q;
+}
+
+// Queue entry idx → what a lane starts from: the record q0 … q4 (PixelRec's five parts; a pixel with a shared decision
+// tree: this sample's leaf), its kind bits, and the sample's part of the two table index sums.
+struct QueueEntry {
+    float4 q0, q1, q2, q3, q4;
+    uint32_t bits, bv, bu;
+};
+PT_DEV QueueEntry queue_fetch(const WaveQueue &q, const DeviceScene &sc, const FrameParams &fp, uint32_t idx) {
+    // pixel of this queue entry: p = idx / count, exactly, without an integer divide:
+    // (idx + 0.5)/count lies >= 0.5/count away from every integer, far more than the rounding
+    // of the float product (idx < 8192, count <= 512)
+    // (a power-of-two count — wave-uniform — needs a shift; otherwise one float multiply:)
+    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t sample = fp.first + (idx - p * q.count);
+    auto part = [&](uint32_t k) {
+        const LdsQueueF4 f = q.rec + (QUEUE_REC_F4 * p + k);
+        return make_float4(f->x, f->y, f->z, f->w);
+    };
+    QueueEntry e;
+    e.q0 = part(0);
+    e.q1 = part(1);
+    e.q2 = part(2);
+    e.q3 = part(3);
+    e.q4 = part(4);
+    e.bv = sample * 8049u + q.xy[p].bv;   // = rnd_base_v(sample, x, y)
+    e.bu = sample * 2683u + q.xy[p].bu;   // = rnd_base_u(sample, x, y)
+    e.bits = __float_as_uint(e.q0.w);
+    if ((e.bits & 0xFFu) == REC_TREE) {   // the pixel has a shared decision tree: this sample's leaf
+        const float4 *lf = tree_leaf(fp.trees + __float_as_uint(e.q4.w), sc.table, e.bu);
+        e.q0 = lf[0]; e.q1 = lf[1]; e.q2 = lf[2]; e.q3 = lf[3]; e.q4 = lf[4];
+        e.bits = __float_as_uint(e.q0.w);
+    }
+    return e;
+}
+
+// the finished sample's radiance, into its own slot
+PT_DEV void queue_put(const WaveQueue &q, uint32_t idx, V3 rgb) {
+    q.slot[3 * idx] = rgb.x;
+    q.slot[3 * idx + 1] = rgb.y;
+    q.slot[3 * idx + 2] = rgb.z;
+}
+
+// Once every sample of the wave is in its slot: the per-pixel sums in pt_render's order (lane l of a pixel's g lanes:
+// samples l, l + g, …; then the xor butterfly), added to the accumulator.  Every lane of the wave calls it.
+PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t lane = threadIdx.x;
+    const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
+    for (uint32_t pb = 0; pb < q.npix; pb += ppp) {
+        uint32_t p = pb + (lane >> fp.group_log2), l = lane & (g - 1u);
+        V3 sum = mk(0.0f, 0.0f, 0.0f);
+        if (p < q.npix)
+            for (uint32_t j = l; j < q.count; j += g) {
+                const LdsF32 sl = q.slot + 3u * (p * q.count + j);
+                sum = sum + mk(sl[0], sl[1], sl[2]);
+            }
+        sum = group_sum(sum, g);
+        if (p < q.npix && l == 0) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, q.count);
+    }
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
 // kernel keeps 6 waves per SIMD.
 template <bool COUNT, bool ACCEL, int GEOM, int WAVES>
-__global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
+__global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
                                                     float4 *__restrict__ accum, unsigned long long *counters,
@@ -433,56 +558,15 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
     Ctx c{sc, stage_materials(sc, s_mat), &cn};
     c.lwin = staged_winners(sc, s_mat);
     c.lpln = staged_planes(sc, s_mat);
-#if PT_LDS_SPHERES
-    c.lsph = stage_spheres(sc, s_dyn + lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count));
-#endif
     if (GEOM != 0 && fp.lds_face_f4) {   // the face records of a scene of a few small meshes (hit_models' candidate loop)
-        float4 *s_faces = s_dyn + lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count);
+        float4 *s_faces = s_dyn + queue_faces_f4(sc);
         for (uint32_t i = threadIdx.x; i < fp.lds_face_f4; i += blockDim.x) s_faces[i] = sc.faces[i];
         __syncthreads();
         c.lfaces = lds_ptr(s_faces);
     }
 
-#if PT_Q_BLOCK_WAVES == 1
-    const uint32_t wave = 0u, lane = threadIdx.x;
-#elif PT_UNIFORM_WAVE
-    // the wave index is wave-uniform, which the compiler cannot see: this puts everything derived from it in SGPRs
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-#else
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-#endif
-    char *wave_lds = reinterpret_cast<char *>(s_dyn + lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count) +
-                                              (PT_LDS_SPHERES ? PT_LDS_SPHERE_CAP : 0) + (GEOM != 0 ? fp.lds_face_f4 : 0u)) +
-                     (size_t)wave * queue_wave_lds_bytes(pixels_per_wave, fp.count);
-    float4 *s_rec = reinterpret_cast<float4 *>(wave_lds);
-    uint32_t *s_xy = reinterpret_cast<uint32_t *>(s_rec + pixels_per_wave * 5u);
-    float *slot = reinterpret_cast<float *>(s_xy + pixels_per_wave * 4u);
-    uint32_t pix0 = 0;
-    const uint32_t npix = live_take(fp, live_count, blockIdx.x * (uint32_t)PT_Q_BLOCK_WAVES + wave, pixels_per_wave, pix0);
-    const uint32_t count = fp.count, total = npix * count;
-    const float4 *rec = s_rec;
-    const uint32_t *xy = s_xy;
+    const WaveQueue q = queue_stage(sc, fp, recs, live, live_count, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
-    // stage this wave's pixel records and coordinates
-    for (uint32_t i = lane; i < npix * 5u; i += 64u) {
-        uint32_t p = i / 5u, part = i - p * 5u;
-        s_rec[i] = reinterpret_cast<const float4 *>(recs + pix0 + p)[part];
-    }
-    if (lane < npix) {
-        uint32_t x = 0, y = 0;
-        (void)slot_to_pixel(fp, live[pix0 + lane], x, y);
-        // (x, y, and the pixel's part of the two table index sums: rnd_base_v = (sample·2683 + x·3931 + y·2504)·3 and
-        // rnd_base_u = sample·2683 + x·3931 + y are linear in uint32 arithmetic, so a refill needs two multiplies, not five)
-        s_xy[4 * lane] = x;
-        s_xy[4 * lane + 1] = y;
-        s_xy[4 * lane + 2] = rnd_base_v(0u, x, y);
-        s_xy[4 * lane + 3] = rnd_base_u(0u, x, y);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-
-    const float inv_count = fp.inv_count;
-    const uint32_t count_log2 = (count & (count - 1u)) == 0u ? (uint32_t)__builtin_ctz(count) : 0xFFu;
     uint32_t next = 0;  // wave-uniform head of the queue
     bool active = false;
     // Per-lane state carried from one iteration to the next, kept small (the kernel sits on its VGPR budget):
@@ -507,40 +591,25 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
         bool need = !active;
         unsigned long long m = __ballot(need);
         // refill when enough lanes idle (or none is active): the refill step issues for the whole wave
-        if (m && next < total && ((uint32_t)__popcll(m) >= PT_REFILL_MIN || m == ~0ull)) {
+        if (m && next < q.total && ((uint32_t)__popcll(m) >= PT_REFILL_MIN || m == ~0ull)) {
             uint32_t cand = next + lanes_below(m);
-            if (need && cand < total) {
+            if (need && cand < q.total) {
                 idx = cand;
-                // pixel of this queue entry: p = idx / count, exactly, without an integer divide:
-                // (idx + 0.5)/count lies >= 0.5/count away from every integer, far more than the rounding
-                // of the float product (idx < 8192, count <= 512)
-                // (a power-of-two count — wave-uniform — needs a shift; otherwise one float multiply:)
-                uint32_t p = count_log2 != 0xFFu ? idx >> count_log2 : (uint32_t)(((float)idx + 0.5f) * inv_count);
-                const uint32_t sample = fp.first + (idx - p * count);
-                float4 q0 = rec[5 * p], q1 = rec[5 * p + 1], q2 = rec[5 * p + 2], q3 = rec[5 * p + 3],
-                       q4 = rec[5 * p + 4];
-                bv = sample * 8049u + xy[4 * p + 2];   // = rnd_base_v(sample, x, y)
-                bu = sample * 2683u + xy[4 * p + 3];   // = rnd_base_u(sample, x, y)
-                uint32_t bits = __float_as_uint(q0.w);
-                if ((bits & 0xFFu) == REC_TREE) {   // the pixel has a shared decision tree: this sample's leaf
-                    const float4 *lf = tree_leaf(fp.trees + __float_as_uint(q4.w), sc.table, bu);
-                    q0 = lf[0]; q1 = lf[1]; q2 = lf[2]; q3 = lf[3]; q4 = lf[4];
-                    bits = __float_as_uint(q0.w);
-                }
+                const QueueEntry e = queue_fetch(q, sc, fp, idx);
+                bv = e.bv;
+                bu = e.bu;
                 if (COUNT) cn.c[CN_SAMPLES]++;
                 // the state of an idle lane is dead: it takes the record whatever its kind, so that the registers are
                 // written in place (a final colour's lane stays idle and its state is never read)
-                depth = (bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
-                hn = xyz(q1);
-                r.o = xyz(q0);
-                r.d = xyz(q2);
-                hmat = __float_as_uint(q2.w);
-                out = xyz(q3);
-                col = xyz(q4);
-                if ((bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
-                    slot[3 * idx] = q3.x;
-                    slot[3 * idx + 1] = q3.y;
-                    slot[3 * idx + 2] = q3.z;
+                depth = (e.bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
+                hn = xyz(e.q1);
+                r.o = xyz(e.q0);
+                r.d = xyz(e.q2);
+                hmat = __float_as_uint(e.q2.w);
+                out = xyz(e.q3);
+                col = xyz(e.q4);
+                if ((e.bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
+                    queue_put(q, idx, out);
                 } else {
                     if (PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
                     active = true;
@@ -548,7 +617,7 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
             }
             next += (uint32_t)__popcll(m);
         }
-        if (!__any(active) && next >= total) break;
+        if (!__any(active) && next >= q.total) break;
         PT_STAMP(c, 0);
 #ifdef PT_EXP_PAD  // timing experiment (tools/pad_experiment.sh): PT_EXP_PAD extra full-rate VALU instructions per iteration
                    // (v_or_b32 x, x, x on a live register: no new VGPR; PT_EXP_PAD_NOP: operand-free v_nop instead).  An
@@ -564,8 +633,8 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
 #ifdef PT_QSTAT  // diagnostic: lane-iterations used / offered (read through rt_get_debug_counters on a BVH-free scene)
         if (COUNT && __any(active)) {   // (an iteration that only refilled final colours is not offered)
             uint32_t na = (uint32_t)__popcll(__ballot(active));
-            if (lane == 0) cn.c[CN_DBG_BVH_NODES] += na;
-            if (lane == 0) cn.c[CN_DBG_BVH_TESTS] += 64u;
+            if (threadIdx.x == 0) cn.c[CN_DBG_BVH_NODES] += na;
+            if (threadIdx.x == 0) cn.c[CN_DBG_BVH_TESTS] += 64u;
         }
 #endif
         // ---- one material interaction for every active lane
@@ -584,9 +653,7 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
             scatter<COUNT>(c, r, out, at, type, extra, col, rnd, false);
             depth++;
             if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
-                slot[3 * idx] = out.x;
-                slot[3 * idx + 1] = out.y;
-                slot[3 * idx + 2] = out.z;
+                queue_put(q, idx, out);
                 active = false;
             }
         }
@@ -623,9 +690,7 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
                 }
             }
             if (done) {
-                slot[3 * idx] = res.x;
-                slot[3 * idx + 1] = res.y;
-                slot[3 * idx + 2] = res.z;
+                queue_put(q, idx, res);
                 active = false;
             } else if (PT_RNG_PREFETCH == 2) {
                 // this lane WILL interact next iteration: its table reads fly during the refill step
@@ -635,25 +700,10 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
         PT_STAMP(c, 4);
     }
 #if PT_STAMPS
-    if (lane == 0 && npix)
+    if (threadIdx.x == 0 && q.npix)
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- per-pixel sums in pt_render's order
-    const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
-    for (uint32_t pb = 0; pb < npix; pb += ppp) {
-        uint32_t p = pb + (lane >> fp.group_log2), l = lane & (g - 1u);
-        V3 sum = mk(0.0f, 0.0f, 0.0f);
-        if (p < npix)
-            for (uint32_t j = l; j < count; j += g) {
-                const float *sl = slot + 3u * (p * count + j);
-                sum = sum + mk(sl[0], sl[1], sl[2]);
-            }
-        sum = group_sum(sum, g);
-        if (p < npix && l == 0) accumulate(accum, (size_t)xy[4 * p + 1] * fp.w + xy[4 * p], sum, count);
-    }
+    queue_sums(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }
 
@@ -670,19 +720,11 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
 #ifndef PT_WALK_STEPS
 #define PT_WALK_STEPS 24u  // A/B: 8 → 122.9 ms, 16 → 118.3, 24 → 116.5, 48 → 118.4
 #endif
-#ifndef PT_W_BATCH
-#define PT_W_BATCH 1u   // lanes that must be waiting for a cheap step before the cheap steps run (pt_samples_w).  A/B on C5 at 1080p x 64 spp:
-                        // 1 → 20.87 ms, 8 → 21.14, 16 → 21.41, 24 → 21.79, 32 → 22.42 (16 with slices of 12 / 8 nodes: 20.79 / 21.01):
-                        // waiting lanes cost more than sparsely filled cheap steps — batching stays off
-#endif
 // The root of the (single) mesh is tested while the lane is still in state 0: a ray that misses the whole mesh (a third of
 // C5's walks) goes straight to state 2 instead of idling through a slice, and the cheap states repeat (at most
 // PT_W_CHEAP_REPEATS times) while at least PT_W_CHEAP_AGAIN lanes came out of them with no walk to join.  C5 at 4K x 512 spp:
 // off 561.8 ms, root test without repeats 571.6, repeats from 4 / 8 / 16 lanes 548.6 / 546.6 / 545.6.  (Ending a slice early once
 // 8 / 16 / 24 of its lanes are through: 593.7 / 558.8 / 553.4 vs 548.2 — the fixed slice stays.)
-#ifndef PT_W_ROOT_FIRST
-#define PT_W_ROOT_FIRST 1
-#endif
 #ifndef PT_W_CHEAP_AGAIN
 #define PT_W_CHEAP_AGAIN 8u
 #endif
@@ -692,14 +734,11 @@ __global__ __launch_bounds__(64 * PT_Q_BLOCK_WAVES, WAVES) void pt_samples_q(Dev
 #ifndef PT_W_WAVES
 #define PT_W_WAVES 6  // A/B on C5 at 16 spp (round 2, 92 VGPRs): 4 → 116.5 ms, 5 → 110.2, 6 → 116.1 (spills); round 3 (the loop reordered: 79 VGPRs) at 1080p x 64 spp: 5 → 20.87, 6 → 20.65
 #endif
-#ifndef PT_W_BLOCK_WAVES
-#define PT_W_BLOCK_WAVES 1  // waves per workgroup (see PT_Q_BLOCK_WAVES)
-#endif
 #ifndef PT_W_WAVES_MULTI
 #define PT_W_WAVES_MULTI 4  // several meshes: the running minimum over the jobs needs 13 more VGPRs — 109, no scratch at 4 waves per SIMD
 #endif
 template <bool MULTI>
-__global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_samples_w(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
+__global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_samples_w(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
                                                     float4 *__restrict__ accum, uint32_t pixels_per_wave,
@@ -713,37 +752,7 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
     Ctx c{sc, stage_materials(sc, s_mat), nullptr};
     c.lwin = staged_winners(sc, s_mat);
     c.lpln = staged_planes(sc, s_mat);
-#if PT_W_BLOCK_WAVES == 1
-    const uint32_t wave = 0u, lane = threadIdx.x;
-#else
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-#endif
-    char *wave_lds = reinterpret_cast<char *>(s_dyn + lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count)) +
-                     (size_t)wave * queue_wave_lds_bytes(pixels_per_wave, fp.count);
-    float4 *s_rec = reinterpret_cast<float4 *>(wave_lds);
-    uint32_t *s_xy = reinterpret_cast<uint32_t *>(s_rec + pixels_per_wave * 5u);
-    float *slot = reinterpret_cast<float *>(s_xy + pixels_per_wave * 4u);
-    uint32_t pix0 = 0;
-    const uint32_t npix = live_take(fp, live_count, blockIdx.x * (uint32_t)PT_W_BLOCK_WAVES + wave, pixels_per_wave, pix0);
-    const uint32_t count = fp.count, total = npix * count;
-    const float4 *rec = s_rec;
-    const uint32_t *xy = s_xy;
-    for (uint32_t i = lane; i < npix * 5u; i += 64u) {
-        uint32_t p = i / 5u, part = i - p * 5u;
-        s_rec[i] = reinterpret_cast<const float4 *>(recs + pix0 + p)[part];
-    }
-    if (lane < npix) {
-        uint32_t x = 0, y = 0;
-        (void)slot_to_pixel(fp, live[pix0 + lane], x, y);
-        // (x, y, and the pixel's part of the two table index sums: rnd_base_v = (sample·2683 + x·3931 + y·2504)·3 and
-        // rnd_base_u = sample·2683 + x·3931 + y are linear in uint32 arithmetic, so a refill needs two multiplies, not five)
-        s_xy[4 * lane] = x;
-        s_xy[4 * lane + 1] = y;
-        s_xy[4 * lane + 2] = rnd_base_v(0u, x, y);
-        s_xy[4 * lane + 3] = rnd_base_u(0u, x, y);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    const WaveQueue q = queue_stage(sc, fp, recs, live, live_count, pixels_per_wave, s_dyn, 0u);
 
     // The walks of a bounce, in the reference's order: jobs[j] = (mesh index, material of its model), model by
     // model, mesh by mesh.  hitModel's "nearest of my meshes" followed by hitScene's "nearer than the best so
@@ -753,8 +762,6 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
     const uint32_t faces0 = sc.meshes[mesh0].face_count;
     const uint32_t root0 = sc.mesh_bvh_root[mesh0];
 
-    const float inv_count = fp.inv_count;
-    const uint32_t count_log2 = (count & (count - 1u)) == 0u ? (uint32_t)__builtin_ctz(count) : 0xFFu;
     uint32_t next = 0;  // wave-uniform head of the queue
     bool active = false;
     int phase = 0;
@@ -793,13 +800,14 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
 #endif
     // every iteration takes samples off the queue, or moves every active lane on (a bounce, or up to
     // PT_WALK_STEPS nodes of a walk that visits each of the < 2^28 nodes at most 3 times)
-    for (unsigned long long guard = ((unsigned long long)total + 1ull) * (RT_DEPTH + 2ull) * (3ull * (1ull << 28) / PT_WALK_STEPS + 4ull); guard; guard--) {
+    for (unsigned long long guard = ((unsigned long long)q.total + 1ull) * (RT_DEPTH + 2ull) * (3ull * (1ull << 28) / PT_WALK_STEPS + 4ull); guard; guard--) {
         // Which lanes are inside a walk, and which want one of the cheap steps (the winner's record after a walk, a new
-        // sample from the queue, a material interaction + the primitives that are not models)?  The cheap steps are
-        // BATCHED: they run when at least PT_W_BATCH lanes want one (or nothing is walking) — run in every iteration
-        // they executed for the handful of lanes whose walks had just ended, at the price of a wave's whole issue time.
+        // sample from the queue, a material interaction + the primitives that are not models)?  The cheap steps run as
+        // soon as ONE lane wants one.  (Holding them back until 8 / 16 / 24 / 32 lanes wait, C5 at 1080p x 64 spp: 21.14 /
+        // 21.41 / 21.79 / 22.42 ms against 20.87, 16 with slices of 12 / 8 nodes 20.79 / 21.01 — waiting lanes cost more
+        // than sparsely filled cheap steps.)
         const bool walking = active && phase == 1;
-        const bool wants_cheap = (active && phase != 1) || (!active && next < total);
+        const bool wants_cheap = (active && phase != 1) || (!active && next < q.total);
         const uint32_t n_cheap = (uint32_t)__popcll(__ballot(wants_cheap));
         const bool any_walk = __any(walking);
         if (n_cheap == 0u && !any_walk) break;   // every path is through and the queue is empty
@@ -810,9 +818,9 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
         it_p1 += __popcll(__ballot(active && phase == 1));
         it_p2 += __popcll(__ballot(active && phase == 2));
 #endif
-        if (n_cheap >= PT_W_BATCH || !any_walk) {
-          // (PT_W_ROOT_FIRST: a ray that misses the mesh's root goes from state 0 straight to state 2; the cheap states
-          // repeat while at least PT_W_CHEAP_AGAIN lanes came out of them without a walk to join)
+        if (n_cheap) {
+          // (a ray that misses the mesh's root goes from state 0 straight to state 2; the cheap states repeat while at
+          // least PT_W_CHEAP_AGAIN lanes came out of them without a walk to join)
           for (uint32_t again = 0;; again++) {
             // ---- state 2: the winner's record, its material
             if (active && phase == 2) {
@@ -854,9 +862,7 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
                 }
                 phase = 0;
                 if (done) {
-                    slot[3 * idx] = res.x;
-                    slot[3 * idx + 1] = res.y;
-                    slot[3 * idx + 2] = res.z;
+                    queue_put(q, idx, res);
                     active = false;
                 } else {   // the next interaction happens here
                     r.o = h.p;
@@ -867,34 +873,23 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
             // ---- refill idle lanes from the queue
             bool need = !active;
             unsigned long long m = __ballot(need);
-            if (m && next < total) {
+            if (m && next < q.total) {
                 uint32_t cand = next + lanes_below(m);
-                if (need && cand < total) {
+                if (need && cand < q.total) {
                     idx = cand;
-                    uint32_t p = count_log2 != 0xFFu ? idx >> count_log2 : (uint32_t)(((float)idx + 0.5f) * inv_count);  // = idx / count exactly (pt_samples_q)
-                    const uint32_t sample = fp.first + (idx - p * count);
-                    float4 q0 = rec[5 * p], q1 = rec[5 * p + 1], q2 = rec[5 * p + 2], q3 = rec[5 * p + 3],
-                           q4 = rec[5 * p + 4];
-                    bv = sample * 8049u + xy[4 * p + 2];   // = rnd_base_v(sample, x, y)
-                    bu = sample * 2683u + xy[4 * p + 3];   // = rnd_base_u(sample, x, y)
-                    uint32_t bits = __float_as_uint(q0.w);
-                    if ((bits & 0xFFu) == REC_TREE) {   // the pixel has a shared decision tree: this sample's leaf
-                        const float4 *lf = tree_leaf(fp.trees + __float_as_uint(q4.w), sc.table, bu);
-                        q0 = lf[0]; q1 = lf[1]; q2 = lf[2]; q3 = lf[3]; q4 = lf[4];
-                        bits = __float_as_uint(q0.w);
-                    }
-                    if ((bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
-                        slot[3 * idx] = q3.x;
-                        slot[3 * idx + 1] = q3.y;
-                        slot[3 * idx + 2] = q3.z;
+                    const QueueEntry e = queue_fetch(q, sc, fp, idx);
+                    bv = e.bv;
+                    bu = e.bu;
+                    if ((e.bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
+                        queue_put(q, idx, xyz(e.q3));
                     } else {
-                        depth = (bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
-                        hn = xyz(q1);
-                        r.o = xyz(q0);
-                        r.d = xyz(q2);
-                        hmat = __float_as_uint(q2.w);
-                        out = xyz(q3);
-                        col = xyz(q4);
+                        depth = (e.bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
+                        hn = xyz(e.q1);
+                        r.o = xyz(e.q0);
+                        r.d = xyz(e.q2);
+                        hmat = __float_as_uint(e.q2.w);
+                        out = xyz(e.q3);
+                        col = xyz(e.q4);
                         active = true;
                         phase = 0;
                     }
@@ -917,9 +912,7 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
                 scatter<false>(c, r, out, at, type, extra, col, rnd, false);
                 depth++;
                 if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
-                    slot[3 * idx] = out.x;
-                    slot[3 * idx + 1] = out.y;
-                    slot[3 * idx + 2] = out.z;
+                    queue_put(q, idx, out);
                     active = false;
                 } else {
                     Nearest nb;
@@ -935,22 +928,16 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
                     wt = wu = wv = 0.0f;
                     job = 0;
                     phase = 1;
-#if PT_W_ROOT_FIRST
                     if (!MULTI) {
                         wpos = mesh_walk_first(sc, r, root0, faces0);
                         if (wpos.cur == PT_MESH_END) phase = 2;
                     } else if (!enter_job()) {
                         phase = 2;
                     }
-#endif
                 }
             }
-#if PT_W_ROOT_FIRST
             if (again >= PT_W_CHEAP_REPEATS) break;
-            if ((uint32_t)__popcll(__ballot((active && phase != 1) || (!active && next < total))) < PT_W_CHEAP_AGAIN) break;
-#else
-            break;
-#endif
+            if ((uint32_t)__popcll(__ballot((active && phase != 1) || (!active && next < q.total))) < PT_W_CHEAP_AGAIN) break;
           }
         }
         // ---- state 1: a slice of the current job's mesh walk
@@ -981,46 +968,20 @@ __global__ __launch_bounds__(64 * PT_W_BLOCK_WAVES, MULTI ? PT_W_WAVES_MULTI : P
                     nb_v = wv;
                 }
                 job++;
-#if PT_W_ROOT_FIRST
                 if (!enter_job()) phase = 2;   // (the next mesh whose root the ray does not miss: stay in state 1)
-#else
-                if (MULTI && job < n_jobs) {  // next mesh: stay in state 1
-                    uint32_t mesh_n = jobs[job].x;
-                    wpos = mesh_walk_start(sc.mesh_bvh_root[mesh_n]);
-                    wbest = sc.meshes[mesh_n].face_count;
-                    wt = wu = wv = 0.0f;
-                } else {
-                    phase = 2;
-                }
-#endif
                 }
             }
         }
     }
     if (active) atomicOr(sc.walk_overflow, PT_OVF_WALK_SLICES);   // cold: the outer loop ended on its guard with a path unfinished
 #ifdef PT_WSTAT
-    if (lane == 0 && npix) {
+    if (threadIdx.x == 0 && q.npix) {
         unsigned long long v[12] = {it_n, it_active, it_p0, it_p1, it_p2, it_walk_calls, ws.steps, ws.node_lanes, 0ull,
                                     ws.leaf_runs, ws.leaf_lanes, ws.idle_lanes};
         for (int k = 0; k < 12; k++) atomicAdd(&wstat[k], v[k]);
     }
 #endif
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- per-pixel sums in pt_render's order
-    const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
-    for (uint32_t pb = 0; pb < npix; pb += ppp) {
-        uint32_t p = pb + (lane >> fp.group_log2), l = lane & (g - 1u);
-        V3 sum = mk(0.0f, 0.0f, 0.0f);
-        if (p < npix)
-            for (uint32_t j = l; j < count; j += g) {
-                const float *sl = slot + 3u * (p * count + j);
-                sum = sum + mk(sl[0], sl[1], sl[2]);
-            }
-        sum = group_sum(sum, g);
-        if (p < npix && l == 0) accumulate(accum, (size_t)xy[4 * p + 1] * fp.w + xy[4 * p], sum, count);
-    }
+    queue_sums(q, fp, accum);
 }
 
 // parity probe: one work-item per listed pixel-sample
@@ -1270,7 +1231,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
     int rc = ensure_slots(ctx, slots);
     if (rc) return rc;
     const rt_context::Slots &ss = ctx->slots;
-    uint32_t *live_count = ss.live.p + ss.capacity + (size_t)LIVE_SEGMENTS * 256u;
+    uint32_t *live_count = ss.live.p + ss.capacity + 256u;
     uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
     if (slots_per_launch == 0) slots_per_launch = 1;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
@@ -1279,7 +1240,7 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         fp.slot_begin = b;
         fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
         uint32_t n = fp.slot_end - fp.slot_begin;
-        HIP_TRY(ctx, hipMemsetAsync(live_count, 0, (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(live_count, 0, LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
         fp.trees = ss.trees.p;
         fp.tree_wait = ss.tree_wait.p;
@@ -1289,17 +1250,17 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         // 0.243 / 0.393 / 0.582 / 1.088 without)
         const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
         fp.tree_cap = (tree_on && !ctx->count_enabled) ? (uint32_t)ss.tree_capacity : 0u;   // (0 without the tree buffers)
-        // workgroup b of pt_prefix appends to segment b mod LIVE_SEGMENTS: a segment holds at most seg_cap entries
+        // the live list holds whole workgroups of pt_prefix
         const uint32_t prefix_blocks = (n + 255) / 256;
-        fp.seg_cap = ((prefix_blocks + LIVE_SEGMENTS - 1) / LIVE_SEGMENTS) * 256u;
+        fp.seg_cap = prefix_blocks * 256u;
         dim3 block(256), grid1(prefix_blocks);
         // sample queue: a wave owns ppw live pixels (<= QUEUE_SLOTS samples); worst case all n pixels are live
-        uint32_t static_f4 = lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count) +
-                             (PT_LDS_SPHERES ? PT_LDS_SPHERE_CAP : 0);
+        fp.lds_face_f4 = 0u;
+        uint32_t static_f4 = queue_static_f4(sc, 0u);
         const bool sphere_bvh_only = sc.bvh_node_count != 0 && sc.mesh_bvh_root == nullptr;
         const bool simple_geom = sc.lens_count == 0 && sc.model_count == 0;   // spheres and planes only
         const uint32_t q_waves = !scene_has_accel(sc) ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
-        uint32_t ppw = queue_pixels_per_wave(count, q_waves, static_f4, PT_Q_BLOCK_WAVES);
+        uint32_t ppw = queue_pixels_per_wave(count, q_waves, static_f4);
         // Small launches (small frames, a rank's share of a sharded frame): fewer pixels per wave, so that there are about
         // PT_UNITS_PER_WAVE_SLOT waves per wave slot of the chip — a wave works through its pixels' samples one batch of
         // 64 after the other, and 4 200 waves of 384 samples leave a third of the slots empty for the whole launch.
@@ -1313,36 +1274,31 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         // Face records in LDS for hit_models' candidate loop: scenes whose meshes are all face-scanned (no mesh BVH) and
         // hold at most PT_LDS_FACE_CAP faces together, and only when the copy fits into what the 1 KiB allocation granule
         // leaves over anyway (C3: 576 bytes of a cube into 609 spare ones) — never at the price of a pixel per wave.
-        fp.lds_face_f4 = 0u;
         if (PT_FACE_MASK && !simple_geom && sc.mesh_bvh_root == nullptr && !ctx->count_enabled) {
             const size_t nf = ctx->h_faces.size() / 3u - (ctx->h_faces.empty() ? 0u : 1u);   // (the array ends with one dummy record)
             if (nf > 0 && nf <= PT_LDS_FACE_CAP &&
-                queue_pixels_per_wave(count, q_waves, static_f4 + 3u * (uint32_t)nf, PT_Q_BLOCK_WAVES) >= ppw) {
+                queue_pixels_per_wave(count, q_waves, static_f4 + 3u * (uint32_t)nf) >= ppw) {
                 fp.lds_face_f4 = 3u * (uint32_t)nf;
-                static_f4 += fp.lds_face_f4;
+                static_f4 = queue_static_f4(sc, fp.lds_face_f4);
             }
         }
-        dim3 blockq(64 * PT_Q_BLOCK_WAVES);
         bool queue = ctx->sample_queue && count <= QUEUE_SLOTS;
-        size_t lds_q = static_f4 * sizeof(float4) + PT_Q_BLOCK_WAVES * (size_t)queue_wave_lds_bytes(ppw, count);
-#define PT_CALL_PREFIX(C, A) \
-    hipLaunchKernelGGL((pt_prefix<C, A>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
+        // (dynamic LDS of a queue kernel's one-wave workgroup: the static prefix, then the wave's queue)
+        auto queue_lds = [&](uint32_t pixels_per_wave) { return static_f4 * sizeof(float4) + (size_t)queue_wave_lds_bytes(pixels_per_wave, count); };
+#define PT_LAUNCH_PREFIX(K) \
+    hipLaunchKernelGGL(K, grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
+#define PT_CALL_PREFIX(C, A) PT_LAUNCH_PREFIX((pt_prefix<C, A>))
         bool accel_on = scene_has_accel(sc);
-        if (fp.tree_cap) {   // (never in counting builds)
-            if (accel_on) hipLaunchKernelGGL((pt_prefix<false, true, true>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
-            else hipLaunchKernelGGL((pt_prefix<false, false, true>), grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
-        } else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
+        if (fp.tree_cap) PT_LAUNCH_PREFIX((accel_on ? pt_prefix<false, true, true> : pt_prefix<false, false, true>));   // (never in counting builds)
+        else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
+#undef PT_CALL_PREFIX
+#undef PT_LAUNCH_PREFIX
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
-        // the sample kernel over a list: (records, slots, its counter, its capacity)
-        auto launch_samples = [&](hipStream_t st, const PixelRec *l_recs, const uint32_t *l_live, const uint32_t *l_count, uint32_t l_cap) {
-            FrameParams fl = fp;
-            fl.seg_cap = l_cap;
-            // (the two parts of the list each end in a partial chunk: one unit more than capacity / chunk)
-            auto units = [&](uint32_t per_unit) { return (l_cap + per_unit - 1) / per_unit + 1u; };
-            dim3 gridq((units(ppw) + PT_Q_BLOCK_WAVES - 1) / PT_Q_BLOCK_WAVES);
-            dim3 grid2((unsigned)((((uint64_t)units(1u) << glog2) + 255) / 256));
+        // the sample kernel over the live list
+        // (the two parts of the list each end in a partial chunk: one unit more than capacity / chunk)
+        auto units = [&](uint32_t per_unit) { return (fp.seg_cap + per_unit - 1) / per_unit + 1u; };
 #define PT_CALL_QUEUE_W(C, A, G, W) \
-    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), gridq, blockq, lds_q, st, sc, fl, l_recs, l_live, l_count, accum, ctx->counters.p, ppw)
+    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), dim3(units(ppw)), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw)
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
         if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
@@ -1350,35 +1306,26 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
     } while (0)
 #define PT_CALL_FIXED(C, A) \
-    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, st, sc, fl, l_recs, l_live, l_count, accum, ctx->counters.p)
-            if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled && !PT_LDS_SPHERES) {
-                // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
-                uint32_t ppw_w = queue_pixels_per_wave(count, ctx->walk_jobs.n == 1 ? PT_W_WAVES : PT_W_WAVES_MULTI, static_f4, PT_W_BLOCK_WAVES);
-                if (ppw_w > ppw_par) ppw_w = ppw_par;
-                size_t lds_w = static_f4 * sizeof(float4) + PT_W_BLOCK_WAVES * (size_t)queue_wave_lds_bytes(ppw_w, count);
-                dim3 gridw((units(ppw_w) + PT_W_BLOCK_WAVES - 1) / PT_W_BLOCK_WAVES), blockw(64 * PT_W_BLOCK_WAVES);
-                if (ctx->walk_jobs.n == 1)
-                    hipLaunchKernelGGL(pt_samples_w<false>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
-                                       accum, ppw_w, ctx->walk_jobs.p, 1u
+    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
+        if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled) {
+            // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
+            const bool multi = ctx->walk_jobs.n != 1;
+            uint32_t ppw_w = queue_pixels_per_wave(count, multi ? PT_W_WAVES_MULTI : PT_W_WAVES, static_f4);
+            if (ppw_w > ppw_par) ppw_w = ppw_par;
+            hipLaunchKernelGGL(multi ? pt_samples_w<true> : pt_samples_w<false>, dim3(units(ppw_w)), dim3(64), queue_lds(ppw_w), ctx->stream,
+                               sc, fp, ss.recs.p, ss.live.p, live_count, accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
 #ifdef PT_WSTAT
-                                       , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
+                               , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
 #endif
-                                       );
-                else
-                    hipLaunchKernelGGL(pt_samples_w<true>, gridw, blockw, lds_w, st, sc, fl, l_recs, l_live, l_count,
-                                       accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
-#ifdef PT_WSTAT
-                                       , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
-#endif
-                                       );
-            } else if (queue) PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_QUEUE);
-            else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_FIXED);
+                               );
+        } else if (queue) PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_QUEUE);
+        else {
+            dim3 grid2((unsigned)((((uint64_t)units(1u) << glog2) + 255) / 256));
+            PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_FIXED);
+        }
 #undef PT_CALL_QUEUE
 #undef PT_CALL_QUEUE_W
 #undef PT_CALL_FIXED
-        };
-        launch_samples(ctx->stream, ss.recs.p, ss.live.p, live_count, fp.seg_cap);
-#undef PT_CALL_PREFIX
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));

@@ -143,7 +143,7 @@ struct FrameParams {
     uint32_t slot_begin, slot_end;  // owned pixel slots handled by this launch
     uint32_t first, count;          // samples first .. first+count-1
     uint32_t group_log2;            // lanes per pixel = 1 << group_log2 (<= 64)
-    uint32_t seg_cap;               // live list: entries per segment (see LIVE_SEGMENTS)
+    uint32_t seg_cap;               // live list: its capacity in entries (whole pt_prefix workgroups; the heavy pixels fill it from the end)
     float inv_count;                // 1 / count, the IEEE quotient computed on the host: a scalar operand of the queue kernels
     PixelTree *trees;               // shared decision trees of this launch (pt_prefix writes, the sample kernels read)
     PixelRec *tree_wait;            // glass vertices waiting for the next level of their tree (PT_TREE_WAITS per tree)
@@ -163,19 +163,18 @@ struct BlockMask {
     uint32_t w_log2, h_log2, blocks_x;
 };
 
-// The live list (pixels that need per-sample work) can be kept in LIVE_SEGMENTS independent segments, workgroup b
-// of pt_prefix appending to segment b mod LIVE_SEGMENTS and the sample kernels dealing their waves over the
-// segments.  Built to take the append counter off a single address; measured on MI355X (profiles/r02_experiments.md):
+// The live list (pixels that need per-sample work) is ONE list behind one counter block.  Keeping it in 4 … 64 independent
+// segments, to take the append counter off a single address, was measured on MI355X (profiles/r02_experiments.md):
 // pt_prefix 0.198 → 0.075 ms, but pt_samples_q 2.35 → 2.75 (4 segments) … 3.07 ms (64) on C2 and 10.8 → 14.8 ms on
-// C3 — the waves of a workgroup (and neighbouring workgroups) then work on distant parts of the image, finish at
-// different times and hold their workgroup's LDS and wave slots until the slowest is through.  The list's ORDER
-// is a performance property: 1 segment ships, and the counter is relieved by one atomic per workgroup instead.
-#ifndef LIVE_SEGMENTS
-#define LIVE_SEGMENTS 1u
-#endif
-#define LIVE_COUNT_STRIDE 32u   // counters 128 bytes apart: one L2 line each
-#define LIVE_HEAVY_COUNTER 24u   // word of the live-count block: how many HEAVY pixels pt_prefix stored from the end of the list downwards
-#define LIVE_TREE_COUNTER 16u   // words of the live-count block (zeroed with it): [16] glass-first pixels = trees
+// C3 — neighbouring waves then work on distant parts of the image and finish at different times.  The list's ORDER
+// is a performance property; the counter is relieved by one atomic per workgroup instead.
+// The live-count block: LIVE_COUNT_STRIDE words (128 bytes) behind the list, zeroed before every pt_prefix.
+//   [0]                   live pixels stored from 0 upwards
+//   [LIVE_TREE_COUNTER]   glass-first pixels = shared decision trees reserved
+//   [LIVE_HEAVY_COUNTER]  HEAVY pixels, stored from the end of the list downwards
+#define LIVE_COUNT_STRIDE 32u
+#define LIVE_TREE_COUNTER 16u
+#define LIVE_HEAVY_COUNTER 24u
 
 // Counters are spread over COUNTER_REPLICAS rows (one per workgroup residue) so
 // that two million waves do not serialise on 14 addresses; the host sums the rows.

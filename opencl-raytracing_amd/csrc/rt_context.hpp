@@ -277,10 +277,10 @@ inline int ensure_slots(rt_context *ctx, size_t slots) {
     rt_context::Slots &s = ctx->slots;
     if (slots <= s.capacity) return RT_OK;
     s = {};
-    // segmented live list: LIVE_SEGMENTS segments of whole workgroups' worth of entries, then the segment counters
-    size_t entries = slots + (size_t)LIVE_SEGMENTS * 256u;
+    // live list: whole pt_prefix workgroups' worth of entries, then the block of counters
+    size_t entries = slots + 256u;
     HIP_TRY(ctx, s.recs.alloc(entries));
-    HIP_TRY(ctx, s.live.alloc(entries + (size_t)LIVE_SEGMENTS * LIVE_COUNT_STRIDE));
+    HIP_TRY(ctx, s.live.alloc(entries + LIVE_COUNT_STRIDE));
     // decision trees for a quarter of the slots (a frame with more dielectric-first pixels keeps plain records for the rest)
     const size_t trees = slots / 4 + 256;
     if (s.trees.alloc(trees) == hipSuccess && s.tree_wait.alloc(trees * PT_TREE_WAITS) == hipSuccess) {

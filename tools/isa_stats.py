@@ -80,7 +80,7 @@ def default_arith():
 def device_asm(force=False, arith=None):
     import __graft_entry__ as g
     arith = default_arith() if arith is None else int(arith)
-    extra = os.environ.get("ISA_EXTRA_FLAGS", "").split()   # e.g. ISA_EXTRA_FLAGS="-DPT_Q_BLOCK_WAVES=1" for a variant
+    extra = os.environ.get("ISA_EXTRA_FLAGS", "").split()   # e.g. ISA_EXTRA_FLAGS="-DPT_Q_WAVES=5" for a variant
     tag = ("_" + "_".join(e.lstrip("-D").replace("=", "") for e in extra)) if extra else ""
     out = os.path.join(ROOT, "build", "pt_kernels_a%d_gfx950%s.s" % (arith, tag))
     os.makedirs(os.path.dirname(out), exist_ok=True)
