@@ -105,6 +105,12 @@ const float *RayTracer::denoise(const Camera *camera, const rt_denoise_params &p
     return pixels.data();
 }
 
+void RayTracer::setPrefixCache(bool on) { check(rt_set_option(ctx, RT_OPT_PREFIX_CACHE, on ? 1 : 0)); }
+
+void RayTracer::prefixCacheStats(uint64_t &hits, uint64_t &misses) const {
+    check(rt_prefix_cache_stats(ctx, &hits, &misses));
+}
+
 uint32_t RayTracer::sampleCounter() const {
     uint32_t v = 0;
     rt_sample_counter(ctx, &v);

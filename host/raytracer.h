@@ -67,6 +67,10 @@ public:
     // features for `camera` (unless it is null: then the last ones) + rt_denoise + read back into the image that
     // transferImage() / lastImage() return; the accumulator is left as it was
     const float *denoise(const Camera *camera, const rt_denoise_params &params);
+    // RT_OPT_PREFIX_CACHE: while camera and scene rest, renderSamples keeps the traced prefix from call to call (default
+    // on; same pixels either way); the counts of fused launches that reused it / traced it in full
+    void setPrefixCache(bool on);
+    void prefixCacheStats(uint64_t &hits, uint64_t &misses) const;
     uint32_t sampleCounter() const;
     rt_context *context() { return ctx; }
     SceneCreator &sceneCreator() { return scene; }

@@ -427,6 +427,13 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
 #define RT_OPT_WAVE_FILL 8              /* 1 (default): a sample-kernel wave owns fewer pixels when the launch is small (a small
                                            frame, a rank's share of a sharded one), so that the chip's wave slots are filled;
                                            0: always as many pixels per wave as its LDS share holds.  Same result bit for bit */
+#define RT_OPT_PREFIX_CACHE 9           /* 1 (default): while the camera block, the scene and every setting stay as they are,
+                                           a fused call keeps what its first stage (pt_prefix) left in the context — records,
+                                           live list, decision trees — and later calls only add the finished pixels' share of
+                                           their samples (pt_final_replay) before the sample kernel runs; a changed camera,
+                                           scene, texture, seed, option, shard, frame size or stream traces the prefix anew.
+                                           0: every call traces it anew.  A process whose environment holds
+                                           RT_PREFIX_CACHE=0 starts its contexts with 0.  Same result bit for bit           */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's
@@ -507,11 +514,16 @@ int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6);
 int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float *out4);
 
 /* The two stages of the same calls separately: a fused rt_render_spp call is pt_prefix
- * (first_ms: one work-item per pixel, the sample-invariant path prefix) followed by the
+ * (first_ms: one work-item per pixel, the sample-invariant path prefix) or, when the call
+ * reuses the kept prefix (RT_OPT_PREFIX_CACHE), pt_final_replay in its place, followed by the
  * per-sample kernel (second_ms: pt_samples_q / pt_samples_w, the dominant kernel that
  * bench.py prices against the roofline); a third event is recorded between them.  Calls
  * on the direct path (rt_render, rt_render_again) report first_ms = 0. */
 int rt_stage_ms_history(rt_context *ctx, float *first_ms, float *second_ms, size_t cap, size_t *n_out);
+
+/* Fused launches (rt_render_spp: one per 512 samples per pixel; rt_render_adaptive: one per round) of this context
+ * that reused the kept prefix (RT_OPT_PREFIX_CACHE) and that traced it in full, since rt_create. */
+int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses);
 
 /* Name, CU count and arch of the context's device, e.g. "gfx950". */
 int rt_device_info(rt_context *ctx, char *name, size_t name_len, int *cu_count, char *arch, size_t arch_len);

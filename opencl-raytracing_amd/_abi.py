@@ -146,6 +146,11 @@ def denoise_prototypes(lib):
     lib.rt_device_denoised.argtypes = [vp, C.POINTER(vp)]
 
 
+def prefix_cache_prototypes(lib):
+    """ctypes prototype of rt_prefix_cache_stats (RT_OPT_PREFIX_CACHE)."""
+    lib.rt_prefix_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+
 def split_features(rec):
     """(H, W) FEATURE records → dict of (H, W, ...) arrays (RayTracer.features())."""
     return {"position": rec["pos"].copy(), "depth": rec["t"].copy(), "normal": rec["normal"].copy(),

@@ -86,6 +86,28 @@ PT_DEV void accumulate(float4 *__restrict__ accum, size_t pix, V3 sum, uint32_t 
     accum[pix] = a;
 }
 
+// `count` samples of one colour, summed in the kernels' order: lane l of the pixel's g = 2^group_log2 lanes adds its samples
+// l, l + g, … one after the other (k or k + 1 of them: the first r = count mod g lanes have one more), then the
+// xor butterfly (offsets g/2 … 1).  Before a butterfly step over n lanes the first r lanes hold one value (X)
+// and the others another (Y); lane l takes T(l) + T(l + n/2), so the pattern survives with n/2 lanes:
+// r <= n/2 → (X + Y, Y + Y, r), else (X + X, X + Y, r − n/2).  Lane 0's value after the last step is the pixel's sum.
+// (Until round 3 only counts that are multiples of g took this shortcut; every other count sent its sky pixels
+// through the sample kernel: 56 samples per pixel took longer than 64.)
+// The ONE place that forms it: pt_prefix and pt_final_replay both call it, so a replayed pixel gets the traced one's bits.
+PT_DEV V3 final_sum(V3 col, uint32_t count, uint32_t group_log2) {
+    const uint32_t g = 1u << group_log2;
+    V3 Y = mk(0.0f, 0.0f, 0.0f);
+    for (uint32_t k = 0; k < (count >> group_log2); k++) Y = Y + col;
+    V3 X = Y + col;
+    uint32_t r = count & (g - 1u);
+    for (uint32_t n = g; n > 1u; n >>= 1) {
+        const uint32_t h = n >> 1;
+        if (r <= h) { X = X + Y; Y = Y + Y; }
+        else { Y = X + Y; X = X + X; r -= h; }
+    }
+    return r ? X : Y;
+}
+
 // Direct path: one work-item per (pixel, sample lane), every sample traced from
 // the camera.  Lane l of a group of g = 2^group_log2 lanes traces samples
 // first+l, first+l+g, ... of its pixel and sums them in that order; the g partial
@@ -151,7 +173,8 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
 template <bool COUNT, bool ACCEL, bool TREES = false>
 __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(DeviceScene sc, FrameParams fp, PixelRec *__restrict__ recs,
                                                  uint32_t *__restrict__ live, uint32_t *__restrict__ live_count,
-                                                 float4 *__restrict__ accum, unsigned long long *counters) {
+                                                 float4 *__restrict__ accum, unsigned long long *counters,
+                                                 FinalPix *__restrict__ finals, uint32_t *__restrict__ final_n) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
     LaneCounters cn;
     if (COUNT) zero_counters(cn);
@@ -162,7 +185,7 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
     uint32_t slot = fp.slot_begin + blockIdx.x * 256u + threadIdx.x;
     uint32_t x = 0, y = 0;
     bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y) && pixel_active(fp, x, y);
-    bool is_live = false;
+    bool is_live = false, is_final = false;
     PixelRec rec;
     rec.p_kind = rec.n_extra = rec.d = rec.out = rec.col = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (valid) {
@@ -170,28 +193,10 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
         rec = trace_prefix<COUNT, ACCEL>(c, r0, x, y);
     }
     if (valid) {
-        uint32_t g = 1u << fp.group_log2;
         bool final_px = (__float_as_uint(rec.p_kind.w) & 0xFFu) == REC_FINAL;
         if (final_px) {
-            // `count` samples of one colour, summed in the kernels' order: lane l of the pixel's g lanes adds its samples
-            // l, l + g, … one after the other (k or k + 1 of them: the first r = count mod g lanes have one more), then the
-            // xor butterfly (offsets g/2 … 1).  Before a butterfly step over n lanes the first r lanes hold one value (X)
-            // and the others another (Y); lane l takes T(l) + T(l + n/2), so the pattern survives with n/2 lanes:
-            // r <= n/2 → (X + Y, Y + Y, r), else (X + X, X + Y, r − n/2).  Lane 0's value after the last step is the pixel's sum.
-            // (Until round 3 only counts that are multiples of g took this shortcut; every other count sent its sky pixels
-            // through the sample kernel: 56 samples per pixel took longer than 64.)
-            const V3 col = xyz(rec.out);
-            V3 Y = mk(0.0f, 0.0f, 0.0f);
-            for (uint32_t k = 0; k < (fp.count >> fp.group_log2); k++) Y = Y + col;
-            V3 X = Y + col;
-            uint32_t r = fp.count & (g - 1u);
-            for (uint32_t n = g; n > 1u; n >>= 1) {
-                const uint32_t h = n >> 1;
-                if (r <= h) { X = X + Y; Y = Y + Y; }
-                else { Y = X + Y; X = X + X; r -= h; }
-            }
-            const V3 sum = r ? X : Y;
-            accumulate(accum, (size_t)y * fp.w + x, sum, fp.count);
+            is_final = true;
+            accumulate(accum, (size_t)y * fp.w + x, final_sum(xyz(rec.out), fp.count, fp.group_log2), fp.count);
             if (COUNT) cn.c[CN_SAMPLES] += 1;  // scaled by count below
         } else {
             is_live = true;
@@ -222,14 +227,16 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
     // two continuations through the glass are traced once per pixel there instead of once per sample.  Their tree
     // indices are reserved with the same one atomic per workgroup.
     const bool glass = TREES && is_live && is_glass_vertex(rec);
-    __shared__ uint32_t s_wave_n[4], s_wave_g[4], s_base, s_tree0;
+    __shared__ uint32_t s_wave_n[4], s_wave_g[4], s_wave_f[4], s_base, s_tree0;
     __shared__ uint32_t s_tpos[256];                                    // live position of the workgroup's tree j
     __shared__ uint32_t s_wn[PT_TREE_LEVELS];                           // [L]: glass vertices waiting for level L
     __shared__ uint16_t s_wait[PT_TREE_LEVELS > 2 ? 2 : 1][256u << (PT_TREE_LEVELS - 1)];   // (heap << 8 | j) of those, by level parity
     unsigned long long m = __ballot(is_live);
     const unsigned long long gm = __ballot(glass);
+    const unsigned long long fm = __ballot(is_final);
     if (lane == 0) {
         s_wave_n[wv] = (uint32_t)__popcll(m);
+        s_wave_f[wv] = (uint32_t)__popcll(fm);
         if (TREES) s_wave_g[wv] = (uint32_t)__popcll(gm);
     }
     __syncthreads();
@@ -252,6 +259,21 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
         live[pos] = slot;
         recs[pos] = rec;
     }
+    // The finished pixels — slot and colour, at [256 b, 256 b + final_n[b]) of the finished list for workgroup b, in ballot
+    // order: no atomic (the run's place is the workgroup's own), and the order is irrelevant because a pixel appears once.
+    // While camera and scene rest, pt_final_replay forms their sums for the next call's samples from this list.
+    // (Not in counting builds: a counting launch is never kept, launch_fused.)
+    if (!COUNT && is_final) {
+        uint32_t before = 0;
+        for (uint32_t k = 0; k < wv; k++) before += s_wave_f[k];
+        FinalPix e;
+        e.slot = slot;
+        e.r = rec.out.x;
+        e.g = rec.out.y;
+        e.b = rec.out.z;
+        finals[blockIdx.x * 256u + before + lanes_below(fm)] = e;
+    }
+    if (!COUNT && threadIdx.x == 0) final_n[blockIdx.x] = s_wave_f[0] + s_wave_f[1] + s_wave_f[2] + s_wave_f[3];
     flush_counters<COUNT>(cn, counters, fp.count);  // the prefix stands for `count` samples' worth of work
     if (!TREES) return;
     // Tree phase (pt_types.hpp PixelTree): the trees of the workgroup's glass-first pixels, level by level, two
@@ -286,6 +308,19 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
         }
         if (level + 1u < PT_TREE_LEVELS) __syncthreads();
     }
+}
+
+// Fused path, stage 1 while the prefix is still valid (launch_fused, rt_context::PrefixCache): records, live list,
+// counters and trees lie in the slot buffers as the last pt_prefix left them, and all that remains of the first stage is
+// the finished pixels' share of THIS call's samples.  One workgroup per pt_prefix workgroup over its run of the
+// finished list; final_sum is the function pt_prefix calls, with this call's count and group size.
+__global__ __launch_bounds__(256) void pt_final_replay(FrameParams fp, const FinalPix *__restrict__ finals,
+                                                       const uint32_t *__restrict__ final_n, float4 *__restrict__ accum) {
+    if (threadIdx.x >= min(final_n[blockIdx.x], 256u)) return;
+    const FinalPix e = finals[blockIdx.x * 256u + threadIdx.x];
+    uint32_t x = 0, y = 0;
+    if (!slot_to_pixel(fp, e.slot, x, y)) return;   // (never: pt_prefix stored the slots of valid pixels only)
+    accumulate(accum, (size_t)y * fp.w + x, final_sum(mk(e.r, e.g, e.b), fp.count, fp.group_log2), fp.count);
 }
 
 // Fused path, stage 2: one group of g lanes per LIVE pixel; each lane continues
@@ -1220,7 +1255,8 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
     return RT_OK;
 }
 
-// Fused path: pt_prefix (one work-item per pixel) + pt_samples (g lanes per live pixel).
+// Fused path: pt_prefix (one work-item per pixel) + pt_samples (g lanes per live pixel).  While camera and scene rest
+// the first stage is pt_final_replay over what the last pt_prefix left (rt_context::PrefixCache).
 int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
                  const BlockMask *mask) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
@@ -1234,13 +1270,23 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
     uint32_t *live_count = ss.live.p + ss.capacity + 256u;
     uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
     if (slots_per_launch == 0) slots_per_launch = 1;
+    // The prefix cache (rt_context::PrefixCache): may this launch's pt_prefix be kept, and is the last one's still good?
+    // Until the launch has gone through the entry is invalid, so an error on the way leaves it so.
+    rt_context::PrefixCache &pc = ctx->prefix_cache;
+    const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
+    const bool keepable = !mask && !ctx->count_enabled && slots_per_launch >= slots;
+    uint32_t cam_bits[12];
+    memcpy(cam_bits, cam, sizeof cam_bits);
+    const bool hit = pc.enabled && pc.valid && keepable && pc.key_generation == pc.generation && pc.key_tree_on == tree_on &&
+                     memcmp(pc.key_cam, cam_bits, sizeof cam_bits) == 0;
+    pc.valid = false;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
     for (uint32_t b = 0; b < slots; b += slots_per_launch) {
         fp.slot_begin = b;
         fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
         uint32_t n = fp.slot_end - fp.slot_begin;
-        HIP_TRY(ctx, hipMemsetAsync(live_count, 0, LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
+        if (!hit) HIP_TRY(ctx, hipMemsetAsync(live_count, 0, LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
         fp.trees = ss.trees.p;
         fp.tree_wait = ss.tree_wait.p;
@@ -1248,7 +1294,6 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         // (and not for a handful of samples per call: tracing both continuations of a pixel costs more than the few samples
         // that would share them — C2 at 1 / 8 / 16 / 32 samples per call: 0.321 / 0.457 / 0.609 / 1.031 ms with trees,
         // 0.243 / 0.393 / 0.582 / 1.088 without)
-        const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
         fp.tree_cap = (tree_on && !ctx->count_enabled) ? (uint32_t)ss.tree_capacity : 0u;   // (0 without the tree buffers)
         // the live list holds whole workgroups of pt_prefix
         const uint32_t prefix_blocks = (n + 255) / 256;
@@ -1286,10 +1331,12 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         // (dynamic LDS of a queue kernel's one-wave workgroup: the static prefix, then the wave's queue)
         auto queue_lds = [&](uint32_t pixels_per_wave) { return static_f4 * sizeof(float4) + (size_t)queue_wave_lds_bytes(pixels_per_wave, count); };
 #define PT_LAUNCH_PREFIX(K) \
-    hipLaunchKernelGGL(K, grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
+    hipLaunchKernelGGL(K, grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ss.finals.p, ss.final_n.p)
 #define PT_CALL_PREFIX(C, A) PT_LAUNCH_PREFIX((pt_prefix<C, A>))
         bool accel_on = scene_has_accel(sc);
-        if (fp.tree_cap) PT_LAUNCH_PREFIX((accel_on ? pt_prefix<false, true, true> : pt_prefix<false, false, true>));   // (never in counting builds)
+        // (a hit: the finished pixels' sums for this call's samples; everything else pt_prefix wrote lies there still)
+        if (hit) hipLaunchKernelGGL(pt_final_replay, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p, accum);
+        else if (fp.tree_cap) PT_LAUNCH_PREFIX((accel_on ? pt_prefix<false, true, true> : pt_prefix<false, false, true>));   // (never in counting builds)
         else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
 #undef PT_CALL_PREFIX
 #undef PT_LAUNCH_PREFIX
@@ -1330,6 +1377,13 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
     ctx->ev_count++;
+    if (hit) pc.hits++; else pc.misses++;   // (launches that went through)
+    if (keepable) {   // the slot buffers hold this camera's whole prefix
+        pc.valid = true;
+        pc.key_generation = pc.generation;
+        pc.key_tree_on = tree_on;
+        memcpy(pc.key_cam, cam_bits, sizeof cam_bits);
+    }
     return RT_OK;
 }
 

@@ -99,6 +99,14 @@ struct PixelRec {        // 80 bytes
 };
 enum { REC_FINAL = 0, REC_VERTEX = 1, REC_TREE = 2 };
 
+// A pixel that pt_prefix finished (REC_FINAL): its owned slot and the radiance every one of its samples has.  pt_prefix
+// workgroup b keeps its finished pixels at [256 b, 256 b + final_n[b]) of the finished list; while the prefix stays valid
+// (rt_context::PrefixCache) pt_final_replay adds their closed-form sums to the accumulator without tracing a ray.
+struct FinalPix {        // 16 bytes
+    uint32_t slot;
+    float r, g, b;
+};
+
 // ---- shared decision tree of a pixel -------------------------------------------------------------------------------
 // A dielectric surface is a random event with only TWO outcomes — refract or reflect (raytracer.cl:407-435): which one a
 // sample takes depends on its own table entry u (reflect_prob < u → refract), but the two continuations are the same

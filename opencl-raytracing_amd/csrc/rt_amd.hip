@@ -11,6 +11,7 @@
 #include <cfloat>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -479,6 +480,7 @@ namespace {
 int alloc_frame(rt_context *ctx, int w, int h) {
     // what was made for the old frame goes with it
     ctx->slots = {};
+    ctx->prefix_changed();
     ctx->adaptive = {};
     ctx->features = {};
     ctx->denoise = {};
@@ -615,6 +617,8 @@ int rt_create(int device, int width, int height, rt_context **out) {
 
     ctx->arith = RT_ARITH_IEEE;
     ctx->ks = kernel_set_a0();
+    // (the environment may switch the prefix cache off for a whole process: A/B of an unchanged caller)
+    if (const char *e = getenv("RT_PREFIX_CACHE")) ctx->prefix_cache.enabled = strcmp(e, "0") != 0;
     if ((rc = alloc_frame(ctx, width, height)) != RT_OK) return bail(rc);
     if ((rc = rt_set_seed(ctx, 0xC0FFEEull)) != RT_OK) return bail(rc);
     if ((rc = rt_set_textures(ctx, nullptr, 0, 0, 0)) != RT_OK) return bail(rc);
@@ -647,6 +651,7 @@ int rt_set_stream(rt_context *ctx, void *hip_stream) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    ctx->prefix_changed();
     ctx->ev_count = 0;
     return RT_OK;
 }
@@ -654,6 +659,7 @@ int rt_set_stream(rt_context *ctx, void *hip_stream) {
 int rt_set_scene(rt_context *ctx, const rt_scene_desc *d) {
     if (!ctx) return RT_EINVAL;
     if (!d) return fail(ctx, RT_EINVAL, "scene is NULL");
+    ctx->prefix_changed();
     ctx->walk_jobs.release();
     struct { const void *p; uint32_t n; const char *name; } arrs[] = {
         {d->materials, d->material_count, "materials"}, {d->spheres, d->sphere_count, "spheres"},
@@ -819,6 +825,7 @@ int rt_set_scene(rt_context *ctx, const rt_scene_desc *d) {
 
 int rt_set_textures(rt_context *ctx, const float *rgba, int w, int h, int layers) {
     if (!ctx) return RT_EINVAL;
+    ctx->prefix_changed();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (layers == 0) {
@@ -840,6 +847,7 @@ int rt_set_textures(rt_context *ctx, const float *rgba, int w, int h, int layers
 int rt_set_random_table(rt_context *ctx, const float *table, size_t n) {
     if (!ctx) return RT_EINVAL;
     if (!table || n != RT_RANDOM_TABLE_FLOATS) return fail(ctx, RT_EINVAL, "table must hold %d floats", RT_RANDOM_TABLE_FLOATS);
+    ctx->prefix_changed();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // 2 floats of slack: getVec reads idx..idx+2 with idx < 100000 — inside the table already
@@ -870,6 +878,7 @@ int rt_set_shard(rt_context *ctx, int rank, int world, int tile_w, int tile_h) {
     if (world < 1 || rank < 0 || rank >= world) return fail(ctx, RT_EINVAL, "rank %d of %d", rank, world);
     if (tile_w < 1 || tile_h < 1 || lw < 0 || lh < 0 || lw + lh > 16)
         return fail(ctx, RT_EINVAL, "tile %dx%d: sides must be powers of two, area <= 65536", tile_w, tile_h);
+    ctx->prefix_changed();
     ctx->rank = rank;
     ctx->world = world;
     ctx->tile_w_log2 = lw;
@@ -1245,6 +1254,7 @@ int rt_device_accum(rt_context *ctx, void **d_rgba) {
 int rt_enable_counters(rt_context *ctx, int enable) {
     if (!ctx) return RT_EINVAL;
     ctx->count_enabled = enable != 0;
+    ctx->prefix_changed();
     return RT_OK;
 }
 
@@ -1642,7 +1652,9 @@ int rt_unpack_accum(rt_context *ctx, const void *d_packed, size_t bytes, int src
 
 int rt_set_option(rt_context *ctx, int option, int value) {
     if (!ctx) return RT_EINVAL;
+    ctx->prefix_changed();   // whichever option it is
     switch (option) {
+        case RT_OPT_PREFIX_CACHE: ctx->prefix_cache.enabled = value != 0; return RT_OK;
         case RT_OPT_PREFIX_SHARING: ctx->prefix_sharing = value != 0; return RT_OK;
         case RT_OPT_SAMPLE_QUEUE: ctx->sample_queue = value != 0; return RT_OK;
         case RT_OPT_WALK_SLICES: ctx->walk_slices = value != 0; return RT_OK;
@@ -1672,6 +1684,13 @@ int rt_set_option(rt_context *ctx, int option, int value) {
             return RT_OK;
         default: return fail(ctx, RT_EINVAL, "unknown option %d", option);
     }
+}
+
+int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses) {
+    if (!ctx || !hits || !misses) return RT_EINVAL;
+    *hits = ctx->prefix_cache.hits;
+    *misses = ctx->prefix_cache.misses;
+    return RT_OK;
 }
 
 int rt_reset_counters(rt_context *ctx) {

@@ -125,7 +125,37 @@ struct rt_context {
         DevBuf<pt::PixelTree> trees;    // tree_capacity of them
         DevBuf<pt::PixelRec> tree_wait; // glass vertices waiting for the next level: PT_TREE_WAITS per tree
         size_t tree_capacity = 0;
+        // the pixels pt_prefix finished: workgroup b's at finals[256 b …], final_n[b] of them (pt_final_replay)
+        DevBuf<pt::FinalPix> finals;
+        DevBuf<uint32_t> final_n;
     } slots;
+    // What the last pt_prefix left in `slots`, kept for as long as it stays true (launch_fused): a fused call that finds
+    // the entry valid and its key unchanged launches pt_final_replay instead of pt_prefix and runs the sample kernel
+    // over the buffers as they lie.
+    //  * What pt_prefix writes — the records, the ordered live list and its counters, the decision trees, the finished
+    //    list — is a function of the scene (DeviceScene: geometry, materials, textures, random table, RT_OPT_ACCEL, the
+    //    policy's records), the policy's kernels, and these FrameParams fields: cam, w, h, tile_*_log2, tiles_x,
+    //    tiles_total, rank, world, slot_begin, slot_end, seg_cap, trees, tree_wait, tree_count, tree_cap and the block
+    //    mask.  trace_prefix and tree_step take no FrameParams at all (pt_device.hpp); `first` is not read; `count` and
+    //    `group_log2` enter the finished pixels' closed-form sum only, which pt_final_replay forms anew per call.
+    //  * The sample kernels (pt_samples_q, pt_samples_w, pt_samples) READ recs, live, live_count and the trees and write
+    //    the accumulator (and the work counters) only, so a launch leaves the entry as it found it.
+    //  * Key: (generation, the camera block's 12 floats as bits, trees on / off — tree_cap follows PT_TREE_MIN_SAMPLES).
+    //    `generation` is bumped (prefix_changed()) by every entry point that can change anything else on the list above
+    //    or reallocates the buffers: scene, textures, random table / seed, every rt_set_option, shard, frame size,
+    //    stream, counters on / off, ensure_slots growing.  When in doubt, bump.
+    //  * A launch that writes the buffers only partly or for another purpose — a block mask (adaptive rounds), counters
+    //    enabled, a frame cut into several slot ranges, an error — takes the full path and leaves the entry invalid.
+    struct PrefixCache {
+        bool enabled = true;            // RT_OPT_PREFIX_CACHE (rt_create: the environment's RT_PREFIX_CACHE=0 turns it off)
+        bool valid = false;
+        uint64_t generation = 0;        // now
+        uint64_t key_generation = 0;    // the entry's
+        uint32_t key_cam[12] = {};
+        bool key_tree_on = false;
+        uint64_t hits = 0, misses = 0;  // fused launches served from the entry / traced in full (rt_prefix_cache_stats)
+    } prefix_cache;
+    void prefix_changed() { prefix_cache.generation++; }
     bool wave_fill = true;              // RT_OPT_WAVE_FILL
     int prefix_tree = 1;                // RT_OPT_PREFIX_TREE: 0 off, 1 from PT_TREE_MIN_SAMPLES samples per call on, 2 always
     bool prefix_sharing = true;
@@ -277,10 +307,13 @@ inline int ensure_slots(rt_context *ctx, size_t slots) {
     rt_context::Slots &s = ctx->slots;
     if (slots <= s.capacity) return RT_OK;
     s = {};
+    ctx->prefix_changed();
     // live list: whole pt_prefix workgroups' worth of entries, then the block of counters
     size_t entries = slots + 256u;
     HIP_TRY(ctx, s.recs.alloc(entries));
     HIP_TRY(ctx, s.live.alloc(entries + LIVE_COUNT_STRIDE));
+    HIP_TRY(ctx, s.finals.alloc(entries));
+    HIP_TRY(ctx, s.final_n.alloc(entries / 256u + 1u));
     // decision trees for a quarter of the slots (a frame with more dielectric-first pixels keeps plain records for the rest)
     const size_t trees = slots / 4 + 256;
     if (s.trees.alloc(trees) == hipSuccess && s.tree_wait.alloc(trees * PT_TREE_WAITS) == hipSuccess) {

@@ -30,10 +30,12 @@ SYMBOLS = (
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
     "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
+    "rt_prefix_cache_stats",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
 OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
+OPT_PREFIX_CACHE = 9
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
 ARITH_NAMES = {"ieee": ARITH_IEEE, "rocm-opencl-nocontract": ARITH_ROCM_OCL_NOCONTRACT, "rocm-opencl": ARITH_ROCM_OCL}
 
@@ -113,6 +115,7 @@ def load_library(path=LIB_PATH):
     lib.rt_debug_builtin.argtypes = [vp, C.c_int, vp, sz, vp]
     _abi.adaptive_prototypes(lib)
     _abi.denoise_prototypes(lib)
+    _abi.prefix_cache_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -232,6 +235,7 @@ class RayTracer:
         self._check(self._lib.rt_set_shard(self._ctx, rank, world, tile_w, tile_h))
 
     OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
+    OPT_PREFIX_CACHE = 9
 
     def setOption(self, option, value):
         self._check(self._lib.rt_set_option(self._ctx, option, int(value)))
@@ -430,6 +434,12 @@ class RayTracer:
         self._check(self._lib.rt_walk_overflow(self._ctx, C.byref(out)))
         return int(out.value)
 
+    def prefixCacheStats(self):
+        """(hits, misses): fused launches that reused the kept prefix (OPT_PREFIX_CACHE) / traced it in full."""
+        hits, misses = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rt_prefix_cache_stats(self._ctx, C.byref(hits), C.byref(misses)))
+        return int(hits.value), int(misses.value)
+
     def setArith(self, arith):
         """Select the arithmetic policy of the trace kernels (RT_OPT_ARITH): ARITH_IEEE (default, the CPU oracle's
         contract), ARITH_ROCM_OCL_NOCONTRACT or ARITH_ROCM_OCL (the reference as ROCm's OpenCL builds it); a name of
@@ -452,8 +462,8 @@ class RayTracer:
         return [buf[i] for i in range(got.value)]
 
     def stageMsHistory(self, n=64):
-        """(first-stage ms, second-stage ms) of the last <= min(n, 64) render launches, oldest first: pt_prefix and
-        the per-sample kernel of a fused call."""
+        """(first-stage ms, second-stage ms) of the last <= min(n, 64) render launches, oldest first: pt_prefix (or, on a
+        call that reuses the kept prefix, pt_final_replay) and the per-sample kernel of a fused call."""
         a, b = (C.c_float * n)(), (C.c_float * n)()
         got = C.c_size_t()
         self._check(self._lib.rt_stage_ms_history(self._ctx, a, b, n, C.byref(got)))
