@@ -107,6 +107,14 @@ const float *RayTracer::denoise(const Camera *camera, const rt_denoise_params &p
 
 void RayTracer::setPrefixCache(bool on) { check(rt_set_option(ctx, RT_OPT_PREFIX_CACHE, on ? 1 : 0)); }
 
+void RayTracer::setLookahead(int samples) { check(rt_set_option(ctx, RT_OPT_LOOKAHEAD, samples)); }
+
+RayTracer::LookaheadStats RayTracer::lookaheadStats() const {
+    LookaheadStats s{};
+    check(rt_lookahead_stats(ctx, &s.batches, &s.served, &s.direct, &s.discarded));
+    return s;
+}
+
 void RayTracer::prefixCacheStats(uint64_t &hits, uint64_t &misses) const {
     check(rt_prefix_cache_stats(ctx, &hits, &misses));
 }

@@ -71,6 +71,13 @@ public:
     // on; same pixels either way); the counts of fused launches that reused it / traced it in full
     void setPrefixCache(bool on);
     void prefixCacheStats(uint64_t &hits, uint64_t &misses) const;
+    // RT_OPT_LOOKAHEAD: while the camera rests, renderAgain computes the images after the next `samples` samples (2 .. 64,
+    // default 16) in one fused launch and hands them out call by call; 0 = every call runs the direct kernel.  Same
+    // pixels either way.  The counts since construction: look-ahead launches, calls served from a look-ahead frame,
+    // calls that ran the direct kernel, frames computed and dropped.
+    void setLookahead(int samples);
+    struct LookaheadStats { uint64_t batches, served, direct, discarded; };
+    LookaheadStats lookaheadStats() const;
     uint32_t sampleCounter() const;
     rt_context *context() { return ctx; }
     SceneCreator &sceneCreator() { return scene; }

@@ -1,12 +1,13 @@
 // rt_cli.cpp — headless driver replacing the reference's GLFW application
 // (main.cpp:62-116 render loop, :262-289 screenshot) for the trace path:
 //   rt_cli --scene assets/scenes/c2_cornell.scene --size 1920x1080 --spp 64
-//          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive]
+//          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive [--lookahead N]]
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a]] [--aov PREFIX]
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
-// per sample); the default is the fused path (all samples in one launch).  --adaptive renders
+// per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
+// whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
 // rounds of --batch samples (default 64) until every 8x8 block's error is below THRESHOLD, with
 // at least --min-spp (default 2 x batch) and at most --spp (default 1024 here) samples per pixel; --counts writes the
 // per-pixel sample counts (16-bit PGM for a .pgm name, raw uint32 otherwise).  --denoise filters the rendered frame
@@ -38,7 +39,7 @@ static void check_rc(int rc) {
 
 static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
-                 "[--seed N] [--progressive] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
+                 "[--seed N] [--progressive [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a]] [--aov PREFIX]\n";
     std::exit(2);
@@ -98,6 +99,7 @@ int main(int argc, char **argv) {
     float cam[5] = {0, 0, 0, 0, 0};
     unsigned long long seed = 0xC0FFEE;
     bool progressive = false;
+    long lookahead = -1;   // (-1: the library's default)
     bool adaptive = false, spp_given = false;
     float threshold = 0.0f;
     long batch = 0, min_spp = 0;
@@ -137,6 +139,7 @@ int main(int argc, char **argv) {
         else if ((v = val("--batch"))) batch = parse_int(v, 1, 512);
         else if ((v = val("--min-spp"))) min_spp = parse_int(v, 1, (long)RT_MAX_SAMPLE + 1);
         else if ((v = val("--counts"))) out_counts = v;
+        else if ((v = val("--lookahead"))) { lookahead = parse_int(v, 0, 64); if (lookahead == 1) usage(); }
         else if ((v = val("--denoise-iterations"))) dn_iterations = parse_int(v, 1, RT_DENOISE_MAX_ITERATIONS);
         else if ((v = val("--sigma"))) { parse_sigmas(v, sigmas); sigmas_given = true; }
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
@@ -147,6 +150,7 @@ int main(int argc, char **argv) {
     if (spp < 1 || w < 1 || h < 1) usage();
     if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
     if (!denoise && (dn_iterations || sigmas_given)) usage();              // denoise-only flags
+    if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
         if (progressive) usage();
@@ -197,6 +201,7 @@ int main(int argc, char **argv) {
         st = tracer.renderAdaptive(&camera, p);
         img = tracer.lastImage();
     } else if (progressive) {
+        if (lookahead >= 0) tracer.setLookahead((int)lookahead);
         tracer.render(&camera);
         for (int s = 1; s < spp; s++) tracer.renderAgain(&camera);
         img = tracer.transferImage();

@@ -260,7 +260,12 @@ int rt_render(rt_context *ctx, const float camera[12]);
 
 /* Replaces RayTracer::renderAgain (src/raytracer.cpp:146-165) + kernel
  * `retrace` (raytracer.cl:512-532): ++sample_counter; running mean kept in
- * gamma space, bit-identical to the reference's arithmetic. */
+ * gamma space, bit-identical to the reference's arithmetic.
+ * Synchronous; when it returns, the image (rt_device_image, rt_read_image) is the
+ * image after that sample and the accumulator is untouched.  While the calls repeat
+ * one camera block, RT_OPT_LOOKAHEAD lets ONE fused launch compute the images after
+ * the next K samples; the calls then hand them out, bit for bit what the direct
+ * kernel would have written (see the option). */
 int rt_render_again(rt_context *ctx, const float camera[12]);
 
 /* Value of RayTracer::sample_counter (include/raytracer.h:21). */
@@ -434,6 +439,22 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
                                            scene, texture, seed, option, shard, frame size or stream traces the prefix anew.
                                            0: every call traces it anew.  A process whose environment holds
                                            RT_PREFIX_CACHE=0 starts its contexts with 0.  Same result bit for bit           */
+#define RT_OPT_LOOKAHEAD 10             /* K = 16 (default), 2 .. 64: an rt_render_again call that repeats the camera block of the
+                                           previous rt_render / rt_render_again call traces the next K samples in one fused
+                                           launch (pt_prefix / the kept prefix + the sample-queue kernel), replays the running mean
+                                           per pixel in sample order and stores the image after each sample in a ring of frames
+                                           owned by the context (at most RT_LOOKAHEAD_MAX_BYTES = 1 GiB: fewer frames per batch for
+                                           large frames, none where two do not fit); this call and the next K - 1 copy their frame
+                                           into the image.  Frames still pending are dropped — and the next call starts from the
+                                           image as it lies — when the camera block changes, after rt_render, rt_resolve,
+                                           rt_render_adaptive, rt_resize, and after any call that changes scene, textures, seed /
+                                           table, an option, the shard, the stream or the counters.  Calls run the direct kernel
+                                           as before while counters are enabled, on a sharded context, with RT_OPT_PREFIX_SHARING or
+                                           RT_OPT_SAMPLE_QUEUE off, or when RT_OPT_MAX_THREADS_PER_LAUNCH splits the frame.
+                                           0: every call runs the direct kernel; 1 and values above 64: RT_EINVAL.  A process whose
+                                           environment holds RT_LOOKAHEAD=0 starts its contexts with 0.  Same result bit for bit.
+                                           The library assumes that nobody else writes the image: a zero-copy consumer that WRITES
+                                           through rt_device_image between rt_render_again calls must set this option to 0       */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's
@@ -518,12 +539,26 @@ int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float 
  * reuses the kept prefix (RT_OPT_PREFIX_CACHE), pt_final_replay in its place, followed by the
  * per-sample kernel (second_ms: pt_samples_q / pt_samples_w, the dominant kernel that
  * bench.py prices against the roofline); a third event is recorded between them.  Calls
- * on the direct path (rt_render, rt_render_again) report first_ms = 0. */
+ * on the direct path (rt_render, rt_render_again) report first_ms = 0; so does an
+ * rt_render_again call that only hands a look-ahead frame out (its copy is second_ms), while
+ * the call that launches a look-ahead batch reports the two stages of that launch. */
 int rt_stage_ms_history(rt_context *ctx, float *first_ms, float *second_ms, size_t cap, size_t *n_out);
 
-/* Fused launches (rt_render_spp: one per 512 samples per pixel; rt_render_adaptive: one per round) of this context
- * that reused the kept prefix (RT_OPT_PREFIX_CACHE) and that traced it in full, since rt_create. */
+/* Fused launches (rt_render_spp: one per 512 samples per pixel; rt_render_adaptive: one per round; rt_render_again: one
+ * per look-ahead batch, RT_OPT_LOOKAHEAD) of this context that reused the kept prefix (RT_OPT_PREFIX_CACHE) and that
+ * traced it in full, since rt_create. */
 int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses);
+
+/* Look-ahead (RT_OPT_LOOKAHEAD) since rt_create: `batches` look-ahead launches; `served` rt_render_again calls whose image
+ * came from a look-ahead frame (the launching call included); `direct` rt_render_again calls that ran the direct kernel;
+ * `discarded` frames computed and dropped before a call could hand them out. */
+int rt_lookahead_stats(rt_context *ctx, uint64_t *batches, uint64_t *served, uint64_t *direct, uint64_t *discarded);
+
+/* Host-only (no device, no context): the number of samples the look-ahead launch of an rt_render_again call would trace
+ * for a width x height frame with RT_OPT_LOOKAHEAD = option_value at this sample counter — min(option_value,
+ * RT_MAX_SAMPLE - sample_counter, frames of the ring budget of 1 GiB), or 0 (the direct kernel) where that is below 2.
+ * rt_render_again calls this very function.  RT_EINVAL: an option value the option refuses, a size outside 1..RT_MAX_DIM. */
+int rt_lookahead_plan(int width, int height, int option_value, uint32_t sample_counter, uint32_t *batch_out);
 
 /* Name, CU count and arch of the context's device, e.g. "gfx950". */
 int rt_device_info(rt_context *ctx, char *name, size_t name_len, int *cu_count, char *arch, size_t arch_len);

@@ -151,6 +151,13 @@ def prefix_cache_prototypes(lib):
     lib.rt_prefix_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
 
 
+def lookahead_prototypes(lib):
+    """ctypes prototypes of rt_lookahead_stats / rt_lookahead_plan (RT_OPT_LOOKAHEAD)."""
+    p64 = C.POINTER(C.c_uint64)
+    lib.rt_lookahead_stats.argtypes = [C.c_void_p, p64, p64, p64, p64]
+    lib.rt_lookahead_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]
+
+
 def split_features(rec):
     """(H, W) FEATURE records → dict of (H, W, ...) arrays (RayTracer.features())."""
     return {"position": rec["pos"].copy(), "depth": rec["t"].copy(), "normal": rec["normal"].copy(),

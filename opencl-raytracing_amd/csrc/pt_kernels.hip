@@ -108,6 +108,20 @@ PT_DEV V3 final_sum(V3 col, uint32_t count, uint32_t group_log2) {
     return r ? X : Y;
 }
 
+// ONE step of the interactive loop's running mean, kept in gamma space (`retrace`, raytracer.cl:524-528): the image after
+// sample s from the image after sample s - 1 and the radiance of sample s — mix(new, prev², s/(s+1)), then gamma_corr.
+// The ONE place that forms it: pt_render<MODE_RETRACE> and the look-ahead replays (queue_replay, pt_final_retrace) all
+// call it with the policy's `/`, mix1 and sqrt1, so a look-ahead frame has the direct kernel's bits.  `sample` is the
+// SUM of a one-sample group, 0.0f + radiance (a radiance of -0 becomes +0 there): every caller forms that sum first.
+PT_DEV float retrace_step1(float prev, float sample, uint32_t s) {
+    const float lin = prev * prev;
+    const float k = (float)s / (float)(s + 1u);
+    return sqrt1(mix1(sample, lin, k));   // mix(new, prev², k/(k+1)) :526
+}
+PT_DEV V3 retrace_step(V3 prev, V3 sample, uint32_t s) {
+    return mk(retrace_step1(prev.x, sample.x, s), retrace_step1(prev.y, sample.y, s), retrace_step1(prev.z, sample.z, s));
+}
+
 // Direct path: one work-item per (pixel, sample lane), every sample traced from
 // the camera.  Lane l of a group of g = 2^group_log2 lanes traces samples
 // first+l, first+l+g, ... of its pixel and sums them in that order; the g partial
@@ -150,10 +164,8 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
         } else {
             if (COUNT) cn.c[CN_IMAGE_READS]++;
             float4 prev = image[pix];
-            V3 lin = mk(prev.x * prev.x, prev.y * prev.y, prev.z * prev.z);
-            float k = (float)fp.first / (float)(fp.first + 1u);
-            V3 o = mk(mix1(sum.x, lin.x, k), mix1(sum.y, lin.y, k), mix1(sum.z, lin.z, k));   // mix(new, prev², k/(k+1)) :526
-            image[pix] = make_float4(sqrt1(o.x), sqrt1(o.y), sqrt1(o.z), 1.0f);
+            V3 o = retrace_step(mk(prev.x, prev.y, prev.z), sum, fp.first);
+            image[pix] = make_float4(o.x, o.y, o.z, 1.0f);
         }
     }
     flush_counters<COUNT>(cn, counters, 1);
@@ -165,6 +177,8 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
 // glass chains) is finished here: all its samples are equal, and their sum in the
 // order of stage 2 (k sequential adds per lane, then log2(g) doublings) is
 // computed in closed form.  Other pixels are appended to the live list.
+// A look-ahead launch (launch_fused_any with a ring) passes accum == NULL: the finished pixels are only LISTED then, and
+// pt_final_retrace forms their frames; everything else the kernel writes is what an ordinary launch writes.
 // TREES: the instantiation that also builds the shared decision trees (RT_OPT_PREFIX_TREE; never in counting builds).
 // The tree phase needs some 120 VGPRs against the prefix's 86: a frame without trees keeps the leaner kernel.
 #ifndef PT_PREFIX_WAVES
@@ -196,7 +210,7 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
         bool final_px = (__float_as_uint(rec.p_kind.w) & 0xFFu) == REC_FINAL;
         if (final_px) {
             is_final = true;
-            accumulate(accum, (size_t)y * fp.w + x, final_sum(xyz(rec.out), fp.count, fp.group_log2), fp.count);
+            if (accum) accumulate(accum, (size_t)y * fp.w + x, final_sum(xyz(rec.out), fp.count, fp.group_log2), fp.count);
             if (COUNT) cn.c[CN_SAMPLES] += 1;  // scaled by count below
         } else {
             is_live = true;
@@ -321,6 +335,32 @@ __global__ __launch_bounds__(256) void pt_final_replay(FrameParams fp, const Fin
     uint32_t x = 0, y = 0;
     if (!slot_to_pixel(fp, e.slot, x, y)) return;   // (never: pt_prefix stored the slots of valid pixels only)
     accumulate(accum, (size_t)y * fp.w + x, final_sum(mk(e.r, e.g, e.b), fp.count, fp.group_log2), fp.count);
+}
+
+// Where frame j of pixel pix lies in the look-ahead ring (in float4).  Shipped: FRAME-MAJOR, frame after frame, so that a frame
+// is handed out as one contiguous device copy.  -DPT_RING_PIXEL_MAJOR=1 builds the A/B variant that keeps a pixel's `count`
+// frames side by side (whole-line stores here, a strided hand-out kernel in rt_amd.hip): profiles/r08_experiments.md.
+PT_DEV size_t ring_at(const FrameParams &fp, size_t pix, uint32_t j) {
+    return PT_RING_PIXEL_MAJOR ? pix * fp.count + j : j * ((size_t)fp.w * fp.h) + pix;
+}
+
+// Look-ahead launches (FrameParams::la_ring): the finished pixels' part of the fp.count frames.  Every sample of such a pixel
+// is the listed colour, so its chain is `count` retrace steps with that colour from the image as it lies, the result of
+// step j going to frame j of the ring.  pt_final_replay's grid; runs after pt_prefix and on a prefix-cache hit alike.
+__global__ __launch_bounds__(256) void pt_final_retrace(FrameParams fp, const FinalPix *__restrict__ finals,
+                                                        const uint32_t *__restrict__ final_n) {
+    if (threadIdx.x >= min(final_n[blockIdx.x], 256u)) return;
+    const FinalPix e = finals[blockIdx.x * 256u + threadIdx.x];
+    uint32_t x = 0, y = 0;
+    if (!slot_to_pixel(fp, e.slot, x, y)) return;   // (never: pt_prefix stored the slots of valid pixels only)
+    const size_t pix = (size_t)y * fp.w + x;
+    const float4 at = fp.la_image[pix];
+    V3 prev = mk(at.x, at.y, at.z);
+    const V3 sum = mk(0.0f, 0.0f, 0.0f) + mk(e.r, e.g, e.b);   // the sum of a one-sample group, as pt_render forms it
+    for (uint32_t j = 0; j < fp.count; j++) {
+        prev = retrace_step(prev, sum, fp.first + j);
+        fp.la_ring[ring_at(fp, pix, j)] = make_float4(prev.x, prev.y, prev.z, 1.0f);
+    }
 }
 
 // Fused path, stage 2: one group of g lanes per LIVE pixel; each lane continues
@@ -576,6 +616,32 @@ PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__rest
     }
 }
 
+// A look-ahead launch ends here instead (FrameParams::la_ring): the wave's pixels take their `count` retrace steps in
+// sample order — pixel p from la_image[pix], step j with the sum of the one-sample group 0.0f + slot[p][j], the image after
+// it into frame j of the ring — and nothing is added to the accumulator.  Lane 4 p' + c owns channel c of the wave's pixel
+// p' (a wave owns at most QUEUE_MAX_PIXELS = 16 of them): the chain of a channel is sequential by definition, and the four
+// lanes of a pixel store its 16 bytes of a frame with one instruction (channel 3 is the alpha of 1).
+// Every lane of the wave calls it.
+static_assert(QUEUE_MAX_PIXELS * 4u <= 64u, "queue_replay maps (pixel, channel) to the wave's lanes");
+PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t lane = threadIdx.x, ch = lane & 3u;
+    const bool alpha = ch == 3u;
+    for (uint32_t pb = 0; pb < q.npix; pb += 16u) {
+        const uint32_t p = pb + (lane >> 2);
+        if (p >= q.npix) continue;
+        const size_t pix = (size_t)q.xy[p].y * fp.w + q.xy[p].x;
+        float prev = reinterpret_cast<const float *>(fp.la_image)[4u * pix + ch];
+        float *out = reinterpret_cast<float *>(fp.la_ring) + ch;
+        const LdsF32 sl = q.slot + 3u * (p * q.count) + (alpha ? 0u : ch);
+        for (uint32_t j = 0; j < q.count; j++) {
+            prev = retrace_step1(prev, 0.0f + sl[3u * j], fp.first + j);
+            out[4u * ring_at(fp, pix, j)] = alpha ? 1.0f : prev;
+        }
+    }
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
@@ -738,7 +804,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     if (threadIdx.x == 0 && q.npix)
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
-    queue_sums(q, fp, accum);
+    if (!COUNT && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one)
+    else queue_sums(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }
 
@@ -1016,7 +1083,8 @@ __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_
         for (int k = 0; k < 12; k++) atomicAdd(&wstat[k], v[k]);
     }
 #endif
-    queue_sums(q, fp, accum);
+    if (fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch)
+    else queue_sums(q, fp, accum);
 }
 
 // parity probe: one work-item per listed pixel-sample
@@ -1257,10 +1325,21 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
 
 // Fused path: pt_prefix (one work-item per pixel) + pt_samples (g lanes per live pixel).  While camera and scene rest
 // the first stage is pt_final_replay over what the last pt_prefix left (rt_context::PrefixCache).
-int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                 const BlockMask *mask) {
+// ring != NULL: a LOOK-AHEAD launch (rt_render_again, RT_OPT_LOOKAHEAD) — the same two stages over the same slot buffers and
+// the same prefix-cache entry, but the `count` samples become `count` frames of the ring (queue_replay, pt_final_retrace)
+// and the accumulator is not touched (accum is NULL).  The caller has checked what such a launch needs: no counters, an
+// unsharded context, the sample queue, the frame in one slot range, count <= the ring's frames.
+static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                            const BlockMask *mask, float4 *ring) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
+    if (ring) {
+        if (accum || mask || ctx->count_enabled || ctx->world != 1 || !ctx->sample_queue || count > QUEUE_SLOTS ||
+            (ctx->max_threads_per_launch >> glog2) < fp.slot_end)
+            return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
+        fp.la_ring = ring;
+        fp.la_image = ctx->image.p;
+    }
     DeviceScene sc = device_scene(ctx);
     uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
@@ -1335,11 +1414,13 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
 #define PT_CALL_PREFIX(C, A) PT_LAUNCH_PREFIX((pt_prefix<C, A>))
         bool accel_on = scene_has_accel(sc);
         // (a hit: the finished pixels' sums for this call's samples; everything else pt_prefix wrote lies there still)
-        if (hit) hipLaunchKernelGGL(pt_final_replay, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p, accum);
+        if (hit && !ring) hipLaunchKernelGGL(pt_final_replay, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p, accum);
+        else if (hit) {}   // (a look-ahead launch: pt_final_retrace below, after a traced prefix and a kept one alike)
         else if (fp.tree_cap) PT_LAUNCH_PREFIX((accel_on ? pt_prefix<false, true, true> : pt_prefix<false, false, true>));   // (never in counting builds)
         else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
 #undef PT_CALL_PREFIX
 #undef PT_LAUNCH_PREFIX
+        if (ring) hipLaunchKernelGGL(pt_final_retrace, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p);
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
         // the sample kernel over the live list
         // (the two parts of the list each end in a partial chunk: one unit more than capacity / chunk)
@@ -1385,6 +1466,16 @@ int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t 
         memcpy(pc.key_cam, cam_bits, sizeof cam_bits);
     }
     return RT_OK;
+}
+
+int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                 const BlockMask *mask) {
+    return launch_fused_any(ctx, cam, first, count, glog2, accum, mask, nullptr);
+}
+
+int launch_lookahead(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, float4 *ring) {
+    if (!ring || count < 1u) return fail(ctx, RT_EINVAL, "look-ahead launch without a ring");
+    return launch_fused_any(ctx, cam, first, count, group_log2_for(count), nullptr, nullptr, ring);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
@@ -1501,7 +1592,7 @@ const pt::KernelSet g_kernel_set = {
 #else
     "rocm-opencl",
 #endif
-    ks_launch_render, launch_fused, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
+    ks_launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin};
 
 }  // namespace

@@ -16,6 +16,10 @@ struct KernelSet {
     // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples, adding to `accum`
     int (*launch_fused)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
                         float4 *accum, const BlockMask *mask);
+    // look-ahead (rt_render_again, RT_OPT_LOOKAHEAD): the fused launch for samples first .. first+count-1, but instead of
+    // sums into the accumulator the image after each of them — `count` frames of W x H float4, frame-major, into `ring`,
+    // starting from the context's image as it lies.  Same slot buffers and prefix-cache entry as launch_fused.
+    int (*launch_lookahead)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, float4 *ring);
     // rt_trace_samples: d_in = n x, n y, n sample (uint32), d_out = 3 n floats
     int (*launch_probe)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out);
     // rt_render_features: pt_features, one rt_feature per pixel of the fp.w x fp.h frame into d_out

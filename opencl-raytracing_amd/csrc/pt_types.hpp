@@ -142,6 +142,10 @@ struct PixelTree {      // 8 x 16 + 8 x 80 = 768 bytes at 3 levels
 
 enum RenderMode { MODE_ACCUM = 0, MODE_TRACE = 1, MODE_RETRACE = 2 };
 
+#ifndef PT_RING_PIXEL_MAJOR
+#define PT_RING_PIXEL_MAJOR 0   // layout of the look-ahead ring: 0 frame-major (shipped), 1 pixel-major (A/B variant; pt_kernels.hip ring_at)
+#endif
+
 struct FrameParams {
     float cam[12];
     int w, h;
@@ -163,6 +167,11 @@ struct FrameParams {
     // unowned slot, so it never reaches the live list and the later kernels see only active work.
     const uint32_t *block_active;
     uint32_t blk_w_log2, blk_h_log2, blocks_x;
+    // look-ahead launches (rt_render_again under RT_OPT_LOOKAHEAD; NULL = an ordinary launch): instead of adding its samples
+    // to the accumulator, a pixel starts from la_image[pix] and takes `count` retrace steps (samples first .. first+count-1
+    // in order), the image after step j going to la_ring[j * w * h + pix] — frame-major, so a frame is handed out as one copy
+    float4 *la_ring;
+    const float4 *la_image;
 };
 
 // the decision-block mask of an adaptive round, as the launchers take it (NULL = every pixel)

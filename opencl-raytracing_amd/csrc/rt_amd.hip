@@ -477,10 +477,30 @@ int fail(rt_context *ctx, int code, const char *fmt, ...) {
 
 namespace {
 
+// pending look-ahead frames that no call will hand out any more
+void lookahead_drop(rt_context *ctx) {
+    rt_context::Lookahead &la = ctx->lookahead;
+    la.discarded += la.pending;
+    la.pending = 0;
+}
+
+// drops them unless they still continue the image as it lies: nothing they were computed from has changed since the batch
+void lookahead_validate(rt_context *ctx) {
+    const rt_context::Lookahead &la = ctx->lookahead;
+    if (la.pending && (la.key_generation != ctx->prefix_cache.generation || la.key_epoch != ctx->image_epoch ||
+                       la.next_sample != ctx->sample_counter + 1u))
+        lookahead_drop(ctx);
+}
+
 int alloc_frame(rt_context *ctx, int w, int h) {
     // what was made for the old frame goes with it
     ctx->slots = {};
     ctx->prefix_changed();
+    ctx->image_epoch++;
+    lookahead_drop(ctx);
+    ctx->lookahead.ring = {};
+    ctx->lookahead.ring_frames = 0;
+    ctx->lookahead.ring_failed = false;
     ctx->adaptive = {};
     ctx->features = {};
     ctx->denoise = {};
@@ -619,6 +639,7 @@ int rt_create(int device, int width, int height, rt_context **out) {
     ctx->ks = kernel_set_a0();
     // (the environment may switch the prefix cache off for a whole process: A/B of an unchanged caller)
     if (const char *e = getenv("RT_PREFIX_CACHE")) ctx->prefix_cache.enabled = strcmp(e, "0") != 0;
+    if (const char *e = getenv("RT_LOOKAHEAD")) { if (strcmp(e, "0") == 0) ctx->lookahead.k = 0; }   // (likewise)
     if ((rc = alloc_frame(ctx, width, height)) != RT_OK) return bail(rc);
     if ((rc = rt_set_seed(ctx, 0xC0FFEEull)) != RT_OK) return bail(rc);
     if ((rc = rt_set_textures(ctx, nullptr, 0, 0, 0)) != RT_OK) return bail(rc);
@@ -886,10 +907,86 @@ int rt_set_shard(rt_context *ctx, int rank, int world, int tile_w, int tile_h) {
     return RT_OK;
 }
 
+extern "C++" {
+namespace {
+
+#if PT_RING_PIXEL_MAJOR
+__global__ __launch_bounds__(256) void pt_ring_handout(const float4 *__restrict__ ring, float4 *__restrict__ image, size_t n,
+                                                       uint32_t frames, uint32_t j) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) image[i] = ring[i * frames + j];
+}
+#endif
+
+// frames a batch of a w x h frame may have at this sample counter: min(option, samples left, frames in the budget); < 2 = none
+uint32_t lookahead_frames(int w, int h, int k, uint32_t sample_counter) {
+    if (k < 2 || sample_counter >= RT_MAX_SAMPLE) return 0u;
+    const uint64_t frame_bytes = (uint64_t)w * (uint64_t)h * sizeof(float4);
+    uint64_t n = std::min<uint64_t>((uint64_t)k, RT_MAX_SAMPLE - sample_counter);
+    n = std::min<uint64_t>(n, RT_LOOKAHEAD_MAX_BYTES / frame_bytes);
+    return n >= 2u ? (uint32_t)n : 0u;
+}
+
+// The batch this rt_render_again call may start (0: the direct path): the call must repeat the previous call's camera,
+// the context must be one a look-ahead launch can serve (launch_fused_any), and the ring must exist.
+uint32_t lookahead_batch(rt_context *ctx, const uint32_t cam_bits[12]) {
+    rt_context::Lookahead &la = ctx->lookahead;
+    if (!la.have_last_cam || memcmp(la.last_cam, cam_bits, sizeof la.last_cam) != 0) return 0u;
+    if (ctx->count_enabled || ctx->world != 1 || !ctx->prefix_sharing || !ctx->sample_queue) return 0u;
+    uint32_t kp = 0;
+    if (rt_lookahead_plan(ctx->width, ctx->height, la.k, ctx->sample_counter, &kp) != RT_OK || kp < 2u) return 0u;
+    if ((ctx->max_threads_per_launch >> group_log2_for(kp)) < shard_of(ctx, 0, 1).slots) return 0u;   // several slot ranges
+    if (la.ring_frames < kp) {
+        if (la.ring_failed) return 0u;
+        // (as many frames as any batch of this frame size and option can have)
+        const uint32_t frames = lookahead_frames(ctx->width, ctx->height, la.k, 0u);
+        la.ring_frames = 0;
+        if (la.ring.alloc((size_t)frames * ctx->width * ctx->height) != hipSuccess) {   // not an error: the direct path
+            (void)hipGetLastError();
+            la.ring_failed = true;
+            return 0u;
+        }
+        la.ring_frames = frames;
+    }
+    return kp;
+}
+
+void remember_camera(rt_context *ctx, const float camera[12]) {
+    memcpy(ctx->lookahead.last_cam, camera, sizeof ctx->lookahead.last_cam);
+    ctx->lookahead.have_last_cam = true;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rt_lookahead_plan(int width, int height, int option_value, uint32_t sample_counter, uint32_t *batch_out) {
+    if (!batch_out) return fail(nullptr, RT_EINVAL, "batch_out is NULL");
+    *batch_out = 0;
+    if (width < 1 || height < 1 || width > RT_MAX_DIM || height > RT_MAX_DIM)
+        return fail(nullptr, RT_EINVAL, "frame size %dx%d outside 1..%d", width, height, RT_MAX_DIM);
+    if (option_value < 0 || option_value == 1 || option_value > RT_LOOKAHEAD_MAX)
+        return fail(nullptr, RT_EINVAL, "RT_OPT_LOOKAHEAD takes 0 or 2..%d", RT_LOOKAHEAD_MAX);
+    *batch_out = lookahead_frames(width, height, option_value, sample_counter);
+    return RT_OK;
+}
+
+int rt_lookahead_stats(rt_context *ctx, uint64_t *batches, uint64_t *served, uint64_t *direct, uint64_t *discarded) {
+    if (!ctx || !batches || !served || !direct || !discarded) return RT_EINVAL;
+    lookahead_validate(ctx);   // (frames that can no longer be handed out count as dropped from the change on)
+    *batches = ctx->lookahead.batches;
+    *served = ctx->lookahead.served;
+    *direct = ctx->lookahead.direct;
+    *discarded = ctx->lookahead.discarded;
+    return RT_OK;
+}
+
 int rt_render(rt_context *ctx, const float camera[12]) {
     int rc = check_ready(ctx, camera);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->image_epoch++;
+    lookahead_drop(ctx);
+    remember_camera(ctx, camera);
     ctx->sample_counter = 0;  // src/raytracer.cpp:128
     if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // queue.finish(), src/raytracer.cpp:140
@@ -901,6 +998,58 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     if (rc) return rc;
     if (ctx->sample_counter >= RT_MAX_SAMPLE) return fail(ctx, RT_EINVAL, "sample counter limit %u reached", RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // Look-ahead (RT_OPT_LOOKAHEAD): the image after sample k is a pure function of the image after sample k - 1 and of
+    // sample k, so while the camera rests one fused launch computes the next frames and the calls hand them out.
+    rt_context::Lookahead &la = ctx->lookahead;
+    uint32_t cam_bits[12];
+    memcpy(cam_bits, camera, sizeof cam_bits);
+    lookahead_validate(ctx);
+    if (la.pending && memcmp(la.key_cam, cam_bits, sizeof cam_bits) != 0) lookahead_drop(ctx);
+    const size_t frame_px = (size_t)ctx->width * ctx->height;
+    bool timed = false;   // the call has its entry in the event history
+    if (!la.pending) {
+        const uint32_t kp = lookahead_batch(ctx, cam_bits);
+        if (kp) {
+            if ((rc = ctx->ks->launch_lookahead(ctx, camera, ctx->sample_counter + 1u, kp, la.ring.p)) != RT_OK) return rc;
+            timed = true;
+            la.batches++;
+            la.pending = la.batch_frames = kp;
+            la.next_frame = 0;
+            la.next_sample = ctx->sample_counter + 1u;
+            la.key_generation = ctx->prefix_cache.generation;   // (after the launch: ensure_slots may have bumped it)
+            la.key_epoch = ctx->image_epoch;
+            memcpy(la.key_cam, cam_bits, sizeof cam_bits);
+        }
+    }
+    remember_camera(ctx, camera);
+    if (la.pending) {   // hand the next frame out
+        hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
+        if (!timed) {
+            HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
+        }
+#if PT_RING_PIXEL_MAJOR   // (A/B variant: a pixel's frames lie side by side, the hand-out gathers one of them)
+        hipLaunchKernelGGL(pt_ring_handout, dim3((unsigned)((frame_px + 255) / 256)), dim3(256), 0, ctx->stream, la.ring.p, ctx->image.p,
+                           frame_px, la.batch_frames, la.next_frame);
+        HIP_TRY(ctx, hipGetLastError());
+#else
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->image.p, la.ring.p + (size_t)la.next_frame * frame_px, frame_px * sizeof(float4),
+                                    hipMemcpyDeviceToDevice, ctx->stream));
+#endif
+        if (!timed) {
+            HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
+            ctx->ev_count++;
+        }
+        la.pending--;
+        la.next_frame++;
+        la.next_sample++;
+        la.served++;
+        ctx->sample_counter++;  // src/raytracer.cpp:147
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    }
+    ctx->image_epoch++;
+    la.direct++;
     ctx->sample_counter++;  // src/raytracer.cpp:147
     if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -954,6 +1103,7 @@ static int resolve_into(rt_context *ctx, int linear_only) {
 int rt_resolve(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->image_epoch++;
     return resolve_into(ctx, 0);
 }
 
@@ -1011,6 +1161,7 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
     rt_context::Adaptive &a = ctx->adaptive;
     a.blocks = 0;
+    ctx->image_epoch++;   // (the call ends in a resolve)
     const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, bytes, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.scratch.p, 0, bytes, ctx->stream));
@@ -1659,6 +1810,11 @@ int rt_set_option(rt_context *ctx, int option, int value) {
         case RT_OPT_SAMPLE_QUEUE: ctx->sample_queue = value != 0; return RT_OK;
         case RT_OPT_WALK_SLICES: ctx->walk_slices = value != 0; return RT_OK;
         case RT_OPT_WAVE_FILL: ctx->wave_fill = value != 0; return RT_OK;
+        case RT_OPT_LOOKAHEAD:
+            if (value < 0 || value == 1 || value > RT_LOOKAHEAD_MAX) return fail(ctx, RT_EINVAL, "RT_OPT_LOOKAHEAD takes 0 or 2..%d", RT_LOOKAHEAD_MAX);
+            ctx->lookahead.k = value;
+            ctx->lookahead.ring_failed = false;
+            return RT_OK;
         case RT_OPT_PREFIX_TREE:
             if (value < 0 || value > 2) return fail(ctx, RT_EINVAL, "RT_OPT_PREFIX_TREE takes 0, 1 or 2");
             ctx->prefix_tree = value;

@@ -58,6 +58,8 @@ namespace pt { struct KernelSet; }
 
 #define ACCEL_MIN_SPHERES 64
 #define RT_SPP_PER_LAUNCH 512u   // samples per pixel of one trace launch (rt_render_spp splits larger calls); = QUEUE_SLOTS of pt_kernels.hip
+#define RT_LOOKAHEAD_MAX 64                     // largest RT_OPT_LOOKAHEAD: frames of one look-ahead batch
+#define RT_LOOKAHEAD_MAX_BYTES (1ull << 30)     // budget of a context's look-ahead ring: a batch holds as many frames as fit
 #ifndef MESH_BVH_MIN_FACES
 #define MESH_BVH_MIN_FACES 32
 #endif
@@ -144,6 +146,10 @@ struct rt_context {
     //    `generation` is bumped (prefix_changed()) by every entry point that can change anything else on the list above
     //    or reallocates the buffers: scene, textures, random table / seed, every rt_set_option, shard, frame size,
     //    stream, counters on / off, ensure_slots growing.  When in doubt, bump.
+    //  * A look-ahead launch (launch_lookahead) is an ordinary fused launch as far as the slot buffers go: its pt_prefix
+    //    differs only in NOT adding the finished pixels' sums (accum == NULL), its sample kernel only in what it does with the
+    //    slots' radiances (queue_replay), and pt_final_retrace reads the finished list.  So it hits, misses and leaves an
+    //    entry under the same key, and an rt_render_spp call with the same camera afterwards may reuse its prefix.
     //  * A launch that writes the buffers only partly or for another purpose — a block mask (adaptive rounds), counters
     //    enabled, a frame cut into several slot ranges, an error — takes the full path and leaves the entry invalid.
     struct PrefixCache {
@@ -156,6 +162,29 @@ struct rt_context {
         uint64_t hits = 0, misses = 0;  // fused launches served from the entry / traced in full (rt_prefix_cache_stats)
     } prefix_cache;
     void prefix_changed() { prefix_cache.generation++; }
+    // Look-ahead for rt_render_again (RT_OPT_LOOKAHEAD): while the camera rests, ONE fused launch traces the next `pending`
+    // samples and replays the gamma-space running mean per pixel, the image after each sample going to a frame of `ring`;
+    // the following calls hand those frames out, one device copy each.  The ring is allocated on the first batch, reset by
+    // alloc_frame, freed with the context.  The frames are valid while nothing they were computed from has changed: the
+    // camera bits, the prefix generation (scene, seed, options, shard, size, stream, counters — prefix_changed()), the
+    // IMAGE EPOCH (bumped by whatever else writes the image: rt_render, rt_resolve, rt_render_adaptive, a direct
+    // rt_render_again, alloc_frame) and the sample counter being the batch's next index.
+    struct Lookahead {
+        int k = 16;                     // RT_OPT_LOOKAHEAD: 0 off, 2 .. 64 samples per batch
+        DevBuf<float4> ring;            // ring_frames frames of W x H, frame-major
+        size_t ring_frames = 0;
+        bool ring_failed = false;       // the allocation failed for this frame size / option: direct path until either changes
+        uint32_t pending = 0;           // frames of the last batch not handed out yet
+        uint32_t batch_frames = 0;      // frames the last batch computed
+        uint32_t next_frame = 0;        // the ring frame handed out next …
+        uint32_t next_sample = 0;       // … which is the image after this sample
+        uint64_t key_generation = 0, key_epoch = 0;
+        uint32_t key_cam[12] = {};
+        bool have_last_cam = false;     // the camera block of the previous rt_render / rt_render_again call
+        uint32_t last_cam[12] = {};
+        uint64_t batches = 0, served = 0, direct = 0, discarded = 0;   // rt_lookahead_stats
+    } lookahead;
+    uint64_t image_epoch = 0;
     bool wave_fill = true;              // RT_OPT_WAVE_FILL
     int prefix_tree = 1;                // RT_OPT_PREFIX_TREE: 0 off, 1 from PT_TREE_MIN_SAMPLES samples per call on, 2 always
     bool prefix_sharing = true;
@@ -292,6 +321,8 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     fp.block_active = nullptr;
     fp.blk_w_log2 = fp.blk_h_log2 = 0;
     fp.blocks_x = 0;
+    fp.la_ring = nullptr;
+    fp.la_image = nullptr;
     {
         volatile float c = (float)count;
         volatile float q = 1.0f / c;

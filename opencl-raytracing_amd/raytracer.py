@@ -30,12 +30,13 @@ SYMBOLS = (
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
     "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
-    "rt_prefix_cache_stats",
+    "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
 OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_PREFIX_CACHE = 9
+OPT_LOOKAHEAD = 10
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
 ARITH_NAMES = {"ieee": ARITH_IEEE, "rocm-opencl-nocontract": ARITH_ROCM_OCL_NOCONTRACT, "rocm-opencl": ARITH_ROCM_OCL}
 
@@ -116,6 +117,7 @@ def load_library(path=LIB_PATH):
     _abi.adaptive_prototypes(lib)
     _abi.denoise_prototypes(lib)
     _abi.prefix_cache_prototypes(lib)
+    _abi.lookahead_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -144,6 +146,17 @@ def make_random_table(seed):
     if rc:
         raise RtError(rc, lib.rt_last_error(None).decode())
     return out
+
+
+def lookahead_plan(width, height, option=16, sample_counter=0):
+    """Samples the look-ahead launch of a renderAgain call would trace (rt_lookahead_plan; host-only, no device needed):
+    0 = that call runs the direct kernel."""
+    lib = load_library()
+    out = C.c_uint32()
+    rc = lib.rt_lookahead_plan(int(width), int(height), int(option), int(sample_counter), C.byref(out))
+    if rc:
+        raise RtError(rc, lib.rt_last_error(None).decode())
+    return int(out.value)
 
 
 def _cam_block(camera):
@@ -236,6 +249,7 @@ class RayTracer:
 
     OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
     OPT_PREFIX_CACHE = 9
+    OPT_LOOKAHEAD = 10
 
     def setOption(self, option, value):
         self._check(self._lib.rt_set_option(self._ctx, option, int(value)))
@@ -439,6 +453,15 @@ class RayTracer:
         hits, misses = C.c_uint64(), C.c_uint64()
         self._check(self._lib.rt_prefix_cache_stats(self._ctx, C.byref(hits), C.byref(misses)))
         return int(hits.value), int(misses.value)
+
+    def lookaheadStats(self):
+        """(batches, served, direct, discarded) of renderAgain since the context was made (OPT_LOOKAHEAD): look-ahead
+        launches, calls served from a look-ahead frame, calls that ran the direct kernel, frames computed and dropped."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self._lib.rt_lookahead_stats(self._ctx, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    lookaheadPlan = staticmethod(lookahead_plan)
 
     def setArith(self, arith):
         """Select the arithmetic policy of the trace kernels (RT_OPT_ARITH): ARITH_IEEE (default, the CPU oracle's
