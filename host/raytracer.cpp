@@ -119,6 +119,14 @@ void RayTracer::prefixCacheStats(uint64_t &hits, uint64_t &misses) const {
     check(rt_prefix_cache_stats(ctx, &hits, &misses));
 }
 
+void RayTracer::setExactGrid(bool on) { check(rt_set_option(ctx, RT_OPT_EXACT_GRID, on ? 1 : 0)); }
+
+RayTracer::SampleGridStats RayTracer::sampleGridStats() const {
+    SampleGridStats s{};
+    check(rt_sample_grid_stats(ctx, &s.launches, &s.exact, &s.workgroups, &s.live_last));
+    return s;
+}
+
 uint32_t RayTracer::sampleCounter() const {
     uint32_t v = 0;
     rt_sample_counter(ctx, &v);

@@ -78,6 +78,12 @@ public:
     void setLookahead(int samples);
     struct LookaheadStats { uint64_t batches, served, direct, discarded; };
     LookaheadStats lookaheadStats() const;
+    // RT_OPT_EXACT_GRID: while renderSamples reuses the kept prefix, its sample kernel is launched with exactly the
+    // workgroups that own a live pixel (default on; same pixels either way).  The counts since construction: fused
+    // launches, those sized by the known live list, workgroups launched in all, workgroups of the last exact launch.
+    void setExactGrid(bool on);
+    struct SampleGridStats { uint64_t launches, exact, workgroups, live_last; };
+    SampleGridStats sampleGridStats() const;
     uint32_t sampleCounter() const;
     rt_context *context() { return ctx; }
     SceneCreator &sceneCreator() { return scene; }

@@ -455,6 +455,13 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
                                            environment holds RT_LOOKAHEAD=0 starts its contexts with 0.  Same result bit for bit.
                                            The library assumes that nobody else writes the image: a zero-copy consumer that WRITES
                                            through rt_device_image between rt_render_again calls must set this option to 0       */
+#define RT_OPT_EXACT_GRID 11            /* 1 (default): while a fused call reuses the kept prefix (RT_OPT_PREFIX_CACHE), the host learns
+                                           the length of the live list — one asynchronous 128-byte copy on the first call that
+                                           reuses it, never waited for — and from then on launches the sample kernel with exactly
+                                           the workgroups that own a pixel (rt_sample_units), none at all for a frame without live
+                                           pixels; 0: always the grid for "every pixel is live" (its surplus workgroups leave at
+                                           once).  A process whose environment holds RT_EXACT_GRID=0 starts its contexts with 0.
+                                           Same result bit for bit                                                          */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's
@@ -559,6 +566,26 @@ int rt_lookahead_stats(rt_context *ctx, uint64_t *batches, uint64_t *served, uin
  * RT_MAX_SAMPLE - sample_counter, frames of the ring budget of 1 GiB), or 0 (the direct kernel) where that is below 2.
  * rt_render_again calls this very function.  RT_EINVAL: an option value the option refuses, a size outside 1..RT_MAX_DIM. */
 int rt_lookahead_plan(int width, int height, int option_value, uint32_t sample_counter, uint32_t *batch_out);
+
+/* Host-only (no device, no context): the workgroups (pixel groups, for the fixed-lane kernel) of a sample-kernel launch
+ * that own at least one pixel, for a live list of capacity seg_cap whose counters read count_light and count_heavy and
+ * pixels_per_unit pixels per workgroup — the host's restatement of the kernels' live_take: both counts clamped to the
+ * capacity as the kernels clamp them (light first, heavy to what is left), ceil(heavy / p) units for the heavy part, which
+ * the kernels hand out first, then ceil(light / p).  Every unit below the result takes a pixel, none from it on.  The
+ * launcher calls this very function (RT_OPT_EXACT_GRID).  RT_EINVAL: pixels_per_unit 0, units_out NULL. */
+int rt_sample_units(uint32_t seg_cap, uint32_t pixels_per_unit, uint32_t count_light, uint32_t count_heavy, uint32_t *units_out);
+
+/* Sample-kernel launches of this context's fused calls since rt_create (RT_OPT_EXACT_GRID): `launches` fused launches that
+ * reached the sample stage; `exact` of them sized by the known length of the live list (a launch of no workgroup at all
+ * included); `workgroups` launched by all of them together; `live_last` the workgroups of the last exact launch, all of
+ * which own a pixel.  The direct path (rt_render, rt_render_again without look-ahead) does not count. */
+int rt_sample_grid_stats(rt_context *ctx, uint64_t *launches, uint64_t *exact, uint64_t *workgroups, uint64_t *live_last);
+
+/* Test instrumentation: what the last fused launch's sample kernel divided — out = {capacity of the live list (seg_cap),
+ * pixels per unit of that launch, the light counter, the heavy counter}, the counters read from the device as they lie
+ * (synchronises the stream).  rt_sample_units of these four is the number of workgroups with a pixel.  RT_EINVAL before
+ * the first fused launch. */
+int rt_debug_live_list(rt_context *ctx, uint32_t out[4]);
 
 /* Name, CU count and arch of the context's device, e.g. "gfx950". */
 int rt_device_info(rt_context *ctx, char *name, size_t name_len, int *cu_count, char *arch, size_t arch_len);

@@ -158,6 +158,14 @@ def lookahead_prototypes(lib):
     lib.rt_lookahead_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]
 
 
+def sample_grid_prototypes(lib):
+    """ctypes prototypes of rt_sample_units / rt_sample_grid_stats (RT_OPT_EXACT_GRID)."""
+    p64, u32 = C.POINTER(C.c_uint64), C.c_uint32
+    lib.rt_sample_units.argtypes = [u32, u32, u32, u32, C.POINTER(u32)]
+    lib.rt_sample_grid_stats.argtypes = [C.c_void_p, p64, p64, p64, p64]
+    lib.rt_debug_live_list.argtypes = [C.c_void_p, C.POINTER(u32)]
+
+
 def split_features(rec):
     """(H, W) FEATURE records → dict of (H, W, ...) arrays (RayTracer.features())."""
     return {"position": rec["pos"].copy(), "depth": rec["t"].copy(), "normal": rec["normal"].copy(),

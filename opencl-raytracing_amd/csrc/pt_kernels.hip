@@ -371,6 +371,12 @@ __global__ __launch_bounds__(256) void pt_samples(DeviceScene sc, FrameParams fp
                                                   const uint32_t *__restrict__ live_count,
                                                   float4 *__restrict__ accum, unsigned long long *counters) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    // A workgroup whose FIRST pixel group lies beyond the live list owns no pixel at all (live_take hands the list out in
+    // unit order): it leaves before anything is staged — no barrier, and only zeros to add to the counters.
+    {
+        uint32_t e0 = 0;
+        if (live_take(fp, live_count, (blockIdx.x * 256u) >> fp.group_log2, 1u, e0) == 0u) return;
+    }
     LaneCounters cn;
     if (COUNT) zero_counters(cn);
     Ctx c{sc, stage_materials(sc, s_mat), &cn};
@@ -512,10 +518,11 @@ struct WaveQueue {
     float inv_count;
 };
 
-// Takes the wave's pixels off the live list and stages their records and coordinates; `lds` is the workgroup's dynamic
+// Stages the records and coordinates of the wave's pixels — the `npix` live-list entries from `pix0` on, which the kernel
+// took with live_take before it staged anything (a wave that took none has left by now); `lds` is the workgroup's dynamic
 // LDS and face_f4 the float4 of face records the kernel staged in it (queue_static_f4).  Every lane of the wave calls it (contains the wave's fence and barrier).
 PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const PixelRec *__restrict__ recs,
-                             const uint32_t *__restrict__ live, const uint32_t *__restrict__ live_count,
+                             const uint32_t *__restrict__ live, uint32_t npix, uint32_t pix0,
                              uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
     float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
     WaveQueue q;
@@ -523,8 +530,7 @@ PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const
     q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
     q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
     const uint32_t lane = threadIdx.x;
-    uint32_t pix0 = 0;
-    q.npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    q.npix = npix;
     q.count = fp.count;
     q.total = q.npix * q.count;
     for (uint32_t i = lane; i < q.npix * QUEUE_REC_F4; i += 64u) {
@@ -653,6 +659,12 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                                                     float4 *__restrict__ accum, unsigned long long *counters,
                                                     uint32_t pixels_per_wave) {
     extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
+    // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
+    // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
+    // anything is staged: no barrier, no sums, and only zeros to add to the counters.
+    uint32_t pix0 = 0;
+    const uint32_t npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    if (npix == 0u) return;
     float4 *s_mat = s_dyn;
     LaneCounters cn;
     if (COUNT) zero_counters(cn);
@@ -666,7 +678,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = queue_stage(sc, fp, recs, live, live_count, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
+    const WaveQueue q = queue_stage(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
     uint32_t next = 0;  // wave-uniform head of the queue
     bool active = false;
@@ -850,11 +862,15 @@ __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_
 #endif
                                                     ) {
     extern __shared__ float4 s_dyn[];
+    // (as in pt_samples_q: a wave without pixels leaves before anything is staged)
+    uint32_t pix0 = 0;
+    const uint32_t npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    if (npix == 0u) return;
     float4 *s_mat = s_dyn;
     Ctx c{sc, stage_materials(sc, s_mat), nullptr};
     c.lwin = staged_winners(sc, s_mat);
     c.lpln = staged_planes(sc, s_mat);
-    const WaveQueue q = queue_stage(sc, fp, recs, live, live_count, pixels_per_wave, s_dyn, 0u);
+    const WaveQueue q = queue_stage(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, 0u);
 
     // The walks of a bounce, in the reference's order: jobs[j] = (mesh index, material of its model), model by
     // model, mesh by mesh.  hitModel's "nearest of my meshes" followed by hitScene's "nearer than the best so
@@ -1359,6 +1375,26 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
     const bool hit = pc.enabled && pc.valid && keepable && pc.key_generation == pc.generation && pc.key_tree_on == tree_on &&
                      memcmp(pc.key_cam, cam_bits, sizeof cam_bits) == 0;
     pc.valid = false;
+    // The entry's live counters on the host (rt_context::PrefixCache, RT_OPT_EXACT_GRID): dropped with the entry by every
+    // launch that does not hit; learnt by an asynchronous copy that the FIRST hit enqueues and later hits only ask after.
+    rt_context::SampleGrid &sg = ctx->sample_grid;
+    if (!hit) pc.counts_state = rt_context::PrefixCache::COUNTS_UNKNOWN;
+    else if (sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_UNKNOWN) {
+        HIP_TRY(ctx, hipMemcpyAsync(sg.h_counts, live_count, LIVE_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(sg.counts_ev, ctx->stream));
+        pc.counts_state = rt_context::PrefixCache::COUNTS_IN_FLIGHT;
+    } else if (sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_IN_FLIGHT) {
+        const hipError_t q = hipEventQuery(sg.counts_ev);
+        if (q == hipSuccess) {
+            pc.count_light = sg.h_counts[0];
+            pc.count_heavy = sg.h_counts[LIVE_HEAVY_COUNTER];
+            pc.counts_state = rt_context::PrefixCache::COUNTS_KNOWN;
+        } else {
+            (void)hipGetLastError();   // (not ready is no error of this launch)
+            if (q != hipErrorNotReady) return fail(ctx, RT_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
+        }
+    }
+    const bool exact = hit && sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_KNOWN;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
     for (uint32_t b = 0; b < slots; b += slots_per_launch) {
@@ -1424,9 +1460,20 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
         // the sample kernel over the live list
         // (the two parts of the list each end in a partial chunk: one unit more than capacity / chunk)
-        auto units = [&](uint32_t per_unit) { return (fp.seg_cap + per_unit - 1) / per_unit + 1u; };
+        // — unless the host knows the entry's counts (a hit is one slot range): then exactly the units that own a pixel
+        // (rt_sample_units, the host's restatement of live_take), and no launch at all where there is none
+        uint32_t launched = 0;
+        auto units = [&](uint32_t per_unit) {
+            uint32_t u = (fp.seg_cap + per_unit - 1) / per_unit + 1u;
+            sg.last_cap = fp.seg_cap;
+            sg.last_per_unit = per_unit;
+            if (exact) (void)rt_sample_units(fp.seg_cap, per_unit, pc.count_light, pc.count_heavy, &u);
+            return u;
+        };
+        // (the launch statement runs only for a grid that is not empty; `launched` is what rt_sample_grid_stats reports)
+#define PT_GRID(U, LAUNCH) do { launched = (U); if (launched) { LAUNCH; } } while (0)
 #define PT_CALL_QUEUE_W(C, A, G, W) \
-    hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), dim3(units(ppw)), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw)
+    PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw))
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
         if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
@@ -1434,13 +1481,15 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
     } while (0)
 #define PT_CALL_FIXED(C, A) \
-    hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p)
+    PT_GRID(grid2.x, hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p))
         if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled) {
             // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
             const bool multi = ctx->walk_jobs.n != 1;
             uint32_t ppw_w = queue_pixels_per_wave(count, multi ? PT_W_WAVES_MULTI : PT_W_WAVES, static_f4);
             if (ppw_w > ppw_par) ppw_w = ppw_par;
-            hipLaunchKernelGGL(multi ? pt_samples_w<true> : pt_samples_w<false>, dim3(units(ppw_w)), dim3(64), queue_lds(ppw_w), ctx->stream,
+            launched = units(ppw_w);
+            if (launched)
+            hipLaunchKernelGGL(multi ? pt_samples_w<true> : pt_samples_w<false>, dim3(launched), dim3(64), queue_lds(ppw_w), ctx->stream,
                                sc, fp, ss.recs.p, ss.live.p, live_count, accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
 #ifdef PT_WSTAT
                                , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
@@ -1454,6 +1503,10 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
 #undef PT_CALL_QUEUE
 #undef PT_CALL_QUEUE_W
 #undef PT_CALL_FIXED
+#undef PT_GRID
+        sg.launches++;
+        sg.workgroups += launched;
+        if (exact) { sg.exact_launches++; sg.live_last = launched; }
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));

@@ -640,6 +640,9 @@ int rt_create(int device, int width, int height, rt_context **out) {
     // (the environment may switch the prefix cache off for a whole process: A/B of an unchanged caller)
     if (const char *e = getenv("RT_PREFIX_CACHE")) ctx->prefix_cache.enabled = strcmp(e, "0") != 0;
     if (const char *e = getenv("RT_LOOKAHEAD")) { if (strcmp(e, "0") == 0) ctx->lookahead.k = 0; }   // (likewise)
+    if (const char *e = getenv("RT_EXACT_GRID")) ctx->sample_grid.exact = strcmp(e, "0") != 0;       // (likewise)
+    if (hipHostMalloc((void **)&ctx->sample_grid.h_counts, LIVE_COUNT_STRIDE * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->sample_grid.counts_ev, hipEventDisableTiming) != hipSuccess) { ctx->error = "live-count read-back allocation failed"; return bail(RT_EHIP); }
     if ((rc = alloc_frame(ctx, width, height)) != RT_OK) return bail(rc);
     if ((rc = rt_set_seed(ctx, 0xC0FFEEull)) != RT_OK) return bail(rc);
     if ((rc = rt_set_textures(ctx, nullptr, 0, 0, 0)) != RT_OK) return bail(rc);
@@ -654,6 +657,8 @@ void rt_destroy(rt_context *ctx) {
     for (int i = 0; i < rt_context::EV_RING; i++)
         for (int k = 0; k < 3; k++)
             if (ctx->ev[i][k]) (void)hipEventDestroy(ctx->ev[i][k]);
+    if (ctx->sample_grid.counts_ev) (void)hipEventDestroy(ctx->sample_grid.counts_ev);
+    if (ctx->sample_grid.h_counts) (void)hipHostFree(ctx->sample_grid.h_counts);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -1810,6 +1815,7 @@ int rt_set_option(rt_context *ctx, int option, int value) {
         case RT_OPT_SAMPLE_QUEUE: ctx->sample_queue = value != 0; return RT_OK;
         case RT_OPT_WALK_SLICES: ctx->walk_slices = value != 0; return RT_OK;
         case RT_OPT_WAVE_FILL: ctx->wave_fill = value != 0; return RT_OK;
+        case RT_OPT_EXACT_GRID: ctx->sample_grid.exact = value != 0; return RT_OK;
         case RT_OPT_LOOKAHEAD:
             if (value < 0 || value == 1 || value > RT_LOOKAHEAD_MAX) return fail(ctx, RT_EINVAL, "RT_OPT_LOOKAHEAD takes 0 or 2..%d", RT_LOOKAHEAD_MAX);
             ctx->lookahead.k = value;
@@ -1846,6 +1852,43 @@ int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses) {
     if (!ctx || !hits || !misses) return RT_EINVAL;
     *hits = ctx->prefix_cache.hits;
     *misses = ctx->prefix_cache.misses;
+    return RT_OK;
+}
+
+int rt_sample_units(uint32_t seg_cap, uint32_t pixels_per_unit, uint32_t count_light, uint32_t count_heavy, uint32_t *units_out) {
+    if (!units_out) return fail(nullptr, RT_EINVAL, "units_out is NULL");
+    *units_out = 0;
+    if (pixels_per_unit == 0) return fail(nullptr, RT_EINVAL, "pixels_per_unit is 0");
+    // live_take's clamps, then its two parts: the heavy one first
+    const uint32_t cnt_l = std::min(count_light, seg_cap);
+    const uint32_t cnt_h = std::min(count_heavy, seg_cap - cnt_l);
+    const uint32_t units_h = cnt_h / pixels_per_unit + (cnt_h % pixels_per_unit != 0u);
+    const uint32_t units_l = cnt_l / pixels_per_unit + (cnt_l % pixels_per_unit != 0u);
+    *units_out = units_h + units_l;   // (<= seg_cap: no overflow)
+    return RT_OK;
+}
+
+int rt_sample_grid_stats(rt_context *ctx, uint64_t *launches, uint64_t *exact, uint64_t *workgroups, uint64_t *live_last) {
+    if (!ctx || !launches || !exact || !workgroups || !live_last) return RT_EINVAL;
+    *launches = ctx->sample_grid.launches;
+    *exact = ctx->sample_grid.exact_launches;
+    *workgroups = ctx->sample_grid.workgroups;
+    *live_last = ctx->sample_grid.live_last;
+    return RT_OK;
+}
+
+int rt_debug_live_list(rt_context *ctx, uint32_t out[4]) {
+    if (!ctx || !out) return RT_EINVAL;
+    const rt_context::Slots &ss = ctx->slots;
+    if (!ss.live.p || ctx->sample_grid.last_per_unit == 0) return fail(ctx, RT_EINVAL, "no fused launch yet");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint32_t h[LIVE_COUNT_STRIDE];
+    HIP_TRY(ctx, hipMemcpyAsync(h, ss.live.p + ss.capacity + 256u, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = ctx->sample_grid.last_cap;
+    out[1] = ctx->sample_grid.last_per_unit;
+    out[2] = h[0];
+    out[3] = h[LIVE_HEAVY_COUNTER];
     return RT_OK;
 }
 

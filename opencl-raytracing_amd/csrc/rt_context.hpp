@@ -160,8 +160,31 @@ struct rt_context {
         uint32_t key_cam[12] = {};
         bool key_tree_on = false;
         uint64_t hits = 0, misses = 0;  // fused launches served from the entry / traced in full (rt_prefix_cache_stats)
+        // The entry's live counters as the HOST knows them (RT_OPT_EXACT_GRID): while the entry is valid nothing writes
+        // the live-count block, so a launch that hits may be sized for the live list instead of for "every pixel is live".
+        //  * The first launch that HITS the entry enqueues an asynchronous copy of the block into `sample_grid.h_counts`
+        //    (pinned, owned by the context) with `sample_grid.counts_ev` behind it — not the miss: a camera that moves with
+        //    every frame never hits and never pays for a copy.  Later hits only query the event, never wait on it; from
+        //    the first query that finds it complete the counts are known and rt_sample_units sizes the launch.
+        //  * The counts are part of the entry: EVERY fused launch that is not a hit drops them (launch_fused), and whatever
+        //    invalidates or re-keys the entry — prefix_changed(), another camera, trees on / off, a masked, counting or
+        //    split launch — makes the next launch such a one.  A copy still in flight then lands in the pinned block
+        //    unread; a later copy follows it on the same stream (rt_set_stream synchronises the old one first).
+        enum { COUNTS_UNKNOWN, COUNTS_IN_FLIGHT, COUNTS_KNOWN } counts_state = COUNTS_UNKNOWN;
+        uint32_t count_light = 0, count_heavy = 0;   // live_count[0], live_count[LIVE_HEAVY_COUNTER], unclamped
     } prefix_cache;
     void prefix_changed() { prefix_cache.generation++; }
+    // RT_OPT_EXACT_GRID and rt_sample_grid_stats; the pinned block and the event are made by rt_create and die with the context
+    struct SampleGrid {
+        bool exact = true;              // RT_OPT_EXACT_GRID (rt_create: the environment's RT_EXACT_GRID=0 turns it off)
+        uint32_t *h_counts = nullptr;   // pinned: LIVE_COUNT_STRIDE words, the target of the counts' copy
+        hipEvent_t counts_ev = nullptr;
+        uint64_t launches = 0;          // fused launches that reached the sample stage
+        uint64_t exact_launches = 0;    // … sized by the known counts (a launch of zero workgroups included)
+        uint64_t workgroups = 0;        // sample-kernel workgroups launched, all launches together
+        uint64_t live_last = 0;         // workgroups of the last EXACT launch's kernel that own a pixel (= its grid)
+        uint32_t last_cap = 0, last_per_unit = 0;   // seg_cap and pixels per unit of the last launch (rt_debug_live_list)
+    } sample_grid;
     // Look-ahead for rt_render_again (RT_OPT_LOOKAHEAD): while the camera rests, ONE fused launch traces the next `pending`
     // samples and replays the gamma-space running mean per pixel, the image after each sample going to a frame of `ring`;
     // the following calls hand those frames out, one device copy each.  The ring is allocated on the first batch, reset by

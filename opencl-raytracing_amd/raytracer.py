@@ -31,12 +31,14 @@ SYMBOLS = (
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
     "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
+    "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
 OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
 OPT_PREFIX_CACHE = 9
 OPT_LOOKAHEAD = 10
+OPT_EXACT_GRID = 11
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
 ARITH_NAMES = {"ieee": ARITH_IEEE, "rocm-opencl-nocontract": ARITH_ROCM_OCL_NOCONTRACT, "rocm-opencl": ARITH_ROCM_OCL}
 
@@ -118,6 +120,7 @@ def load_library(path=LIB_PATH):
     _abi.denoise_prototypes(lib)
     _abi.prefix_cache_prototypes(lib)
     _abi.lookahead_prototypes(lib)
+    _abi.sample_grid_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -154,6 +157,18 @@ def lookahead_plan(width, height, option=16, sample_counter=0):
     lib = load_library()
     out = C.c_uint32()
     rc = lib.rt_lookahead_plan(int(width), int(height), int(option), int(sample_counter), C.byref(out))
+    if rc:
+        raise RtError(rc, lib.rt_last_error(None).decode())
+    return int(out.value)
+
+
+def sample_units(seg_cap, pixels_per_unit, count_light, count_heavy):
+    """Workgroups of a sample-kernel launch that own a pixel, for a live list of capacity `seg_cap` whose two counters
+    read `count_light` and `count_heavy` (rt_sample_units; host-only, no device needed): what a launch under
+    OPT_EXACT_GRID has."""
+    lib = load_library()
+    out = C.c_uint32()
+    rc = lib.rt_sample_units(int(seg_cap), int(pixels_per_unit), int(count_light), int(count_heavy), C.byref(out))
     if rc:
         raise RtError(rc, lib.rt_last_error(None).decode())
     return int(out.value)
@@ -250,6 +265,7 @@ class RayTracer:
     OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
     OPT_PREFIX_CACHE = 9
     OPT_LOOKAHEAD = 10
+    OPT_EXACT_GRID = 11
 
     def setOption(self, option, value):
         self._check(self._lib.rt_set_option(self._ctx, option, int(value)))
@@ -462,6 +478,23 @@ class RayTracer:
         return tuple(int(x.value) for x in v)
 
     lookaheadPlan = staticmethod(lookahead_plan)
+
+    def sampleGridStats(self):
+        """(launches, exact, workgroups, live_last) of the fused calls' sample kernels since the context was made
+        (OPT_EXACT_GRID): launches, those sized by the known length of the live list, workgroups launched in all, and the
+        workgroups — all of them with a pixel — of the last exact launch."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self._lib.rt_sample_grid_stats(self._ctx, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    sampleUnits = staticmethod(sample_units)
+
+    def liveList(self):
+        """(seg_cap, pixels per unit, light count, heavy count) of the last fused launch's sample kernel, the counts
+        read from the device (rt_debug_live_list; test instrumentation, synchronises)."""
+        out = (C.c_uint32 * 4)()
+        self._check(self._lib.rt_debug_live_list(self._ctx, out))
+        return tuple(int(v) for v in out)
 
     def setArith(self, arith):
         """Select the arithmetic policy of the trace kernels (RT_OPT_ARITH): ARITH_IEEE (default, the CPU oracle's
