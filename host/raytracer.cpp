@@ -105,6 +105,20 @@ const float *RayTracer::denoise(const Camera *camera, const rt_denoise_params &p
     return pixels.data();
 }
 
+const float *RayTracer::denoiseVariance(const Camera *camera, const rt_denoise_variance_params &params) {
+    if (camera) renderFeatures(camera);
+    check(rt_denoise_variance(ctx, &params));
+    pixels.resize((size_t)width * height * 4);
+    check(rt_read_denoised(ctx, pixels.data(), pixels.size() * sizeof(float)));
+    return pixels.data();
+}
+
+std::vector<float> RayTracer::variance(int which) {
+    std::vector<float> v((size_t)width * height);
+    check(rt_read_variance(ctx, which, v.data(), v.size() * sizeof(float)));
+    return v;
+}
+
 void RayTracer::setPrefixCache(bool on) { check(rt_set_option(ctx, RT_OPT_PREFIX_CACHE, on ? 1 : 0)); }
 
 void RayTracer::setLookahead(int samples) { check(rt_set_option(ctx, RT_OPT_LOOKAHEAD, samples)); }

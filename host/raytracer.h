@@ -67,6 +67,10 @@ public:
     // features for `camera` (unless it is null: then the last ones) + rt_denoise + read back into the image that
     // transferImage() / lastImage() return; the accumulator is left as it was
     const float *denoise(const Camera *camera, const rt_denoise_params &params);
+    // the same with the variance-guided filter for low sample counts (rt_denoise_variance); variance(0) is its 7x7
+    // luminance-variance estimate v0, variance(1) the filtered variance v(L), W x H floats each
+    const float *denoiseVariance(const Camera *camera, const rt_denoise_variance_params &params);
+    std::vector<float> variance(int which = 0);
     // RT_OPT_PREFIX_CACHE: while camera and scene rest, renderSamples keeps the traced prefix from call to call (default
     // on; same pixels either way); the counts of fused launches that reused it / traced it in full
     void setPrefixCache(bool on);

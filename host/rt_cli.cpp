@@ -4,7 +4,7 @@
 //          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive [--lookahead N]]
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
-//          [--denoise [--denoise-iterations N] [--sigma c,n,x,a]] [--aov PREFIX]
+//          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S]]] [--aov PREFIX]
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -16,6 +16,9 @@
 // denoised frame.  The denoiser reads the linear accumulator; --progressive keeps its running mean in the image only, so
 // there the same samples 0..spp-1 are first accumulated with the fused path.  --aov writes the feature buffers as
 // PREFIX_normal.pfm, PREFIX_albedo.pfm and PREFIX_depth.pfm (the hit's t, +inf where the primary ray misses).
+// --denoise --variance-guided selects the variance-guided filter for low sample counts instead (rt_denoise_variance:
+// --sigma-luminance, default 4, > 0, inf = term off; --sigma keeps its four values, of which the colour one is unused);
+// --aov then also writes PREFIX_variance.pfm, its 7x7 luminance-variance estimate v0.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -41,7 +44,8 @@ static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
                  "[--seed N] [--progressive [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a]] [--aov PREFIX]\n";
+                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S]]] "
+                 "[--aov PREFIX]\n";
     std::exit(2);
 }
 
@@ -109,6 +113,8 @@ int main(int argc, char **argv) {
     long dn_iterations = 0;
     float sigmas[4] = {0.5f, 0.1f, 2.0f, 0.2f};
     bool sigmas_given = false;
+    bool variance_guided = false, sigma_l_given = false;
+    float sigma_l = 4.0f;
     std::string aov_prefix;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -141,15 +147,23 @@ int main(int argc, char **argv) {
         else if ((v = val("--counts"))) out_counts = v;
         else if ((v = val("--lookahead"))) { lookahead = parse_int(v, 0, 64); if (lookahead == 1) usage(); }
         else if ((v = val("--denoise-iterations"))) dn_iterations = parse_int(v, 1, RT_DENOISE_MAX_ITERATIONS);
+        else if ((v = val("--sigma-luminance"))) {
+            char *end = nullptr;
+            sigma_l = std::strtof(v, &end);
+            if (!*v || *end || !(sigma_l > 0.0f)) usage();
+            sigma_l_given = true;
+        }
         else if ((v = val("--sigma"))) { parse_sigmas(v, sigmas); sigmas_given = true; }
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
         else if (a == "--denoise") denoise = true;
+        else if (a == "--variance-guided") variance_guided = true;
         else if (a == "--progressive") progressive = true;
         else usage();
     }
     if (spp < 1 || w < 1 || h < 1) usage();
     if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
-    if (!denoise && (dn_iterations || sigmas_given)) usage();              // denoise-only flags
+    if (!denoise && (dn_iterations || sigmas_given || variance_guided || sigma_l_given)) usage();   // denoise-only flags
+    if (sigma_l_given && !variance_guided) usage();
     if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
@@ -227,9 +241,11 @@ int main(int argc, char **argv) {
             tracer.renderSamples(&camera, 0, (uint32_t)spp);
         }
         rt_denoise_params dp{(uint32_t)dn_iterations, sigmas[0], sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
+        rt_denoise_variance_params vp{(uint32_t)dn_iterations, sigma_l, sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
         auto d0 = std::chrono::steady_clock::now();
-        img = tracer.denoise(nullptr, dp);
-        std::cout << "denoised: " << dn_iterations << " iterations, sigma " << sigmas[0] << "," << sigmas[1] << ","
+        img = variance_guided ? tracer.denoiseVariance(nullptr, vp) : tracer.denoise(nullptr, dp);
+        std::cout << "denoised" << (variance_guided ? " (variance-guided)" : "") << ": " << dn_iterations
+                  << " iterations, sigma " << (variance_guided ? sigma_l : sigmas[0]) << "," << sigmas[1] << ","
                   << sigmas[2] << "," << sigmas[3] << ": "
                   << std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count() * 1e3
                   << " ms incl. read-back" << std::endl;
@@ -241,6 +257,7 @@ int main(int argc, char **argv) {
         write_pfm(aov_prefix + "_normal.pfm", fd, stride, offsetof(rt_feature, normal) / sizeof(float), 3, w, h);
         write_pfm(aov_prefix + "_albedo.pfm", fd, stride, offsetof(rt_feature, albedo) / sizeof(float), 3, w, h);
         write_pfm(aov_prefix + "_depth.pfm", fd, stride, offsetof(rt_feature, t) / sizeof(float), 1, w, h);
+        if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);
     }
 
     if (!out_raw.empty()) {

@@ -382,6 +382,48 @@ int rt_denoise(rt_context *ctx, const rt_denoise_params *p);
 int rt_read_denoised(rt_context *ctx, float *rgba, size_t bytes);
 int rt_device_denoised(rt_context *ctx, void **d_rgba);
 
+/*
+ * Variance-guided denoiser for low sample counts (new): the spatial half of SVGF, Schied et al. 2017, "Spatiotemporal
+ * Variance-Guided Filtering".  Notation as for rt_denoise: c0_p = accum.rgb / accum.w, or 0 where accum.w == 0; n, x, a
+ * the feature record's normal, position and albedo; e(z) = exp(-z); h = (1/16, 1/4, 3/8, 1/4, 1/16); key_p the object
+ * id with RT_DENOISE_SPLIT_OBJECTS, else the hit flag.  New: l(c) = 0.2126 c.r + 0.7152 c.g + 0.0722 c.b;
+ * k = (1/4, 1/2, 1/4); eps = RT_DENOISE_VARIANCE_EPS.
+ * The guide weight is g_pq = e(|n_p-n_q|^2/sigma_normal^2 + |x_p-x_q|^2/sigma_position^2 + |a_p-a_q|^2/sigma_albedo^2),
+ * and 0 when key_q != key_p; a sigma of +inf switches its term off.
+ *   1. Variance estimate, 7x7: over the taps q = p + (dx, dy), dx, dy in -3..3, inside the frame,
+ *        M0 = sum g_pq,  m = sum g_pq l(c0_q) / M0,  v0_p = sum g_pq (l(c0_q) - m)^2 / M0
+ *      (the two-pass form, not M2/M0 - m^2, which in binary32 cancels to noise of the order of eps on flat regions;
+ *      the centre tap has weight 1, so M0 >= 1).
+ *   2. For i = 0 .. L-1, s = 2^i:
+ *        vt_p = sum k[dx] k[dy] v(i)_q / sum k[dx] k[dy] over the 3x3 UNIT neighbours of p inside the frame (no edge
+ *          stopping);
+ *        d_p = sigma_luminance sqrt(vt_p) + eps;
+ *        w_pq = h[dx] h[dy] g_pq e(|l(c(i)_p) - l(c(i)_q)| / d_p) over q = p + s*(dx, dy), dx, dy in -2..2 (dy outer,
+ *          dx inner), taps outside the frame skipped; sigma_luminance = +inf switches the luminance term off;
+ *        c(i+1)_p = sum w c(i)_q / sum w;   v(i+1)_p = sum w^2 v(i)_q / (sum w)^2.
+ *   3. Output RGBA = (sqrt(c(L)_p), 1) where accum.w > 0, else 0, into the SAME buffer rt_denoise writes, so
+ *      rt_read_denoised and rt_device_denoised serve both.  v0 and v(L) are kept as W x H floats.
+ * A filter for LOW sample counts (1 .. 4 spp): from about 16 spp on the spatial estimate takes illumination gradients
+ * for noise and rt_denoise is the better filter (DESIGN.md "Variance-guided filter").
+ * Asynchronous on the context's stream; one launch for step 1 and one per iteration.  Leaves the image, the
+ * accumulator, the sample counter and the feature records untouched.  RT_EINVAL: iterations outside 1..8, a sigma <= 0
+ * or NaN, unknown flags, a NULL pointer, `which` outside 0..1, a sharded context; RT_ESTATE: no features since the frame
+ * was (re)allocated.
+ * rt_read_variance: which 0: v0, 1: v(L); bytes = W*H*4.  rt_device_variance: the device address of the W x H floats.
+ * Both give RT_ESTATE until rt_denoise_variance has run since the frame was (re)allocated.
+ */
+typedef struct rt_denoise_variance_params {
+    uint32_t iterations;    /* L, 1 .. 8 (5 suggested)                                                       */
+    float sigma_luminance;  /* > 0 (4 suggested); +inf = term off                                            */
+    float sigma_normal, sigma_position, sigma_albedo;   /* as rt_denoise_params                               */
+    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS                                                       */
+} rt_denoise_variance_params;
+#define RT_DENOISE_VARIANCE_EPS 1e-4f
+
+int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p);
+int rt_read_variance(rt_context *ctx, int which, float *out, size_t bytes);
+int rt_device_variance(rt_context *ctx, int which, void **d_out);
+
 /* Wait for everything queued on the context's stream (reference:
  * queue.finish(), src/raytracer.cpp:140).  rt_render/rt_render_again already
  * return synchronously; rt_render_spp/rt_resolve/rt_clear are asynchronous. */

@@ -135,6 +135,19 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
 
 
+# rt_denoise_variance defaults of the Python and C++ surfaces (sigma_luminance 4 is SVGF's; DESIGN.md "Variance-guided
+# filter")
+DENOISE_VARIANCE_EPS = 1e-4
+DENOISE_VARIANCE_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.1, sigma_position=2.0,
+                                 sigma_albedo=0.2, split_objects=True)
+
+
+class DenoiseVarianceParams(C.Structure):
+    """rt_denoise_variance_params"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("sigma_albedo", C.c_float), ("flags", C.c_uint32)]
+
+
 def denoise_prototypes(lib):
     """ctypes prototypes of the feature-buffer and denoiser entry points (rt_render_features & co.)."""
     vp, sz = C.c_void_p, C.c_size_t
@@ -144,6 +157,9 @@ def denoise_prototypes(lib):
     lib.rt_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
     lib.rt_read_denoised.argtypes = [vp, vp, sz]
     lib.rt_device_denoised.argtypes = [vp, C.POINTER(vp)]
+    lib.rt_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams)]
+    lib.rt_read_variance.argtypes = [vp, C.c_int, vp, sz]
+    lib.rt_device_variance.argtypes = [vp, C.c_int, C.POINTER(vp)]
 
 
 def prefix_cache_prototypes(lib):

@@ -240,6 +240,10 @@ struct rt_context {
         DevBuf<float4> pingpong[2];     // W x H: the à-trous iterations' ping-pong buffers (linear colour, count)
         DevBuf<float4> out;             // W x H: the last rt_denoise result, gamma RGBA
         bool ready = false;             // written since the frame was (re)allocated
+        // rt_denoise_variance, allocated on ITS first call (with the three above when rt_denoise has not run yet; its
+        // iterations ping-pong (linear colour, variance) through `pingpong` and its result goes to `out`)
+        DevBuf<float> var[2];           // W x H each: v0 (the 7x7 estimate) and v(L) (the filtered variance)
+        bool var_ready = false;         // both written since the frame was (re)allocated
     } denoise;
 
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;

@@ -30,6 +30,7 @@ SYMBOLS = (
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
     "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
+    "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list",
 )
@@ -396,6 +397,43 @@ class RayTracer:
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         self._check(self._lib.rt_read_denoised(self._ctx, out.ctypes.data, out.nbytes))
         return out
+
+    def denoiseVariance(self, camera=None, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
+                        sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                        sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
+                        sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
+                        sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """Variance-guided à-trous filter for low sample counts (rt_denoise_variance); renders the features for
+        `camera` first when one is given.  → the denoised gamma image (h, w, 4), the buffer denoisedImage() reads."""
+        if camera is not None:
+            self.renderFeatures(camera)
+        self.denoiseVarianceOnDevice(iterations, sigma_luminance, sigma_normal, sigma_position, sigma_albedo,
+                                     split_objects)
+        return self.denoisedImage()
+
+    def denoiseVarianceOnDevice(self, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
+                                sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                                sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
+                                sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
+                                sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """rt_denoise_variance enqueued, nothing read back."""
+        p = _abi.DenoiseVarianceParams(int(iterations), float(sigma_luminance), float(sigma_normal),
+                                       float(sigma_position), float(sigma_albedo),
+                                       _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+        self._check(self._lib.rt_denoise_variance(self._ctx, C.byref(p)))
+
+    def variance(self, which=0):
+        """The last denoiseVariance call's luminance variance → (h, w) float32: which 0 the 7x7 estimate v0, 1 the
+        filtered v(L)."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self._lib.rt_read_variance(self._ctx, int(which), out.ctypes.data, out.nbytes))
+        return out
+
+    def deviceVariance(self, which=0):
+        """Device address of the W x H floats of variance(which) (rt_device_variance)."""
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_variance(self._ctx, int(which), C.byref(p)))
+        return p.value
 
     def deviceFeatures(self):
         """Device address of the W x H feature records (rt_device_features)."""

@@ -4,10 +4,12 @@ For each scene: a fixed 4096-spp frame is the ground truth.  For 1 / 4 / 16 / 64
 of the noisy frame and of the denoised frame (default sigmas), the device time of rt_render_features and of rt_denoise
 (events on the tracer's stream, median of --reps), and the smallest fixed spp (a power of two) whose noisy RMSE reaches
 the denoised 16-spp RMSE.  --sweep instead scores a grid of sigmas at 16 spp (the choice of the defaults).
---profile-only runs just the denoise, --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
+--variance-guided instead prints, per scene and spp, the RMSE and the device time of rt_denoise and of rt_denoise_variance
+(default parameters each) side by side, on the same frames in the same run.
+--profile-only runs just the denoise (with --variance-guided: rt_denoise_variance), --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
 such a run's kernel_trace.csv into per-iteration times.
 
-    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep]
+    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided]
 """
 import argparse
 import csv
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--truth-spp", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--variance-guided", action="store_true")
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--json", default=None)
@@ -72,9 +75,11 @@ def main():
         t.renderFrameOnDevice(wl.camera, 16)   # warm-up (code objects, buffers)
         t.renderFeatures(wl.camera)
         t.denoiseOnDevice()
+        if a.variance_guided:
+            t.denoiseVarianceOnDevice()
         if a.profile_only:
             for _ in range(a.reps):
-                t.denoiseOnDevice()
+                t.denoiseVarianceOnDevice() if a.variance_guided else t.denoiseOnDevice()
             t.sync()
             t.setStream(None)
             t.close()
@@ -95,6 +100,18 @@ def main():
             for sc, sn, sx, sa in grid:
                 t.denoiseOnDevice(D["iterations"], sc, sn, sx, sa, True)
                 sweep.append(dict(scene=name, sigma=[sc, sn, sx, sa], rmse=rmse(t.deviceDenoised()), noisy=noisy))
+            t.setStream(None)
+            t.close()
+            continue
+        if a.variance_guided:
+            for spp in (1, 4, 16, 64):
+                t.renderFrameOnDevice(wl.camera, spp)
+                noisy = rmse(t.deviceImage())
+                ms_d = float(np.median([timed(lambda: t.denoiseOnDevice()) for _ in range(a.reps)]))
+                den = rmse(t.deviceDenoised())
+                ms_v = float(np.median([timed(lambda: t.denoiseVarianceOnDevice()) for _ in range(a.reps)]))
+                rows.append(dict(scene=name, spp=spp, rmse_noisy=noisy, rmse_denoised=den,
+                                 rmse_variance_guided=rmse(t.deviceDenoised()), ms_denoise=ms_d, ms_denoise_variance=ms_v))
             t.setStream(None)
             t.close()
             continue
@@ -133,6 +150,13 @@ def main():
         for k, v in ranked[:12]:
             print("| %s | %s | %.3f |" % (", ".join("%g" % x for x in k), ", ".join("%.3f" % x for x in v), np.mean(v)))
         out = sweep
+    elif a.variance_guided:
+        print("| scene | spp | RMSE noisy | RMSE rt_denoise | RMSE rt_denoise_variance | rt_denoise ms | rt_denoise_variance ms |")
+        print("|---|---:|---:|---:|---:|---:|---:|")
+        for r in rows:
+            print("| %s | %d | %.4f | %.4f | %.4f | %.3f | %.3f |" % (r["scene"].upper(), r["spp"], r["rmse_noisy"], r["rmse_denoised"],
+                                                                   r["rmse_variance_guided"], r["ms_denoise"], r["ms_denoise_variance"]))
+        out = rows
     else:
         print("| scene | spp | RMSE noisy | RMSE denoised | features ms | denoise ms | fixed spp matching denoised 16 |")
         print("|---|---:|---:|---:|---:|---:|---:|")

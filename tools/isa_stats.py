@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""tools/isa_stats.py [--arith K] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
+"""tools/isa_stats.py [--arith K] [--unit rt_amd] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
 
 Compiles csrc/pt_kernels.hip for the device only (-S, the flags of __graft_entry__ for arithmetic policy K = 0 | 1 | 2,
 default 2 = rocm-opencl, the policy bench.py times; ISA_ARITH in the environment does the same) and prints, per
 kernel: VGPRs / SGPRs / scratch bytes / spilled VGPRs from the code-object metadata and the static opcode
 histogram grouped into the issue-cost classes measured by tools/valu_microbench.hip
-(profiles/r02_valu_microbench.md).  --json dumps everything for bench.py / profile summaries."""
+(profiles/r02_valu_microbench.md).  --unit rt_amd reads the policy-free kernels of csrc/rt_amd.hip instead (pt_atrous,
+pt_dn_variance, pt_atrous_vg, pt_adaptive_merge: compiled once, with the IEEE divide).  --json dumps everything for bench.py / profile summaries."""
 import collections
 import json
 import os
@@ -79,6 +80,15 @@ def default_arith():
 
 def device_asm(force=False, arith=None):
     import __graft_entry__ as g
+    if "--unit" in sys.argv and sys.argv[sys.argv.index("--unit") + 1:][:1] == ["rt_amd"]:
+        out = os.path.join(ROOT, "build", "rt_amd_gfx950.s")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        srcs = g.hip_sources()
+        if force or not os.path.isfile(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
+            flags = [f for f in g.HIP_FLAGS if f not in ("-shared", "-fPIC")] + [g.IEEE_DIV]
+            subprocess.check_call([g.HIPCC] + flags + ["--cuda-device-only", "-S", srcs[0], "-o", out],
+                                  stderr=subprocess.DEVNULL)
+        return out
     arith = default_arith() if arith is None else int(arith)
     extra = os.environ.get("ISA_EXTRA_FLAGS", "").split()   # e.g. ISA_EXTRA_FLAGS="-DPT_Q_WAVES=5" for a variant
     tag = ("_" + "_".join(e.lstrip("-D").replace("=", "") for e in extra)) if extra else ""
@@ -144,18 +154,18 @@ def summarize(k):
 
 
 if __name__ == "__main__":
-    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--arith"]
+    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--arith", "--unit")]
     ks = kernels(device_asm("--force" in sys.argv))
     if "--json" in sys.argv:
         print(json.dumps({k["demangled"]: dict(summarize(k), vgpr=k["vgpr"], sgpr=k["sgpr"], scratch=k["scratch"],
-                                               spilled_vgprs=k["spilled_vgprs"]) for k in ks.values()}, indent=1))
+                                               spilled_vgprs=k["spilled_vgprs"], lds_static=k["lds_static"]) for k in ks.values()}, indent=1))
         sys.exit(0)
     for k in ks.values():
         if args and not any(a in k["demangled"] for a in args):
             continue
         s = summarize(k)
-        print("%-44s vgpr %3d sgpr %3d scratch %3d B (%d spilled)  VALU %5d  SALU %5d  SMEM %3d  VMEM %3d  scratch-ops %3d  LDS %3d" %
-              (k["demangled"], k["vgpr"], k["sgpr"], k["scratch"], k["spilled_vgprs"], s["valu"], s["salu"], s["smem"],
+        print("%-44s vgpr %3d sgpr %3d scratch %3d B (%d spilled)  LDS %5d B  VALU %5d  SALU %5d  SMEM %3d  VMEM %3d  scratch-ops %3d  LDS %3d" %
+              (k["demangled"], k["vgpr"], k["sgpr"], k["scratch"], k["spilled_vgprs"], k["lds_static"], s["valu"], s["salu"], s["smem"],
                s["vmem"], s["scratch_ops"], s["lds"]))
         if args:
             print("   classes:", {c: "%d (%.0f%%)" % (n, 100.0 * n / s["valu"]) for c, n in s["classes"].items()})
