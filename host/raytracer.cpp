@@ -119,6 +119,22 @@ std::vector<float> RayTracer::variance(int which) {
     return v;
 }
 
+void RayTracer::setMoments(bool on) { check(rt_set_option(ctx, RT_OPT_MOMENTS, on ? 1 : 0)); }
+
+std::vector<float> RayTracer::moments() {
+    std::vector<float> m((size_t)width * height);
+    check(rt_read_moments(ctx, m.data(), m.size() * sizeof(float)));
+    return m;
+}
+
+const float *RayTracer::denoiseMoments(const Camera *camera, const rt_denoise_variance_params &params) {
+    if (camera) renderFeatures(camera);
+    check(rt_denoise_moments(ctx, &params));
+    pixels.resize((size_t)width * height * 4);
+    check(rt_read_denoised(ctx, pixels.data(), pixels.size() * sizeof(float)));
+    return pixels.data();
+}
+
 void RayTracer::setPrefixCache(bool on) { check(rt_set_option(ctx, RT_OPT_PREFIX_CACHE, on ? 1 : 0)); }
 
 void RayTracer::setLookahead(int samples) { check(rt_set_option(ctx, RT_OPT_LOOKAHEAD, samples)); }

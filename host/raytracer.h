@@ -71,6 +71,13 @@ public:
     // luminance-variance estimate v0, variance(1) the filtered variance v(L), W x H floats each
     const float *denoiseVariance(const Camera *camera, const rt_denoise_variance_params &params);
     std::vector<float> variance(int which = 0);
+    // RT_OPT_MOMENTS: the context keeps every pixel's centred second luminance moment M2 beside the accumulator, from the
+    // next renderFrame / renderAdaptive (rt_clear) on; moments() reads the W x H floats.  denoiseMoments is
+    // denoiseVariance on the variance MEASURED from them, M2 / (n (n - 1)), wherever a pixel holds >= 4 samples
+    // (rt_denoise_moments); variance() serves it as well
+    void setMoments(bool on);
+    std::vector<float> moments();
+    const float *denoiseMoments(const Camera *camera, const rt_denoise_variance_params &params);
     // RT_OPT_PREFIX_CACHE: while camera and scene rest, renderSamples keeps the traced prefix from call to call (default
     // on; same pixels either way); the counts of fused launches that reused it / traced it in full
     void setPrefixCache(bool on);

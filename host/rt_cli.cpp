@@ -4,7 +4,8 @@
 //          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive [--lookahead N]]
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
-//          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S]]] [--aov PREFIX]
+//          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
+//          [--aov PREFIX]
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -19,6 +20,9 @@
 // --denoise --variance-guided selects the variance-guided filter for low sample counts instead (rt_denoise_variance:
 // --sigma-luminance, default 4, > 0, inf = term off; --sigma keeps its four values, of which the colour one is unused);
 // --aov then also writes PREFIX_variance.pfm, its 7x7 luminance-variance estimate v0.
+// --denoise --variance-guided --measured keeps the per-pixel sample moments while accumulating (RT_OPT_MOMENTS) and filters
+// on the variance measured from them wherever a pixel holds >= 4 samples (rt_denoise_moments); --aov then also writes
+// PREFIX_samplevar.pfm, the measured variance of every pixel's mean luminance, M2 / (n (n - 1)) (0 where n < 2).
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -44,7 +48,7 @@ static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
                  "[--seed N] [--progressive [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S]]] "
+                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]] "
                  "[--aov PREFIX]\n";
     std::exit(2);
 }
@@ -113,7 +117,7 @@ int main(int argc, char **argv) {
     long dn_iterations = 0;
     float sigmas[4] = {0.5f, 0.1f, 2.0f, 0.2f};
     bool sigmas_given = false;
-    bool variance_guided = false, sigma_l_given = false;
+    bool variance_guided = false, sigma_l_given = false, measured = false;
     float sigma_l = 4.0f;
     std::string aov_prefix;
     for (int i = 1; i < argc; i++) {
@@ -157,13 +161,14 @@ int main(int argc, char **argv) {
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
         else if (a == "--denoise") denoise = true;
         else if (a == "--variance-guided") variance_guided = true;
+        else if (a == "--measured") measured = true;
         else if (a == "--progressive") progressive = true;
         else usage();
     }
     if (spp < 1 || w < 1 || h < 1) usage();
     if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
     if (!denoise && (dn_iterations || sigmas_given || variance_guided || sigma_l_given)) usage();   // denoise-only flags
-    if (sigma_l_given && !variance_guided) usage();
+    if ((sigma_l_given || measured) && !variance_guided) usage();
     if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
@@ -206,6 +211,7 @@ int main(int argc, char **argv) {
         return f ? 0 : 1;
     }
     RayTracer tracer(w, h, "kernels/raytracer.cl", scene_path, device, seed);
+    if (measured) tracer.setMoments(true);   // before anything is accumulated: every path below starts with a clear
 
     auto t0 = std::chrono::steady_clock::now();
     const float *img;
@@ -243,8 +249,8 @@ int main(int argc, char **argv) {
         rt_denoise_params dp{(uint32_t)dn_iterations, sigmas[0], sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
         rt_denoise_variance_params vp{(uint32_t)dn_iterations, sigma_l, sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
         auto d0 = std::chrono::steady_clock::now();
-        img = variance_guided ? tracer.denoiseVariance(nullptr, vp) : tracer.denoise(nullptr, dp);
-        std::cout << "denoised" << (variance_guided ? " (variance-guided)" : "") << ": " << dn_iterations
+        img = measured ? tracer.denoiseMoments(nullptr, vp) : variance_guided ? tracer.denoiseVariance(nullptr, vp) : tracer.denoise(nullptr, dp);
+        std::cout << "denoised" << (measured ? " (variance-guided, measured)" : variance_guided ? " (variance-guided)" : "") << ": " << dn_iterations
                   << " iterations, sigma " << (variance_guided ? sigma_l : sigmas[0]) << "," << sigmas[1] << ","
                   << sigmas[2] << "," << sigmas[3] << ": "
                   << std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count() * 1e3
@@ -258,6 +264,13 @@ int main(int argc, char **argv) {
         write_pfm(aov_prefix + "_albedo.pfm", fd, stride, offsetof(rt_feature, albedo) / sizeof(float), 3, w, h);
         write_pfm(aov_prefix + "_depth.pfm", fd, stride, offsetof(rt_feature, t) / sizeof(float), 1, w, h);
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);
+        if (denoise && measured) {
+            const std::vector<float> m2 = tracer.moments();
+            const std::vector<uint32_t> n = tracer.sampleCounts();
+            std::vector<float> sv(m2.size());
+            for (size_t i = 0; i < sv.size(); i++) sv[i] = n[i] >= 2u ? (float)((double)m2[i] / ((double)n[i] * ((double)n[i] - 1.0))) : 0.0f;
+            write_pfm(aov_prefix + "_samplevar.pfm", sv.data(), 1, 0, 1, w, h);
+        }
     }
 
     if (!out_raw.empty()) {

@@ -424,6 +424,37 @@ int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p);
 int rt_read_variance(rt_context *ctx, int which, float *out, size_t bytes);
 int rt_device_variance(rt_context *ctx, int which, void **d_out);
 
+/*
+ * Per-pixel sample moments (new; RT_OPT_MOMENTS) and the variance-guided filter on MEASURED variance.
+ * With l(c) the luminance above and s_0 .. s_(n-1) the samples a pixel's accumulator holds (n = accum.w), the moment
+ * buffer keeps M2_p = sum_j (l(s_j) - m_p)^2, m_p = sum_j l(s_j) / n: one float per pixel, W x H, row-major.
+ * The moments become VALID at rt_clear and at the start of rt_render_adaptive while RT_OPT_MOMENTS is 1 (both zero them
+ * on the stream); they become invalid when the option's value changes and after rt_resize.  While they are valid,
+ * every call that adds to the accumulator — rt_render_spp and rt_render_adaptive, on every path they can take — updates
+ * them; rt_render, rt_render_again and its look-ahead launches never touch them.  While they are invalid nothing
+ * writes the buffer, and rt_read_moments, rt_device_moments and rt_denoise_moments give RT_ESTATE.
+ * Two partial states (n, RGB sum S, M2) of a pixel are combined in ONE place, by the pairwise update of Chan, Golub &
+ * LeVeque 1979 — rt_moments_merge, the very function the kernels call:
+ *   nA == 0: M2B exactly;  nB == 0: M2A exactly;
+ *   otherwise delta = l(SB)/nB - l(SA)/nA,  M2 = M2A + M2B + delta^2 nA nB / (nA + nB).
+ * A launch's own M2B is the centred sum about the launch's mean, sum_j (l(s_j) - l(S_B)/nB)^2 — never sum l^2 - n m^2,
+ * which cancels in binary32; a pixel whose samples are all one colour (finished by the prefix stage) has M2B = 0.
+ * The summation order inside a launch is not part of the contract: the result is specified to a tolerance.
+ * rt_read_moments: bytes = W*H*4.  rt_device_moments: the device address of the W x H floats.
+ * rt_moments_merge: host-only, no context.  RT_EINVAL: a NULL pointer.
+ * rt_denoise_moments is rt_denoise_variance in every respect — parameters, validation, the buffers written, the outputs
+ * behind rt_read_denoised and rt_read_variance, asynchrony, nothing else moves — except step 1:
+ *   v0_p = M2_p / (n_p (n_p - 1))  where n_p >= RT_DENOISE_MOMENTS_MIN_COUNT (SVGF's history threshold),
+ * the variance of the pixel's MEAN measured from its own samples; elsewhere (n_p = 0 included) the 7x7 estimate.
+ * From 4 spp on it is never worse than the spatial estimate and from 16 spp on clearly better (DESIGN.md "Measured
+ * variance"); additionally RT_ESTATE while the moments are not valid.
+ */
+#define RT_DENOISE_MOMENTS_MIN_COUNT 4u
+int rt_read_moments(rt_context *ctx, float *m2, size_t bytes);
+int rt_device_moments(rt_context *ctx, void **d_m2);
+int rt_moments_merge(uint32_t nA, const float sumA[3], float m2A, uint32_t nB, const float sumB[3], float m2B, float *m2_out);
+int rt_denoise_moments(rt_context *ctx, const rt_denoise_variance_params *p);
+
 /* Wait for everything queued on the context's stream (reference:
  * queue.finish(), src/raytracer.cpp:140).  rt_render/rt_render_again already
  * return synchronously; rt_render_spp/rt_resolve/rt_clear are asynchronous. */
@@ -504,6 +535,13 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
                                            pixels; 0: always the grid for "every pixel is live" (its surplus workgroups leave at
                                            once).  A process whose environment holds RT_EXACT_GRID=0 starts its contexts with 0.
                                            Same result bit for bit                                                          */
+#define RT_OPT_MOMENTS 12               /* 0 (default): no sample moments — nothing is allocated and every launch gets a NULL moment
+                                           pointer; 1: the context keeps each pixel's centred second luminance moment beside the
+                                           accumulator (rt_read_moments; one more pass over a wave's sample slots in the sample
+                                           kernels' epilogue, 4 more bytes per pixel).  Any other value: RT_EINVAL.  Unsharded
+                                           contexts only: setting 1 on a context with world > 1, and rt_set_shard to world > 1
+                                           while it is 1, give RT_EINVAL.  A change of value invalidates the moments until the next
+                                           rt_clear / rt_render_adaptive.  Image and accumulator: the same bit for bit        */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's

@@ -162,6 +162,19 @@ def denoise_prototypes(lib):
     lib.rt_device_variance.argtypes = [vp, C.c_int, C.POINTER(vp)]
 
 
+DENOISE_MOMENTS_MIN_COUNT = 4   # RT_DENOISE_MOMENTS_MIN_COUNT: samples from which rt_denoise_moments trusts a pixel's own variance
+
+
+def moments_prototypes(lib):
+    """ctypes prototypes of the sample-moment entry points (RT_OPT_MOMENTS: rt_read_moments & co.)."""
+    vp, sz, u32, f32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_float
+    f3 = C.POINTER(f32)
+    lib.rt_read_moments.argtypes = [vp, vp, sz]
+    lib.rt_device_moments.argtypes = [vp, C.POINTER(vp)]
+    lib.rt_moments_merge.argtypes = [u32, f3, f32, u32, f3, f32, f3]
+    lib.rt_denoise_moments.argtypes = [vp, C.POINTER(DenoiseVarianceParams)]
+
+
 def prefix_cache_prototypes(lib):
     """ctypes prototype of rt_prefix_cache_stats (RT_OPT_PREFIX_CACHE)."""
     lib.rt_prefix_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "pt_device.hpp"
+#include "pt_moments.hpp"
 #include "rt_context.hpp"
 #include "pt_kernels.hpp"
 
@@ -86,6 +87,38 @@ PT_DEV void accumulate(float4 *__restrict__ accum, size_t pix, V3 sum, uint32_t 
     accum[pix] = a;
 }
 
+// ---- per-pixel sample moments (FrameParams::m2, RT_OPT_MOMENTS; pt_moments.hpp) --------------------------------------
+// A launch that adds `count` samples of sum `sum` to a pixel merges their centred second moment m2B — about the launch's
+// own mean l(sum) / count — with the state the pixel holds BEFORE the launch's accumulate: (accum.w, accum.rgb, m2).
+// Called by the one lane that then accumulates, in the kernels' epilogues only.
+PT_DEV void moments_update(const float4 *accum, float *m2, size_t pix, V3 sum, uint32_t count, float m2B) {
+    const float4 a = accum[pix];
+    m2[pix] = moments_merge(a.w, a.x, a.y, a.z, m2[pix], (float)count, sum.x, sum.y, sum.z, m2B);
+}
+
+// The fixed-lane kernels (pt_render<MODE_ACCUM>, pt_samples): a lane keeps (n, its partial sum, M2) over its own samples,
+// folding each one in as a one-sample state BEFORE it joins the sum; the butterfly then merges the lanes' states pairwise
+// while it adds their sums exactly as group_sum does (same operands, same order: the sum keeps its bits).
+struct LaneMoments {
+    float n, m2;
+};
+PT_DEV void moments_fold(LaneMoments &lm, V3 sum, V3 s) {
+    lm.m2 = moments_merge(lm.n, sum.x, sum.y, sum.z, lm.m2, 1.0f, s.x, s.y, s.z, 0.0f);
+    lm.n += 1.0f;
+}
+PT_DEV V3 group_sum_moments(V3 sum, LaneMoments &lm, uint32_t g) {
+    for (uint32_t off = g >> 1; off > 0; off >>= 1) {
+        const V3 o = mk(__shfl_xor(sum.x, off), __shfl_xor(sum.y, off), __shfl_xor(sum.z, off));
+        const float on = __shfl_xor(lm.n, off), om2 = __shfl_xor(lm.m2, off);
+        lm.m2 = moments_merge(lm.n, sum.x, sum.y, sum.z, lm.m2, on, o.x, o.y, o.z, om2);
+        lm.n += on;
+        sum.x += o.x;
+        sum.y += o.y;
+        sum.z += o.z;
+    }
+    return sum;
+}
+
 // `count` samples of one colour, summed in the kernels' order: lane l of the pixel's g = 2^group_log2 lanes adds its samples
 // l, l + g, … one after the other (k or k + 1 of them: the first r = count mod g lanes have one more), then the
 // xor butterfly (offsets g/2 … 1).  Before a butterfly step over n lanes the first r lanes hold one value (X)
@@ -147,17 +180,22 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
     bool valid = slot < fp.slot_end && slot_to_pixel(fp, slot, x, y) && pixel_active(fp, x, y);
 
     V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const bool mom = MODE == MODE_ACCUM && fp.m2 != nullptr;   // (uniform; never in the compat modes)
+    LaneMoments lm{0.0f, 0.0f};
     if (valid) {
         Ray r0 = primary_ray(fp.cam, x, y, fp.w, fp.h);
         for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
             if (COUNT) cn.c[CN_SAMPLES]++;
-            sum = sum + radiance<COUNT, ACCEL>(c, r0, s, x, y);
+            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, x, y);
+            if (mom) moments_fold(lm, sum, rad);
+            sum = sum + rad;
         }
     }
-    sum = group_sum(sum, g);
+    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
     if (valid && lane == 0) {
         size_t pix = (size_t)y * fp.w + x;
         if (MODE == MODE_ACCUM) {
+            if (mom) moments_update(accum, fp.m2, pix, sum, fp.count, lm.m2);
             accumulate(accum, pix, sum, fp.count);
         } else if (MODE == MODE_TRACE) {
             image[pix] = make_float4(sqrt1(sum.x), sqrt1(sum.y), sqrt1(sum.z), 1.0f);   // gamma_corr :488
@@ -210,7 +248,11 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
         bool final_px = (__float_as_uint(rec.p_kind.w) & 0xFFu) == REC_FINAL;
         if (final_px) {
             is_final = true;
-            if (accum) accumulate(accum, (size_t)y * fp.w + x, final_sum(xyz(rec.out), fp.count, fp.group_log2), fp.count);
+            if (accum) {   // (every sample of a finished pixel is the same colour: the launch's own M2 is 0)
+                const V3 fsum = final_sum(xyz(rec.out), fp.count, fp.group_log2);
+                if (fp.m2) moments_update(accum, fp.m2, (size_t)y * fp.w + x, fsum, fp.count, 0.0f);
+                accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
+            }
             if (COUNT) cn.c[CN_SAMPLES] += 1;  // scaled by count below
         } else {
             is_live = true;
@@ -334,7 +376,9 @@ __global__ __launch_bounds__(256) void pt_final_replay(FrameParams fp, const Fin
     const FinalPix e = finals[blockIdx.x * 256u + threadIdx.x];
     uint32_t x = 0, y = 0;
     if (!slot_to_pixel(fp, e.slot, x, y)) return;   // (never: pt_prefix stored the slots of valid pixels only)
-    accumulate(accum, (size_t)y * fp.w + x, final_sum(mk(e.r, e.g, e.b), fp.count, fp.group_log2), fp.count);
+    const V3 fsum = final_sum(mk(e.r, e.g, e.b), fp.count, fp.group_log2);
+    if (fp.m2) moments_update(accum, fp.m2, (size_t)y * fp.w + x, fsum, fp.count, 0.0f);   // (as pt_prefix)
+    accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
 }
 
 // Where frame j of pixel pix lies in the look-ahead ring (in float4).  Shipped: FRAME-MAJOR, frame after frame, so that a frame
@@ -391,17 +435,24 @@ __global__ __launch_bounds__(256) void pt_samples(DeviceScene sc, FrameParams fp
     bool valid = live_take(fp, live_count, li, 1u, entry) != 0u;
     uint32_t x = 0, y = 0;
     V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const bool mom = fp.m2 != nullptr;   // (uniform)
+    LaneMoments lm{0.0f, 0.0f};
     if (valid) {
         uint32_t slot = live[entry];
         (void)slot_to_pixel(fp, slot, x, y);
         PixelRec rec = recs[entry];
         for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
             if (COUNT) cn.c[CN_SAMPLES]++;
-            sum = sum + radiance_from_rec<COUNT, ACCEL>(c, rec, s, x, y, fp.trees);
+            const V3 rad = radiance_from_rec<COUNT, ACCEL>(c, rec, s, x, y, fp.trees);
+            if (mom) moments_fold(lm, sum, rad);
+            sum = sum + rad;
         }
     }
-    sum = group_sum(sum, g);
-    if (valid && lane == 0) accumulate(accum, (size_t)y * fp.w + x, sum, fp.count);
+    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
+    if (valid && lane == 0) {
+        if (mom) moments_update(accum, fp.m2, (size_t)y * fp.w + x, sum, fp.count, lm.m2);
+        accumulate(accum, (size_t)y * fp.w + x, sum, fp.count);
+    }
     flush_counters<COUNT>(cn, counters, 1);
 }
 
@@ -604,6 +655,13 @@ PT_DEV void queue_put(const WaveQueue &q, uint32_t idx, V3 rgb) {
 
 // Once every sample of the wave is in its slot: the per-pixel sums in pt_render's order (lane l of a pixel's g lanes:
 // samples l, l + g, …; then the xor butterfly), added to the accumulator.  Every lane of the wave calls it.
+// MOMENTS: the instantiation for launches that keep sample moments (FrameParams::m2 != NULL) — the slots are read a second
+// time, for the squared deviations from the pixel's mean.  A template parameter of the two queue kernels, not a branch on
+// the pointer like fp.la_ring: read as a kernel argument the pointer holds two SGPRs through the hot loop, where
+// pt_samples_q<false, false, 1, 6> of policy 0 parks exactly 64 SGPRs in the lanes of ONE VGPR — the two more took a second
+// one and the loop spilled three VGPRs to scratch, with the option off.  The instantiations without moments never read
+// the field and compile to what they compiled to before it existed.
+template <bool MOMENTS>
 PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -618,6 +676,19 @@ PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__rest
                 sum = sum + mk(sl[0], sl[1], sl[2]);
             }
         sum = group_sum(sum, g);
+        if (MOMENTS) {   // a second pass over the same slots, the sum being in all g lanes
+            // the launch's centred second moment about its own mean — never sum l^2 - n m^2 (pt_moments.hpp)
+            const float mean = moments_lum(sum.x, sum.y, sum.z) / (float)q.count;
+            float dev2 = 0.0f;
+            if (p < q.npix)
+                for (uint32_t j = l; j < q.count; j += g) {
+                    const LdsF32 sl = q.slot + 3u * (p * q.count + j);
+                    const float d = moments_lum(sl[0], sl[1], sl[2]) - mean;
+                    dev2 += d * d;
+                }
+            for (uint32_t off = g >> 1; off > 0; off >>= 1) dev2 += __shfl_xor(dev2, off);
+            if (p < q.npix && l == 0) moments_update(accum, fp.m2, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, q.count, dev2);
+        }
         if (p < q.npix && l == 0) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, q.count);
     }
 }
@@ -652,7 +723,7 @@ PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
 // kernel keeps 6 waves per SIMD.
-template <bool COUNT, bool ACCEL, int GEOM, int WAVES>
+template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
@@ -816,8 +887,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     if (threadIdx.x == 0 && q.npix)
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
-    if (!COUNT && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one)
-    else queue_sums(q, fp, accum);
+    if (!COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
+    else queue_sums<MOMENTS>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }
 
@@ -851,7 +922,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
 #ifndef PT_W_WAVES_MULTI
 #define PT_W_WAVES_MULTI 4  // several meshes: the running minimum over the jobs needs 13 more VGPRs — 109, no scratch at 4 waves per SIMD
 #endif
-template <bool MULTI>
+template <bool MULTI, bool MOMENTS = false>
 __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_samples_w(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
@@ -1099,8 +1170,8 @@ __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_
         for (int k = 0; k < 12; k++) atomicAdd(&wstat[k], v[k]);
     }
 #endif
-    if (fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch)
-    else queue_sums(q, fp, accum);
+    if (!MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never with moments)
+    else queue_sums<MOMENTS>(q, fp, accum);
 }
 
 // parity probe: one work-item per listed pixel-sample
@@ -1311,9 +1382,10 @@ static void apply_mask(FrameParams &fp, const BlockMask *mask) {
 
 template <int MODE>
 int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                  const BlockMask *mask) {
+                  const BlockMask *mask, float *m2) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
+    fp.m2 = MODE == MODE_ACCUM ? m2 : nullptr;
     DeviceScene sc = device_scene(ctx);
     uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
@@ -1346,11 +1418,12 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
 // and the accumulator is not touched (accum is NULL).  The caller has checked what such a launch needs: no counters, an
 // unsharded context, the sample queue, the frame in one slot range, count <= the ring's frames.
 static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                            const BlockMask *mask, float4 *ring) {
+                            const BlockMask *mask, float4 *ring, float *m2) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
+    fp.m2 = m2;   // (NULL for a look-ahead launch: the compat path keeps no moments)
     if (ring) {
-        if (accum || mask || ctx->count_enabled || ctx->world != 1 || !ctx->sample_queue || count > QUEUE_SLOTS ||
+        if (accum || m2 || mask || ctx->count_enabled || ctx->world != 1 || !ctx->sample_queue || count > QUEUE_SLOTS ||
             (ctx->max_threads_per_launch >> glog2) < fp.slot_end)
             return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
         fp.la_ring = ring;
@@ -1472,8 +1545,9 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         };
         // (the launch statement runs only for a grid that is not empty; `launched` is what rt_sample_grid_stats reports)
 #define PT_GRID(U, LAUNCH) do { launched = (U); if (launched) { LAUNCH; } } while (0)
-#define PT_CALL_QUEUE_W(C, A, G, W) \
-    PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<C, A, G, W>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw))
+#define PT_CALL_QUEUE_M(C, A, G, W, M) \
+    PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<C, A, G, W, M>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw))
+#define PT_CALL_QUEUE_W(C, A, G, W) do { if (fp.m2) PT_CALL_QUEUE_M(C, A, G, W, true); else PT_CALL_QUEUE_M(C, A, G, W, false); } while (0)
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
         if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
@@ -1489,7 +1563,7 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
             if (ppw_w > ppw_par) ppw_w = ppw_par;
             launched = units(ppw_w);
             if (launched)
-            hipLaunchKernelGGL(multi ? pt_samples_w<true> : pt_samples_w<false>, dim3(launched), dim3(64), queue_lds(ppw_w), ctx->stream,
+            hipLaunchKernelGGL(fp.m2 ? (multi ? pt_samples_w<true, true> : pt_samples_w<false, true>) : (multi ? pt_samples_w<true> : pt_samples_w<false>), dim3(launched), dim3(64), queue_lds(ppw_w), ctx->stream,
                                sc, fp, ss.recs.p, ss.live.p, live_count, accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
 #ifdef PT_WSTAT
                                , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
@@ -1502,6 +1576,7 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         }
 #undef PT_CALL_QUEUE
 #undef PT_CALL_QUEUE_W
+#undef PT_CALL_QUEUE_M
 #undef PT_CALL_FIXED
 #undef PT_GRID
         sg.launches++;
@@ -1522,13 +1597,13 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
 }
 
 int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                 const BlockMask *mask) {
-    return launch_fused_any(ctx, cam, first, count, glog2, accum, mask, nullptr);
+                 const BlockMask *mask, float *m2) {
+    return launch_fused_any(ctx, cam, first, count, glog2, accum, mask, nullptr, m2);
 }
 
 int launch_lookahead(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, float4 *ring) {
     if (!ring || count < 1u) return fail(ctx, RT_EINVAL, "look-ahead launch without a ring");
-    return launch_fused_any(ctx, cam, first, count, group_log2_for(count), nullptr, nullptr, ring);
+    return launch_fused_any(ctx, cam, first, count, group_log2_for(count), nullptr, nullptr, ring, nullptr);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
@@ -1570,11 +1645,11 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
 namespace {
 
 int ks_launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
-                     float4 *accum, const BlockMask *mask) {
+                     float4 *accum, const BlockMask *mask, float *m2) {
     switch (mode) {
-        case MODE_ACCUM: return launch_render<MODE_ACCUM>(ctx, cam, first, count, glog2, accum, mask);
-        case MODE_TRACE: return launch_render<MODE_TRACE>(ctx, cam, first, count, glog2, accum, mask);
-        case MODE_RETRACE: return launch_render<MODE_RETRACE>(ctx, cam, first, count, glog2, accum, mask);
+        case MODE_ACCUM: return launch_render<MODE_ACCUM>(ctx, cam, first, count, glog2, accum, mask, m2);
+        case MODE_TRACE: return launch_render<MODE_TRACE>(ctx, cam, first, count, glog2, accum, mask, m2);
+        case MODE_RETRACE: return launch_render<MODE_RETRACE>(ctx, cam, first, count, glog2, accum, mask, m2);
         default: return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
     }
 }

@@ -10,12 +10,13 @@ struct KernelSet {
     int arith;             // RT_ARITH_* this set was compiled for
     const char *name;
     // direct path: MODE_ACCUM / MODE_TRACE / MODE_RETRACE (rt_render, rt_render_again, prefix sharing off)
-    // `accum`: the accumulator MODE_ACCUM adds to; `mask`: the pixels traced (NULL = every owned pixel)
+    // `accum`: the accumulator MODE_ACCUM adds to; `mask`: the pixels traced (NULL = every owned pixel); `m2`: the sample
+    // moments kept beside `accum` (MODE_ACCUM only; NULL = none, FrameParams::m2)
     int (*launch_render)(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
-                         float4 *accum, const BlockMask *mask);
-    // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples, adding to `accum`
+                         float4 *accum, const BlockMask *mask, float *m2);
+    // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples, adding to `accum` (and updating `m2`, as above)
     int (*launch_fused)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
-                        float4 *accum, const BlockMask *mask);
+                        float4 *accum, const BlockMask *mask, float *m2);
     // look-ahead (rt_render_again, RT_OPT_LOOKAHEAD): the fused launch for samples first .. first+count-1, but instead of
     // sums into the accumulator the image after each of them — `count` frames of W x H float4, frame-major, into `ring`,
     // starting from the context's image as it lies.  Same slot buffers and prefix-cache entry as launch_fused.

@@ -172,6 +172,9 @@ struct FrameParams {
     // in order), the image after step j going to la_ring[j * w * h + pix] — frame-major, so a frame is handed out as one copy
     float4 *la_ring;
     const float4 *la_image;
+    // per-pixel sample moments (RT_OPT_MOMENTS; NULL = off): W x H floats beside the accumulator the launch adds to, the
+    // centred second moment of each pixel's sample luminances (pt_moments.hpp).  Read in the kernels' epilogues only
+    float *m2;
 };
 
 // the decision-block mask of an adaptive round, as the launchers take it (NULL = every pixel)

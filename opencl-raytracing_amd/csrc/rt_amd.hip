@@ -21,6 +21,7 @@
 
 #include "rt_context.hpp"
 #include "pt_kernels.hpp"
+#include "pt_moments.hpp"
 #include "mesh_bvh_build.hpp"
 
 using namespace pt;
@@ -69,6 +70,9 @@ __global__ __launch_bounds__(256) void pt_resolve(const float4 *__restrict__ acc
 // order (lane l sums pixels l, l + 64, ... in turn, then an xor butterfly), and lane 0 decides whether the block is
 // traced by the next round.  stats (PT_MERGE_REPLICAS rows, summed by the host): [0] blocks active next round,
 // [1] blocks stopped at max_spp unconverged, [2] pixel samples of the blocks that stopped.
+// With sample moments (RT_OPT_MOMENTS; m2 != NULL) the round's sample kernels have left the launch's own centred second
+// moment in m2_scratch — scratch was zero, the merge rule's nA == 0 — and the pixel's state (accum, m2) takes the round's
+// (scratch, m2_scratch) in with the merge rule (pt_moments.hpp) BEFORE accum += scratch; m2_scratch is zeroed with scratch.
 struct MergeParams {
     uint32_t w, h;
     uint32_t bw_log2, bh_log2, blocks_x, blocks;
@@ -83,7 +87,8 @@ struct MergeParams {
 #define PT_MERGE_STRIDE 16u      // (MI355X, C2 1080p: 190-395 us per round on one row, most of the merge's time)
 __global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge(MergeParams mp, float4 *__restrict__ accum, float4 *__restrict__ half,
                                                         float4 *__restrict__ scratch, uint32_t *__restrict__ active,
-                                                        float *__restrict__ block_err, unsigned long long *__restrict__ stats) {
+                                                        float *__restrict__ block_err, unsigned long long *__restrict__ stats,
+                                                        float *__restrict__ m2, float *__restrict__ m2_scratch) {
     const uint32_t b = blockIdx.x * PT_MERGE_WAVES + (threadIdx.x >> 6);
     if (b >= mp.blocks || active[b] == 0u) return;   // (uniform over the wave; no workgroup barrier follows)
     const uint32_t lane = threadIdx.x & 63u;
@@ -98,6 +103,10 @@ __global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge(MergePa
         const size_t p = (size_t)y * mp.w + x;
         const float4 s = scratch[p];
         float4 m = accum[p];
+        if (m2) {   // (uniform)
+            m2[p] = moments_merge(m.w, m.x, m.y, m.z, m2[p], s.w, s.x, s.y, s.z, m2_scratch[p]);
+            m2_scratch[p] = 0.0f;
+        }
         m.x += s.x; m.y += s.y; m.z += s.z; m.w += s.w;
         accum[p] = m;
         float4 a = half[p];
@@ -332,6 +341,16 @@ __global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const 
         }
     }
     var0[(size_t)y * dv.w + x] = m2 / m0;
+}
+
+// Step 1 of rt_denoise_moments, after pt_dn_variance: where a pixel holds at least RT_DENOISE_MOMENTS_MIN_COUNT samples its
+// MEASURED variance of the mean, M2 / (n (n - 1)) (the sample moments, RT_OPT_MOMENTS), replaces the 7x7 estimate.
+__global__ __launch_bounds__(256) void pt_dn_measured(const float4 *__restrict__ accum, const float *__restrict__ m2,
+                                                      float *__restrict__ var0, uint32_t n_px) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_px) return;
+    const float n = accum[i].w;
+    if (n >= (float)RT_DENOISE_MOMENTS_MIN_COUNT) var0[i] = m2[i] / (n * (n - 1.0f));
 }
 
 // Step 2, one iteration: pt_atrous's lattice tiling, XCD remap and key select, with the colour staged as (rgb, v(i)) and
@@ -704,6 +723,8 @@ int alloc_frame(rt_context *ctx, int w, int h) {
     ctx->adaptive = {};
     ctx->features = {};
     ctx->denoise = {};
+    ctx->moments.m2 = {};
+    ctx->moments.valid = false;
     const size_t px = (size_t)w * h;
     HIP_TRY(ctx, ctx->image.alloc(px));
     HIP_TRY(ctx, ctx->accum.alloc(px));
@@ -1102,6 +1123,7 @@ int rt_set_shard(rt_context *ctx, int rank, int world, int tile_w, int tile_h) {
     auto log2_exact = [](int v) { int l = 0; while ((1 << l) < v) l++; return (1 << l) == v ? l : -1; };
     int lw = log2_exact(tile_w), lh = log2_exact(tile_h);
     if (world < 1 || rank < 0 || rank >= world) return fail(ctx, RT_EINVAL, "rank %d of %d", rank, world);
+    if (world > 1 && ctx->moments.on) return fail(ctx, RT_EINVAL, "RT_OPT_MOMENTS is 1: sample moments are kept on unsharded contexts only");
     if (tile_w < 1 || tile_h < 1 || lw < 0 || lh < 0 || lw + lh > 16)
         return fail(ctx, RT_EINVAL, "tile %dx%d: sides must be powers of two, area <= 65536", tile_w, tile_h);
     ctx->prefix_changed();
@@ -1193,7 +1215,7 @@ int rt_render(rt_context *ctx, const float camera[12]) {
     lookahead_drop(ctx);
     remember_camera(ctx, camera);
     ctx->sample_counter = 0;  // src/raytracer.cpp:128
-    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // queue.finish(), src/raytracer.cpp:140
     return RT_OK;
 }
@@ -1256,7 +1278,7 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     ctx->image_epoch++;
     la.direct++;
     ctx->sample_counter++;  // src/raytracer.cpp:147
-    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->accum.p, nullptr)) != RT_OK) return rc;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -1267,12 +1289,29 @@ int rt_sample_counter(const rt_context *ctx, uint32_t *out) {
     return RT_OK;
 }
 
+extern "C++" {
+namespace {
+// The sample moments start anew with the accumulator (rt_clear, rt_render_adaptive) while RT_OPT_MOMENTS is 1: the buffer is
+// made on the first such call since the frame was (re)allocated, zeroed on the stream, and valid from here on.
+int moments_begin(rt_context *ctx) {
+    rt_context::Moments &mo = ctx->moments;
+    if (!mo.on) return RT_OK;
+    const size_t px = (size_t)ctx->width * ctx->height;
+    mo.valid = false;
+    if (!mo.m2.p) HIP_TRY(ctx, mo.m2.alloc(px));
+    HIP_TRY(ctx, hipMemsetAsync(mo.m2.p, 0, px * sizeof(float), ctx->stream));
+    mo.valid = true;
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 int rt_clear(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
     ctx->accum_count = 0;
-    return RT_OK;
+    return moments_begin(ctx);
 }
 
 int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample, uint32_t n_samples) {
@@ -1287,9 +1326,10 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
     // 18.4 ms where 512 take 10.2); the accumulator then is the sum of those launches' sums, on every path alike.
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr)
+        float *m2 = ctx->moments.target();
+        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr, m2)
                                  : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c),
-                                                          ctx->accum.p, nullptr);
+                                                          ctx->accum.p, nullptr, m2);
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
@@ -1366,6 +1406,9 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
     rt_context::Adaptive &a = ctx->adaptive;
     a.blocks = 0;
+    // sample moments (RT_OPT_MOMENTS): the rounds leave theirs in a scratch of its own, made once the option is on
+    const bool mom = ctx->moments.on;
+    if (mom && !a.m2_scratch.p) HIP_TRY(ctx, a.m2_scratch.alloc((size_t)ctx->width * ctx->height));
     ctx->image_epoch++;   // (the call ends in a resolve)
     const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, bytes, ctx->stream));
@@ -1374,6 +1417,9 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     HIP_TRY(ctx, hipMemsetAsync(a.block_active.p, 0xFF, blocks * sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.block_err.p, 0, blocks * sizeof(float), ctx->stream));
     ctx->accum_count = 0;
+    if ((rc = moments_begin(ctx)) != RT_OK) return rc;
+    if (mom) HIP_TRY(ctx, hipMemsetAsync(a.m2_scratch.p, 0, bytes / 4, ctx->stream));
+    float *const m2 = mom ? ctx->moments.m2.p : nullptr, *const m2_scratch = mom ? a.m2_scratch.p : nullptr;
     const BlockMask mask{a.block_active.p, (uint32_t)bwl, (uint32_t)bhl, bx};
     MergeParams mp;
     mp.w = (uint32_t)ctx->width;
@@ -1393,14 +1439,15 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
         const uint32_t first = k * p->batch;
         const uint32_t c = std::min(p->batch, p->max_spp - first);
         rc = ctx->prefix_sharing
-                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), a.scratch.p, &mask)
-                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), a.scratch.p, &mask);
+                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), a.scratch.p, &mask, m2_scratch)
+                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), a.scratch.p, &mask, m2_scratch);
         if (rc != RT_OK) return rc;
         mp.round = k;
         mp.count = first + c;
         HIP_TRY(ctx, hipMemsetAsync(a.stats.p, 0, st_bytes, ctx->stream));
         hipLaunchKernelGGL(pt_adaptive_merge, dim3((blocks + PT_MERGE_WAVES - 1) / PT_MERGE_WAVES), dim3(64 * PT_MERGE_WAVES), 0,
-                           ctx->stream, mp, ctx->accum.p, a.half.p, a.scratch.p, a.block_active.p, a.block_err.p, a.stats.p);
+                           ctx->stream, mp, ctx->accum.p, a.half.p, a.scratch.p, a.block_active.p, a.block_err.p, a.stats.p,
+                           m2, m2_scratch);
         HIP_TRY(ctx, hipGetLastError());
         rounds++;
         ctx->accum_count = first + c;
@@ -1545,7 +1592,11 @@ int rt_device_denoised(rt_context *ctx, void **d_rgba) {
     return RT_OK;
 }
 
-int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p) {
+extern "C++" {
+namespace {
+// rt_denoise_variance and rt_denoise_moments: one filter, two sources of v0 (`measured`: the sample moments where a pixel
+// holds enough samples, the 7x7 estimate elsewhere)
+int denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p, bool measured) {
     if (!ctx) return RT_EINVAL;
     if (!p) return fail(ctx, RT_EINVAL, "denoise parameters are NULL");
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "denoising a sharded context (rank %d of %d)", ctx->rank, ctx->world);
@@ -1556,6 +1607,8 @@ int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p) {
         if (!(v > 0.0f)) return fail(ctx, RT_EINVAL, "every sigma must be > 0 (+inf switches its term off)");
     if (p->flags & ~RT_DENOISE_SPLIT_OBJECTS) return fail(ctx, RT_EINVAL, "unknown denoise flags 0x%x", p->flags);
     if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+    if (measured && !ctx->moments.target())
+        return fail(ctx, RT_ESTATE, "the sample moments are not valid: set RT_OPT_MOMENTS to 1, then rt_clear or rt_render_adaptive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rt_context::Denoise &d = ctx->denoise;
     if (!d.out.p || !d.var[1].p) {
@@ -1591,6 +1644,11 @@ int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p) {
     hipLaunchKernelGGL(pt_dn_variance, dim3(dv.tiles_x * ((h + PT_DN_TILE - 1u) / PT_DN_TILE)), dim3(256), 0, ctx->stream, dv,
                        ctx->accum.p, feat, d.var[0].p);
     HIP_TRY(ctx, hipGetLastError());
+    if (measured) {
+        hipLaunchKernelGGL(pt_dn_measured, dim3((w * h + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->accum.p, ctx->moments.m2.p,
+                           d.var[0].p, w * h);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     for (uint32_t i = 0; i < p->iterations; i++) {
         DenoiseVgStep ds;
         ds.w = w;
@@ -1618,6 +1676,32 @@ int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p) {
     }
     d.ready = true;
     d.var_ready = true;
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_denoise_variance(rt_context *ctx, const rt_denoise_variance_params *p) { return denoise_variance(ctx, p, false); }
+int rt_denoise_moments(rt_context *ctx, const rt_denoise_variance_params *p) { return denoise_variance(ctx, p, true); }
+
+int rt_read_moments(rt_context *ctx, float *m2, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const size_t need = (size_t)ctx->width * ctx->height * sizeof(float);
+    if (!m2 || bytes != need) return fail(ctx, RT_EINVAL, "moment buffer must be %zu bytes", need);
+    if (!ctx->moments.target()) return fail(ctx, RT_ESTATE, "the sample moments are not valid: set RT_OPT_MOMENTS to 1, then rt_clear or rt_render_adaptive");
+    return read_back(ctx, m2, bytes, ctx->moments.m2.p, need, "moment");
+}
+
+int rt_device_moments(rt_context *ctx, void **d_m2) {
+    if (!ctx || !d_m2) return RT_EINVAL;
+    if (!ctx->moments.target()) return fail(ctx, RT_ESTATE, "the sample moments are not valid: set RT_OPT_MOMENTS to 1, then rt_clear or rt_render_adaptive");
+    *d_m2 = ctx->moments.m2.p;
+    return RT_OK;
+}
+
+int rt_moments_merge(uint32_t nA, const float sumA[3], float m2A, uint32_t nB, const float sumB[3], float m2B, float *m2_out) {
+    if (!sumA || !sumB || !m2_out) return fail(nullptr, RT_EINVAL, "rt_moments_merge: a pointer is NULL");
+    *m2_out = moments_merge((float)nA, sumA[0], sumA[1], sumA[2], m2A, (float)nB, sumB[0], sumB[1], sumB[2], m2B);
     return RT_OK;
 }
 
@@ -2108,6 +2192,13 @@ int rt_set_option(rt_context *ctx, int option, int value) {
         case RT_OPT_WALK_SLICES: ctx->walk_slices = value != 0; return RT_OK;
         case RT_OPT_WAVE_FILL: ctx->wave_fill = value != 0; return RT_OK;
         case RT_OPT_EXACT_GRID: ctx->sample_grid.exact = value != 0; return RT_OK;
+        case RT_OPT_MOMENTS:
+            if (value != 0 && value != 1) return fail(ctx, RT_EINVAL, "RT_OPT_MOMENTS takes 0 or 1");
+            if (value == 1 && ctx->world > 1)
+                return fail(ctx, RT_EINVAL, "sample moments on a sharded context (rank %d of %d)", ctx->rank, ctx->world);
+            if ((value != 0) != ctx->moments.on) ctx->moments.valid = false;   // (until the next rt_clear / rt_render_adaptive)
+            ctx->moments.on = value != 0;
+            return RT_OK;
         case RT_OPT_LOOKAHEAD:
             if (value < 0 || value == 1 || value > RT_LOOKAHEAD_MAX) return fail(ctx, RT_EINVAL, "RT_OPT_LOOKAHEAD takes 0 or 2..%d", RT_LOOKAHEAD_MAX);
             ctx->lookahead.k = value;

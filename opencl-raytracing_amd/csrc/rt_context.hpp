@@ -227,6 +227,7 @@ struct rt_context {
         DevBuf<uint32_t> block_active;  // per decision block: traced by the next round
         DevBuf<float> block_err;        // per decision block: its error after the last round it was traced in
         DevBuf<unsigned long long> stats;   // pt_adaptive_merge's counter rows (rt_amd.hip)
+        DevBuf<float> m2_scratch;       // W x H: the current round's moments (zero outside it); only with RT_OPT_MOMENTS 1
         size_t block_capacity = 0;
         uint32_t blocks = 0;            // blocks of the last completed rt_render_adaptive call (0: none)
     } adaptive;
@@ -245,6 +246,18 @@ struct rt_context {
         DevBuf<float> var[2];           // W x H each: v0 (the 7x7 estimate) and v(L) (the filtered variance)
         bool var_ready = false;         // both written since the frame was (re)allocated
     } denoise;
+
+    // per-pixel sample moments (RT_OPT_MOMENTS): the centred second moment of every pixel's sample luminances, kept beside
+    // the accumulator by every call that adds to it (pt_moments.hpp).  Allocated by the first rt_clear / rt_render_adaptive
+    // with the option on; reset by alloc_frame.  `valid`: zeroed together with the accumulator and updated by every launch
+    // since — set by rt_clear and rt_render_adaptive while the option is 1, dropped when the option's value changes and
+    // by alloc_frame.  While it is false every launch gets a NULL moment pointer and nothing writes the buffer.
+    struct Moments {
+        bool on = false;
+        bool valid = false;
+        DevBuf<float> m2;               // W x H
+        float *target() const { return on && valid ? m2.p : nullptr; }   // what a launch that adds to `accum` updates
+    } moments;
 
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
@@ -350,6 +363,7 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     fp.blocks_x = 0;
     fp.la_ring = nullptr;
     fp.la_image = nullptr;
+    fp.m2 = nullptr;
     {
         volatile float c = (float)count;
         volatile float q = 1.0f / c;

@@ -31,6 +31,7 @@ SYMBOLS = (
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
     "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
     "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
+    "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list",
 )
@@ -40,6 +41,7 @@ OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT
 OPT_PREFIX_CACHE = 9
 OPT_LOOKAHEAD = 10
 OPT_EXACT_GRID = 11
+OPT_MOMENTS = 12
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
 ARITH_NAMES = {"ieee": ARITH_IEEE, "rocm-opencl-nocontract": ARITH_ROCM_OCL_NOCONTRACT, "rocm-opencl": ARITH_ROCM_OCL}
 
@@ -119,6 +121,7 @@ def load_library(path=LIB_PATH):
     lib.rt_debug_builtin.argtypes = [vp, C.c_int, vp, sz, vp]
     _abi.adaptive_prototypes(lib)
     _abi.denoise_prototypes(lib)
+    _abi.moments_prototypes(lib)
     _abi.prefix_cache_prototypes(lib)
     _abi.lookahead_prototypes(lib)
     _abi.sample_grid_prototypes(lib)
@@ -173,6 +176,19 @@ def sample_units(seg_cap, pixels_per_unit, count_light, count_heavy):
     if rc:
         raise RtError(rc, lib.rt_last_error(None).decode())
     return int(out.value)
+
+
+def moments_merge(nA, sumA, m2A, nB, sumB, m2B):
+    """M2 of the union of two partial states (count, RGB sum, centred second luminance moment) of a pixel
+    (rt_moments_merge; host-only, no device needed): the float32 function the kernels call."""
+    lib = load_library()
+    a = (C.c_float * 3)(*[float(v) for v in sumA])
+    b = (C.c_float * 3)(*[float(v) for v in sumB])
+    out = C.c_float()
+    rc = lib.rt_moments_merge(int(nA), a, float(m2A), int(nB), b, float(m2B), C.byref(out))
+    if rc:
+        raise RtError(rc, lib.rt_last_error(None).decode())
+    return np.float32(out.value)
 
 
 def _cam_block(camera):
@@ -267,6 +283,7 @@ class RayTracer:
     OPT_PREFIX_CACHE = 9
     OPT_LOOKAHEAD = 10
     OPT_EXACT_GRID = 11
+    OPT_MOMENTS = 12
 
     def setOption(self, option, value):
         self._check(self._lib.rt_set_option(self._ctx, option, int(value)))
@@ -434,6 +451,52 @@ class RayTracer:
         p = C.c_void_p()
         self._check(self._lib.rt_device_variance(self._ctx, int(which), C.byref(p)))
         return p.value
+
+    def moments(self):
+        """Per-pixel centred second moment of the sample luminances, M2 = sum (l(s_j) - mean)^2 over the samples the
+        accumulator holds (rt_read_moments; OPT_MOMENTS 1, valid from clear / renderAdaptive on) → (h, w) float32."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self._lib.rt_read_moments(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def deviceMoments(self):
+        """Device address of the W x H floats of moments() (rt_device_moments)."""
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_moments(self._ctx, C.byref(p)))
+        return p.value
+
+    def sampleVariance(self):
+        """Measured variance of every pixel's MEAN luminance, M2 / (n (n - 1)); 0 where n < 2 → (h, w) float32."""
+        m2 = self.moments().astype(np.float64)
+        n = self.sampleCounts().astype(np.float64)
+        ok = n >= 2
+        return np.where(ok, m2 / np.where(ok, n * (n - 1.0), 1.0), 0.0).astype(np.float32)
+
+    def denoiseMoments(self, camera=None, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
+                       sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                       sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
+                       sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
+                       sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """The variance-guided filter on MEASURED variance (rt_denoise_moments): denoiseVariance with each pixel's own
+        sample variance in place of the 7x7 estimate wherever the pixel holds >= 4 samples; needs OPT_MOMENTS 1 since
+        the last clear / renderAdaptive.  Renders the features for `camera` first when one is given.  → the denoised
+        gamma image (h, w, 4), the buffer denoisedImage() reads; variance(0 / 1) read its v0 and v(L)."""
+        if camera is not None:
+            self.renderFeatures(camera)
+        self.denoiseMomentsOnDevice(iterations, sigma_luminance, sigma_normal, sigma_position, sigma_albedo,
+                                    split_objects)
+        return self.denoisedImage()
+
+    def denoiseMomentsOnDevice(self, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
+                               sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                               sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
+                               sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
+                               sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+        """rt_denoise_moments enqueued, nothing read back."""
+        p = _abi.DenoiseVarianceParams(int(iterations), float(sigma_luminance), float(sigma_normal),
+                                       float(sigma_position), float(sigma_albedo),
+                                       _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+        self._check(self._lib.rt_denoise_moments(self._ctx, C.byref(p)))
 
     def deviceFeatures(self):
         """Device address of the W x H feature records (rt_device_features)."""

@@ -6,10 +6,13 @@ of the noisy frame and of the denoised frame (default sigmas), the device time o
 the denoised 16-spp RMSE.  --sweep instead scores a grid of sigmas at 16 spp (the choice of the defaults).
 --variance-guided instead prints, per scene and spp, the RMSE and the device time of rt_denoise and of rt_denoise_variance
 (default parameters each) side by side, on the same frames in the same run.
+--measured prints that table with a fourth filter, rt_denoise_moments (the variance-guided filter on the variance measured
+from the per-pixel sample moments, RT_OPT_MOMENTS), its device time, and what keeping the moments costs the frame: the
+two stages of the fused 64-spp call (rt_stage_ms_history, median of --reps) with the option off and on.
 --profile-only runs just the denoise (with --variance-guided: rt_denoise_variance), --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
 such a run's kernel_trace.csv into per-iteration times.
 
-    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided]
+    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided | --measured]
 """
 import argparse
 import csv
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--variance-guided", action="store_true")
+    ap.add_argument("--measured", action="store_true")
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--json", default=None)
@@ -103,6 +107,32 @@ def main():
             t.setStream(None)
             t.close()
             continue
+        if a.measured:
+            def frame_ms(on):   # the fused call's two stages, median of reps: camera and scene rest, so the prefix is kept
+                t.setOption(t.OPT_MOMENTS, on)
+                first, second = [], []
+                for _ in range(a.reps + 1):
+                    t.renderFrameOnDevice(wl.camera, 64)
+                    t.sync()
+                    f, s2 = t.stageMsHistory(1)
+                    first.append(float(f[-1]))
+                    second.append(float(s2[-1]))
+                return float(np.median(first[1:])), float(np.median(second[1:]))
+            off, on = frame_ms(0), frame_ms(1)
+            for spp in (2, 4, 16, 64):
+                t.renderFrameOnDevice(wl.camera, spp)
+                noisy = rmse(t.deviceImage())
+                ms_d = float(np.median([timed(lambda: t.denoiseOnDevice()) for _ in range(a.reps)]))
+                den = rmse(t.deviceDenoised())
+                ms_v = float(np.median([timed(lambda: t.denoiseVarianceOnDevice()) for _ in range(a.reps)]))
+                vg = rmse(t.deviceDenoised())
+                ms_m = float(np.median([timed(lambda: t.denoiseMomentsOnDevice()) for _ in range(a.reps)]))
+                rows.append(dict(scene=name, spp=spp, rmse_noisy=noisy, rmse_denoised=den, rmse_variance_guided=vg,
+                                 rmse_moments=rmse(t.deviceDenoised()), ms_denoise=ms_d, ms_denoise_variance=ms_v,
+                                 ms_denoise_moments=ms_m, frame64_ms_moments_off=off, frame64_ms_moments_on=on))
+            t.setStream(None)
+            t.close()
+            continue
         if a.variance_guided:
             for spp in (1, 4, 16, 64):
                 t.renderFrameOnDevice(wl.camera, spp)
@@ -150,6 +180,20 @@ def main():
         for k, v in ranked[:12]:
             print("| %s | %s | %.3f |" % (", ".join("%g" % x for x in k), ", ".join("%.3f" % x for x in v), np.mean(v)))
         out = sweep
+    elif a.measured:
+        print("| scene | spp | RMSE noisy | RMSE rt_denoise | RMSE rt_denoise_variance | RMSE rt_denoise_moments | rt_denoise ms | rt_denoise_variance ms | rt_denoise_moments ms |")
+        print("|---|---:|---:|---:|---:|---:|---:|---:|---:|")
+        for r in rows:
+            print("| %s | %d | %.4f | %.4f | %.4f | %.4f | %.3f | %.3f | %.3f |" %
+                  (r["scene"].upper(), r["spp"], r["rmse_noisy"], r["rmse_denoised"], r["rmse_variance_guided"], r["rmse_moments"],
+                   r["ms_denoise"], r["ms_denoise_variance"], r["ms_denoise_moments"]))
+        print()
+        print("| scene | 64 spp frame, moments off: first + second stage ms | moments on |")
+        print("|---|---:|---:|")
+        for name in a.scenes.split(","):
+            r = next(r for r in rows if r["scene"] == name)
+            print("| %s | %.3f + %.3f | %.3f + %.3f |" % ((name.upper(),) + tuple(r["frame64_ms_moments_off"]) + tuple(r["frame64_ms_moments_on"])))
+        out = rows
     elif a.variance_guided:
         print("| scene | spp | RMSE noisy | RMSE rt_denoise | RMSE rt_denoise_variance | rt_denoise ms | rt_denoise_variance ms |")
         print("|---|---:|---:|---:|---:|---:|---:|")
