@@ -1,6 +1,7 @@
 // rt_context.hpp — the context behind the C ABI (include/rt_amd.h) and the helpers every translation unit of
-// librt_amd.so shares: rt_amd.hip (host side: C ABI, scene upload, BVH builders, policy-free kernels) and
-// pt_kernels.hip (the path-tracing kernels and their launchers, compiled once per arithmetic policy).
+// librt_amd.so shares: rt_amd.hip (host side: C ABI, scene upload, BVH builders, policy-free kernels), rt_denoise.hip
+// (the denoisers, policy-free) and pt_kernels.hip (the path-tracing kernels and their launchers, compiled once per
+// arithmetic policy).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -268,6 +269,10 @@ using namespace pt;
 
 // records the message on the context (or, for ctx == nullptr, as the last rt_create failure) and returns `code`
 int fail(rt_context *ctx, int code, const char *fmt, ...);
+// Copies the `need` bytes of device buffer `src` into the caller's `dst` of `bytes` bytes and waits for them: EINVAL
+// unless the sizes match, then ESTATE unless `src` is `ready` (written by a `producer` call since the frame was made).
+int read_back(rt_context *ctx, void *dst, size_t bytes, const void *src, size_t need, const char *what, bool ready = true,
+              const char *producer = nullptr);
 
 #define HIP_TRY(ctx, expr)                                                                        \
     do {                                                                                          \

@@ -253,6 +253,21 @@ def test_filter_matches_the_restatement_c3(sig):
         t.close()
 
 
+@pytest.mark.parametrize("size", [(37, 23), (7, 5), (1, 1)])
+def test_filter_matches_the_restatement_on_tiny_frames(size):
+    """Frames smaller than a tile, than the halo and than the late steps: staging, the out-of-frame key and the empty
+    tiles of the sparse classes."""
+    wl = rt.workloads.get("c2", width=size[0], height=size[1])
+    t = rt.RayTracer(wl.width, wl.height, scene=wl.scene, seed=cases.SEED)
+    try:
+        t.renderFrame(wl.camera, 4)
+        for sig in sorted(SIGMAS):
+            _against_restatement(t, wl, **SIGMAS[sig])
+        _against_restatement(t, wl, iterations=8)
+    finally:
+        t.close()
+
+
 def gamma_rmse(a, b):
     return float(np.sqrt(((a[..., :3].astype(np.float64) - b[..., :3]) ** 2).mean()))
 

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""tools/isa_stats.py [--arith K] [--unit rt_amd] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
+"""tools/isa_stats.py [--arith K] [--unit rt_amd | rt_denoise] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
 
 Compiles csrc/pt_kernels.hip for the device only (-S, the flags of __graft_entry__ for arithmetic policy K = 0 | 1 | 2,
 default 2 = rocm-opencl, the policy bench.py times; ISA_ARITH in the environment does the same) and prints, per
 kernel: VGPRs / SGPRs / scratch bytes / spilled VGPRs from the code-object metadata and the static opcode
 histogram grouped into the issue-cost classes measured by tools/valu_microbench.hip
-(profiles/r02_valu_microbench.md).  --unit rt_amd reads the policy-free kernels of csrc/rt_amd.hip instead (pt_atrous,
-pt_dn_variance, pt_atrous_vg, pt_adaptive_merge: compiled once, with the IEEE divide).  --json dumps everything for bench.py / profile summaries."""
+(profiles/r02_valu_microbench.md).  --unit rt_denoise / --unit rt_amd read the policy-free kernels of csrc/rt_denoise.hip
+(pt_atrous, pt_dn_variance, pt_atrous_vg) / csrc/rt_amd.hip (pt_adaptive_merge, ...) instead: compiled once, with the
+IEEE divide.  --json dumps everything for bench.py / profile summaries."""
 import collections
 import json
 import os
@@ -80,13 +81,17 @@ def default_arith():
 
 def device_asm(force=False, arith=None):
     import __graft_entry__ as g
-    if "--unit" in sys.argv and sys.argv[sys.argv.index("--unit") + 1:][:1] == ["rt_amd"]:
-        out = os.path.join(ROOT, "build", "rt_amd_gfx950.s")
+    srcs = g.hip_sources()
+    by_name = {os.path.splitext(os.path.basename(s))[0]: s for s in srcs if s.endswith(".hip")}
+    unit = sys.argv[sys.argv.index("--unit") + 1:][:1] if "--unit" in sys.argv else []
+    if unit and unit[0] != "pt_kernels":
+        if unit[0] not in by_name:
+            sys.exit("--unit %s: not one of %s" % (unit[0], ", ".join(sorted(by_name))))
+        out = os.path.join(ROOT, "build", "%s_gfx950.s" % unit[0])
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        srcs = g.hip_sources()
         if force or not os.path.isfile(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
             flags = [f for f in g.HIP_FLAGS if f not in ("-shared", "-fPIC")] + [g.IEEE_DIV]
-            subprocess.check_call([g.HIPCC] + flags + ["--cuda-device-only", "-S", srcs[0], "-o", out],
+            subprocess.check_call([g.HIPCC] + flags + ["--cuda-device-only", "-S", by_name[unit[0]], "-o", out],
                                   stderr=subprocess.DEVNULL)
         return out
     arith = default_arith() if arith is None else int(arith)
@@ -94,10 +99,9 @@ def device_asm(force=False, arith=None):
     tag = ("_" + "_".join(e.lstrip("-D").replace("=", "") for e in extra)) if extra else ""
     out = os.path.join(ROOT, "build", "pt_kernels_a%d_gfx950%s.s" % (arith, tag))
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    srcs = g.hip_sources()
     if force or not os.path.isfile(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         flags = [f for f in g.HIP_FLAGS if f not in ("-shared", "-fPIC")] + g.POLICY_FLAGS[arith]
-        subprocess.check_call([g.HIPCC] + flags + extra + ["--cuda-device-only", "-S", srcs[1], "-o", out],
+        subprocess.check_call([g.HIPCC] + flags + extra + ["--cuda-device-only", "-S", by_name["pt_kernels"], "-o", out],
                               stderr=subprocess.DEVNULL)
     return out
 
