@@ -620,6 +620,11 @@ int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6);
  * bits).  in8: n × 8 floats {a.xyz, b.xyz, t, -}; out4: n × 4 floats.  tests/test_gpu_ref950.py compares policies
  * 1 / 2 with probe kernels that call ROCm's OpenCL builtins themselves. */
 int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float *out4);
+/* rt_debug_queue_sums: the sample-queue kernels' per-pixel summation on its own.  ONE wave owns npix pixels of `count`
+ * samples each (npix <= 16, npix × count <= 512), finds their radiances in its queue — in3: npix × count × 3 floats,
+ * pixel-major — and sums them with 1 << group_log2 lanes per pixel (group_log2 <= 6) as a launch without sample moments
+ * does.  out4: npix × 4 floats {sum.rgb, count}, the accumulator after the launch when it was zero before. */
+int rt_debug_queue_sums(rt_context *ctx, const float *in3, uint32_t npix, uint32_t count, uint32_t group_log2, float *out4);
 
 /* The two stages of the same calls separately: a fused rt_render_spp call is pt_prefix
  * (first_ms: one work-item per pixel, the sample-invariant path prefix) or, when the call

@@ -195,6 +195,12 @@ def sample_grid_prototypes(lib):
     lib.rt_debug_live_list.argtypes = [C.c_void_p, C.POINTER(u32)]
 
 
+def queue_sums_prototypes(lib):
+    """ctypes prototype of rt_debug_queue_sums (the sample queue's per-pixel summation, one wave)."""
+    u32 = C.c_uint32
+    lib.rt_debug_queue_sums.argtypes = [C.c_void_p, C.c_void_p, u32, u32, u32, C.c_void_p]
+
+
 def split_features(rec):
     """(H, W) FEATURE records → dict of (H, W, ...) arrays (RayTracer.features())."""
     return {"position": rec["pos"].copy(), "depth": rec["t"].copy(), "normal": rec["normal"].copy(),

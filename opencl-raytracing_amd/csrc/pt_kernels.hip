@@ -661,10 +661,85 @@ PT_DEV void queue_put(const WaveQueue &q, uint32_t idx, V3 rgb) {
 // pt_samples_q<false, false, 1, 6> of policy 0 parks exactly 64 SGPRs in the lanes of ONE VGPR — the two more took a second
 // one and the loop spilled three VGPRs to scratch, with the option off.  The instantiations without moments never read
 // the field and compile to what they compiled to before it existed.
-template <bool MOMENTS>
+//
+// Without moments only lane 0 of a pixel's g lanes is used, and after the butterfly step `off` lanes l and l ^ off hold
+// the same value (IEEE addition commutes): lane 0's sum is, bit for bit, that of the half-lane tree
+//   for off = g/2 … 1, for l < off: T(l) = T(l) + T(l + off)
+// (tests/test_queue_sums_host.py).  queue_sums_tree forms that tree without LDS permutes (PT_QUEUE_SUMS_TREE 0: the butterfly):
+//   offset 32     at the LDS read: half-wave h takes a pixel of its own and lane i of it forms S(i) and S(i + 32)
+//   offset 16     v_permlane16_swap of two such registers (pixels pb, pb+1 | pb+2, pb+3) and one add: four pixels, one per
+//                 row of 16 lanes, in row order pb, pb+2, pb+1, pb+3
+//   offsets 8 … 1 v_add_f32 with a DPP row shift (lane i takes lane i + off of its row); the lanes outside lane 0's cone
+//                 add neighbours or zeros and are never stored
+// and the four (g >= 32) or 64 / g rows' first lanes add to the accumulator together.  g <= 16 keeps a pass per 64 / g pixels
+// and needs the row shifts only.  All of it runs under the full EXEC mask: a pixel the wave does not own has a trip count
+// of 0, never a branch around a cross-lane operation, and reads nothing.
+// A NaN in a slot gives a NaN sum in both forms, but its payload is not pinned: the compiler picks the operand order of a
+// DPP add.  No radiance is a NaN (no test produces one).
+#ifndef PT_QUEUE_SUMS_TREE
+#define PT_QUEUE_SUMS_TREE 1
+#endif
+// lane l of pixel p's g lanes: 0.0f + its slots l, l + g, … in that order (nothing for a pixel the wave does not own)
+PT_DEV V3 queue_lane_sum(const WaveQueue &q, uint32_t p, uint32_t l, uint32_t g) {
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const uint32_t n = p < q.npix ? q.count : 0u;
+    for (uint32_t j = l; j < n; j += g) {
+        const LdsF32 sl = q.slot + 3u * (p * q.count + j);
+        sum = sum + mk(sl[0], sl[1], sl[2]);
+    }
+    return sum;
+}
+// v(i) + v(i + OFF) within a row of 16 lanes (one v_add_f32_dpp row_shl:OFF; a lane whose partner lies outside its row adds 0)
+template <int OFF>
+PT_DEV float row_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + OFF, 0xF, 0xF, false));
+}
+template <int OFF>
+PT_DEV V3 row_add(V3 v) { return mk(row_add<OFF>(v.x), row_add<OFF>(v.y), row_add<OFF>(v.z)); }
+// rows (a0 a1 a2 a3), (b0 b1 b2 b3) → (a0 + a1, b0 + b1, a2 + a3, b2 + b3): the swap exchanges a's odd rows with b's even rows
+PT_DEV float row_pair_add(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+PT_DEV void queue_sums_tree(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
+    const uint32_t lane = threadIdx.x, gl = fp.group_log2;
+    if (gl >= 5u) {
+        const uint32_t half = lane >> 5, i = lane & 31u, g = 1u << gl, row = lane >> 4;
+        for (uint32_t pb = 0; pb < q.npix; pb += 4u) {
+            V3 a = queue_lane_sum(q, pb + half, i, g), b = queue_lane_sum(q, pb + 2u + half, i, g);
+            if (gl == 6u) {   // offset 32
+                a = a + queue_lane_sum(q, pb + half, i + 32u, g);
+                b = b + queue_lane_sum(q, pb + 2u + half, i + 32u, g);
+            }
+            V3 sum = mk(row_pair_add(a.x, b.x), row_pair_add(a.y, b.y), row_pair_add(a.z, b.z));   // offset 16
+            sum = row_add<1>(row_add<2>(row_add<4>(row_add<8>(sum))));
+            const uint32_t p = pb + ((row & 1u) << 1 | row >> 1);
+            if (p < q.npix && (lane & 15u) == 0u) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, q.count);
+        }
+    } else {
+        const uint32_t g = 1u << gl, ppp = 64u >> gl;
+        for (uint32_t pb = 0; pb < q.npix; pb += ppp) {
+            const uint32_t p = pb + (lane >> gl), l = lane & (g - 1u);
+            V3 sum = queue_lane_sum(q, p, l, g);
+            if (gl >= 4u) sum = row_add<8>(sum);
+            if (gl >= 3u) sum = row_add<4>(sum);
+            if (gl >= 2u) sum = row_add<2>(sum);
+            if (gl >= 1u) sum = row_add<1>(sum);
+            if (p < q.npix && l == 0u) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, q.count);
+        }
+    }
+}
+// BUTTERFLY: the instantiation keeps the butterfly and is the code it was before the tree existed —
+//   the counting builds, whose 14 counters live through the epilogue: with the tree two of them (policy 0 <true, true, 0, 6>,
+//   policy 1 <true, true, 1, 5>) spill more registers in the sample loop;
+//   the kernels with a BVH walk (pt_samples_q<…, ACCEL = true>, pt_samples_w): their waves live for milliseconds, the
+//   epilogue is nothing to them, and with the tree C4 and C5 measured 1.2 % and 0.9 % SLOWER than the parent
+//   (profiles/r13_experiments.md) — the walk loops' code moved with the epilogue behind them.
+template <bool MOMENTS, bool BUTTERFLY = false>
 PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    if (PT_QUEUE_SUMS_TREE && !MOMENTS && !BUTTERFLY) return queue_sums_tree(q, fp, accum);   // (moments need the sum in all g lanes)
     const uint32_t lane = threadIdx.x;
     const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
     for (uint32_t pb = 0; pb < q.npix; pb += ppp) {
@@ -888,7 +963,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
     if (!COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
-    else queue_sums<MOMENTS>(q, fp, accum);
+    else queue_sums<MOMENTS, COUNT || ACCEL>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }
 
@@ -1171,7 +1246,7 @@ __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_
     }
 #endif
     if (!MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never with moments)
-    else queue_sums<MOMENTS>(q, fp, accum);
+    else queue_sums<MOMENTS, true>(q, fp, accum);
 }
 
 // parity probe: one work-item per listed pixel-sample
@@ -1360,6 +1435,35 @@ __global__ __launch_bounds__(256) void pt_debug_div3(const float *__restrict__ i
     }
     float *o = out + 6 * (size_t)i;
     o[0] = s.x; o[1] = s.y; o[2] = s.z; o[3] = q.x; o[4] = q.y; o[5] = q.z;
+}
+
+// queue_sums on its own (rt_debug_queue_sums): ONE wave fills the slot region of its queue from `in` (npix × count × 3
+// floats, pixel-major), owns pixels (p, 0) of an npix × 1 frame, and runs the sample kernels' epilogue into `accum`
+// (npix float4, zeroed by the caller).  The host checks npix <= QUEUE_MAX_PIXELS and npix × count <= QUEUE_SLOTS.
+__global__ __launch_bounds__(64) void pt_debug_queue_sums(const float *__restrict__ in, uint32_t npix, uint32_t count,
+                                                          uint32_t group_log2, float4 *__restrict__ accum) {
+    __shared__ float4 s_q[QUEUE_MAX_PIXELS * QUEUE_XY_F4 + (QUEUE_SLOTS * 3u + 3u) / 4u];
+    WaveQueue q;
+    q.rec = nullptr;
+    q.xy = (LdsQueueXY)s_q;
+    q.slot = (LdsF32)(s_q + QUEUE_MAX_PIXELS * QUEUE_XY_F4);
+    q.npix = npix;
+    q.count = count;
+    q.total = npix * count;
+    q.count_log2 = 0xFFu;
+    q.inv_count = 0.0f;
+    const uint32_t lane = threadIdx.x;
+    if (lane < npix) {
+        q.xy[lane].x = lane;
+        q.xy[lane].y = 0u;
+    }
+    for (uint32_t i = lane; i < 3u * q.total; i += 64u) q.slot[i] = in[i];
+    FrameParams fp = {};
+    fp.w = (int)npix;
+    fp.h = 1;
+    fp.count = count;
+    fp.group_log2 = group_log2;
+    queue_sums<false>(q, fp, accum);
 }
 
 // ================================== launchers ==================================
@@ -1698,6 +1802,15 @@ int ks_launch_debug_div3(rt_context *ctx, const float *d_in, uint32_t n, float *
     return RT_OK;
 }
 
+int ks_launch_debug_queue_sums(rt_context *ctx, const float *d_in, uint32_t npix, uint32_t count, uint32_t glog2, float *d_out) {
+    if (npix < 1u || npix > QUEUE_MAX_PIXELS || count < 1u || npix * count > QUEUE_SLOTS || glog2 > 6u)
+        return fail(ctx, RT_EINVAL, "queue_sums probe: %u pixels of %u samples do not fit one wave's queue", npix, count);
+    HIP_TRY(ctx, hipMemsetAsync(d_out, 0, npix * sizeof(float4), ctx->stream));
+    hipLaunchKernelGGL(pt_debug_queue_sums, dim3(1), dim3(64), 0, ctx->stream, d_in, npix, count, glog2, (float4 *)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_face_normals(rt_context *ctx, float4 *d_records, uint32_t n_records) {
     if (n_records == 0) return RT_OK;
     hipLaunchKernelGGL(pt_face_normals, dim3((n_records + 255u) / 256u), dim3(256), 0, ctx->stream, d_records, n_records);
@@ -1721,7 +1834,7 @@ const pt::KernelSet g_kernel_set = {
     "rocm-opencl",
 #endif
     ks_launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
-    ks_launch_face_normals, ks_launch_debug_builtin};
+    ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums};
 
 }  // namespace
 

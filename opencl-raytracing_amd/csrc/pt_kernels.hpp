@@ -36,6 +36,8 @@ struct KernelSet {
     // one builtin per record, for tests against oracle/_ref/gfx950's probe kernels: op 0 dot, 1 cross, 2 normalize,
     // 3 a/b, 4 sqrt, 5 mix, 6 min, 7 sign, 8 pow(x,5), 9 the table hash; in: n × 8 floats, out: n × 4 floats
     int (*launch_debug_builtin)(rt_context *ctx, int op, const float *d_in, uint32_t n, float *d_out);
+    // rt_debug_queue_sums: one wave's queue_sums over npix × count × 3 slot floats into npix float4 (zeroed here)
+    int (*launch_debug_queue_sums)(rt_context *ctx, const float *d_in, uint32_t npix, uint32_t count, uint32_t glog2, float *d_out);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

@@ -1654,6 +1654,16 @@ int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6) {
     });
 }
 
+int rt_debug_queue_sums(rt_context *ctx, const float *in3, uint32_t npix, uint32_t count, uint32_t group_log2, float *out4) {
+    if (!ctx || !in3 || !out4) return RT_EINVAL;
+    if (npix < 1u || npix > 16u || count < 1u || npix * (uint64_t)count > 512u || group_log2 > 6u)   // (a wave's queue: 16 pixels, 512 slots)
+        return fail(ctx, RT_EINVAL, "queue_sums probe: %u pixels of %u samples do not fit one wave's queue", npix, count);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return debug_roundtrip(ctx, in3, (size_t)npix * count * 3 * sizeof(float), out4, (size_t)npix * 4 * sizeof(float), [&](void *d_in, void *d_out) {
+        return ctx->ks->launch_debug_queue_sums(ctx, (const float *)d_in, npix, count, group_log2, (float *)d_out);
+    });
+}
+
 int rt_shard_slots(rt_context *ctx, int world, uint32_t *slots_out) {
     if (!ctx || !slots_out || world < 1) return RT_EINVAL;
     uint32_t tw = 1u << ctx->tile_w_log2, th = 1u << ctx->tile_h_log2;

@@ -33,7 +33,7 @@ SYMBOLS = (
     "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
     "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
-    "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list",
+    "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_queue_sums",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -125,6 +125,7 @@ def load_library(path=LIB_PATH):
     _abi.prefix_cache_prototypes(lib)
     _abi.lookahead_prototypes(lib)
     _abi.sample_grid_prototypes(lib)
+    _abi.queue_sums_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -656,6 +657,14 @@ class RayTracer:
         vec = np.ascontiguousarray(vec, dtype=np.float32).reshape(-1, 4)
         out = np.zeros((len(vec), 6), dtype=np.float32)
         self._check(self._lib.rt_debug_div3(self._ctx, vec.ctypes.data, len(vec), out.ctypes.data))
+        return out
+
+    def debugQueueSums(self, slots, group_log2):
+        """One wave's queue_sums (rt_debug_queue_sums): slots (npix, count, 3) float32 → (npix, 4) {sum.rgb, count}."""
+        slots = np.ascontiguousarray(slots, dtype=np.float32)
+        npix, count = slots.shape[0], slots.shape[1]
+        out = np.zeros((npix, 4), dtype=np.float32)
+        self._check(self._lib.rt_debug_queue_sums(self._ctx, slots.ctypes.data, npix, count, group_log2, out.ctypes.data))
         return out
 
     def deviceInfo(self):
