@@ -617,8 +617,10 @@ int rt_debug_material(rt_context *ctx, int routine, const float *in16, size_t n,
 int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6);
 /* rt_debug_builtin: ONE builtin of the selected arithmetic policy per record — op 0 dot, 1 cross, 2 normalize,
  * 3 {a0/a1, 1/a0, (a.yz)/a6}, 4 sqrt, 5 mix(a, b, a6), 6 min, 7 sign, 8 pow(a0, 5), 9 the table hash of a.xyz (uint
- * bits).  in8: n × 8 floats {a.xyz, b.xyz, t, -}; out4: n × 4 floats.  tests/test_gpu_ref950.py compares policies
- * 1 / 2 with probe kernels that call ROCm's OpenCL builtins themselves. */
+ * bits); 10 sqrt and 11 normalize in the tagged forms the sample queue runs (csrc/pt_arith.hpp: the WAVE — 64
+ * consecutive records — chooses between the bare instruction and the untagged form; same bits as ops 4 and 2,
+ * tests/test_gpu_fast_builtins.py).  in8: n × 8 floats {a.xyz, b.xyz, t, -}; out4: n × 4 floats.
+ * tests/test_gpu_ref950.py compares policies 1 / 2 with probe kernels that call ROCm's OpenCL builtins themselves. */
 int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float *out4);
 /* rt_debug_queue_sums: the sample-queue kernels' per-pixel summation on its own.  ONE wave owns npix pixels of `count`
  * samples each (npix <= 16, npix × count <= 512), finds their radiances in its queue — in3: npix × count × 3 floats,

@@ -189,6 +189,60 @@ PT_DEV V3 normalize(V3 v) {
 }
 #endif
 
+// ---- tagged forms: the builtins without the range scaling a wave does not need (policies 1, 2) ------------------
+// The tool chain's expansions of sqrt and normalize carry range scaling that is an exact identity on ordinary
+// operands and is still issued in full, mostly as half-rate opcodes.  A kernel that sets the
+// compile-time tag FAST (pt_samples_q without counters and without a BVH walk, nothing else) asks the WAVE whether
+// any active lane needs them: if none does, it runs the bare instruction — the one the expansion itself reaches
+// with shifts of 0 and factors of 1.0 — and otherwise exactly the untagged function above, behind a real scalar
+// branch.  FAST = false, and policy 0 with either value, IS the untagged function.
+//   The slow arms start with an empty, non-volatile asm on their operand: without it the compiler if-converts the
+// choice (both forms issued, a select after them — nothing saved) and, speculating __builtin_sqrtf, loses its
+// !fpmath 3.0 expansion for the correctly rounded one, whose bits differ.  A volatile asm would be a memory clobber
+// and turn the scalar loads of the sphere records into per-lane vector loads.
+// Each part has its own switch for A/B builds (tools/build_variant.sh <name> -DPT_FAST_SQRT=0 ...).
+#ifndef PT_FAST_SQRT
+#define PT_FAST_SQRT 1
+#endif
+#ifndef PT_FAST_NORMALIZE
+#define PT_FAST_NORMALIZE 1
+#endif
+// true in every ACTIVE lane of the wave (one v_cmp of the negated predicate and a scalar compare of its mask with 0)
+PT_DEV bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }
+// sqrt: the 3-ulp expansion is ldexp(v_sqrt_f32(ldexp(x, x < FLT_MIN ? 32 : 0)), x < FLT_MIN ? -16 : 0).  With no
+// lane below FLT_MIN (negative numbers count as below; NaN and +inf do not, and are not scaled by the expansion
+// either) both ldexp shift by 0.
+template <bool FAST>
+PT_DEV float sqrt1(float x) {
+#if PT_OCL
+    if (FAST && PT_FAST_SQRT) {
+        if (__builtin_expect(wave_all(!(x < 0x1p-126f)), 1)) return __builtin_amdgcn_sqrtf(x);
+        asm("" : "+v"(x));
+    }
+#endif
+    return sqrt1(x);
+}
+// normalize: a squared length that is a positive normal number (one v_cmp_class_f32) means the vector is not zero,
+// neither rescaling branch is taken, and __ocml_rsqrt_f32's own factors (2^24 below FLT_MIN, 2^12 after) are 1.0.
+template <bool FAST>
+PT_DEV V3 normalize(V3 v) {
+#if PT_OCL
+    if (FAST && PT_FAST_NORMALIZE) {
+        const float d = dot(v, v);
+        // (a ballot compared as a scalar: the guard is no per-lane value the structurizer would keep in a register)
+        const bool plain = __builtin_amdgcn_ballot_w64(__builtin_amdgcn_classf(d, 0x2FF /* anything but +normal */)) == 0ull;
+        V3 n;
+        if (__builtin_expect(plain, 1)) {
+            n = v * __builtin_amdgcn_rsqf(d);
+        } else {
+            asm("" : "+v"(v.x));
+            n = normalize(v);
+        }
+        return n;
+    }
+#endif
+    return normalize(v);
+}
 // :127 — false for NaN
 PT_DEV bool in_range(float x) { return (x - RT_MAX_DISTANCE) * (x - RT_MIN_DISTANCE) <= 0.0f; }
 

@@ -196,6 +196,7 @@ enum : uint32_t { K_SPHERE = 0u << 30, K_PLANE = 1u << 30, K_LENS = 2u << 30, K_
 // :149-174.  s = (centre, r²) with r² the same float product, computed once at upload — or, under policy 2,
 // (centre, r): there `dot(oc,oc) - r*r` and `b*b - c` are contracted (:152-153), so the product never exists on
 // its own.  Returns the accepted root, or PT_MISS.
+template <bool FAST = false>
 PT_DEV float sphere_root(float b, float cc, float dis);
 PT_DEV void sphere_disc(const Ray &r, float4 s, float &b, float &cc, float &dis) {
     V3 oc = xyz(s) - r.o;
@@ -208,10 +209,11 @@ PT_DEV void sphere_disc(const Ray &r, float4 s, float &b, float &cc, float &dis)
     dis = b * b - cc;
 #endif
 }
+template <bool FAST = false>
 PT_DEV float sphere_t(const Ray &r, float4 s) {
     float b, cc, dis;
     sphere_disc(r, s, b, cc, dis);
-    return sphere_root(b, cc, dis);
+    return sphere_root<FAST>(b, cc, dis);
 }
 // what the host stores in the fourth component of a sphere's test record (sph4, bvh_sph)
 #define PT_SPHERE_W_IS_RADIUS PT_CONTRACT
@@ -227,8 +229,9 @@ PT_DEV bool sphere_needs_roots(float b, float cc, float dis) {
     return dis > 0 && !(PT_BEHIND_SKIP && b < 0.0f && cc > 0.0f && b > (PT_OCL ? -1024.0f : -4096.0f));
 }
 // :155-171 — the accepted root for dis > 0, or PT_MISS
+template <bool FAST = false>
 PT_DEV float sphere_roots(float b, float dis) {
-    float d = sqrt1(dis);
+    float d = sqrt1<FAST>(dis);
     float t = PT_MISS;
     float t0 = b - d;
     if (in_range(t0)) t = t0;
@@ -239,8 +242,29 @@ PT_DEV float sphere_roots(float b, float dis) {
     return t;
 }
 // second half of :149-174: the accepted root, or PT_MISS
+template <bool FAST>
 PT_DEV float sphere_root(float b, float cc, float dis) {
-    return sphere_needs_roots(b, cc, dis) ? sphere_roots(b, dis) : PT_MISS;
+    return sphere_needs_roots(b, cc, dis) ? sphere_roots<FAST>(b, dis) : PT_MISS;
+}
+// The brute-force scan's step for one sphere, tagged kernels: a sphere that needs no roots returns PT_MISS, and
+// `PT_MISS < best_t` is false for every best_t (it starts at MAX_DISTANCE and only ever decreases), so the comparison
+// with the best hit and the two selects after it belong INSIDE the divergent block that takes the roots — which a
+// wave enters for about one sphere in ten — instead of after every sphere.  Same comparisons in the same order for
+// every sphere that has a root: the same winner, ties included.
+#ifndef PT_ROOT_UPDATE
+#define PT_ROOT_UPDATE 1
+#endif
+template <bool FAST>
+PT_DEV void sphere_take(const Ray &r, float4 s, uint32_t id, float &best_t, uint32_t &best_id) {
+    float b, cc, dis;
+    sphere_disc(r, s, b, cc, dis);
+    if (sphere_needs_roots(b, cc, dis)) {
+        const float t = sphere_roots<FAST>(b, dis);
+        if (t < best_t) {
+            best_t = t;
+            best_id = id;
+        }
+    }
 }
 // ---- sphere BVH -------------------------------------------------------------------
 // The reference tests every sphere on every bounce (:327-333).  For large sphere counts
@@ -460,7 +484,8 @@ struct Nearest {
     float u = 0.0f, v = 0.0f;
 };
 // LENSES = false compiles the lens loop out (kernels specialised for scenes of spheres and planes only)
-template <bool COUNT, bool ACCEL, bool LENSES = true>
+// FAST: the brute-force sphere tests take their square roots through sqrt1<true> (pt_arith.hpp "tagged forms")
+template <bool COUNT, bool ACCEL, bool LENSES = true, bool FAST = false>
 PT_DEV void hit_primitives(const Ctx &c, const Ray &r, Nearest &nb) {
     const DeviceScene &sc = c.sc;
     float best_t = nb.t;
@@ -485,11 +510,19 @@ PT_DEV void hit_primitives(const Ctx &c, const Ray &r, Nearest &nb) {
             sp += PT_SPHERE_BATCH;  // the array ends with one dummy batch, so this prefetch is always in bounds
             float4 n0_ = sp[0], n1_ = sp[1], n2_ = sp[2], n3_ = sp[3];
             uint32_t i = b * PT_SPHERE_BATCH;
+            if (FAST && PT_ROOT_UPDATE) {
+                sphere_take<FAST>(r, a0, K_SPHERE | i, best_t, best_id);
+                sphere_take<FAST>(r, a1, K_SPHERE | (i + 1), best_t, best_id);
+                sphere_take<FAST>(r, a2, K_SPHERE | (i + 2), best_t, best_id);
+                sphere_take<FAST>(r, a3, K_SPHERE | (i + 3), best_t, best_id);
+                a0 = n0_; a1 = n1_; a2 = n2_; a3 = n3_;
+                continue;
+            }
             float t0, t1, t2, t3;
-            t0 = sphere_t(r, a0);
-            t1 = sphere_t(r, a1);
-            t2 = sphere_t(r, a2);
-            t3 = sphere_t(r, a3);
+            t0 = sphere_t<FAST>(r, a0);
+            t1 = sphere_t<FAST>(r, a1);
+            t2 = sphere_t<FAST>(r, a2);
+            t3 = sphere_t<FAST>(r, a3);
             if (t0 < best_t) { best_t = t0; best_id = K_SPHERE | i; }
             if (t1 < best_t) { best_t = t1; best_id = K_SPHERE | (i + 1); }
             if (t2 < best_t) { best_t = t2; best_id = K_SPHERE | (i + 2); }
@@ -814,7 +847,8 @@ PT_DEV GlassTerms glass_terms(const Ctx &c, V3 d, V3 hn, uint32_t mat, float ext
 }
 PT_DEV float glass_disc(const GlassTerms &g) { return nmad(g.ratio * g.ratio, nmad(g.cai, g.cai, 1.0f), 1.0f); }   // 1 - ratio * ratio * (1 - cai * cai)   (:381,:424)
 
-template <bool COUNT>
+// FAST: the glass refraction's square root and the shared tail's normalize in their tagged forms (pt_arith.hpp)
+template <bool COUNT, bool FAST = false>
 PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float extra, V3 col, const Rnd &rnd,
                     bool set_origin = true) {
     V3 v;
@@ -839,7 +873,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
         float disc = glass_disc(g);
         if (want && disc > 0.0f) {
             // ratio * dir - n * (ratio * cai + sqrt(disc))   (:385,:428): the LEFT product is the one clang contracts
-            V3 nk = n * mad(ratio, cai, sqrt1(disc));
+            V3 nk = n * mad(ratio, cai, sqrt1<FAST>(disc));
             v = PT_CONTRACT ? mk(__builtin_fmaf(ratio, r.d.x, -nk.x), __builtin_fmaf(ratio, r.d.y, -nk.y), __builtin_fmaf(ratio, r.d.z, -nk.z))
                             : r.d * ratio - nk;
             renorm = false;
@@ -851,7 +885,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
         return;  // unknown type: the reference's switch has no default (rejected by rt_set_scene)
     }
     if (set_origin) r.o = h.p;
-    if (renorm) v = normalize(v);
+    if (renorm) v = normalize<FAST>(v);
     r.d = v;
     out = vmin(out, col);  // mixCol is min(), :437
 }

@@ -805,6 +805,10 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                                                     float4 *__restrict__ accum, unsigned long long *counters,
                                                     uint32_t pixels_per_wave) {
     extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
+    // The tagged forms of sqrt and normalize (pt_arith.hpp) and the sphere scan that compares inside the root block
+    // (pt_device.hpp sphere_take): this kernel without counters and without a BVH walk only — every other kernel, and
+    // every other instantiation of this one, keeps the untagged code.
+    constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
     // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
     // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
     // anything is staged: no barrier, no sums, and only zeros to add to the counters.
@@ -909,7 +913,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             float extra;
             V3 mcol;
             load_material(c, hmat, type, extra, mcol);   // type and extra_data are not carried: one LDS read each
-            scatter<COUNT>(c, r, out, at, type, extra, col, rnd, false);
+            scatter<COUNT, FAST>(c, r, out, at, type, extra, col, rnd, false);
             depth++;
             if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
                 queue_put(q, idx, out);
@@ -925,7 +929,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             bool done = false;
             Hit h;   // (every field is written by hit_finish on a hit, and read only then)
             Nearest nb;
-            hit_primitives<COUNT, ACCEL, GEOM != 0>(c, r, nb);
+            hit_primitives<COUNT, ACCEL, GEOM != 0, FAST>(c, r, nb);
             if (GEOM != 0) hit_models<COUNT, GEOM == 2>(c, r, nb);
             if (!hit_finish<COUNT, GEOM == 0>(c, r, nb, h)) {
                 res = mk(0.0f, 0.0f, 0.0f);
@@ -1743,6 +1747,9 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
     else if (op == 7) o.x = sign1(a[0]);
     else if (op == 8) o.x = pow5(a[0]);
     else if (op == 9) o.x = __uint_as_float(dir_hash(x));
+    // the tagged forms of pt_arith.hpp as the sample queue runs them (the wave decides: 64 consecutive records)
+    else if (op == 10) o.x = sqrt1<true>(a[0]);
+    else if (op == 11) { V3 c = normalize<true>(x); o = make_float4(c.x, c.y, c.z, 0.0f); }
     reinterpret_cast<float4 *>(out)[i] = o;
 }
 

@@ -34,7 +34,8 @@ struct KernelSet {
     // (A, e1, e2, n) records: n_records records of 3 float4 each
     int (*launch_face_normals)(rt_context *ctx, float4 *d_records, uint32_t n_records);
     // one builtin per record, for tests against oracle/_ref/gfx950's probe kernels: op 0 dot, 1 cross, 2 normalize,
-    // 3 a/b, 4 sqrt, 5 mix, 6 min, 7 sign, 8 pow(x,5), 9 the table hash; in: n × 8 floats, out: n × 4 floats
+    // 3 a/b, 4 sqrt, 5 mix, 6 min, 7 sign, 8 pow(x,5), 9 the table hash, 10 / 11 sqrt / normalize in their tagged forms;
+    // in: n × 8 floats, out: n × 4 floats
     int (*launch_debug_builtin)(rt_context *ctx, int op, const float *d_in, uint32_t n, float *d_out);
     // rt_debug_queue_sums: one wave's queue_sums over npix × count × 3 slot floats into npix float4 (zeroed here)
     int (*launch_debug_queue_sums)(rt_context *ctx, const float *d_in, uint32_t npix, uint32_t count, uint32_t glog2, float *d_out);
