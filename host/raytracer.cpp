@@ -91,6 +91,11 @@ void RayTracer::renderFeatures(const Camera *camera) {
     check(rt_render_features(ctx, camera->transferData()));
 }
 
+void RayTracer::renderFeaturesChain(const Camera *camera, uint32_t follow, uint32_t max_chain) {
+    const rt_feature_chain_params p{follow, max_chain};
+    check(rt_render_features_chain(ctx, camera->transferData(), &p));
+}
+
 std::vector<rt_feature> RayTracer::features() {
     std::vector<rt_feature> f((size_t)width * height);
     check(rt_read_features(ctx, f.data(), f.size() * sizeof(rt_feature)));

@@ -64,6 +64,10 @@ public:
     // first-hit feature records of every pixel (rt_render_features, asynchronous) and their read-back
     void renderFeatures(const Camera *camera);
     std::vector<rt_feature> features();
+    // the records at the end of every pixel's mirror / glass chain instead (rt_render_features_chain, asynchronous): hits
+    // whose material type is in `follow` (RT_FOLLOW_* bits) are followed, at most max_chain of them; features() and the
+    // denoisers with a null camera then work on these
+    void renderFeaturesChain(const Camera *camera, uint32_t follow, uint32_t max_chain = RT_FEATURE_CHAIN_MAX);
     // features for `camera` (unless it is null: then the last ones) + rt_denoise + read back into the image that
     // transferImage() / lastImage() return; the accumulator is left as it was
     const float *denoise(const Camera *camera, const rt_denoise_params &params);

@@ -5,6 +5,7 @@
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
+//              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
 //          [--aov PREFIX]
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
@@ -23,6 +24,12 @@
 // --denoise --variance-guided --measured keeps the per-pixel sample moments while accumulating (RT_OPT_MOMENTS) and filters
 // on the variance measured from them wherever a pixel holds >= 4 samples (rt_denoise_moments); --aov then also writes
 // PREFIX_samplevar.pfm, the measured variance of every pixel's mean luminance, M2 / (n (n - 1)) (0 where n < 2).
+// --follow mirror,glass,dielectric (any of the three, comma-separated; with --denoise and / or --aov) guides the filter by the records at the
+// end of every pixel's mirror / glass chain instead of the first hit (rt_render_features_chain: reflective, refractive
+// and — by rayRefract's rule — dielectric hits are followed, at most --max-chain of them, default and maximum 29);
+// --split-chains adds RT_DENOISE_SPLIT_CHAINS, so that pixels whose chains differ in length or objects never mix.
+// --aov then writes the chain's records and also PREFIX_chain.pfm: per pixel (followed vertices, the signature's upper
+// half as a number 0 .. 65535, 1 where the chain was cut at --max-chain).
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -48,7 +55,8 @@ static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
                  "[--seed N] [--progressive [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]] "
+                 "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
+                 "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
                  "[--aov PREFIX]\n";
     std::exit(2);
 }
@@ -72,6 +80,24 @@ static void parse_sigmas(const char *v, float out[4]) {
         p = end + (k < 3 ? 1 : 0);
     }
     if (*p) usage();
+}
+
+// --follow: a comma-separated list of mirror / glass / dielectric → RT_FOLLOW_* bits (at least one), or usage()
+static uint32_t parse_follow(const char *v) {
+    uint32_t mask = 0;
+    std::string s = v;
+    size_t at = 0;
+    while (at <= s.size()) {
+        size_t end = s.find(',', at);
+        if (end == std::string::npos) end = s.size();
+        const std::string word = s.substr(at, end - at);
+        if (word == "mirror") mask |= RT_FOLLOW_REFLECTIVE;
+        else if (word == "glass") mask |= RT_FOLLOW_REFRACTIVE;
+        else if (word == "dielectric") mask |= RT_FOLLOW_DIELECTRIC;
+        else usage();
+        at = end + 1;
+    }
+    return mask;
 }
 
 // PFM of `ch` (1 or 3) channels taken from records of `stride` floats at offset `off`; rows bottom-up as the image's
@@ -120,6 +146,9 @@ int main(int argc, char **argv) {
     bool variance_guided = false, sigma_l_given = false, measured = false;
     float sigma_l = 4.0f;
     std::string aov_prefix;
+    uint32_t follow = 0;
+    long max_chain = -1;   // (-1: RT_FEATURE_CHAIN_MAX)
+    bool split_chains = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -158,10 +187,13 @@ int main(int argc, char **argv) {
             sigma_l_given = true;
         }
         else if ((v = val("--sigma"))) { parse_sigmas(v, sigmas); sigmas_given = true; }
+        else if ((v = val("--follow"))) follow = parse_follow(v);
+        else if ((v = val("--max-chain"))) max_chain = parse_int(v, 0, RT_FEATURE_CHAIN_MAX);
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
         else if (a == "--denoise") denoise = true;
         else if (a == "--variance-guided") variance_guided = true;
         else if (a == "--measured") measured = true;
+        else if (a == "--split-chains") split_chains = true;
         else if (a == "--progressive") progressive = true;
         else usage();
     }
@@ -169,6 +201,10 @@ int main(int argc, char **argv) {
     if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
     if (!denoise && (dn_iterations || sigmas_given || variance_guided || sigma_l_given)) usage();   // denoise-only flags
     if ((sigma_l_given || measured) && !variance_guided) usage();
+    if (follow && !denoise && aov_prefix.empty()) usage();                 // --follow guides --denoise and / or fills --aov
+    if ((max_chain >= 0 || split_chains) && !follow) usage();
+    if (split_chains && !denoise) usage();
+    if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
     if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
@@ -240,16 +276,21 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 
-    if (denoise || !aov_prefix.empty()) tracer.renderFeatures(&camera);
+    if (follow) tracer.renderFeaturesChain(&camera, follow, (uint32_t)max_chain);
+    else if (denoise || !aov_prefix.empty()) tracer.renderFeatures(&camera);
     if (denoise) {
         if (progressive) {   // the running mean of --progressive lives in the image: accumulate the same samples
             check_rc(rt_clear(tracer.context()));
             tracer.renderSamples(&camera, 0, (uint32_t)spp);
         }
-        rt_denoise_params dp{(uint32_t)dn_iterations, sigmas[0], sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
-        rt_denoise_variance_params vp{(uint32_t)dn_iterations, sigma_l, sigmas[1], sigmas[2], sigmas[3], RT_DENOISE_SPLIT_OBJECTS};
+        const uint32_t dn_flags = RT_DENOISE_SPLIT_OBJECTS | (split_chains ? RT_DENOISE_SPLIT_CHAINS : 0u);
+        rt_denoise_params dp{(uint32_t)dn_iterations, sigmas[0], sigmas[1], sigmas[2], sigmas[3], dn_flags};
+        rt_denoise_variance_params vp{(uint32_t)dn_iterations, sigma_l, sigmas[1], sigmas[2], sigmas[3], dn_flags};
         auto d0 = std::chrono::steady_clock::now();
         img = measured ? tracer.denoiseMoments(nullptr, vp) : variance_guided ? tracer.denoiseVariance(nullptr, vp) : tracer.denoise(nullptr, dp);
+        if (follow)
+            std::cout << "guides: chains through follow mask " << follow << ", at most " << max_chain << " vertices"
+                      << (split_chains ? ", split" : "") << std::endl;
         std::cout << "denoised" << (measured ? " (variance-guided, measured)" : variance_guided ? " (variance-guided)" : "") << ": " << dn_iterations
                   << " iterations, sigma " << (variance_guided ? sigma_l : sigmas[0]) << "," << sigmas[1] << ","
                   << sigmas[2] << "," << sigmas[3] << ": "
@@ -263,6 +304,15 @@ int main(int argc, char **argv) {
         write_pfm(aov_prefix + "_normal.pfm", fd, stride, offsetof(rt_feature, normal) / sizeof(float), 3, w, h);
         write_pfm(aov_prefix + "_albedo.pfm", fd, stride, offsetof(rt_feature, albedo) / sizeof(float), 3, w, h);
         write_pfm(aov_prefix + "_depth.pfm", fd, stride, offsetof(rt_feature, t) / sizeof(float), 1, w, h);
+        if (follow) {
+            std::vector<float> ch(f.size() * 3);
+            for (size_t i = 0; i < f.size(); i++) {
+                ch[3 * i] = (float)RT_FEATURE_CHAIN_LENGTH(f[i].flags);
+                ch[3 * i + 1] = (float)(RT_FEATURE_CHAIN_SIGNATURE(f[i].flags) >> 16);
+                ch[3 * i + 2] = (f[i].flags & RT_FEATURE_CUT) ? 1.0f : 0.0f;
+            }
+            write_pfm(aov_prefix + "_chain.pfm", ch.data(), 3, 0, 3, w, h);
+        }
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);
         if (denoise && measured) {
             const std::vector<float> m2 = tracer.moments();

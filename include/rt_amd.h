@@ -338,7 +338,7 @@ typedef struct rt_feature {
     uint32_t face;      /* face index inside the mesh for a mesh hit, else 0xFFFFFFFF                         */
     float u, v;         /* texture coordinates (mesh hits; 0 otherwise)                                       */
     uint32_t tex;       /* texture id (mesh hits; 0 otherwise)                                                */
-    uint32_t flags;     /* RT_FEATURE_HIT                                                                     */
+    uint32_t flags;     /* RT_FEATURE_HIT; after rt_render_features_chain also RT_FEATURE_CUT and the chain fields     */
 } rt_feature;
 #define RT_FEATURE_HIT 1u
 
@@ -349,6 +349,42 @@ typedef struct rt_feature {
 int rt_render_features(rt_context *ctx, const float camera[12]);
 int rt_read_features(rt_context *ctx, rt_feature *out, size_t bytes);
 int rt_device_features(rt_context *ctx, void **d_features);
+
+/*
+ * Feature records that follow mirror and glass chains to the first rough hit (new).  The primary ray is not jittered
+ * and reflective / refractive interactions draw no random number (raytracer.cl:362-391), so every pixel has ONE
+ * deterministic chain.  Start with the primary ray:
+ *   1. take the nearest hit (the search of rt_render_features);
+ *   2. if the hit's material type is selected in `follow` and fewer than `max_chain` vertices have been followed so
+ *      far, apply that material's interaction — the device's own scatter; a followed RT_DIELECTRIC goes through the
+ *      RT_REFRACTIVE branch, i.e. rayRefract's rule: refract where the discriminant is > 0, else reflect, no random
+ *      number — and continue from the hit point;
+ *   3. otherwise that hit is the TERMINAL.  A miss ends the chain.
+ * The result REPLACES the context's feature records, in the same layout, so rt_read_features, rt_device_features and
+ * the three denoisers work on it unchanged:
+ *   pos, normal, albedo, material, object, face, u, v, tex describe the terminal exactly as rt_render_features fills
+ *     them for a first hit (the miss values on a terminal miss);
+ *   t is the fp32 sum of the segments' t in path order ((t0 + t1) + t2 ...), +inf on a miss: hit == (t < inf) holds;
+ *   dir stays the primary direction;
+ *   flags: bit 0 RT_FEATURE_HIT (the terminal exists), bit 1 RT_FEATURE_CUT (the terminal has a followed type, but
+ *     max_chain >= 1 vertices had been followed), bits 8..12 the number of followed vertices (RT_FEATURE_CHAIN_LENGTH),
+ *     bits 16..31 the upper half of the chain signature (RT_FEATURE_CHAIN_SIGNATURE).
+ * Signature: h = 0; for each followed vertex in path order h = (h ^ object) * 0x9E3779B1 (mod 2^32), `object` the id an
+ * rt_feature record holds.  rt_feature_chain_signature is the very function the kernel calls (host-only, no context).
+ * With follow == 0 or max_chain == 0 the records equal rt_render_features', bit for bit, flags included.
+ * RT_EINVAL: unknown follow bits, max_chain > RT_FEATURE_CHAIN_MAX, a NULL pointer, a sharded context.  State rules,
+ * asynchrony and what stays untouched: as rt_render_features.
+ */
+#define RT_FOLLOW_REFLECTIVE 1u
+#define RT_FOLLOW_REFRACTIVE 2u
+#define RT_FOLLOW_DIELECTRIC 4u   /* by rayRefract's rule: refract where the discriminant is > 0, else reflect; no random number */
+#define RT_FEATURE_CHAIN_MAX 29u
+#define RT_FEATURE_CUT 2u
+#define RT_FEATURE_CHAIN_LENGTH(flags) (((flags) >> 8) & 31u)
+#define RT_FEATURE_CHAIN_SIGNATURE(flags) ((flags) & 0xFFFF0000u)   /* == signature & 0xFFFF0000 */
+typedef struct rt_feature_chain_params { uint32_t follow; uint32_t max_chain; } rt_feature_chain_params;
+int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_feature_chain_params *p);
+int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out);   /* host-only, no context */
 
 /*
  * Edge-avoiding à-trous denoiser (new; the reference has no such entry point): Dammertz et al. 2010, "Edge-Avoiding
@@ -362,7 +398,10 @@ int rt_device_features(rt_context *ctx, void **d_features);
  *          e(|x_p - x_q|^2 / sigma_position^2) e(|a_p - a_q|^2 / sigma_albedo^2),
  *     h = (1/16, 1/4, 3/8, 1/4, 1/16), e(z) = exp(-z); a sigma of +inf switches its term off;
  *     w_pq = 0 when the hit flags of p and q differ, and with RT_DENOISE_SPLIT_OBJECTS also when their object ids
- *     differ (the centre tap always has weight > 0);
+ *     differ, and with RT_DENOISE_SPLIT_CHAINS also when their `flags >> 8` (chain length and signature of
+ *     rt_render_features_chain; 0 in first-hit records, where the flag changes nothing) differ — the pair (key, flags >> 8)
+ *     is compared, so a mirror's silhouette stays a hard edge even where it reflects the surface behind it (the centre tap
+ *     always has weight > 0);
  *   output RGBA = (sqrt(c(L)_p), 1) where accum.w > 0, else 0 (as rt_resolve), into a buffer of its own.
  * Asynchronous on the context's stream; one launch per iteration.  Leaves the image, the accumulator and the sample
  * counter untouched.  RT_EINVAL: iterations outside 1..8, a sigma <= 0 or NaN, unknown flags, a NULL pointer, a
@@ -373,9 +412,10 @@ int rt_device_features(rt_context *ctx, void **d_features);
 typedef struct rt_denoise_params {
     uint32_t iterations;    /* L, 1 .. 8 (5 suggested)                                                       */
     float sigma_color, sigma_normal, sigma_position, sigma_albedo;   /* > 0; +inf = term off                  */
-    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS                                                       */
+    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS | RT_DENOISE_SPLIT_CHAINS                             */
 } rt_denoise_params;
 #define RT_DENOISE_SPLIT_OBJECTS 1u
+#define RT_DENOISE_SPLIT_CHAINS 4u   /* (2u stays an unknown bit: callers that probed it keep their RT_EINVAL) */
 #define RT_DENOISE_MAX_ITERATIONS 8u
 
 int rt_denoise(rt_context *ctx, const rt_denoise_params *p);
@@ -389,7 +429,8 @@ int rt_device_denoised(rt_context *ctx, void **d_rgba);
  * id with RT_DENOISE_SPLIT_OBJECTS, else the hit flag.  New: l(c) = 0.2126 c.r + 0.7152 c.g + 0.0722 c.b;
  * k = (1/4, 1/2, 1/4); eps = RT_DENOISE_VARIANCE_EPS.
  * The guide weight is g_pq = e(|n_p-n_q|^2/sigma_normal^2 + |x_p-x_q|^2/sigma_position^2 + |a_p-a_q|^2/sigma_albedo^2),
- * and 0 when key_q != key_p; a sigma of +inf switches its term off.
+ * and 0 when key_q != key_p, with RT_DENOISE_SPLIT_CHAINS also when `flags >> 8` of the two records differ (as for
+ * rt_denoise); a sigma of +inf switches its term off.
  *   1. Variance estimate, 7x7: over the taps q = p + (dx, dy), dx, dy in -3..3, inside the frame,
  *        M0 = sum g_pq,  m = sum g_pq l(c0_q) / M0,  v0_p = sum g_pq (l(c0_q) - m)^2 / M0
  *      (the two-pass form, not M2/M0 - m^2, which in binary32 cancels to noise of the order of eps on flat regions;
@@ -416,7 +457,7 @@ typedef struct rt_denoise_variance_params {
     uint32_t iterations;    /* L, 1 .. 8 (5 suggested)                                                       */
     float sigma_luminance;  /* > 0 (4 suggested); +inf = term off                                            */
     float sigma_normal, sigma_position, sigma_albedo;   /* as rt_denoise_params                               */
-    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS                                                       */
+    uint32_t flags;         /* RT_DENOISE_SPLIT_OBJECTS | RT_DENOISE_SPLIT_CHAINS                             */
 } rt_denoise_variance_params;
 #define RT_DENOISE_VARIANCE_EPS 1e-4f
 

@@ -120,13 +120,28 @@ FEATURE = np.dtype([("pos", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)),
                     ("u", "<f4"), ("v", "<f4"), ("tex", "<u4"), ("flags", "<u4")])
 assert FEATURE.itemsize == 80
 FEATURE_HIT = 1
+FEATURE_CUT = 2             # rt_render_features_chain: the terminal has a followed type, max_chain was reached
+FOLLOW_REFLECTIVE, FOLLOW_REFRACTIVE, FOLLOW_DIELECTRIC = 1, 2, 4   # RT_FOLLOW_*
+FOLLOW_NAMES = {"mirror": FOLLOW_REFLECTIVE, "glass": FOLLOW_REFRACTIVE, "dielectric": FOLLOW_DIELECTRIC}
+FEATURE_CHAIN_MAX = 29
 NO_ID = 0xFFFFFFFF          # object / material / face of a miss; face of a hit that is not a mesh's
 OBJECT_KINDS = ("sphere", "plane", "lens", "mesh")   # object id >> 30
 DENOISE_SPLIT_OBJECTS = 1
+DENOISE_SPLIT_CHAINS = 4
 DENOISE_MAX_ITERATIONS = 8
 # rt_denoise defaults of the Python and C++ surfaces (DESIGN.md "Feature buffers and denoising": the sweep that chose them)
 DENOISE_DEFAULTS = dict(iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_position=2.0, sigma_albedo=0.2,
                         split_objects=True)
+
+
+def denoise_flags(split_objects, split_chains=False):
+    """rt_denoise_params.flags of the Python surfaces' two switches."""
+    return (DENOISE_SPLIT_OBJECTS if split_objects else 0) | (DENOISE_SPLIT_CHAINS if split_chains else 0)
+
+
+class FeatureChainParams(C.Structure):
+    """rt_feature_chain_params"""
+    _fields_ = [("follow", C.c_uint32), ("max_chain", C.c_uint32)]
 
 
 class DenoiseParams(C.Structure):
@@ -160,6 +175,8 @@ def denoise_prototypes(lib):
     lib.rt_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams)]
     lib.rt_read_variance.argtypes = [vp, C.c_int, vp, sz]
     lib.rt_device_variance.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.rt_render_features_chain.argtypes = [vp, vp, C.POINTER(FeatureChainParams)]
+    lib.rt_feature_chain_signature.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
 
 
 DENOISE_MOMENTS_MIN_COUNT = 4   # RT_DENOISE_MOMENTS_MIN_COUNT: samples from which rt_denoise_moments trusts a pixel's own variance
@@ -207,7 +224,12 @@ def split_features(rec):
             "albedo": rec["albedo"].copy(), "object": rec["object"].copy(), "material": rec["material"].copy(),
             "face": rec["face"].copy(), "direction": rec["dir"].copy(),
             "uv": np.stack([rec["u"], rec["v"]], axis=-1), "texture": rec["tex"].copy(),
-            "hit": (rec["flags"] & FEATURE_HIT) != 0}
+            "hit": (rec["flags"] & FEATURE_HIT) != 0,
+            # rt_render_features_chain (all 0 / False in first-hit records): followed vertices, the signature's upper half
+            # (as flags & 0xFFFF0000), the cut flag, and flags >> 8 — the word RT_DENOISE_SPLIT_CHAINS compares
+            "chain_length": ((rec["flags"] >> 8) & 31).astype(np.uint32),
+            "chain_signature": (rec["flags"] & np.uint32(0xFFFF0000)).astype(np.uint32),
+            "cut": (rec["flags"] & FEATURE_CUT) != 0, "chain_word": (rec["flags"] >> 8).astype(np.uint32)}
 
 
 def ptr(a):

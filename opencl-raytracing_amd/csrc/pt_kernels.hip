@@ -13,6 +13,7 @@
 
 #include "pt_device.hpp"
 #include "pt_moments.hpp"
+#include "pt_chain.hpp"
 #include "rt_context.hpp"
 #include "pt_kernels.hpp"
 
@@ -1322,6 +1323,70 @@ __global__ __launch_bounds__(256) void pt_features(DeviceScene sc, FrameParams f
     }
 }
 
+// Feature buffers at the end of the pixel's mirror / glass chain (rt_render_features_chain): pt_features' search and
+// record, in a loop of at most max_chain + 1 hits.  A hit whose material type is selected in `follow` (RT_FOLLOW_*) is
+// followed through scatter() — a dielectric as RT_REFRACTIVE, rayRefract's rule, so no lane draws a random number and
+// nothing reads the table — while fewer than max_chain vertices have been followed; the first hit that is not is the
+// terminal.  t sums the segments in path order; the flags carry RT_FEATURE_CUT, the chain length (bits 8..12) and the
+// upper half of the signature (pt_chain.hpp).  follow == 0 or max_chain == 0: pt_features' record, bit for bit.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FrameParams fp, uint32_t follow, uint32_t max_chain,
+                                                         float4 *__restrict__ out) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
+    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
+    Ray r = primary_ray(fp.cam, x, y, fp.w, fp.h);
+    const V3 d0 = r.d;
+    float4 *o = out + 5 * (size_t)i;
+    float t_sum = 0.0f;
+    uint32_t len = 0u, sig = 0u;
+    for (uint32_t k = 0u; k <= max_chain; k++) {   // (max_chain <= RT_FEATURE_CHAIN_MAX: at most RT_DEPTH hits)
+        Nearest nb;
+        hit_primitives<false, ACCEL>(c, r, nb);
+        hit_models<false, ACCEL>(c, r, nb);
+        Hit h;
+        if (!hit_finish<false>(c, r, nb, h)) break;
+        int type;
+        float extra;
+        V3 col;
+        load_material(c, h.mat, type, extra, col);
+        t_sum = k == 0u ? nb.t : t_sum + nb.t;
+        const bool followed = (type == RT_REFLECTIVE && (follow & RT_FOLLOW_REFLECTIVE)) ||
+                              (type == RT_REFRACTIVE && (follow & RT_FOLLOW_REFRACTIVE)) ||
+                              (type == RT_DIELECTRIC && (follow & RT_FOLLOW_DIELECTRIC));
+        if (followed && len < max_chain) {
+            sig = pt::chain_signature_step(sig, nb.id);
+            len++;
+            Rnd none;  // mirror / glass by rayRefract's rule: no random numbers
+            none.v = mk(0.0f, 0.0f, 0.0f);
+            none.u = 0.0f;
+            V3 path = mk(1.0f, 1.0f, 1.0f);   // (the path colour is not needed)
+            scatter<false>(c, r, path, h, type == RT_DIELECTRIC ? RT_REFRACTIVE : type, extra, col, none);
+            continue;
+        }
+        if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
+        const bool mesh = (nb.id & K_MASK) == K_MESH;
+        const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
+        o[0] = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
+        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
+        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
+        o[3] = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
+        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
+        return;
+    }
+    // the chain left the scene (a terminal exists whenever the loop runs out: its last pass cannot follow)
+    const float none = __uint_as_float(0xFFFFFFFFu);
+    o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+    o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
+    o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
+    o[3] = make_float4(d0.x, d0.y, d0.z, none);
+    o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
+}
+
 // ---- unit probes of the device routines (tests only; rt_debug_hit / rt_debug_material / rt_debug_div3) -----------
 // One work-item per record; the routines are the very ones the trace kernels inline (hit_primitives' sphere_t /
 // plane_t / lens_t, triangle_t, hit_scene + hit_finish, scatter), so a unit vector that matches the oracle here
@@ -1786,6 +1851,17 @@ int ks_launch_features(rt_context *ctx, const FrameParams &fp, const DeviceScene
     return RT_OK;
 }
 
+int ks_launch_features_chain(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, uint32_t follow, uint32_t max_chain,
+                             rt_feature *d_out) {
+    const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
+    dim3 grid((n + 255u) / 256u), block(256);
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    if (scene_has_accel(sc)) hipLaunchKernelGGL(pt_features_chain<true>, grid, block, 0, ctx->stream, sc, fp, follow, max_chain, o);
+    else hipLaunchKernelGGL(pt_features_chain<false>, grid, block, 0, ctx->stream, sc, fp, follow, max_chain, o);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -1841,7 +1917,7 @@ const pt::KernelSet g_kernel_set = {
     "rocm-opencl",
 #endif
     ks_launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
-    ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums};
+    ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain};
 
 }  // namespace
 

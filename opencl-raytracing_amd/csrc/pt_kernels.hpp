@@ -39,6 +39,10 @@ struct KernelSet {
     int (*launch_debug_builtin)(rt_context *ctx, int op, const float *d_in, uint32_t n, float *d_out);
     // rt_debug_queue_sums: one wave's queue_sums over npix × count × 3 slot floats into npix float4 (zeroed here)
     int (*launch_debug_queue_sums)(rt_context *ctx, const float *d_in, uint32_t npix, uint32_t count, uint32_t glog2, float *d_out);
+    // rt_render_features_chain: pt_features_chain, the record at the end of every pixel's mirror / glass chain (`follow`:
+    // RT_FOLLOW_* bits, at most max_chain <= RT_FEATURE_CHAIN_MAX followed vertices) into d_out
+    int (*launch_features_chain)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, uint32_t follow, uint32_t max_chain,
+                                 rt_feature *d_out);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

@@ -22,6 +22,7 @@
 #include "rt_context.hpp"
 #include "pt_kernels.hpp"
 #include "pt_moments.hpp"
+#include "pt_chain.hpp"
 #include "mesh_bvh_build.hpp"
 
 using namespace pt;
@@ -1180,17 +1181,56 @@ int rt_read_block_error(rt_context *ctx, float *err, size_t bytes) {
 
 // ---- feature buffers (the denoisers that read them: rt_denoise.hip) ---------------------------------------------------
 
-int rt_render_features(rt_context *ctx, const float camera[12]) {
-    int rc = check_ready(ctx, camera);
-    if (rc) return rc;
+}  // extern "C"
+
+namespace {
+// What rt_render_features and rt_render_features_chain share — the state rules, the records' allocation, the frame and
+// scene blocks, `ready` — round the one launch in which they differ (`params_ok`: the caller's own argument checks,
+// made after check_ready and before the shard check, 0 or an RT_* code already recorded on the context).
+template <class Launch>
+int render_features_with(rt_context *ctx, const float camera[12], int params_ok, Launch launch) {
+    if (params_ok) return params_ok;
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "features of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rt_context::Features &f = ctx->features;
     if (!f.records.p) HIP_TRY(ctx, f.records.alloc((size_t)ctx->width * ctx->height));
     const FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
     const DeviceScene sc = device_scene(ctx);
-    if ((rc = ctx->ks->launch_features(ctx, fp, sc, f.records.p)) != RT_OK) return rc;
+    const int rc = launch(fp, sc, f.records.p);
+    if (rc != RT_OK) return rc;
     f.ready = true;
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_render_features(rt_context *ctx, const float camera[12]) {
+    const int rc = check_ready(ctx, camera);
+    if (rc) return rc;
+    return render_features_with(ctx, camera, RT_OK, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
+        return ctx->ks->launch_features(ctx, fp, sc, out);
+    });
+}
+
+int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_feature_chain_params *p) {
+    const int rc = check_ready(ctx, camera);
+    if (rc) return rc;
+    int ok = RT_OK;
+    if (!p) ok = fail(ctx, RT_EINVAL, "feature chain parameters are NULL");
+    else if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
+        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
+    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    return render_features_with(ctx, camera, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
+        return ctx->ks->launch_features_chain(ctx, fp, sc, p->follow, p->max_chain, out);
+    });
+}
+
+int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out) {
+    if (!sig_out || (n && !objects)) return fail(nullptr, RT_EINVAL, "rt_feature_chain_signature: a pointer is NULL");
+    uint32_t h = 0u;
+    for (uint32_t i = 0; i < n; i++) h = chain_signature_step(h, objects[i]);
+    *sig_out = h;
     return RT_OK;
 }
 

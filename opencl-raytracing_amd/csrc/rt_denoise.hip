@@ -22,6 +22,9 @@ using namespace rtamd;
 // construction of pt_features).
 // A staged point carries a key in pos.w: the object id (split objects) or the hit flag, and PT_DN_OFF for a point
 // outside the frame, whose data are zeros — a tap's weight is 0 unless its key equals the centre's (a select, no branch).
+// CHAINS (RT_DENOISE_SPLIT_CHAINS, kernels of their own so that the others compile as they did): a staged point also
+// carries the record's flags >> 8 — chain length and signature of rt_render_features_chain — in albedo.w, which no term
+// reads (there the record holds the material id); a tap then counts only if key AND that word equal the centre's.
 // Workgroup ids are remapped so that the s classes of one tile row, which share cache lines, run on one XCD.
 #define PT_DN_TILE 16
 #define PT_DN_SIDE (PT_DN_TILE + 4)
@@ -55,6 +58,7 @@ PT_DEV float4 dn_mean(float4 c) {
 // pos of a point outside the frame: zeros, the key PT_DN_OFF in w
 PT_DEV float4 dn_off() { return make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(PT_DN_OFF)); }
 // the guide of in-frame pixel q, its key in pos.w
+template <bool CHAINS>
 PT_DEV void dn_guide(const float4 *__restrict__ feat, size_t q, uint32_t split, float4 &p, float4 &n, float4 &a) {
     const float4 *f = feat + 5 * q;
     p = f[0];
@@ -62,6 +66,12 @@ PT_DEV void dn_guide(const float4 *__restrict__ feat, size_t q, uint32_t split, 
     a = f[2];
     const bool hit = p.w < INFINITY;
     p.w = __uint_as_float(split ? __float_as_uint(n.w) : (hit ? 0u : 1u));
+    if (CHAINS) a.w = __uint_as_float(__float_as_uint(f[4].w) >> 8);
+}
+// a tap's pair (key, chain word) against the centre's
+template <bool CHAINS>
+PT_DEV bool dn_same(float4 pq, float4 aq, uint32_t keyp, uint32_t chainp) {
+    return __float_as_uint(pq.w) == keyp && (!CHAINS || __float_as_uint(aq.w) == chainp);
 }
 // what a filter's last iteration writes: (sqrt(c), 1), or 0 for a pixel whose accumulator holds no sample
 PT_DEV float4 dn_gamma(float r, float g, float b, float count) {
@@ -73,7 +83,7 @@ PT_DEV float4 dn_gamma(float r, float g, float b, float count) {
 // v(i) (v0 in the first iteration), a point's luminance rides in normal.w (which the key has already been taken from),
 // the first term is |l_p - l_q| / (sigma_l sqrt(vt_p) + eps), and the variance is filtered with the squared weights;
 // var0, accum and var_out are read and written by this variant only.
-template <bool VG>
+template <bool VG, bool CHAINS>
 PT_DEV void dn_atrous(const DenoiseStep &ds, const float4 *__restrict__ src, const float *__restrict__ var0,
                       const float4 *__restrict__ accum, const float4 *__restrict__ feat, float4 *__restrict__ dst,
                       float *__restrict__ var_out) {
@@ -104,7 +114,7 @@ PT_DEV void dn_atrous(const DenoiseStep &ds, const float4 *__restrict__ src, con
                 if (VG) c.w = var0[q];
             }
             if (VG) l = dn_lum(c);
-            dn_guide(feat, q, ds.split, p, n, a);
+            dn_guide<CHAINS>(feat, q, ds.split, p, n, a);
         }
         if (VG) n.w = l;
         s_col[k] = c;
@@ -139,7 +149,7 @@ PT_DEV void dn_atrous(const DenoiseStep &ds, const float4 *__restrict__ src, con
     }
     const uint32_t ci = (lj + 2u) * PT_DN_SIDE + li + 2u;
     const float4 cp = s_col[ci], pp = s_pos[ci], np = s_nrm[ci], ap = s_alb[ci];
-    const uint32_t keyp = __float_as_uint(pp.w);
+    const uint32_t keyp = __float_as_uint(pp.w), chainp = __float_as_uint(ap.w);
     const float hk[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
 #pragma unroll
@@ -151,7 +161,7 @@ PT_DEV void dn_atrous(const DenoiseStep &ds, const float4 *__restrict__ src, con
             const float z = (VG ? inv_d * fabsf(np.w - nq.w) : ds.inv_c * dn_d2(cp, cq)) + ds.inv_n * dn_d2(np, nq) +
                             ds.inv_x * dn_d2(pp, pq) + ds.inv_a * dn_d2(ap, aq);
             float wt = (hk[dx] * hk[dy]) * __expf(-z);
-            wt = __float_as_uint(pq.w) == keyp ? wt : 0.0f;
+            wt = dn_same<CHAINS>(pq, aq, keyp, chainp) ? wt : 0.0f;
             sw += wt;
             sr += wt * cq.x;
             sg += wt * cq.y;
@@ -171,13 +181,23 @@ PT_DEV void dn_atrous(const DenoiseStep &ds, const float4 *__restrict__ src, con
 
 __global__ __launch_bounds__(256) void pt_atrous(DenoiseStep ds, const float4 *__restrict__ src,
                                                  const float4 *__restrict__ feat, float4 *__restrict__ dst) {
-    dn_atrous<false>(ds, src, nullptr, nullptr, feat, dst, nullptr);
+    dn_atrous<false, false>(ds, src, nullptr, nullptr, feat, dst, nullptr);
+}
+__global__ __launch_bounds__(256) void pt_atrous_ch(DenoiseStep ds, const float4 *__restrict__ src,
+                                                    const float4 *__restrict__ feat, float4 *__restrict__ dst) {
+    dn_atrous<false, true>(ds, src, nullptr, nullptr, feat, dst, nullptr);
 }
 __global__ __launch_bounds__(256) void pt_atrous_vg(DenoiseStep ds, const float4 *__restrict__ src,
                                                     const float *__restrict__ var0, const float4 *__restrict__ accum,
                                                     const float4 *__restrict__ feat, float4 *__restrict__ dst,
                                                     float *__restrict__ var_out) {
-    dn_atrous<true>(ds, src, var0, accum, feat, dst, var_out);
+    dn_atrous<true, false>(ds, src, var0, accum, feat, dst, var_out);
+}
+__global__ __launch_bounds__(256) void pt_atrous_vg_ch(DenoiseStep ds, const float4 *__restrict__ src,
+                                                       const float *__restrict__ var0, const float4 *__restrict__ accum,
+                                                       const float4 *__restrict__ feat, float4 *__restrict__ dst,
+                                                       float *__restrict__ var_out) {
+    dn_atrous<true, true>(ds, src, var0, accum, feat, dst, var_out);
 }
 
 // Step 1 of the variance-guided filter, the 7x7 two-pass estimate v0: a workgroup owns a 16x16 pixel tile and stages the
@@ -194,8 +214,9 @@ struct DenoiseVariance {
     uint32_t split;                     // RT_DENOISE_SPLIT_OBJECTS
 };
 
-__global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const float4 *__restrict__ accum,
-                                                      const float4 *__restrict__ feat, float *__restrict__ var0) {
+template <bool CHAINS>
+PT_DEV void dn_variance(DenoiseVariance dv, const float4 *__restrict__ accum, const float4 *__restrict__ feat,
+                        float *__restrict__ var0) {
     __shared__ float4 s_pos[PT_DV_POINTS], s_nrm[PT_DV_POINTS], s_alb[PT_DV_POINTS];
     const uint32_t tx = blockIdx.x % dv.tiles_x, ty = blockIdx.x / dv.tiles_x;
     const int i0 = (int)(tx * PT_DN_TILE), j0 = (int)(ty * PT_DN_TILE);
@@ -207,7 +228,7 @@ __global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const 
         if (x >= 0 && y >= 0 && x < (int)dv.w && y < (int)dv.h) {
             const size_t q = (size_t)y * dv.w + (size_t)x;
             l = dn_lum(dn_mean(accum[q]));
-            dn_guide(feat, q, dv.split, p, n, a);
+            dn_guide<CHAINS>(feat, q, dv.split, p, n, a);
         }
         n.w = l;
         s_pos[k] = p;
@@ -220,7 +241,7 @@ __global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const 
     if (x >= dv.w || y >= dv.h) return;
     const uint32_t ci = (lj + PT_DV_HALO) * PT_DV_SIDE + li + PT_DV_HALO;
     const float4 pp = s_pos[ci], np = s_nrm[ci], ap = s_alb[ci];
-    const uint32_t keyp = __float_as_uint(pp.w);
+    const uint32_t keyp = __float_as_uint(pp.w), chainp = __float_as_uint(ap.w);
     float m0 = 0.0f, m1 = 0.0f;
     for (int dy = -PT_DV_HALO; dy <= PT_DV_HALO; dy++) {
 #pragma unroll
@@ -228,7 +249,7 @@ __global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const 
             const uint32_t q = ci + (uint32_t)(dy * PT_DV_SIDE + dx);
             const float4 pq = s_pos[q], nq = s_nrm[q], aq = s_alb[q];
             const float z = dv.inv_n * dn_d2(np, nq) + dv.inv_x * dn_d2(pp, pq) + dv.inv_a * dn_d2(ap, aq);
-            const float g = __float_as_uint(pq.w) == keyp ? __expf(-z) : 0.0f;
+            const float g = dn_same<CHAINS>(pq, aq, keyp, chainp) ? __expf(-z) : 0.0f;
             m0 += g;
             m1 += g * nq.w;
         }
@@ -241,12 +262,20 @@ __global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const 
             const uint32_t q = ci + (uint32_t)(dy * PT_DV_SIDE + dx);
             const float4 pq = s_pos[q], nq = s_nrm[q], aq = s_alb[q];
             const float z = dv.inv_n * dn_d2(np, nq) + dv.inv_x * dn_d2(pp, pq) + dv.inv_a * dn_d2(ap, aq);
-            const float g = __float_as_uint(pq.w) == keyp ? __expf(-z) : 0.0f;
+            const float g = dn_same<CHAINS>(pq, aq, keyp, chainp) ? __expf(-z) : 0.0f;
             const float d = nq.w - m;
             m2 += g * (d * d);
         }
     }
     var0[(size_t)y * dv.w + x] = m2 / m0;
+}
+__global__ __launch_bounds__(256) void pt_dn_variance(DenoiseVariance dv, const float4 *__restrict__ accum,
+                                                      const float4 *__restrict__ feat, float *__restrict__ var0) {
+    dn_variance<false>(dv, accum, feat, var0);
+}
+__global__ __launch_bounds__(256) void pt_dn_variance_ch(DenoiseVariance dv, const float4 *__restrict__ accum,
+                                                         const float4 *__restrict__ feat, float *__restrict__ var0) {
+    dn_variance<true>(dv, accum, feat, var0);
 }
 
 // Step 1 of rt_denoise_moments, after pt_dn_variance: where a pixel holds at least RT_DENOISE_MOMENTS_MIN_COUNT samples its
@@ -280,7 +309,7 @@ int validate(rt_context *ctx, bool have, const Params &p) {
     const float sig[4] = {p.sigma_own, p.sigma_normal, p.sigma_position, p.sigma_albedo};
     for (float v : sig)
         if (!(v > 0.0f)) return fail(ctx, RT_EINVAL, "every sigma must be > 0 (+inf switches its term off)");
-    if (p.flags & ~RT_DENOISE_SPLIT_OBJECTS) return fail(ctx, RT_EINVAL, "unknown denoise flags 0x%x", p.flags);
+    if (p.flags & ~(RT_DENOISE_SPLIT_OBJECTS | RT_DENOISE_SPLIT_CHAINS)) return fail(ctx, RT_EINVAL, "unknown denoise flags 0x%x", p.flags);
     if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
     return RT_OK;
 }
@@ -368,8 +397,9 @@ int denoise_variance(rt_context *ctx, const rt_denoise_variance_params *vp, bool
     dv.inv_x = inv_sq(p.sigma_position);
     dv.inv_a = inv_sq(p.sigma_albedo);
     dv.split = (p.flags & RT_DENOISE_SPLIT_OBJECTS) ? 1u : 0u;
-    hipLaunchKernelGGL(pt_dn_variance, dim3(dv.tiles_x * ((h + PT_DN_TILE - 1u) / PT_DN_TILE)), dim3(256), 0, ctx->stream, dv,
-                       ctx->accum.p, guide(ctx), d.var[0].p);
+    const bool chains = (p.flags & RT_DENOISE_SPLIT_CHAINS) != 0;
+    hipLaunchKernelGGL(chains ? pt_dn_variance_ch : pt_dn_variance, dim3(dv.tiles_x * ((h + PT_DN_TILE - 1u) / PT_DN_TILE)), dim3(256),
+                       0, ctx->stream, dv, ctx->accum.p, guide(ctx), d.var[0].p);
     HIP_TRY(ctx, hipGetLastError());
     if (measured) {
         hipLaunchKernelGGL(pt_dn_measured, dim3((w * h + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->accum.p, ctx->moments.m2.p,
@@ -380,7 +410,7 @@ int denoise_variance(rt_context *ctx, const rt_denoise_variance_params *vp, bool
         StepPlan sp = plan_step(ctx, p, i);
         sp.ds.lum_on = std::isinf(p.sigma_own) ? 0u : 1u;
         sp.ds.sigma_l = sp.ds.lum_on ? p.sigma_own : 0.0f;
-        hipLaunchKernelGGL(pt_atrous_vg, dim3(sp.grid), dim3(256), 0, ctx->stream, sp.ds, sp.src, d.var[0].p, ctx->accum.p,
+        hipLaunchKernelGGL(chains ? pt_atrous_vg_ch : pt_atrous_vg, dim3(sp.grid), dim3(256), 0, ctx->stream, sp.ds, sp.src, d.var[0].p, ctx->accum.p,
                            guide(ctx), sp.dst, d.var[1].p);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -405,7 +435,7 @@ int rt_denoise(rt_context *ctx, const rt_denoise_params *dp) {
     for (uint32_t i = 0; i < p.iterations; i++) {
         StepPlan sp = plan_step(ctx, p, i);
         sp.ds.inv_c = inv_sq(p.sigma_own, (int)i);
-        hipLaunchKernelGGL(pt_atrous, dim3(sp.grid), dim3(256), 0, ctx->stream, sp.ds, sp.src, guide(ctx), sp.dst);
+        hipLaunchKernelGGL((p.flags & RT_DENOISE_SPLIT_CHAINS) ? pt_atrous_ch : pt_atrous, dim3(sp.grid), dim3(256), 0, ctx->stream, sp.ds, sp.src, guide(ctx), sp.dst);
         HIP_TRY(ctx, hipGetLastError());
     }
     ctx->denoise.ready = true;

@@ -29,7 +29,8 @@ SYMBOLS = (
     "rt_kernel_ms_history", "rt_stage_ms_history", "rt_debug_hit", "rt_debug_material", "rt_debug_div3", "rt_device_info", "rt_set_option", "rt_shard_slots", "rt_pack_accum", "rt_unpack_accum",
     "rt_get_debug_counters", "rt_debug_check_accel", "rt_walk_overflow", "rt_debug_builtin",
     "rt_render_adaptive", "rt_read_sample_counts", "rt_read_block_error",
-    "rt_render_features", "rt_read_features", "rt_device_features", "rt_denoise", "rt_read_denoised", "rt_device_denoised",
+    "rt_render_features", "rt_read_features", "rt_device_features", "rt_render_features_chain", "rt_feature_chain_signature",
+    "rt_denoise", "rt_read_denoised", "rt_device_denoised",
     "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
     "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
@@ -43,6 +44,9 @@ OPT_LOOKAHEAD = 10
 OPT_EXACT_GRID = 11
 OPT_MOMENTS = 12
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
+# rt_render_features_chain: the material types a chain is followed through
+FOLLOW_REFLECTIVE, FOLLOW_REFRACTIVE, FOLLOW_DIELECTRIC = _abi.FOLLOW_REFLECTIVE, _abi.FOLLOW_REFRACTIVE, _abi.FOLLOW_DIELECTRIC
+FOLLOW_ALL = FOLLOW_REFLECTIVE | FOLLOW_REFRACTIVE | FOLLOW_DIELECTRIC
 ARITH_NAMES = {"ieee": ARITH_IEEE, "rocm-opencl-nocontract": ARITH_ROCM_OCL_NOCONTRACT, "rocm-opencl": ARITH_ROCM_OCL}
 
 
@@ -190,6 +194,18 @@ def moments_merge(nA, sumA, m2A, nB, sumB, m2B):
     if rc:
         raise RtError(rc, lib.rt_last_error(None).decode())
     return np.float32(out.value)
+
+
+def feature_chain_signature(objects):
+    """Signature of a chain through the listed object ids, in path order (rt_feature_chain_signature; host-only, no device
+    needed): the function the kernel calls.  A record's flags hold its upper 16 bits."""
+    lib = load_library()
+    o = np.ascontiguousarray(objects, dtype=np.uint32).reshape(-1)
+    out = C.c_uint32()
+    rc = lib.rt_feature_chain_signature(o.ctypes.data if len(o) else None, len(o), C.byref(out))
+    if rc:
+        raise RtError(rc, lib.rt_last_error(None).decode())
+    return int(out.value)
 
 
 def _cam_block(camera):
@@ -378,36 +394,45 @@ class RayTracer:
         the accumulator and the sample counter untouched."""
         self._check(self._lib.rt_render_features(self._ctx, _cam_block(camera).ctypes.data))
 
+    def renderFeaturesChain(self, camera, follow=FOLLOW_ALL, max_chain=_abi.FEATURE_CHAIN_MAX):
+        """Feature records at the end of every pixel's mirror / glass chain (rt_render_features_chain, asynchronous):
+        hits whose material type is in `follow` (FOLLOW_* bits) are followed, at most `max_chain` of them, and the first
+        hit that is not is recorded.  Replaces the feature records: featureRecords(), features() and the denoisers
+        then work on these.  follow 0 or max_chain 0: renderFeatures."""
+        p = _abi.FeatureChainParams(int(follow), int(max_chain))
+        self._check(self._lib.rt_render_features_chain(self._ctx, _cam_block(camera).ctypes.data, C.byref(p)))
+
     def featureRecords(self):
-        """The last renderFeatures call's records → (h, w) array of _abi.FEATURE."""
+        """The last renderFeatures / renderFeaturesChain call's records → (h, w) array of _abi.FEATURE."""
         out = np.empty((self.height, self.width), dtype=_abi.FEATURE)
         self._check(self._lib.rt_read_features(self._ctx, out.ctypes.data, out.nbytes))
         return out
 
     def features(self):
         """The last renderFeatures call's records as (h, w, ...) arrays: position, depth (t, +inf on a miss), normal,
-        albedo, object (kind << 30 | index), material, face, direction, uv, texture, hit."""
+        albedo, object (kind << 30 | index), material, face, direction, uv, texture, hit; after renderFeaturesChain
+        also chain_length, chain_signature (the signature's upper half), cut and chain_word (flags >> 8)."""
         return _abi.split_features(self.featureRecords())
 
     def denoise(self, camera=None, iterations=_abi.DENOISE_DEFAULTS["iterations"],
                 sigma_color=_abi.DENOISE_DEFAULTS["sigma_color"], sigma_normal=_abi.DENOISE_DEFAULTS["sigma_normal"],
                 sigma_position=_abi.DENOISE_DEFAULTS["sigma_position"],
-                sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True):
+                sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """Edge-avoiding à-trous filter of the linear accumulator guided by the feature records (rt_denoise); renders
         the features for `camera` first when one is given.  → the denoised gamma image (h, w, 4)."""
         if camera is not None:
             self.renderFeatures(camera)
-        self.denoiseOnDevice(iterations, sigma_color, sigma_normal, sigma_position, sigma_albedo, split_objects)
+        self.denoiseOnDevice(iterations, sigma_color, sigma_normal, sigma_position, sigma_albedo, split_objects, split_chains)
         return self.denoisedImage()
 
     def denoiseOnDevice(self, iterations=_abi.DENOISE_DEFAULTS["iterations"],
                         sigma_color=_abi.DENOISE_DEFAULTS["sigma_color"],
                         sigma_normal=_abi.DENOISE_DEFAULTS["sigma_normal"],
                         sigma_position=_abi.DENOISE_DEFAULTS["sigma_position"],
-                        sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True):
+                        sigma_albedo=_abi.DENOISE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """rt_denoise enqueued, nothing read back."""
         p = _abi.DenoiseParams(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_position),
-                               float(sigma_albedo), _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+                               float(sigma_albedo), _abi.denoise_flags(split_objects, split_chains))
         self._check(self._lib.rt_denoise(self._ctx, C.byref(p)))
 
     def denoisedImage(self):
@@ -420,24 +445,24 @@ class RayTracer:
                         sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
                         sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
                         sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
-                        sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+                        sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """Variance-guided à-trous filter for low sample counts (rt_denoise_variance); renders the features for
         `camera` first when one is given.  → the denoised gamma image (h, w, 4), the buffer denoisedImage() reads."""
         if camera is not None:
             self.renderFeatures(camera)
         self.denoiseVarianceOnDevice(iterations, sigma_luminance, sigma_normal, sigma_position, sigma_albedo,
-                                     split_objects)
+                                     split_objects, split_chains)
         return self.denoisedImage()
 
     def denoiseVarianceOnDevice(self, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
                                 sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
                                 sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
                                 sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
-                                sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+                                sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """rt_denoise_variance enqueued, nothing read back."""
         p = _abi.DenoiseVarianceParams(int(iterations), float(sigma_luminance), float(sigma_normal),
                                        float(sigma_position), float(sigma_albedo),
-                                       _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+                                       _abi.denoise_flags(split_objects, split_chains))
         self._check(self._lib.rt_denoise_variance(self._ctx, C.byref(p)))
 
     def variance(self, which=0):
@@ -477,7 +502,7 @@ class RayTracer:
                        sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
                        sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
                        sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
-                       sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+                       sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """The variance-guided filter on MEASURED variance (rt_denoise_moments): denoiseVariance with each pixel's own
         sample variance in place of the 7x7 estimate wherever the pixel holds >= 4 samples; needs OPT_MOMENTS 1 since
         the last clear / renderAdaptive.  Renders the features for `camera` first when one is given.  → the denoised
@@ -485,18 +510,18 @@ class RayTracer:
         if camera is not None:
             self.renderFeatures(camera)
         self.denoiseMomentsOnDevice(iterations, sigma_luminance, sigma_normal, sigma_position, sigma_albedo,
-                                    split_objects)
+                                    split_objects, split_chains)
         return self.denoisedImage()
 
     def denoiseMomentsOnDevice(self, iterations=_abi.DENOISE_VARIANCE_DEFAULTS["iterations"],
                                sigma_luminance=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
                                sigma_normal=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_normal"],
                                sigma_position=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_position"],
-                               sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True):
+                               sigma_albedo=_abi.DENOISE_VARIANCE_DEFAULTS["sigma_albedo"], split_objects=True, split_chains=False):
         """rt_denoise_moments enqueued, nothing read back."""
         p = _abi.DenoiseVarianceParams(int(iterations), float(sigma_luminance), float(sigma_normal),
                                        float(sigma_position), float(sigma_albedo),
-                                       _abi.DENOISE_SPLIT_OBJECTS if split_objects else 0)
+                                       _abi.denoise_flags(split_objects, split_chains))
         self._check(self._lib.rt_denoise_moments(self._ctx, C.byref(p)))
 
     def deviceFeatures(self):

@@ -9,10 +9,14 @@ the denoised 16-spp RMSE.  --sweep instead scores a grid of sigmas at 16 spp (th
 --measured prints that table with a fourth filter, rt_denoise_moments (the variance-guided filter on the variance measured
 from the per-pixel sample moments, RT_OPT_MOMENTS), its device time, and what keeping the moments costs the frame: the
 two stages of the fused 64-spp call (rt_stage_ms_history, median of --reps) with the option off and on.
+--chain prints, per scene, the device time of rt_render_features and of rt_render_features_chain (all three glass-like
+types followed, median of --reps), how many pixels have a chain, and per spp the RMSE of rt_denoise_variance guided by the
+first-hit records, by the chain records, and by the chain records with RT_DENOISE_SPLIT_CHAINS — on the whole frame and
+on the pixels with a chain — with the filter's device time without and with the flag.
 --profile-only runs just the denoise (with --variance-guided: rt_denoise_variance), --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
 such a run's kernel_trace.csv into per-iteration times.
 
-    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided | --measured]
+    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided | --measured | --chain]
 """
 import argparse
 import csv
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--variance-guided", action="store_true")
     ap.add_argument("--measured", action="store_true")
+    ap.add_argument("--chain", action="store_true")
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--json", default=None)
@@ -104,6 +109,36 @@ def main():
             for sc, sn, sx, sa in grid:
                 t.denoiseOnDevice(D["iterations"], sc, sn, sx, sa, True)
                 sweep.append(dict(scene=name, sigma=[sc, sn, sx, sa], rmse=rmse(t.deviceDenoised()), noisy=noisy))
+            t.setStream(None)
+            t.close()
+            continue
+        if a.chain:
+            ms_f = float(np.median([timed(lambda: t.renderFeatures(wl.camera)) for _ in range(a.reps)]))
+            ms_c = float(np.median([timed(lambda: t.renderFeaturesChain(wl.camera, rt.FOLLOW_ALL)) for _ in range(a.reps)]))
+            f = t.features()
+            sub = torch.as_tensor(f["chain_length"] >= 1, device="cuda")
+            stats = dict(chain1=int((f["chain_length"] >= 1).sum()), chain2=int((f["chain_length"] >= 2).sum()),
+                         longest=int(f["chain_length"].max()), sky=int((~f["hit"] & (f["chain_length"] >= 1)).sum()))
+
+            def rmse2(buf):
+                t.sync()
+                d2 = ((dev(buf) - truth) ** 2)
+                return float(torch.sqrt(d2.mean())), (float(torch.sqrt(d2[sub].mean())) if stats["chain1"] else 0.0)
+
+            for spp in (1, 4, 16):
+                t.renderFrameOnDevice(wl.camera, spp)
+                noisy = rmse2(t.deviceImage())
+                t.renderFeatures(wl.camera)
+                t.denoiseVarianceOnDevice()
+                first = rmse2(t.deviceDenoised())
+                t.renderFeaturesChain(wl.camera, rt.FOLLOW_ALL)
+                ms_v = float(np.median([timed(lambda: t.denoiseVarianceOnDevice()) for _ in range(a.reps)]))
+                chain = rmse2(t.deviceDenoised())
+                ms_s = float(np.median([timed(lambda: t.denoiseVarianceOnDevice(split_chains=True)) for _ in range(a.reps)]))
+                split = rmse2(t.deviceDenoised())
+                rows.append(dict(scene=name, spp=spp, ms_features=ms_f, ms_features_chain=ms_c, rmse_noisy=noisy,
+                                 rmse_first_hit=first, rmse_chain=chain, rmse_chain_split=split, ms_denoise_variance=ms_v,
+                                 ms_denoise_variance_split=ms_s, **stats))
             t.setStream(None)
             t.close()
             continue
@@ -180,6 +215,22 @@ def main():
         for k, v in ranked[:12]:
             print("| %s | %s | %.3f |" % (", ".join("%g" % x for x in k), ", ".join("%.3f" % x for x in v), np.mean(v)))
         out = sweep
+    elif a.chain:
+        print("| scene | pixels with a chain (>= 2 vertices, longest, ending in the sky) | rt_render_features ms | rt_render_features_chain ms |")
+        print("|---|---|---:|---:|")
+        for name in a.scenes.split(","):
+            r = next(r for r in rows if r["scene"] == name)
+            print("| %s | %d (%d, %d, %d) | %.3f | %.3f |" % (name.upper(), r["chain1"], r["chain2"], r["longest"], r["sky"],
+                                                          r["ms_features"], r["ms_features_chain"]))
+        print()
+        print("| scene | spp | pixels | RMSE noisy | first-hit guides | chain guides | chain guides, split | filter ms | filter ms, split |")
+        print("|---|---:|---|---:|---:|---:|---:|---:|---:|")
+        for r in rows:
+            for k, what in ((0, "whole frame"), (1, "chain >= 1")):
+                print("| %s | %d | %s | %.4f | %.4f | %.4f | %.4f | %.3f | %.3f |" %
+                      (r["scene"].upper(), r["spp"], what, r["rmse_noisy"][k], r["rmse_first_hit"][k], r["rmse_chain"][k],
+                       r["rmse_chain_split"][k], r["ms_denoise_variance"], r["ms_denoise_variance_split"]))
+        out = rows
     elif a.measured:
         print("| scene | spp | RMSE noisy | RMSE rt_denoise | RMSE rt_denoise_variance | RMSE rt_denoise_moments | rt_denoise ms | rt_denoise_variance ms | rt_denoise_moments ms |")
         print("|---|---:|---:|---:|---:|---:|---:|---:|---:|")
