@@ -715,6 +715,27 @@ int rt_sample_grid_stats(rt_context *ctx, uint64_t *launches, uint64_t *exact, u
  * the first fused launch. */
 int rt_debug_live_list(rt_context *ctx, uint32_t out[4]);
 
+/* Test instrumentation, no device needed: pixels a wave of the sample queue owns at `count` samples per pixel with
+ * `waves_per_simd` one-wave workgroups per SIMD and `static_float4` float4 of staged tables, when LDS is handed out in blocks
+ * of `granule` bytes (0: the granule the launcher uses).  RT_EINVAL: count 0, waves outside 1..8, a granule outside 16..8192. */
+int rt_debug_queue_pixels(uint32_t count, uint32_t waves_per_simd, uint32_t static_float4, uint32_t granule, uint32_t *pixels_out);
+
+/* Test instrumentation: resident workgroups per compute unit the runtime reports for the headline sample-queue kernel
+ * (one wave per workgroup) at `lds_bytes` of dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor; no kernel runs). */
+int rt_debug_queue_occupancy(rt_context *ctx, uint32_t lds_bytes, int *blocks_out);
+
+/* Test instrumentation: out = {sample-kernel launches (one per slot range of a fused call; an empty grid launches nothing) of the instantiation of pt_samples_q written for
+ * exactly 64 samples per pixel, builds of the staged scene block (the LDS tables the sample queue copies)} since the
+ * context was made. */
+int rt_debug_wave_fixed(rt_context *ctx, uint64_t out[2]);
+
+/* Test instrumentation: the staged scene block as it lies on the device — *float4_out float4 (0 for a scene none of whose
+ * sets fits its cap) in the layout of the sample kernels' LDS tables: per material (r, g, b, extra_data), (type bits,
+ * 1 / extra_data, Schlick's r0 of extra_data, of 1 / extra_data); per sphere (x, y, z, r), (mat_ID bits, 0, 0, 0); per
+ * plane (normal, mat_ID bits); a set over its cap (64 materials, 64 spheres, 16 planes) is left out.  Synchronises the
+ * stream.  RT_EINVAL: no fused launch since the scene, an option or the shard last changed, or capacity_float4 too small. */
+int rt_debug_stage_block(rt_context *ctx, float *out, size_t capacity_float4, uint32_t *float4_out);
+
 /* Name, CU count and arch of the context's device, e.g. "gfx950". */
 int rt_device_info(rt_context *ctx, char *name, size_t name_len, int *cu_count, char *arch, size_t arch_len);
 

@@ -210,6 +210,23 @@ def sample_grid_prototypes(lib):
     lib.rt_sample_units.argtypes = [u32, u32, u32, u32, C.POINTER(u32)]
     lib.rt_sample_grid_stats.argtypes = [C.c_void_p, p64, p64, p64, p64]
     lib.rt_debug_live_list.argtypes = [C.c_void_p, C.POINTER(u32)]
+    lib.rt_debug_wave_fixed.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.rt_debug_stage_block.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(u32)]
+    lib.rt_debug_queue_pixels.argtypes = [u32, u32, u32, u32, C.POINTER(u32)]
+    lib.rt_debug_queue_occupancy.argtypes = [C.c_void_p, u32, C.POINTER(C.c_int)]
+
+
+# the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)
+LDS_MATERIALS, LDS_WINNERS, LDS_PLANES = 64, 64, 16
+
+
+def stage_block_layout(n_materials, n_spheres, n_planes):
+    """(first row of the materials, of the sphere records, of the plane records, rows in all) of the staged scene block
+    (rt_debug_stage_block): two rows per material, two per sphere, one per plane; a set over its cap has no rows."""
+    nm = 2 * n_materials if n_materials <= LDS_MATERIALS else 0
+    nw = 2 * n_spheres if n_spheres <= LDS_WINNERS else 0
+    npl = n_planes if n_planes <= LDS_PLANES else 0
+    return 0, nm, nm + nw, nm + nw + npl
 
 
 def queue_sums_prototypes(lib):

@@ -91,9 +91,9 @@ PT_DEV float schlick_r0(float ratio) {
     return r0;
 }
 
-// call at kernel start by every thread of the workgroup (contains a barrier)
-PT_DEV LdsV4 stage_materials(const DeviceScene &sc, float4 *lds) {
-    const uint32_t nm = lds_mat_n(sc.material_count), nw = lds_win_n(sc.sphere_count), np = lds_pln_n(sc.plane_count);
+// The scene's tables (pt_types.hpp: materials, sphere winner records, plane records), written to `lds` by the threads of
+// one workgroup: stage_materials' loops — into a workgroup's LDS, or by pt_stage_block into the context's staged block.
+PT_DEV void stage_tables(const DeviceScene &sc, float4 *lds, const uint32_t nm, const uint32_t nw, const uint32_t np) {
     if (nm)
         for (uint32_t i = threadIdx.x; i < sc.material_count; i += blockDim.x) {
             const rt_material &m = sc.materials[i];
@@ -117,8 +117,24 @@ PT_DEV LdsV4 stage_materials(const DeviceScene &sc, float4 *lds) {
             const rt_plane &p = sc.planes[i];
             lds[nm + nw + i] = make_float4(p.normal.x, p.normal.y, p.normal.z, __uint_as_float(p.mat_ID));
         }
+}
+// call at kernel start by every thread of the workgroup (contains a barrier)
+PT_DEV LdsV4 stage_materials(const DeviceScene &sc, float4 *lds) {
+    const uint32_t nm = lds_mat_n(sc.material_count), nw = lds_win_n(sc.sphere_count), np = lds_pln_n(sc.plane_count);
+    stage_tables(sc, lds, nm, nw, np);
     __syncthreads();
     return nm ? lds_ptr(lds) : (LdsV4) nullptr;
+}
+// the same tables copied from the context's staged block (rt_context::StageBlock), one 16-byte read and write per entry
+PT_DEV const float4 *stage_block_of(const DeviceScene &sc) {
+    return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sc.materials) + stage_block_offset(sc.material_count));
+}
+PT_DEV LdsV4 stage_materials_copy(const DeviceScene &sc, float4 *lds) {
+    const uint32_t n = lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count);
+    const float4 *__restrict__ blk = stage_block_of(sc);
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) lds[i] = blk[i];
+    __syncthreads();
+    return lds_mat_n(sc.material_count) ? lds_ptr(lds) : (LdsV4) nullptr;
 }
 PT_DEV LdsV4 staged_winners(const DeviceScene &sc, const float4 *lds) {
     return lds_win_n(sc.sphere_count) ? lds_ptr(lds + lds_mat_n(sc.material_count)) : (LdsV4) nullptr;

@@ -515,13 +515,13 @@ static_assert(QUEUE_SLOTS >= RT_SPP_PER_LAUNCH, "rt_render_spp's launches must f
 #ifndef PT_LDS_GRANULE
 #define PT_LDS_GRANULE 1024u
 #endif
-__host__ inline uint32_t queue_pixels_per_wave(uint32_t count, uint32_t waves, uint32_t static_float4) {
+__host__ inline uint32_t queue_pixels_per_wave(uint32_t count, uint32_t waves, uint32_t static_float4, uint32_t granule = PT_LDS_GRANULE) {
     auto fit = [&](uint32_t waves_per_simd) {
         uint32_t workgroups = waves_per_simd * 4u;  // resident workgroups per CU: one wave each
         // (LDS is handed out in blocks: a request of 6 584 bytes — 7 pixels of 64 samples — left fewer than 24 workgroups
         // resident although 24 × 6 584 < 160 KiB, and 6 pixels (5 728 bytes) are 4.5 % faster on C2; the budget is
-        // therefore rounded DOWN to a multiple of PT_LDS_GRANULE)
-        uint32_t budget = 163840u / workgroups / PT_LDS_GRANULE * PT_LDS_GRANULE;
+        // therefore rounded DOWN to a multiple of the granule: PT_LDS_GRANULE, or the one rt_debug_queue_pixels asks about)
+        uint32_t budget = 163840u / workgroups / granule * granule;
         uint32_t per_wave = budget - static_float4 * (uint32_t)sizeof(float4) - 15u;   // (15: queue_wave_lds_bytes rounds up)
         uint32_t p = per_wave / queue_pixel_bytes(count);
         if (p * count > QUEUE_SLOTS) p = QUEUE_SLOTS / count;
@@ -570,9 +570,51 @@ struct WaveQueue {
     float inv_count;
 };
 
+// The fixed cost a wave pays around its sample loop (profiles/r16_experiments.md), one switch per part:
+#ifndef PT_Q_COUNT64
+#define PT_Q_COUNT64 1       // pt_samples_q<…, COUNT_LOG2 = 6>: launches of exactly 64 samples per pixel with 64 lanes per pixel
+#endif
+#ifndef PT_TEXEL_LAZY
+#define PT_TEXEL_LAZY 1      // GEOM 0: the texel's address arithmetic stays inside the textured branch
+#endif
+#ifndef PT_STAGE_XY_FAST
+#define PT_STAGE_XY_FAST 1   // queue_stage: an unsharded frame's (x, y) without the integer division
+#endif
+#ifndef PT_STAGE_COPY
+#define PT_STAGE_COPY 1      // pt_samples_q<false, false, …> copies the scene's LDS tables from the context's block
+#endif
+
+// queue_stage's slot → (x, y).  slot_to_pixel divides the tile index by fp.tiles_x, a launch constant, with the generic
+// uint32 division (about 25 VALU instructions).  An unsharded frame (world == 1, so rank == 0 and t = slot >> tpix_log2)
+// of at most 2^20 tiles — both wave-uniform — takes the quotient as queue_fetch takes idx / count:
+//     ty = (uint32_t)(((float)t + 0.5f) * rcp((float)tiles_x)),   tx = t - ty * tiles_x.
+// Exact: t < 2^20 and tiles_x <= tiles_total <= 2^20, so (float)tiles_x, (float)t and t + 0.5 (22 significant bits) are
+// exact; v_rcp_f32 is within 1 ulp (relative 2^-23) and the product rounds once (2^-24), so the computed value is within
+//     (t + 0.5) / tiles_x · (2^-23 + 2^-24 + 2^-47) < 2^20 · 1.5001 · 2^-23 / tiles_x < 0.19 / tiles_x
+// of (t + 0.5) / tiles_x = Q + (r + 0.5) / tiles_x (0 <= r < tiles_x), which lies at least 0.5 / tiles_x away from
+// both Q and Q + 1: the truncation is Q.  (tests/test_wave_fixed_host.py restates it for every reciprocal within 1 ulp.)
+// The live list holds slots of valid pixels only (pt_prefix), so slot_to_pixel's range checks — whose result queue_stage
+// never used — have nothing to say here.  Sharded and larger frames keep slot_to_pixel.
+#define PT_XY_FAST_MAX_TILES (1u << 20)
+template <bool FAST>
+PT_DEV void stage_xy(const FrameParams &fp, uint32_t slot, uint32_t &x, uint32_t &y) {
+    if (FAST && PT_STAGE_XY_FAST && fp.world == 1u && fp.tiles_total <= PT_XY_FAST_MAX_TILES) {
+        const uint32_t tpix_log2 = fp.tile_w_log2 + fp.tile_h_log2;
+        const uint32_t t = slot >> tpix_log2, in = slot & ((1u << tpix_log2) - 1u);
+        const uint32_t ty = (uint32_t)(((float)t + 0.5f) * __builtin_amdgcn_rcpf((float)fp.tiles_x)), tx = t - ty * fp.tiles_x;
+        x = (tx << fp.tile_w_log2) + (in & ((1u << fp.tile_w_log2) - 1u));
+        y = (ty << fp.tile_h_log2) + (in >> fp.tile_w_log2);
+    } else {
+        (void)slot_to_pixel(fp, slot, x, y);
+    }
+}
+
 // Stages the records and coordinates of the wave's pixels — the `npix` live-list entries from `pix0` on, which the kernel
 // took with live_take before it staged anything (a wave that took none has left by now); `lds` is the workgroup's dynamic
 // LDS and face_f4 the float4 of face records the kernel staged in it (queue_static_f4).  Every lane of the wave calls it (contains the wave's fence and barrier).
+// CL: the launch's sample count is the compile-time 1 << CL (pt_samples_q's COUNT_LOG2; -1: any count, read from fp).
+// XY_FAST: stage_xy's short form (pt_samples_q without counters and without a BVH walk; every other kernel keeps slot_to_pixel).
+template <int CL = -1, bool XY_FAST = false>
 PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const PixelRec *__restrict__ recs,
                              const uint32_t *__restrict__ live, uint32_t npix, uint32_t pix0,
                              uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
@@ -583,7 +625,7 @@ PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const
     q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
     const uint32_t lane = threadIdx.x;
     q.npix = npix;
-    q.count = fp.count;
+    q.count = CL >= 0 ? 1u << (CL & 31) : fp.count;
     q.total = q.npix * q.count;
     for (uint32_t i = lane; i < q.npix * QUEUE_REC_F4; i += 64u) {
         uint32_t p = i / QUEUE_REC_F4, part = i - p * QUEUE_REC_F4;
@@ -596,7 +638,7 @@ PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const
     }
     if (lane < q.npix) {
         uint32_t x = 0, y = 0;
-        (void)slot_to_pixel(fp, live[pix0 + lane], x, y);
+        stage_xy<XY_FAST>(fp, live[pix0 + lane], x, y);
         // (x, y, and the pixel's part of the two table index sums: rnd_base_v = (sample·2683 + x·3931 + y·2504)·3 and
         // rnd_base_u = sample·2683 + x·3931 + y are linear in uint32 arithmetic, so a refill needs two multiplies, not five)
         q.xy[lane].x = x;
@@ -609,7 +651,7 @@ PT_DEV WaveQueue queue_stage(const DeviceScene &sc, const FrameParams &fp, const
     // (the two operands of queue_fetch's division, formed here, where the parent kernels formed them: before the staging
     // loop they change the register allocation of every instantiation)
     q.inv_count = fp.inv_count;
-    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    q.count_log2 = CL >= 0 ? (uint32_t)CL : (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
     return q;
 }
 
@@ -619,13 +661,15 @@ struct QueueEntry {
     float4 q0, q1, q2, q3, q4;
     uint32_t bits, bv, bu;
 };
+template <int CL = -1>
 PT_DEV QueueEntry queue_fetch(const WaveQueue &q, const DeviceScene &sc, const FrameParams &fp, uint32_t idx) {
     // pixel of this queue entry: p = idx / count, exactly, without an integer divide:
     // (idx + 0.5)/count lies >= 0.5/count away from every integer, far more than the rounding
     // of the float product (idx < 8192, count <= 512)
     // (a power-of-two count — wave-uniform — needs a shift; otherwise one float multiply:)
-    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
-    const uint32_t sample = fp.first + (idx - p * q.count);
+    // (a compile-time count: a shift and a mask, and the record's address by shifts and adds)
+    const uint32_t p = CL >= 0 ? idx >> (CL & 31) : q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t sample = fp.first + (CL >= 0 ? idx & ((1u << (CL & 31)) - 1u) : idx - p * q.count);
     auto part = [&](uint32_t k) {
         const LdsQueueF4 f = q.rec + (QUEUE_REC_F4 * p + k);
         return make_float4(f->x, f->y, f->z, f->w);
@@ -702,7 +746,35 @@ PT_DEV float row_pair_add(float a, float b) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// count == g == 64 (queue_sums_tree<6>): queue_lane_sum's loop runs exactly one trip for a pixel the wave owns and none
+// otherwise — one guarded read, the same operands in the same order (0.0f + slot), no loop
+PT_DEV V3 queue_lane_slot64(const WaveQueue &q, uint32_t p, uint32_t l) {
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    if (p < q.npix) {
+        const LdsF32 sl = q.slot + 3u * (p * 64u + l);
+        sum = sum + mk(sl[0], sl[1], sl[2]);
+    }
+    return sum;
+}
+// CL = 6: a launch of 64 samples per pixel with 64 lanes per pixel (at most QUEUE_SLOTS / 64 = 8 pixels: two passes)
+template <int CL = -1>
 PT_DEV void queue_sums_tree(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
+    if (CL == 6) {
+        static_assert(QUEUE_SLOTS / 64u <= 8u, "two passes of four pixels");
+        const uint32_t lane = threadIdx.x, half = lane >> 5, i = lane & 31u, row = lane >> 4;
+#pragma unroll
+        for (uint32_t pb = 0; pb < 8u; pb += 4u) {
+            if (pb >= q.npix) break;
+            V3 a = queue_lane_slot64(q, pb + half, i), b = queue_lane_slot64(q, pb + 2u + half, i);
+            a = a + queue_lane_slot64(q, pb + half, i + 32u);   // offset 32
+            b = b + queue_lane_slot64(q, pb + 2u + half, i + 32u);
+            V3 sum = mk(row_pair_add(a.x, b.x), row_pair_add(a.y, b.y), row_pair_add(a.z, b.z));   // offset 16
+            sum = row_add<1>(row_add<2>(row_add<4>(row_add<8>(sum))));
+            const uint32_t p = pb + ((row & 1u) << 1 | row >> 1);
+            if (p < q.npix && (lane & 15u) == 0u) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, 64u);
+        }
+        return;
+    }
     const uint32_t lane = threadIdx.x, gl = fp.group_log2;
     if (gl >= 5u) {
         const uint32_t half = lane >> 5, i = lane & 31u, g = 1u << gl, row = lane >> 4;
@@ -736,11 +808,11 @@ PT_DEV void queue_sums_tree(const WaveQueue &q, const FrameParams &fp, float4 *_
 //   the kernels with a BVH walk (pt_samples_q<…, ACCEL = true>, pt_samples_w): their waves live for milliseconds, the
 //   epilogue is nothing to them, and with the tree C4 and C5 measured 1.2 % and 0.9 % SLOWER than the parent
 //   (profiles/r13_experiments.md) — the walk loops' code moved with the epilogue behind them.
-template <bool MOMENTS, bool BUTTERFLY = false>
+template <bool MOMENTS, bool BUTTERFLY = false, int CL = -1>
 PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (PT_QUEUE_SUMS_TREE && !MOMENTS && !BUTTERFLY) return queue_sums_tree(q, fp, accum);   // (moments need the sum in all g lanes)
+    if (PT_QUEUE_SUMS_TREE && !MOMENTS && !BUTTERFLY) return queue_sums_tree<CL>(q, fp, accum);   // (moments need the sum in all g lanes)
     const uint32_t lane = threadIdx.x;
     const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
     for (uint32_t pb = 0; pb < q.npix; pb += ppp) {
@@ -799,7 +871,9 @@ PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
 // kernel keeps 6 waves per SIMD.
-template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false>
+// COUNT_LOG2 = 6: the launch has exactly 64 samples per pixel and 64 lanes per pixel (fp.count == 64, fp.group_log2 == 6;
+// launch_fused picks it for <false, false, …> only) — the queue's index arithmetic and sums are written for that count.
+template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
@@ -819,7 +893,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     float4 *s_mat = s_dyn;
     LaneCounters cn;
     if (COUNT) zero_counters(cn);
-    Ctx c{sc, stage_materials(sc, s_mat), &cn};
+    // (without counters and without a BVH walk: the tables by copy from the context's staged block — launch_fused built it)
+    Ctx c{sc, PT_STAGE_COPY && !COUNT && !ACCEL ? stage_materials_copy(sc, s_mat) : stage_materials(sc, s_mat), &cn};
     c.lwin = staged_winners(sc, s_mat);
     c.lpln = staged_planes(sc, s_mat);
     if (GEOM != 0 && fp.lds_face_f4) {   // the face records of a scene of a few small meshes (hit_models' candidate loop)
@@ -829,7 +904,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = queue_stage(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
+    const WaveQueue q = queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
     uint32_t next = 0;  // wave-uniform head of the queue
     bool active = false;
@@ -859,7 +934,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             uint32_t cand = next + lanes_below(m);
             if (need && cand < q.total) {
                 idx = cand;
-                const QueueEntry e = queue_fetch(q, sc, fp, idx);
+                const QueueEntry e = queue_fetch<COUNT_LOG2>(q, sc, fp, idx);
                 bv = e.bv;
                 bu = e.bu;
                 if (COUNT) cn.c[CN_SAMPLES]++;
@@ -950,7 +1025,15 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                     done = true;
                 } else if (type == RT_TEXTURED) {
                     if (COUNT) cn.c[CN_N_TEXFETCH]++;
-                    col = texture_rgb(c.sc, h.u, h.v, h.tex);
+                    float tu = h.u, tv = h.v;
+                    // (GEOM 0: hit_finish leaves u = v = 0 and layer 0, constants — the texel's address arithmetic, four
+                    // 64-bit addresses and four weights, was lifted to the kernel's entry and carried through the loop in
+                    // 11 VGPRs, for a branch C2 never takes; opaque to the optimiser, the same operations stay in here)
+                    // (Nothing but the compiler's present cost model keeps LICM from lifting the asm together with what hangs
+                    // on it — it is not volatile and its inputs are loop-invariant: tools/isa_stats.py shows it, as a GEOM 0
+                    // kernel back at 71 VGPRs.)
+                    if (PT_TEXEL_LAZY && GEOM == 0 && !COUNT && !ACCEL) asm("" : "+v"(tu), "+v"(tv));
+                    col = texture_rgb(c.sc, tu, tv, h.tex);
                 }
             }
             if (done) {
@@ -968,8 +1051,14 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
     if (!COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
-    else queue_sums<MOMENTS, COUNT || ACCEL>(q, fp, accum);
+    else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
+}
+
+// The context's staged scene block (rt_context::StageBlock): stage_materials' tables by stage_materials' loops, compiled
+// in this translation unit — the divisions are the policy's.  One workgroup.
+__global__ __launch_bounds__(64) void pt_stage_block(DeviceScene sc, float4 *__restrict__ block) {
+    stage_tables(sc, block, lds_mat_n(sc.material_count), lds_win_n(sc.sphere_count), lds_pln_n(sc.plane_count));
 }
 
 // pt_samples_w — the sample queue for scenes in which every mesh of every model has a BVH (C5: one mesh of
@@ -1608,6 +1697,14 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
     int rc = ensure_slots(ctx, slots);
     if (rc) return rc;
     const rt_context::Slots &ss = ctx->slots;
+    // the staged scene block, for the sample kernels that copy it: (re)built when anything it holds may have changed
+    if (PT_STAGE_COPY && ctx->stage_block.generation != ctx->prefix_cache.generation) {
+        if (lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count))
+            hipLaunchKernelGGL(pt_stage_block, dim3(1), dim3(64), 0, ctx->stream, sc,
+                               reinterpret_cast<float4 *>(reinterpret_cast<char *>(ctx->materials.p) + stage_block_offset(sc.material_count)));
+        ctx->stage_block.generation = ctx->prefix_cache.generation;
+        ctx->stage_block.builds++;
+    }
     uint32_t *live_count = ss.live.p + ss.capacity + 256u;
     uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
     if (slots_per_launch == 0) slots_per_launch = 1;
@@ -1720,10 +1817,20 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
 #define PT_GRID(U, LAUNCH) do { launched = (U); if (launched) { LAUNCH; } } while (0)
 #define PT_CALL_QUEUE_M(C, A, G, W, M) \
     PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<C, A, G, W, M>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw))
+    // (the count-specialised instantiation: exactly 64 samples on 64 lanes per pixel, no counters, no BVH, no moments)
+    const bool count64 = PT_Q_COUNT64 && count == 64u && fp.group_log2 == 6u;
+    (void)count64;
+#define PT_CALL_QUEUE_64(G, W) \
+    do { PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<false, false, G, W, false, 6>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw)); if (launched) sg.count64_launches++; } while (0)
 #define PT_CALL_QUEUE_W(C, A, G, W) do { if (fp.m2) PT_CALL_QUEUE_M(C, A, G, W, true); else PT_CALL_QUEUE_M(C, A, G, W, false); } while (0)
+#if PT_Q_COUNT64
+#define PT_CALL_QUEUE_N(C, G) do { if (!(C) && count64 && !fp.m2) PT_CALL_QUEUE_64(G, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, G, PT_Q_WAVES); } while (0)
+#else
+#define PT_CALL_QUEUE_N(C, G) PT_CALL_QUEUE_W(C, false, G, PT_Q_WAVES)
+#endif
 #define PT_CALL_QUEUE(C, A)                                                                       \
     do {                                                                                          \
-        if (!(A)) { if (simple_geom) PT_CALL_QUEUE_W(C, false, 0, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, 1, PT_Q_WAVES); } \
+        if (!(A)) { if (simple_geom) PT_CALL_QUEUE_N(C, 0); else PT_CALL_QUEUE_N(C, 1); } \
         else if (sphere_bvh_only) { if (simple_geom) PT_CALL_QUEUE_W(C, true, 0, PT_Q_WAVES_SPHERE_BVH); else PT_CALL_QUEUE_W(C, true, 1, PT_Q_WAVES_ACCEL); } \
         else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
     } while (0)
@@ -1749,6 +1856,8 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         }
 #undef PT_CALL_QUEUE
 #undef PT_CALL_QUEUE_W
+#undef PT_CALL_QUEUE_N
+#undef PT_CALL_QUEUE_64
 #undef PT_CALL_QUEUE_M
 #undef PT_CALL_FIXED
 #undef PT_GRID
@@ -1907,6 +2016,17 @@ int ks_launch_debug_builtin(rt_context *ctx, int op, const float *d_in, uint32_t
     return RT_OK;
 }
 
+// rt_debug_queue_pixels: queue_pixels_per_wave as the launcher calls it, under a granule of the caller's choice (0: PT_LDS_GRANULE)
+uint32_t ks_queue_pixels(uint32_t count, uint32_t waves, uint32_t static_float4, uint32_t granule) {
+    return queue_pixels_per_wave(count, waves, static_float4, granule ? granule : PT_LDS_GRANULE);
+}
+
+// rt_debug_queue_occupancy: what the runtime says about the headline instantiation at a dynamic LDS size — no kernel runs
+int ks_queue_occupancy(rt_context *ctx, uint32_t lds_bytes, int *blocks) {
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1>, 64, lds_bytes));
+    return RT_OK;
+}
+
 const pt::KernelSet g_kernel_set = {
     PT_ARITH,
 #if PT_ARITH == 0
@@ -1917,7 +2037,8 @@ const pt::KernelSet g_kernel_set = {
     "rocm-opencl",
 #endif
     ks_launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
-    ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain};
+    ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
+    ks_queue_pixels, ks_queue_occupancy};
 
 }  // namespace
 

@@ -43,6 +43,10 @@ struct KernelSet {
     // RT_FOLLOW_* bits, at most max_chain <= RT_FEATURE_CHAIN_MAX followed vertices) into d_out
     int (*launch_features_chain)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, uint32_t follow, uint32_t max_chain,
                                  rt_feature *d_out);
+    // rt_debug_queue_pixels: the launcher's queue_pixels_per_wave under an LDS allocation granule (0: the shipped one)
+    uint32_t (*queue_pixels)(uint32_t count, uint32_t waves, uint32_t static_float4, uint32_t granule);
+    // rt_debug_queue_occupancy: hipOccupancyMaxActiveBlocksPerMultiprocessor of pt_samples_q<false, false, 0, PT_Q_WAVES> at a dynamic LDS size
+    int (*queue_occupancy)(rt_context *ctx, uint32_t lds_bytes, int *blocks);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

@@ -84,6 +84,12 @@ PT_HD uint32_t lds_static_used(uint32_t material_count, uint32_t sphere_count, u
     return lds_mat_n(material_count) + lds_win_n(sphere_count) + lds_pln_n(plane_count);  // float4 units
 }
 
+// The staged scene block (rt_context::StageBlock): these tables in this layout, built once per scene and policy by
+// pt_stage_block, behind the materials array in the same allocation (an empty array is a one-element dummy; a material
+// is 48 bytes, so the block is 16-byte aligned like the allocation).
+static_assert(sizeof(rt_material) % 16 == 0, "the staged scene block follows the materials 16-byte aligned");
+PT_HD size_t stage_block_offset(uint32_t material_count) { return (size_t)(material_count ? material_count : 1u) * sizeof(rt_material); }
+
 // ---- shared deterministic prefix ---------------------------------------------------
 // The reference does not jitter the primary ray (:500-505), so all samples of a
 // pixel follow the SAME path until the first random event (a diffuse / textured /

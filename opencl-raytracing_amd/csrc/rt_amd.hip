@@ -643,7 +643,10 @@ int rt_set_scene(rt_context *ctx, const rt_scene_desc *d) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_scene = false;
-    HIP_TRY(ctx, ctx->materials.upload(d->materials, d->material_count));
+    // (behind the materials: room for the staged scene block, rt_context::StageBlock)
+    HIP_TRY(ctx, ctx->materials.upload(d->materials, d->material_count,
+                                       lds_static_used(d->material_count, d->sphere_count, d->plane_count) * sizeof(float4)));
+    ctx->stage_block.generation = ~0ull;
     HIP_TRY(ctx, ctx->spheres.upload(d->spheres, d->sphere_count));
     ctx->h_spheres.assign(d->spheres, d->spheres + d->sphere_count);   // the test records follow in apply_arith()
     ctx->h_bvh_idx.clear();
@@ -1830,6 +1833,42 @@ int rt_debug_live_list(rt_context *ctx, uint32_t out[4]) {
     out[1] = ctx->sample_grid.last_per_unit;
     out[2] = h[0];
     out[3] = h[LIVE_HEAVY_COUNTER];
+    return RT_OK;
+}
+
+int rt_debug_queue_pixels(uint32_t count, uint32_t waves_per_simd, uint32_t static_float4, uint32_t granule, uint32_t *pixels_out) {
+    if (!pixels_out || count < 1u || waves_per_simd < 1u || waves_per_simd > 8u || static_float4 > PT_LDS_STATIC_FLOAT4 ||
+        (granule != 0u && (granule < 16u || granule > 8192u)))
+        return RT_EINVAL;
+    *pixels_out = pt::kernel_set_a2()->queue_pixels(count, waves_per_simd, static_float4, granule);   // (host code: the same in every policy)
+    return RT_OK;
+}
+
+int rt_debug_queue_occupancy(rt_context *ctx, uint32_t lds_bytes, int *blocks_out) {
+    if (!ctx || !blocks_out) return RT_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ctx->ks->queue_occupancy(ctx, lds_bytes, blocks_out);
+}
+
+int rt_debug_wave_fixed(rt_context *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return RT_EINVAL;
+    out[0] = ctx->sample_grid.count64_launches;
+    out[1] = ctx->stage_block.builds;
+    return RT_OK;
+}
+
+int rt_debug_stage_block(rt_context *ctx, float *out, size_t capacity_float4, uint32_t *float4_out) {
+    if (!ctx || !float4_out) return RT_EINVAL;
+    if (!ctx->have_scene || ctx->stage_block.generation != ctx->prefix_cache.generation)
+        return fail(ctx, RT_EINVAL, "the staged scene block is not built (no fused launch since the last change)");
+    const uint32_t n = lds_static_used((uint32_t)ctx->materials.n, (uint32_t)ctx->spheres.n, (uint32_t)ctx->planes.n);
+    *float4_out = n;
+    if (n == 0) return RT_OK;
+    if (!out || capacity_float4 < n) return fail(ctx, RT_EINVAL, "the staged scene block holds %u float4", n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(out, reinterpret_cast<const char *>(ctx->materials.p) + stage_block_offset((uint32_t)ctx->materials.n),
+                                n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

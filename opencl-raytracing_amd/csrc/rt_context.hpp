@@ -38,10 +38,11 @@ struct DevBuf {
         n = count;
         return e;
     }
-    hipError_t upload(const T *src, size_t count) {
+    // tail_bytes: uninitialised room behind the array, in the same allocation (the staged scene block behind the materials)
+    hipError_t upload(const T *src, size_t count, size_t tail_bytes = 0) {
         release();
         size_t alloc = count ? count : 1;  // empty arrays become 1-element dummies (src/scene.cpp:41-44)
-        hipError_t e = hipMalloc((void **)&p, alloc * sizeof(T));
+        hipError_t e = hipMalloc((void **)&p, alloc * sizeof(T) + tail_bytes);
         if (e != hipSuccess) { p = nullptr; return e; }
         n = count;
         if (count) e = hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
@@ -175,6 +176,16 @@ struct rt_context {
         uint32_t count_light = 0, count_heavy = 0;   // live_count[0], live_count[LIVE_HEAVY_COUNTER], unclamped
     } prefix_cache;
     void prefix_changed() { prefix_cache.generation++; }
+    // The staged scene block: the LDS tables of stage_materials (pt_device.hpp) as the selected policy's kernels compute
+    // them, lds_static_used(...) float4 BEHIND the materials array in the same allocation (stage_block_of; rt_set_scene
+    // leaves the room) — pt_samples_q without counters and without a BVH walk copies it instead of computing it per wave.
+    // Whatever can change a word of it (the scene's materials, spheres or planes; the arithmetic policy, whose divisions
+    // it holds) bumps the prefix generation already, so launch_fused rebuilds it when `generation` is not the prefix
+    // cache's — a superset of the reasons, one tiny kernel each, and nothing of the prefix cache is touched.
+    struct StageBlock {
+        uint64_t generation = ~0ull;    // prefix_cache.generation the block was built at
+        uint64_t builds = 0;            // (rt_debug_wave_fixed)
+    } stage_block;
     // RT_OPT_EXACT_GRID and rt_sample_grid_stats; the pinned block and the event are made by rt_create and die with the context
     struct SampleGrid {
         bool exact = true;              // RT_OPT_EXACT_GRID (rt_create: the environment's RT_EXACT_GRID=0 turns it off)
@@ -185,6 +196,7 @@ struct rt_context {
         uint64_t workgroups = 0;        // sample-kernel workgroups launched, all launches together
         uint64_t live_last = 0;         // workgroups of the last EXACT launch's kernel that own a pixel (= its grid)
         uint32_t last_cap = 0, last_per_unit = 0;   // seg_cap and pixels per unit of the last launch (rt_debug_live_list)
+        uint64_t count64_launches = 0;  // sample-stage launches that took pt_samples_q<…, COUNT_LOG2 = 6> (rt_debug_wave_fixed)
     } sample_grid;
     // Look-ahead for rt_render_again (RT_OPT_LOOKAHEAD): while the camera rests, ONE fused launch traces the next `pending`
     // samples and replays the gamma-space running mean per pixel, the image after each sample going to a frame of `ring`;

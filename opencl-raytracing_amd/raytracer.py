@@ -34,7 +34,7 @@ SYMBOLS = (
     "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
     "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
-    "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_queue_sums",
+    "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy", "rt_debug_queue_sums",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -225,6 +225,15 @@ class DeviceBuffer:
         self._owner = owner
         self.__cuda_array_interface__ = {"shape": (h, w, 4), "typestr": "<f4", "data": (int(ptr), False),
                                          "version": 3, "strides": None}
+
+
+def queue_pixels(count, waves_per_simd=6, static_float4=0, granule=0):
+    """Pixels a wave of the sample queue owns (rt_debug_queue_pixels: the launcher's own function; granule 0 = the shipped one)."""
+    n = C.c_uint32()
+    rc = load_library().rt_debug_queue_pixels(int(count), int(waves_per_simd), int(static_float4), int(granule), C.byref(n))
+    if rc:
+        raise RtError(rc, "rt_debug_queue_pixels: invalid argument")
+    return int(n.value)
 
 
 class RayTracer:
@@ -622,6 +631,30 @@ class RayTracer:
         out = (C.c_uint32 * 4)()
         self._check(self._lib.rt_debug_live_list(self._ctx, out))
         return tuple(int(v) for v in out)
+
+    def waveFixedStats(self):
+        """(count64 launches, stage block builds) since the context was made (rt_debug_wave_fixed; test instrumentation):
+        fused launches whose sample stage ran the 64-samples-per-pixel instantiation of pt_samples_q, and builds of the
+        staged scene block."""
+        out = (C.c_uint64 * 2)()
+        self._check(self._lib.rt_debug_wave_fixed(self._ctx, out))
+        return tuple(int(v) for v in out)
+
+    def queueOccupancy(self, lds_bytes):
+        """Resident workgroups per compute unit the runtime reports for the headline sample-queue kernel at `lds_bytes` of
+        dynamic LDS (rt_debug_queue_occupancy; no kernel runs)."""
+        n = C.c_int()
+        self._check(self._lib.rt_debug_queue_occupancy(self._ctx, int(lds_bytes), C.byref(n)))
+        return int(n.value)
+
+    def stageBlock(self):
+        """The staged scene block as it lies on the device, (n, 4) float32 (rt_debug_stage_block; test instrumentation,
+        synchronises): the LDS tables the sample queue copies — _abi.stage_block_layout names the rows."""
+        cap = 2 * 64 + 2 * 64 + 16
+        out = np.zeros((cap, 4), dtype=np.float32)
+        n = C.c_uint32()
+        self._check(self._lib.rt_debug_stage_block(self._ctx, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def setArith(self, arith):
         """Select the arithmetic policy of the trace kernels (RT_OPT_ARITH): ARITH_IEEE (default, the CPU oracle's
