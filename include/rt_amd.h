@@ -720,6 +720,45 @@ int rt_debug_live_list(rt_context *ctx, uint32_t out[4]);
  * of `granule` bytes (0: the granule the launcher uses).  RT_EINVAL: count 0, waves outside 1..8, a granule outside 16..8192. */
 int rt_debug_queue_pixels(uint32_t count, uint32_t waves_per_simd, uint32_t static_float4, uint32_t granule, uint32_t *pixels_out);
 
+/* What a fused launch's choice of sample kernel reads (one slot range of one call); flags are 0 / 1. */
+typedef struct rt_sample_facts {
+    uint32_t count, glog2;              /* samples per pixel of the call, log2 of the lanes per pixel */
+    uint32_t n, seg_cap;                /* slots of the range; capacity of its live list (n rounded up to 256) */
+    uint32_t material_count, sphere_count, plane_count, lens_count, model_count;
+    uint32_t sphere_bvh, mesh_bvh;      /* the launch walks a sphere BVH / per-mesh BVHs */
+    uint32_t walk_jobs;                 /* meshes of the walk-slice kernel (0 unless every mesh has a BVH) */
+    uint32_t faces;                     /* triangles of all meshes together */
+    uint32_t cu_count;
+    uint32_t count_enabled, sample_queue, walk_slices, wave_fill, moments;
+    uint32_t exact, count_light, count_heavy;   /* the live list's counters are known to the host (else both 0) */
+} rt_sample_facts;
+
+#define RT_PLAN_FIXED 0u   /* pt_samples<COUNT, ACCEL> */
+#define RT_PLAN_QUEUE 1u   /* pt_samples_q<COUNT, ACCEL, GEOM, WAVES, MOMENTS, COUNT_LOG2> */
+#define RT_PLAN_WALK 2u    /* pt_samples_w<MULTI, MOMENTS> */
+#define RT_PLAN_GENERIC_COUNT 0xFFFFFFFFu   /* count_log2 of the instantiations for any count (COUNT_LOG2 = -1) */
+
+/* The sample-kernel launch chosen for an rt_sample_facts: the instantiation and its launch geometry.  count (counters on),
+ * accel (the scene has a BVH) and moments (the launch keeps them) are set for every family, whether or not its template
+ * takes them; geom, count_log2 belong to RT_PLAN_QUEUE and multi to RT_PLAN_WALK (0 elsewhere), waves is 0 for
+ * RT_PLAN_FIXED.  grid_units 0: nothing is launched. */
+typedef struct rt_sample_plan {
+    uint32_t family;
+    uint32_t count, accel, geom, waves, moments, count_log2, multi;
+    uint32_t pixels_per_wave;           /* pixels per unit of the live list (1 for RT_PLAN_FIXED) */
+    uint32_t lds_face_f4;               /* float4 of face records the launch stages in LDS (FrameParams::lds_face_f4) */
+    uint32_t lds_bytes;                 /* dynamic LDS of a workgroup */
+    uint32_t grid_units, block_size;    /* workgroups, threads of each */
+} rt_sample_plan;
+
+/* Test instrumentation, no device needed: the plan the fused launcher makes for `facts` — the launcher calls this very
+ * function.  RT_EINVAL: a NULL pointer, count 0, glog2 above 6, seg_cap below n. */
+int rt_debug_plan_samples(const rt_sample_facts *facts, rt_sample_plan *plan_out);
+
+/* Test instrumentation: the facts and the plan of the context's last fused launch (its last slot range).  RT_EINVAL before
+ * the first one. */
+int rt_debug_last_sample_plan(rt_context *ctx, rt_sample_facts *facts_out, rt_sample_plan *plan_out);
+
 /* Test instrumentation: resident workgroups per compute unit the runtime reports for the headline sample-queue kernel
  * (one wave per workgroup) at `lds_bytes` of dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor; no kernel runs). */
 int rt_debug_queue_occupancy(rt_context *ctx, uint32_t lds_bytes, int *blocks_out);

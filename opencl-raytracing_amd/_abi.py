@@ -214,6 +214,37 @@ def sample_grid_prototypes(lib):
     lib.rt_debug_stage_block.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(u32)]
     lib.rt_debug_queue_pixels.argtypes = [u32, u32, u32, u32, C.POINTER(u32)]
     lib.rt_debug_queue_occupancy.argtypes = [C.c_void_p, u32, C.POINTER(C.c_int)]
+    lib.rt_debug_plan_samples.argtypes = [C.POINTER(SampleFacts), C.POINTER(SamplePlan)]
+    lib.rt_debug_last_sample_plan.argtypes = [C.c_void_p, C.POINTER(SampleFacts), C.POINTER(SamplePlan)]
+
+
+class _U32Record(C.Structure):
+    """A C struct of uint32_t fields only, made from and turned into a dict."""
+
+    def __init__(self, **kw):
+        super().__init__(**{k: int(v) for k, v in kw.items()})
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SampleFacts(_U32Record):
+    """rt_sample_facts: what the fused launcher's choice of sample kernel reads"""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "count", "glog2", "n", "seg_cap", "material_count", "sphere_count", "plane_count", "lens_count", "model_count",
+        "sphere_bvh", "mesh_bvh", "walk_jobs", "faces", "cu_count", "count_enabled", "sample_queue", "walk_slices",
+        "wave_fill", "moments", "exact", "count_light", "count_heavy")]
+
+
+PLAN_FIXED, PLAN_QUEUE, PLAN_WALK = 0, 1, 2   # rt_sample_plan.family
+PLAN_GENERIC_COUNT = 0xFFFFFFFF               # rt_sample_plan.count_log2 of COUNT_LOG2 = -1
+
+
+class SamplePlan(_U32Record):
+    """rt_sample_plan: the sample kernel's instantiation and launch geometry"""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "family", "count", "accel", "geom", "waves", "moments", "count_log2", "multi", "pixels_per_wave", "lds_face_f4",
+        "lds_bytes", "grid_units", "block_size")]
 
 
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)

@@ -1625,35 +1625,30 @@ __global__ __launch_bounds__(64) void pt_debug_queue_sums(const float *__restric
 }
 
 // ================================== launchers ==================================
-
-#define PT_DISPATCH(count_on, accel_on, CALL)                           \
-    do {                                                                \
-        if (count_on) { if (accel_on) CALL(true, true); else CALL(true, false); }   \
-        else { if (accel_on) CALL(false, true); else CALL(false, false); }          \
-    } while (0)
-
-// Direct path (every sample from the camera): trace / retrace compat modes, and the
-// fused mode when prefix sharing is switched off.
-static void apply_mask(FrameParams &fp, const BlockMask *mask) {
-    if (!mask) return;
-    fp.block_active = mask->active;
-    fp.blk_w_log2 = mask->w_log2;
-    fp.blk_h_log2 = mask->h_log2;
-    fp.blocks_x = mask->blocks_x;
+// All instantiations of a kernel template share a signature: a launch picks its instantiation from an explicit table (the
+// tables together ARE the kernels of a policy's code object — an entry more is a kernel more) and goes through the pointer.
+using RenderKernel = void (*)(DeviceScene, FrameParams, float4 *, float4 *, unsigned long long *);
+static_assert(MODE_ACCUM == 0 && MODE_TRACE == 1 && MODE_RETRACE == 2, "render_kernel's table is indexed by the mode");
+static RenderKernel render_kernel(int mode, bool count, bool accel) {   // [MODE][COUNT][ACCEL]
+    static const RenderKernel k[3][2][2] = {
+        {{pt_render<MODE_ACCUM, false, false>, pt_render<MODE_ACCUM, false, true>}, {pt_render<MODE_ACCUM, true, false>, pt_render<MODE_ACCUM, true, true>}},
+        {{pt_render<MODE_TRACE, false, false>, pt_render<MODE_TRACE, false, true>}, {pt_render<MODE_TRACE, true, false>, pt_render<MODE_TRACE, true, true>}},
+        {{pt_render<MODE_RETRACE, false, false>, pt_render<MODE_RETRACE, false, true>}, {pt_render<MODE_RETRACE, true, false>, pt_render<MODE_RETRACE, true, true>}}};
+    return k[mode][count][accel];
 }
-
-template <int MODE>
-int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+// Direct path (every sample from the camera): trace / retrace compat modes, and the fused mode when prefix sharing is switched off.
+int launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
                   const BlockMask *mask, float *m2) {
+    if (mode < MODE_ACCUM || mode > MODE_RETRACE) return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
-    fp.m2 = MODE == MODE_ACCUM ? m2 : nullptr;
+    fp.m2 = mode == MODE_ACCUM ? m2 : nullptr;
     DeviceScene sc = device_scene(ctx);
     uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
     // split very long launches into slot ranges (keeps single kernels short on huge scenes)
-    uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
-    if (slots_per_launch == 0) slots_per_launch = 1;
+    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
+    const RenderKernel kernel = render_kernel(mode, ctx->count_enabled, scene_has_accel(sc));
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
     HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // no first stage on the direct path
@@ -1661,11 +1656,7 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
         fp.slot_begin = b;
         fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
         uint64_t threads = (uint64_t)(fp.slot_end - fp.slot_begin) << glog2;
-        dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-#define PT_CALL(C, A) \
-    hipLaunchKernelGGL((pt_render<MODE, C, A>), grid, block, 0, ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p)
-        PT_DISPATCH(ctx->count_enabled, scene_has_accel(sc), PT_CALL);
-#undef PT_CALL
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p);
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
@@ -1673,77 +1664,204 @@ int launch_render(rt_context *ctx, const float cam[12], uint32_t first, uint32_t
     return RT_OK;
 }
 
-// Fused path: pt_prefix (one work-item per pixel) + pt_samples (g lanes per live pixel).  While camera and scene rest
-// the first stage is pt_final_replay over what the last pt_prefix left (rt_context::PrefixCache).
+// ---- the fused path's sample stage: facts (sample_facts, rt_context.hpp) → plan → launch --------------------------------
+// plan_samples is THE place that decides which sample kernel a slot range of a fused call runs, with how many pixels per
+// wave, how much LDS and how many workgroups: a pure function of the facts (no HIP call, no context), so the table can be
+// pinned without a device (rt_debug_plan_samples, tests/test_sample_plan_host.py).
+using SampleFacts = rt_sample_facts;
+using SamplePlan = rt_sample_plan;
+static SamplePlan plan_samples(const SampleFacts &f) {
+    SamplePlan p = {};
+    const bool queue = f.sample_queue && f.count <= QUEUE_SLOTS;
+    const bool accel = f.sphere_bvh || f.mesh_bvh;
+    const bool simple_geom = f.lens_count == 0 && f.model_count == 0;   // spheres and planes only
+    const bool sphere_bvh_only = f.sphere_bvh && !f.mesh_bvh;
+    const uint32_t q_waves = !accel ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
+    // sample queue: a wave owns ppw live pixels (<= QUEUE_SLOTS samples); its LDS is the static prefix (tables, then faces), then the queue
+    uint32_t static_f4 = lds_static_used(f.material_count, f.sphere_count, f.plane_count);
+    // Small launches (small frames, a rank's share of a sharded frame): fewer pixels per wave, so that there are about
+    // PT_UNITS_PER_WAVE_SLOT waves per wave slot of the chip — a wave works through its pixels' samples one batch of
+    // 64 after the other, and 4 200 waves of 384 samples leave a third of the slots empty for the whole launch.
+    // C2 at 64 spp, 6 pixels per wave vs this rule: 200 x 126 0.314 → 0.140 ms, 320 x 180 0.336 → 0.187, 480 x 270
+    // 0.344 → 0.268, 640 x 360 0.419 → 0.369, 960 x 540 0.619 → 0.59; 1080p and up unchanged (6).
+    const uint32_t want_units = (f.cu_count ? f.cu_count : 256u) * 4u * 6u * PT_UNITS_PER_WAVE_SLOT;
+    const uint32_t ppw_full = (64u + f.count - 1u) / f.count;   // (never fewer than the 64 samples that fill a wave's lanes once)
+    const uint32_t ppw_par = !f.wave_fill ? QUEUE_MAX_PIXELS : std::max(f.n / want_units, ppw_full);
+    uint32_t ppw = std::min(queue_pixels_per_wave(f.count, q_waves, static_f4), ppw_par);
+    // Face records in LDS for hit_models' candidate loop: scenes whose meshes are all face-scanned (no mesh BVH) and
+    // hold at most PT_LDS_FACE_CAP faces together, and only when the copy fits into what the 1 KiB allocation granule
+    // leaves over anyway (C3: 576 bytes of a cube into 609 spare ones) — never at the price of a pixel per wave.
+    if (PT_FACE_MASK && !simple_geom && !f.mesh_bvh && !f.count_enabled && f.faces > 0 && f.faces <= PT_LDS_FACE_CAP &&
+        queue_pixels_per_wave(f.count, q_waves, static_f4 + 3u * f.faces) >= ppw) {
+        p.lds_face_f4 = 3u * f.faces;
+        static_f4 += p.lds_face_f4;
+    }
+    p.count = f.count_enabled;
+    p.accel = accel;
+    p.moments = f.moments;
+    p.block_size = 64u;
+    if (queue && f.mesh_bvh && f.walk_jobs && f.walk_slices && !f.count_enabled) {   // every mesh has a BVH: walk slices, sized for their own occupancy
+        p.family = RT_PLAN_WALK;
+        p.multi = f.walk_jobs != 1u;
+        p.waves = p.multi ? PT_W_WAVES_MULTI : PT_W_WAVES;
+        ppw = std::min(queue_pixels_per_wave(f.count, p.waves, static_f4), ppw_par);
+    } else if (queue) {
+        p.family = RT_PLAN_QUEUE;
+        p.geom = !accel || sphere_bvh_only ? (simple_geom ? 0u : 1u) : 2u;
+        p.waves = q_waves;
+        // (the count-specialised instantiation: exactly 64 samples on 64 lanes per pixel, no counters, no BVH, no moments)
+        const bool count64 = PT_Q_COUNT64 && !accel && !p.count && !p.moments && f.count == 64u && f.glog2 == 6u;
+        p.count_log2 = count64 ? 6u : RT_PLAN_GENERIC_COUNT;
+    } else {
+        p.family = RT_PLAN_FIXED;
+        p.block_size = 256u;
+        ppw = 1u;   // a unit of the live list is one pixel: 2^glog2 lanes
+    }
+    p.pixels_per_wave = ppw;
+    // the units of the live list (its two parts each end in a partial chunk: one unit more than capacity / chunk) — unless the host knows
+    // the list's counts: then exactly the units that own a pixel (rt_sample_units restates live_take), and no launch where there is none
+    uint32_t units = (f.seg_cap + ppw - 1u) / ppw + 1u;
+    if (f.exact) (void)rt_sample_units(f.seg_cap, ppw, f.count_light, f.count_heavy, &units);
+    p.grid_units = p.family == RT_PLAN_FIXED ? (uint32_t)((((uint64_t)units << f.glog2) + 255u) / 256u) : units;
+    if (p.family != RT_PLAN_FIXED) p.lds_bytes = static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(ppw, f.count);
+    return p;
+}
+
+using FixedKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *);
+static FixedKernel fixed_kernel(const SamplePlan &p) {   // [COUNT][ACCEL]
+    static const FixedKernel k[2][2] = {{pt_samples<false, false>, pt_samples<false, true>}, {pt_samples<true, false>, pt_samples<true, true>}};
+    return k[p.count != 0u][p.accel != 0u];
+}
+using QueueKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *, uint32_t);
+static QueueKernel queue_kernel(const SamplePlan &p) {   // NULL: no such instantiation (plan_samples never asks for one)
+    struct Row { uint32_t accel, geom, waves; QueueKernel k[2][2]; };   // [COUNT][MOMENTS]
+    static const Row rows[] = {
+        {0u, 0u, PT_Q_WAVES, {{pt_samples_q<false, false, 0, PT_Q_WAVES, false>, pt_samples_q<false, false, 0, PT_Q_WAVES, true>},
+          {pt_samples_q<true, false, 0, PT_Q_WAVES, false>, pt_samples_q<true, false, 0, PT_Q_WAVES, true>}}},
+        {0u, 1u, PT_Q_WAVES, {{pt_samples_q<false, false, 1, PT_Q_WAVES, false>, pt_samples_q<false, false, 1, PT_Q_WAVES, true>},
+          {pt_samples_q<true, false, 1, PT_Q_WAVES, false>, pt_samples_q<true, false, 1, PT_Q_WAVES, true>}}},
+        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, {{pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false>, pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, true>},
+          {pt_samples_q<true, true, 0, PT_Q_WAVES_SPHERE_BVH, false>, pt_samples_q<true, true, 0, PT_Q_WAVES_SPHERE_BVH, true>}}},
+        {1u, 1u, PT_Q_WAVES_ACCEL, {{pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false>, pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, true>},
+          {pt_samples_q<true, true, 1, PT_Q_WAVES_ACCEL, false>, pt_samples_q<true, true, 1, PT_Q_WAVES_ACCEL, true>}}},
+        {1u, 2u, PT_Q_WAVES_ACCEL, {{pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false>, pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, true>},
+          {pt_samples_q<true, true, 2, PT_Q_WAVES_ACCEL, false>, pt_samples_q<true, true, 2, PT_Q_WAVES_ACCEL, true>}}}};
+#if PT_Q_COUNT64
+    static const QueueKernel k64[2] = {pt_samples_q<false, false, 0, PT_Q_WAVES, false, 6>, pt_samples_q<false, false, 1, PT_Q_WAVES, false, 6>};   // [GEOM]
+    if (p.count_log2 == 6u) return !p.count && !p.accel && !p.moments && p.geom < 2u && p.waves == PT_Q_WAVES ? k64[p.geom] : nullptr;
+#endif
+    if (p.count_log2 != RT_PLAN_GENERIC_COUNT) return nullptr;
+    for (const Row &r : rows)
+        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k[p.count != 0u][p.moments != 0u];
+    return nullptr;
+}
+#ifdef PT_WSTAT   // (the diagnostic build's kernels take their statistics block as one argument more)
+using WalkKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, uint32_t, const uint2 *, uint32_t, unsigned long long *);
+#else
+using WalkKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, uint32_t, const uint2 *, uint32_t);
+#endif
+static WalkKernel walk_kernel(const SamplePlan &p) {   // [MULTI][MOMENTS]
+    static const WalkKernel k[2][2] = {{pt_samples_w<false, false>, pt_samples_w<false, true>}, {pt_samples_w<true, false>, pt_samples_w<true, true>}};
+    return k[p.multi != 0u][p.moments != 0u];
+}
+
+// the sample kernel over the live list, as planned; an empty grid launches nothing
+static int launch_plan(rt_context *ctx, const SamplePlan &p, const DeviceScene &sc, const FrameParams &fp, float4 *accum, uint32_t *live_count) {
+    if (p.grid_units == 0u) return RT_OK;
+    const rt_context::Slots &ss = ctx->slots;
+    const dim3 grid(p.grid_units), block(p.block_size);
+    if (p.family == RT_PLAN_WALK) {
+#ifdef PT_WSTAT
+        hipLaunchKernelGGL(walk_kernel(p), grid, block, p.lds_bytes, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum,
+                           p.pixels_per_wave, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n, ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8);
+#else
+        hipLaunchKernelGGL(walk_kernel(p), grid, block, p.lds_bytes, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum,
+                           p.pixels_per_wave, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n);
+#endif
+    } else if (p.family == RT_PLAN_QUEUE) {
+        const QueueKernel kernel = queue_kernel(p);
+        if (!kernel) return fail(ctx, RT_ESTATE, "no pt_samples_q instantiation for the plan");
+        hipLaunchKernelGGL(kernel, grid, block, p.lds_bytes, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum,
+                           ctx->counters.p, p.pixels_per_wave);
+    } else hipLaunchKernelGGL(fixed_kernel(p), grid, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
+    return RT_OK;
+}
+
+// ---- the fused path's first stage and what is kept of it ----------------------------------------------------------------
+using PrefixKernel = void (*)(DeviceScene, FrameParams, PixelRec *, uint32_t *, uint32_t *, float4 *, unsigned long long *, FinalPix *, uint32_t *);
+static PrefixKernel prefix_kernel(bool count, bool accel, bool trees) {
+    static const PrefixKernel plain[2][2] = {{pt_prefix<false, false>, pt_prefix<false, true>}, {pt_prefix<true, false>, pt_prefix<true, true>}};   // [COUNT][ACCEL]
+    static const PrefixKernel tree[2] = {pt_prefix<false, false, true>, pt_prefix<false, true, true>};   // [ACCEL] (never in counting builds)
+    return trees ? tree[accel] : plain[count][accel];
+}
+// A miss traces the prefix.  A hit adds the finished pixels' sums for this call's samples (everything else pt_prefix wrote lies
+// there still); a look-ahead launch replays the finished pixels into the ring instead, after a traced prefix and a kept one alike.
+static void launch_first_stage(rt_context *ctx, const DeviceScene &sc, const FrameParams &fp, bool hit, bool lookahead, float4 *accum, uint32_t *live_count) {
+    const rt_context::Slots &ss = ctx->slots;
+    const dim3 grid(fp.seg_cap / 256u), block(256);
+    if (!hit)
+        hipLaunchKernelGGL(prefix_kernel(ctx->count_enabled, scene_has_accel(sc), fp.tree_cap != 0u), grid, block, 0, ctx->stream, sc, fp,
+                           ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ss.finals.p, ss.final_n.p);
+    else if (!lookahead)
+        hipLaunchKernelGGL(pt_final_replay, grid, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p, accum);
+    if (lookahead) hipLaunchKernelGGL(pt_final_retrace, grid, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p);
+}
+
+// what a look-ahead launch needs: the sample queue, an unsharded frame in one slot range, no counters, no accumulator
+static bool lookahead_ok(const rt_context *ctx, const FrameParams &fp, const float4 *accum, const BlockMask *mask, const float *m2) {
+    return !accum && !m2 && !mask && !ctx->count_enabled && ctx->world == 1 && ctx->sample_queue && fp.count <= QUEUE_SLOTS &&
+           (ctx->max_threads_per_launch >> fp.group_log2) >= fp.slot_end;
+}
+
+// the staged scene block, for the sample kernels that copy it: (re)built when anything it holds may have changed
+static void refresh_stage_block(rt_context *ctx, const DeviceScene &sc) {
+    if (!PT_STAGE_COPY || ctx->stage_block.generation == ctx->prefix_cache.generation) return;
+    if (lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count))
+        hipLaunchKernelGGL(pt_stage_block, dim3(1), dim3(64), 0, ctx->stream, sc,
+                           reinterpret_cast<float4 *>(reinterpret_cast<char *>(ctx->materials.p) + stage_block_offset(sc.material_count)));
+    ctx->stage_block.generation = ctx->prefix_cache.generation;
+    ctx->stage_block.builds++;
+}
+
+// Fused path: pt_prefix (one work-item per pixel) + the planned sample kernel (g lanes per live pixel).  While camera and
+// scene rest the first stage is pt_final_replay over what the last pt_prefix left (rt_context::PrefixCache).
 // ring != NULL: a LOOK-AHEAD launch (rt_render_again, RT_OPT_LOOKAHEAD) — the same two stages over the same slot buffers and
 // the same prefix-cache entry, but the `count` samples become `count` frames of the ring (queue_replay, pt_final_retrace)
-// and the accumulator is not touched (accum is NULL).  The caller has checked what such a launch needs: no counters, an
-// unsharded context, the sample queue, the frame in one slot range, count <= the ring's frames.
+// and the accumulator is not touched (accum is NULL).
 static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
                             const BlockMask *mask, float4 *ring, float *m2) {
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
     fp.m2 = m2;   // (NULL for a look-ahead launch: the compat path keeps no moments)
     if (ring) {
-        if (accum || m2 || mask || ctx->count_enabled || ctx->world != 1 || !ctx->sample_queue || count > QUEUE_SLOTS ||
-            (ctx->max_threads_per_launch >> glog2) < fp.slot_end)
+        if (!lookahead_ok(ctx, fp, accum, mask, m2))
             return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
         fp.la_ring = ring;
         fp.la_image = ctx->image.p;
     }
-    DeviceScene sc = device_scene(ctx);
-    uint32_t slots = fp.slot_end;
+    const DeviceScene sc = device_scene(ctx);
+    const uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
     int rc = ensure_slots(ctx, slots);
     if (rc) return rc;
+    refresh_stage_block(ctx, sc);
     const rt_context::Slots &ss = ctx->slots;
-    // the staged scene block, for the sample kernels that copy it: (re)built when anything it holds may have changed
-    if (PT_STAGE_COPY && ctx->stage_block.generation != ctx->prefix_cache.generation) {
-        if (lds_static_used(sc.material_count, sc.sphere_count, sc.plane_count))
-            hipLaunchKernelGGL(pt_stage_block, dim3(1), dim3(64), 0, ctx->stream, sc,
-                               reinterpret_cast<float4 *>(reinterpret_cast<char *>(ctx->materials.p) + stage_block_offset(sc.material_count)));
-        ctx->stage_block.generation = ctx->prefix_cache.generation;
-        ctx->stage_block.builds++;
-    }
     uint32_t *live_count = ss.live.p + ss.capacity + 256u;
-    uint32_t slots_per_launch = ctx->max_threads_per_launch >> glog2;
-    if (slots_per_launch == 0) slots_per_launch = 1;
-    // The prefix cache (rt_context::PrefixCache): may this launch's pt_prefix be kept, and is the last one's still good?
-    // Until the launch has gone through the entry is invalid, so an error on the way leaves it so.
-    rt_context::PrefixCache &pc = ctx->prefix_cache;
+    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
+    // may this launch's pt_prefix be kept, and is the last one's still good?
     const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
     const bool keepable = !mask && !ctx->count_enabled && slots_per_launch >= slots;
     uint32_t cam_bits[12];
     memcpy(cam_bits, cam, sizeof cam_bits);
-    const bool hit = pc.enabled && pc.valid && keepable && pc.key_generation == pc.generation && pc.key_tree_on == tree_on &&
-                     memcmp(pc.key_cam, cam_bits, sizeof cam_bits) == 0;
-    pc.valid = false;
-    // The entry's live counters on the host (rt_context::PrefixCache, RT_OPT_EXACT_GRID): dropped with the entry by every
-    // launch that does not hit; learnt by an asynchronous copy that the FIRST hit enqueues and later hits only ask after.
+    const bool hit = prefix_lookup(ctx->prefix_cache, keepable, tree_on, cam_bits);   // (a hit is one slot range)
+    bool exact = false;
+    if ((rc = learn_live_counts(ctx, hit, live_count, &exact)) != RT_OK) return rc;
     rt_context::SampleGrid &sg = ctx->sample_grid;
-    if (!hit) pc.counts_state = rt_context::PrefixCache::COUNTS_UNKNOWN;
-    else if (sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_UNKNOWN) {
-        HIP_TRY(ctx, hipMemcpyAsync(sg.h_counts, live_count, LIVE_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(sg.counts_ev, ctx->stream));
-        pc.counts_state = rt_context::PrefixCache::COUNTS_IN_FLIGHT;
-    } else if (sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_IN_FLIGHT) {
-        const hipError_t q = hipEventQuery(sg.counts_ev);
-        if (q == hipSuccess) {
-            pc.count_light = sg.h_counts[0];
-            pc.count_heavy = sg.h_counts[LIVE_HEAVY_COUNTER];
-            pc.counts_state = rt_context::PrefixCache::COUNTS_KNOWN;
-        } else {
-            (void)hipGetLastError();   // (not ready is no error of this launch)
-            if (q != hipErrorNotReady) return fail(ctx, RT_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
-        }
-    }
-    const bool exact = hit && sg.exact && pc.counts_state == rt_context::PrefixCache::COUNTS_KNOWN;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
     for (uint32_t b = 0; b < slots; b += slots_per_launch) {
         fp.slot_begin = b;
         fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
-        uint32_t n = fp.slot_end - fp.slot_begin;
         if (!hit) HIP_TRY(ctx, hipMemsetAsync(live_count, 0, LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
         fp.trees = ss.trees.p;
@@ -1753,133 +1871,29 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         // that would share them — C2 at 1 / 8 / 16 / 32 samples per call: 0.321 / 0.457 / 0.609 / 1.031 ms with trees,
         // 0.243 / 0.393 / 0.582 / 1.088 without)
         fp.tree_cap = (tree_on && !ctx->count_enabled) ? (uint32_t)ss.tree_capacity : 0u;   // (0 without the tree buffers)
-        // the live list holds whole workgroups of pt_prefix
-        const uint32_t prefix_blocks = (n + 255) / 256;
-        fp.seg_cap = prefix_blocks * 256u;
-        dim3 block(256), grid1(prefix_blocks);
-        // sample queue: a wave owns ppw live pixels (<= QUEUE_SLOTS samples); worst case all n pixels are live
-        fp.lds_face_f4 = 0u;
-        uint32_t static_f4 = queue_static_f4(sc, 0u);
-        const bool sphere_bvh_only = sc.bvh_node_count != 0 && sc.mesh_bvh_root == nullptr;
-        const bool simple_geom = sc.lens_count == 0 && sc.model_count == 0;   // spheres and planes only
-        const uint32_t q_waves = !scene_has_accel(sc) ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
-        uint32_t ppw = queue_pixels_per_wave(count, q_waves, static_f4);
-        // Small launches (small frames, a rank's share of a sharded frame): fewer pixels per wave, so that there are about
-        // PT_UNITS_PER_WAVE_SLOT waves per wave slot of the chip — a wave works through its pixels' samples one batch of
-        // 64 after the other, and 4 200 waves of 384 samples leave a third of the slots empty for the whole launch.
-        // C2 at 64 spp, 6 pixels per wave vs this rule: 200 x 126 0.314 → 0.140 ms, 320 x 180 0.336 → 0.187, 480 x 270
-        // 0.344 → 0.268, 640 x 360 0.419 → 0.369, 960 x 540 0.619 → 0.59; 1080p and up unchanged (6).
-        const uint32_t want_units = (uint32_t)(ctx->cu_count > 0 ? ctx->cu_count : 256) * 4u * 6u * PT_UNITS_PER_WAVE_SLOT;
-        // (never fewer than the 64 samples that fill a wave's lanes once)
-        const uint32_t ppw_full = (64u + count - 1u) / count;
-        const uint32_t ppw_par = !ctx->wave_fill ? QUEUE_MAX_PIXELS : std::max(n / want_units, ppw_full);
-        if (ppw > ppw_par) ppw = ppw_par;
-        // Face records in LDS for hit_models' candidate loop: scenes whose meshes are all face-scanned (no mesh BVH) and
-        // hold at most PT_LDS_FACE_CAP faces together, and only when the copy fits into what the 1 KiB allocation granule
-        // leaves over anyway (C3: 576 bytes of a cube into 609 spare ones) — never at the price of a pixel per wave.
-        if (PT_FACE_MASK && !simple_geom && sc.mesh_bvh_root == nullptr && !ctx->count_enabled) {
-            const size_t nf = ctx->h_faces.size() / 3u - (ctx->h_faces.empty() ? 0u : 1u);   // (the array ends with one dummy record)
-            if (nf > 0 && nf <= PT_LDS_FACE_CAP &&
-                queue_pixels_per_wave(count, q_waves, static_f4 + 3u * (uint32_t)nf) >= ppw) {
-                fp.lds_face_f4 = 3u * (uint32_t)nf;
-                static_f4 = queue_static_f4(sc, fp.lds_face_f4);
-            }
-        }
-        bool queue = ctx->sample_queue && count <= QUEUE_SLOTS;
-        // (dynamic LDS of a queue kernel's one-wave workgroup: the static prefix, then the wave's queue)
-        auto queue_lds = [&](uint32_t pixels_per_wave) { return static_f4 * sizeof(float4) + (size_t)queue_wave_lds_bytes(pixels_per_wave, count); };
-#define PT_LAUNCH_PREFIX(K) \
-    hipLaunchKernelGGL(K, grid1, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ss.finals.p, ss.final_n.p)
-#define PT_CALL_PREFIX(C, A) PT_LAUNCH_PREFIX((pt_prefix<C, A>))
-        bool accel_on = scene_has_accel(sc);
-        // (a hit: the finished pixels' sums for this call's samples; everything else pt_prefix wrote lies there still)
-        if (hit && !ring) hipLaunchKernelGGL(pt_final_replay, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p, accum);
-        else if (hit) {}   // (a look-ahead launch: pt_final_retrace below, after a traced prefix and a kept one alike)
-        else if (fp.tree_cap) PT_LAUNCH_PREFIX((accel_on ? pt_prefix<false, true, true> : pt_prefix<false, false, true>));   // (never in counting builds)
-        else PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_PREFIX);
-#undef PT_CALL_PREFIX
-#undef PT_LAUNCH_PREFIX
-        if (ring) hipLaunchKernelGGL(pt_final_retrace, grid1, block, 0, ctx->stream, fp, ss.finals.p, ss.final_n.p);
+        // the live list holds whole workgroups of pt_prefix; worst case all n pixels are live
+        fp.seg_cap = (fp.slot_end - fp.slot_begin + 255u) / 256u * 256u;
+        const SampleFacts facts = sample_facts(ctx, sc, fp, exact);
+        const SamplePlan plan = plan_samples(facts);
+        fp.lds_face_f4 = plan.lds_face_f4;
+        launch_first_stage(ctx, sc, fp, hit, ring != nullptr, accum, live_count);
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
-        // the sample kernel over the live list
-        // (the two parts of the list each end in a partial chunk: one unit more than capacity / chunk)
-        // — unless the host knows the entry's counts (a hit is one slot range): then exactly the units that own a pixel
-        // (rt_sample_units, the host's restatement of live_take), and no launch at all where there is none
-        uint32_t launched = 0;
-        auto units = [&](uint32_t per_unit) {
-            uint32_t u = (fp.seg_cap + per_unit - 1) / per_unit + 1u;
-            sg.last_cap = fp.seg_cap;
-            sg.last_per_unit = per_unit;
-            if (exact) (void)rt_sample_units(fp.seg_cap, per_unit, pc.count_light, pc.count_heavy, &u);
-            return u;
-        };
-        // (the launch statement runs only for a grid that is not empty; `launched` is what rt_sample_grid_stats reports)
-#define PT_GRID(U, LAUNCH) do { launched = (U); if (launched) { LAUNCH; } } while (0)
-#define PT_CALL_QUEUE_M(C, A, G, W, M) \
-    PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<C, A, G, W, M>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw))
-    // (the count-specialised instantiation: exactly 64 samples on 64 lanes per pixel, no counters, no BVH, no moments)
-    const bool count64 = PT_Q_COUNT64 && count == 64u && fp.group_log2 == 6u;
-    (void)count64;
-#define PT_CALL_QUEUE_64(G, W) \
-    do { PT_GRID(units(ppw), hipLaunchKernelGGL((pt_samples_q<false, false, G, W, false, 6>), dim3(launched), dim3(64), queue_lds(ppw), ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p, ppw)); if (launched) sg.count64_launches++; } while (0)
-#define PT_CALL_QUEUE_W(C, A, G, W) do { if (fp.m2) PT_CALL_QUEUE_M(C, A, G, W, true); else PT_CALL_QUEUE_M(C, A, G, W, false); } while (0)
-#if PT_Q_COUNT64
-#define PT_CALL_QUEUE_N(C, G) do { if (!(C) && count64 && !fp.m2) PT_CALL_QUEUE_64(G, PT_Q_WAVES); else PT_CALL_QUEUE_W(C, false, G, PT_Q_WAVES); } while (0)
-#else
-#define PT_CALL_QUEUE_N(C, G) PT_CALL_QUEUE_W(C, false, G, PT_Q_WAVES)
-#endif
-#define PT_CALL_QUEUE(C, A)                                                                       \
-    do {                                                                                          \
-        if (!(A)) { if (simple_geom) PT_CALL_QUEUE_N(C, 0); else PT_CALL_QUEUE_N(C, 1); } \
-        else if (sphere_bvh_only) { if (simple_geom) PT_CALL_QUEUE_W(C, true, 0, PT_Q_WAVES_SPHERE_BVH); else PT_CALL_QUEUE_W(C, true, 1, PT_Q_WAVES_ACCEL); } \
-        else PT_CALL_QUEUE_W(C, true, 2, PT_Q_WAVES_ACCEL);                                       \
-    } while (0)
-#define PT_CALL_FIXED(C, A) \
-    PT_GRID(grid2.x, hipLaunchKernelGGL((pt_samples<C, A>), grid2, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p))
-        if (queue && sc.mesh_bvh_root && ctx->walk_jobs.n && ctx->walk_slices && !ctx->count_enabled) {
-            // every mesh has a BVH: interleaved walk slices (pt_samples_w), sized for its own occupancy target
-            const bool multi = ctx->walk_jobs.n != 1;
-            uint32_t ppw_w = queue_pixels_per_wave(count, multi ? PT_W_WAVES_MULTI : PT_W_WAVES, static_f4);
-            if (ppw_w > ppw_par) ppw_w = ppw_par;
-            launched = units(ppw_w);
-            if (launched)
-            hipLaunchKernelGGL(fp.m2 ? (multi ? pt_samples_w<true, true> : pt_samples_w<false, true>) : (multi ? pt_samples_w<true> : pt_samples_w<false>), dim3(launched), dim3(64), queue_lds(ppw_w), ctx->stream,
-                               sc, fp, ss.recs.p, ss.live.p, live_count, accum, ppw_w, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n
-#ifdef PT_WSTAT
-                               , ctx->counters.p + COUNTER_REPLICAS * COUNTER_STRIDE + 8
-#endif
-                               );
-        } else if (queue) PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_QUEUE);
-        else {
-            dim3 grid2((unsigned)((((uint64_t)units(1u) << glog2) + 255) / 256));
-            PT_DISPATCH(ctx->count_enabled, accel_on, PT_CALL_FIXED);
-        }
-#undef PT_CALL_QUEUE
-#undef PT_CALL_QUEUE_W
-#undef PT_CALL_QUEUE_N
-#undef PT_CALL_QUEUE_64
-#undef PT_CALL_QUEUE_M
-#undef PT_CALL_FIXED
-#undef PT_GRID
+        if ((rc = launch_plan(ctx, plan, sc, fp, accum, live_count)) != RT_OK) return rc;
+        sg.last_facts = facts, sg.last_plan = plan;
         sg.launches++;
-        sg.workgroups += launched;
-        if (exact) { sg.exact_launches++; sg.live_last = launched; }
+        sg.workgroups += plan.grid_units;   // (what rt_sample_grid_stats reports)
+        if (plan.grid_units && plan.family == RT_PLAN_QUEUE && plan.count_log2 == 6u) sg.count64_launches++;
+        if (exact) { sg.exact_launches++; sg.live_last = plan.grid_units; }
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
     ctx->ev_count++;
-    if (hit) pc.hits++; else pc.misses++;   // (launches that went through)
-    if (keepable) {   // the slot buffers hold this camera's whole prefix
-        pc.valid = true;
-        pc.key_generation = pc.generation;
-        pc.key_tree_on = tree_on;
-        memcpy(pc.key_cam, cam_bits, sizeof cam_bits);
-    }
+    if (hit) ctx->prefix_cache.hits++; else ctx->prefix_cache.misses++;   // (launches that went through)
+    if (keepable) prefix_keep(ctx->prefix_cache, tree_on, cam_bits);
     return RT_OK;
 }
 
-int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                 const BlockMask *mask, float *m2) {
+int launch_fused(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum, const BlockMask *mask, float *m2) {
     return launch_fused_any(ctx, cam, first, count, glog2, accum, mask, nullptr, m2);
 }
 
@@ -1929,22 +1943,10 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
 
 namespace {
 
-int ks_launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
-                     float4 *accum, const BlockMask *mask, float *m2) {
-    switch (mode) {
-        case MODE_ACCUM: return launch_render<MODE_ACCUM>(ctx, cam, first, count, glog2, accum, mask, m2);
-        case MODE_TRACE: return launch_render<MODE_TRACE>(ctx, cam, first, count, glog2, accum, mask, m2);
-        case MODE_RETRACE: return launch_render<MODE_RETRACE>(ctx, cam, first, count, glog2, accum, mask, m2);
-        default: return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
-    }
-}
-
 int ks_launch_probe(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
-    if (scene_has_accel(sc))
-        hipLaunchKernelGGL(pt_probe<true>, grid, block, 0, ctx->stream, sc, fp, d_in, d_in + n, d_in + 2 * (size_t)n, n, d_out);
-    else
-        hipLaunchKernelGGL(pt_probe<false>, grid, block, 0, ctx->stream, sc, fp, d_in, d_in + n, d_in + 2 * (size_t)n, n, d_out);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_probe<true> : pt_probe<false>, grid, block, 0, ctx->stream, sc, fp, d_in, d_in + n,
+                       d_in + 2 * (size_t)n, n, d_out);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1954,8 +1956,7 @@ int ks_launch_features(rt_context *ctx, const FrameParams &fp, const DeviceScene
     const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
     dim3 grid((n + 255u) / 256u), block(256);
     float4 *o = reinterpret_cast<float4 *>(d_out);
-    if (scene_has_accel(sc)) hipLaunchKernelGGL(pt_features<true>, grid, block, 0, ctx->stream, sc, fp, o);
-    else hipLaunchKernelGGL(pt_features<false>, grid, block, 0, ctx->stream, sc, fp, o);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features<true> : pt_features<false>, grid, block, 0, ctx->stream, sc, fp, o);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1965,8 +1966,8 @@ int ks_launch_features_chain(rt_context *ctx, const FrameParams &fp, const Devic
     const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
     dim3 grid((n + 255u) / 256u), block(256);
     float4 *o = reinterpret_cast<float4 *>(d_out);
-    if (scene_has_accel(sc)) hipLaunchKernelGGL(pt_features_chain<true>, grid, block, 0, ctx->stream, sc, fp, follow, max_chain, o);
-    else hipLaunchKernelGGL(pt_features_chain<false>, grid, block, 0, ctx->stream, sc, fp, follow, max_chain, o);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features_chain<true> : pt_features_chain<false>, grid, block, 0, ctx->stream, sc, fp,
+                       follow, max_chain, o);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1974,10 +1975,8 @@ int ks_launch_features_chain(rt_context *ctx, const FrameParams &fp, const Devic
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
-    if (scene_has_accel(sc))
-        hipLaunchKernelGGL(pt_debug_hit<true>, grid, block, 0, ctx->stream, sc, kind, d_rays, d_prim, d_face, n, d_out);
-    else
-        hipLaunchKernelGGL(pt_debug_hit<false>, grid, block, 0, ctx->stream, sc, kind, d_rays, d_prim, d_face, n, d_out);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_debug_hit<true> : pt_debug_hit<false>, grid, block, 0, ctx->stream, sc, kind, d_rays,
+                       d_prim, d_face, n, d_out);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -2036,9 +2035,9 @@ const pt::KernelSet g_kernel_set = {
 #else
     "rocm-opencl",
 #endif
-    ks_launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
+    launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
-    ks_queue_pixels, ks_queue_occupancy};
+    ks_queue_pixels, ks_queue_occupancy, plan_samples};
 
 }  // namespace
 

@@ -14,7 +14,8 @@ struct KernelSet {
     // moments kept beside `accum` (MODE_ACCUM only; NULL = none, FrameParams::m2)
     int (*launch_render)(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
                          float4 *accum, const BlockMask *mask, float *m2);
-    // fused path: pt_prefix + pt_samples_q / pt_samples_w / pt_samples, adding to `accum` (and updating `m2`, as above)
+    // fused path: pt_prefix + the sample kernel plan_samples chooses (pt_samples_q / pt_samples_w / pt_samples), adding to
+    // `accum` (and updating `m2`, as above)
     int (*launch_fused)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2,
                         float4 *accum, const BlockMask *mask, float *m2);
     // look-ahead (rt_render_again, RT_OPT_LOOKAHEAD): the fused launch for samples first .. first+count-1, but instead of
@@ -47,6 +48,8 @@ struct KernelSet {
     uint32_t (*queue_pixels)(uint32_t count, uint32_t waves, uint32_t static_float4, uint32_t granule);
     // rt_debug_queue_occupancy: hipOccupancyMaxActiveBlocksPerMultiprocessor of pt_samples_q<false, false, 0, PT_Q_WAVES> at a dynamic LDS size
     int (*queue_occupancy)(rt_context *ctx, uint32_t lds_bytes, int *blocks);
+    // rt_debug_plan_samples: the fused launcher's choice of sample kernel and launch geometry — a pure function, no device
+    rt_sample_plan (*plan_samples)(const rt_sample_facts &facts);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

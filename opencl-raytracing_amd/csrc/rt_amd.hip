@@ -1824,15 +1824,29 @@ int rt_sample_grid_stats(rt_context *ctx, uint64_t *launches, uint64_t *exact, u
 int rt_debug_live_list(rt_context *ctx, uint32_t out[4]) {
     if (!ctx || !out) return RT_EINVAL;
     const rt_context::Slots &ss = ctx->slots;
-    if (!ss.live.p || ctx->sample_grid.last_per_unit == 0) return fail(ctx, RT_EINVAL, "no fused launch yet");
+    if (!ss.live.p || ctx->sample_grid.last_plan.pixels_per_wave == 0) return fail(ctx, RT_EINVAL, "no fused launch yet");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t h[LIVE_COUNT_STRIDE];
     HIP_TRY(ctx, hipMemcpyAsync(h, ss.live.p + ss.capacity + 256u, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    out[0] = ctx->sample_grid.last_cap;
-    out[1] = ctx->sample_grid.last_per_unit;
+    out[0] = ctx->sample_grid.last_facts.seg_cap;
+    out[1] = ctx->sample_grid.last_plan.pixels_per_wave;
     out[2] = h[0];
     out[3] = h[LIVE_HEAVY_COUNTER];
+    return RT_OK;
+}
+
+int rt_debug_plan_samples(const rt_sample_facts *facts, rt_sample_plan *plan_out) {
+    if (!facts || !plan_out || facts->count < 1u || facts->glog2 > 6u || facts->seg_cap < facts->n) return RT_EINVAL;
+    *plan_out = pt::kernel_set_a2()->plan_samples(*facts);   // (host code: the same in every policy)
+    return RT_OK;
+}
+
+int rt_debug_last_sample_plan(rt_context *ctx, rt_sample_facts *facts_out, rt_sample_plan *plan_out) {
+    if (!ctx || !facts_out || !plan_out) return RT_EINVAL;
+    if (ctx->sample_grid.last_plan.pixels_per_wave == 0) return fail(ctx, RT_EINVAL, "no fused launch yet");
+    *facts_out = ctx->sample_grid.last_facts;
+    *plan_out = ctx->sample_grid.last_plan;
     return RT_OK;
 }
 

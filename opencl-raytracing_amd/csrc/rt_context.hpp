@@ -195,8 +195,11 @@ struct rt_context {
         uint64_t exact_launches = 0;    // … sized by the known counts (a launch of zero workgroups included)
         uint64_t workgroups = 0;        // sample-kernel workgroups launched, all launches together
         uint64_t live_last = 0;         // workgroups of the last EXACT launch's kernel that own a pixel (= its grid)
-        uint32_t last_cap = 0, last_per_unit = 0;   // seg_cap and pixels per unit of the last launch (rt_debug_live_list)
-        uint64_t count64_launches = 0;  // sample-stage launches that took pt_samples_q<…, COUNT_LOG2 = 6> (rt_debug_wave_fixed)
+        // what the last launch's sample stage was chosen from and what was chosen (plan_samples, pt_kernels.hip);
+        // pixels_per_wave 0: no launch yet (rt_debug_last_sample_plan, rt_debug_live_list)
+        rt_sample_facts last_facts = {};
+        rt_sample_plan last_plan = {};
+        uint64_t count64_launches = 0;  // sample-stage launches whose plan was pt_samples_q<…, COUNT_LOG2 = 6> (rt_debug_wave_fixed)
     } sample_grid;
     // Look-ahead for rt_render_again (RT_OPT_LOOKAHEAD): while the camera rests, ONE fused launch traces the next `pending`
     // samples and replays the gamma-space running mean per pixel, the image after each sample going to a frame of `ring`;
@@ -389,6 +392,14 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     return fp;
 }
 
+inline void apply_mask(FrameParams &fp, const BlockMask *mask) {
+    if (!mask) return;
+    fp.block_active = mask->active;
+    fp.blk_w_log2 = mask->w_log2;
+    fp.blk_h_log2 = mask->h_log2;
+    fp.blocks_x = mask->blocks_x;
+}
+
 // kernels come in (COUNT, ACCEL) instantiations; scenes without any BVH run the ACCEL = false ones
 inline bool scene_has_accel(const DeviceScene &sc) { return sc.bvh_node_count != 0 || sc.mesh_bvh_root != nullptr; }
 
@@ -413,6 +424,80 @@ inline int ensure_slots(rt_context *ctx, size_t slots) {
         s.tree_wait.release();
     }
     s.capacity = slots;
+    return RT_OK;
+}
+
+// ---- steps of the fused launch that are the same under every policy (launch_fused_any, pt_kernels.hip) ------------------
+// What plan_samples reads, for the slot range fp holds.  exact: the host knows the live list's counters.
+inline rt_sample_facts sample_facts(const rt_context *ctx, const DeviceScene &sc, const FrameParams &fp, bool exact) {
+    rt_sample_facts f = {};
+    f.count = fp.count;
+    f.glog2 = fp.group_log2;
+    f.n = fp.slot_end - fp.slot_begin;
+    f.seg_cap = fp.seg_cap;
+    f.material_count = sc.material_count;
+    f.sphere_count = sc.sphere_count;
+    f.plane_count = sc.plane_count;
+    f.lens_count = sc.lens_count;
+    f.model_count = sc.model_count;
+    f.sphere_bvh = sc.bvh_node_count != 0;
+    f.mesh_bvh = sc.mesh_bvh_root != nullptr;
+    f.walk_jobs = (uint32_t)ctx->walk_jobs.n;
+    f.faces = ctx->h_faces.empty() ? 0u : (uint32_t)(ctx->h_faces.size() / 3u - 1u);   // (the array ends with one dummy record)
+    f.cu_count = ctx->cu_count > 0 ? (uint32_t)ctx->cu_count : 0u;
+    f.count_enabled = ctx->count_enabled;
+    f.sample_queue = ctx->sample_queue;
+    f.walk_slices = ctx->walk_slices;
+    f.wave_fill = ctx->wave_fill;
+    f.moments = fp.m2 != nullptr;   // (the launch keeps the sample moments)
+    f.exact = exact;
+    f.count_light = exact ? ctx->prefix_cache.count_light : 0u;
+    f.count_heavy = exact ? ctx->prefix_cache.count_heavy : 0u;
+    return f;
+}
+
+// The prefix cache (rt_context::PrefixCache): is the last launch's pt_prefix still good for this one?  Until the launch has
+// gone through (prefix_keep) the entry is invalid, so an error on the way leaves it so.
+inline bool prefix_lookup(rt_context::PrefixCache &pc, bool keepable, bool tree_on, const uint32_t cam_bits[12]) {
+    const bool hit = pc.enabled && pc.valid && keepable && pc.key_generation == pc.generation && pc.key_tree_on == tree_on &&
+                     memcmp(pc.key_cam, cam_bits, sizeof pc.key_cam) == 0;
+    pc.valid = false;
+    return hit;
+}
+
+// the slot buffers hold this camera's whole prefix
+inline void prefix_keep(rt_context::PrefixCache &pc, bool tree_on, const uint32_t cam_bits[12]) {
+    pc.valid = true;
+    pc.key_generation = pc.generation;
+    pc.key_tree_on = tree_on;
+    memcpy(pc.key_cam, cam_bits, sizeof pc.key_cam);
+}
+
+// The entry's live counters on the host (rt_context::PrefixCache, RT_OPT_EXACT_GRID): dropped with the entry by every
+// launch that does not hit; learnt by an asynchronous copy that the FIRST hit enqueues and later hits only ask after.
+// *exact: this launch may be sized by them.
+inline int learn_live_counts(rt_context *ctx, bool hit, const uint32_t *live_count, bool *exact) {
+    using PC = rt_context::PrefixCache;
+    PC &pc = ctx->prefix_cache;
+    rt_context::SampleGrid &sg = ctx->sample_grid;
+    *exact = false;
+    if (!hit) pc.counts_state = PC::COUNTS_UNKNOWN;
+    else if (sg.exact && pc.counts_state == PC::COUNTS_UNKNOWN) {
+        HIP_TRY(ctx, hipMemcpyAsync(sg.h_counts, live_count, LIVE_COUNT_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(sg.counts_ev, ctx->stream));
+        pc.counts_state = PC::COUNTS_IN_FLIGHT;
+    } else if (sg.exact && pc.counts_state == PC::COUNTS_IN_FLIGHT) {
+        const hipError_t q = hipEventQuery(sg.counts_ev);
+        if (q == hipSuccess) {
+            pc.count_light = sg.h_counts[0];
+            pc.count_heavy = sg.h_counts[LIVE_HEAVY_COUNTER];
+            pc.counts_state = PC::COUNTS_KNOWN;
+        } else {
+            (void)hipGetLastError();   // (not ready is no error of this launch)
+            if (q != hipErrorNotReady) return fail(ctx, RT_EHIP, "hipEventQuery: %s", hipGetErrorString(q));
+        }
+    }
+    *exact = hit && sg.exact && pc.counts_state == PC::COUNTS_KNOWN;
     return RT_OK;
 }
 

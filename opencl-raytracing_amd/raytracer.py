@@ -35,6 +35,7 @@ SYMBOLS = (
     "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy", "rt_debug_queue_sums",
+    "rt_debug_plan_samples", "rt_debug_last_sample_plan",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -234,6 +235,16 @@ def queue_pixels(count, waves_per_simd=6, static_float4=0, granule=0):
     if rc:
         raise RtError(rc, "rt_debug_queue_pixels: invalid argument")
     return int(n.value)
+
+
+def plan_samples(**facts):
+    """The sample-kernel launch the fused launcher plans for these facts (rt_debug_plan_samples: the launcher's own function;
+    host-only, no device needed): the fields of _abi.SampleFacts (those left out are 0) → the fields of _abi.SamplePlan."""
+    f, p = _abi.SampleFacts(**facts), _abi.SamplePlan()
+    rc = load_library().rt_debug_plan_samples(C.byref(f), C.byref(p))
+    if rc:
+        raise RtError(rc, "rt_debug_plan_samples: invalid argument")
+    return p.as_dict()
 
 
 class RayTracer:
@@ -639,6 +650,15 @@ class RayTracer:
         out = (C.c_uint64 * 2)()
         self._check(self._lib.rt_debug_wave_fixed(self._ctx, out))
         return tuple(int(v) for v in out)
+
+    planSamples = staticmethod(plan_samples)
+
+    def lastSamplePlan(self):
+        """(facts, plan) of the last fused launch's sample stage, as dicts of the fields of _abi.SampleFacts and
+        _abi.SamplePlan (rt_debug_last_sample_plan; test instrumentation)."""
+        f, p = _abi.SampleFacts(), _abi.SamplePlan()
+        self._check(self._lib.rt_debug_last_sample_plan(self._ctx, C.byref(f), C.byref(p)))
+        return f.as_dict(), p.as_dict()
 
     def queueOccupancy(self, lds_bytes):
         """Resident workgroups per compute unit the runtime reports for the headline sample-queue kernel at `lds_bytes` of

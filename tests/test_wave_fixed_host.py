@@ -23,10 +23,11 @@ def _define(text, name):
 
 def test_library_exports_the_debug_getters(built):
     lib = C.CDLL(rt.LIB_PATH)
-    for s in ("rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy"):
+    for s in ("rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy",
+              "rt_debug_plan_samples", "rt_debug_last_sample_plan"):
         assert hasattr(lib, s), s
         assert s in rt.raytracer.SYMBOLS
-    for m in ("waveFixedStats", "stageBlock", "queueOccupancy"):
+    for m in ("waveFixedStats", "stageBlock", "queueOccupancy", "planSamples", "lastSamplePlan"):
         assert callable(getattr(rt.RayTracer, m))
 
 
