@@ -88,3 +88,45 @@ float *Camera::transferData() const {
     }
     return data;
 }
+
+double Camera::radicalInverse(uint32_t base, uint32_t index) {
+    double f = 1.0, r = 0.0;
+    for (uint32_t i = index; i > 0; i /= base) {
+        f /= (double)base;
+        r += f * (double)(i % base);
+    }
+    return r;
+}
+
+std::vector<float> Camera::sampleBlocks(uint32_t n, uint32_t first_sample, int width, int height, bool pixel_jitter,
+                                        float aperture, float focus) const {
+    const bool dof = aperture != 0.0f;
+    const float F = focus, a = aperture;
+    const vec3 hor = dof ? F * horizontal : horizontal, ver = dof ? F * vertical : vertical;
+    const vec3 llc0 = dof ? F * lower_left_corner : lower_left_corner;
+    std::vector<float> out((size_t)n * 12);
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t i = first_sample + j + 1u;
+        vec3 pos = position, llc = llc0;
+        if (pixel_jitter) {
+            const float dx = (float)radicalInverse(2, i) - 0.5f, dy = (float)radicalInverse(3, i) - 0.5f;
+            llc = llc + (dx / (float)width) * hor;
+            llc = llc + (dy / (float)height) * ver;
+        }
+        if (dof) {
+            const float rad = std::sqrt((float)radicalInverse(5, i));
+            const float phi = 6.28318530717958647692f * (float)radicalInverse(7, i);
+            const float lx = rad * std::cos(phi), ly = rad * std::sin(phi);
+            const vec3 off = a * (lx * u + ly * v);
+            pos = pos + off;
+            llc = llc - off;
+        }
+        const vec3 *src[4] = {&pos, &llc, &hor, &ver};
+        for (int k = 0; k < 4; k++) {
+            out[(size_t)j * 12 + 3 * k] = src[k]->x;
+            out[(size_t)j * 12 + 3 * k + 1] = src[k]->y;
+            out[(size_t)j * 12 + 3 * k + 2] = src[k]->z;
+        }
+    }
+    return out;
+}

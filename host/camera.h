@@ -3,6 +3,9 @@
 // What the trace kernels see of it is transferData(): 12 floats = position,
 // lower_left_corner, horizontal, vertical (kernels/raytracer.cl:129-134,503).
 #pragma once
+#include <cstdint>
+#include <vector>
+
 #include "vecmath.h"
 
 enum CameraMovementDirection { FORWARD, BACK, LEFT, RIGHT };
@@ -34,4 +37,19 @@ public:
     // pointer to a function-static float[12]: valid until the next call, not thread-safe
     // (the reference's contract, src/camera.cpp:94-110)
     float *transferData() const;
+
+    // n x 12 floats: one camera block per sample first_sample .. first_sample + n - 1, for RayTracer::renderSamplesCameras
+    // (rt_render_spp_cameras) — pixel jitter (anti-aliasing) and / or a thin lens (depth of field).  Block j, in float and
+    // in this order, with i = first_sample + j + 1 the index into the Halton sequences:
+    //     hor' = F * horizontal, ver' = F * vertical                       (F = focus; only with aperture != 0)
+    //     off = a * (lx * u + ly * v)                                       (a = aperture; (lx, ly) the lens point)
+    //     position' = position + off
+    //     llc' = (F * llc + (dx / width) * hor' + (dy / height) * ver') - off
+    // (dx, dy) = Halton(2, 3)(i) - 0.5; (lx, ly) = sqrt(h5) * (cos, sin)(2 pi h7), (h5, h7) = Halton(5, 7)(i); the radical
+    // inverses in double, rounded once.  A term that is switched off is not computed: with jitter off and aperture 0
+    // every block is transferData().  The same arithmetic as camera.py's sampleBlocks, bit for bit.
+    std::vector<float> sampleBlocks(uint32_t n, uint32_t first_sample, int width, int height, bool pixel_jitter = true,
+                                    float aperture = 0.0f, float focus = 1.0f) const;
+    // van der Corput radical inverse of `index` in `base`
+    static double radicalInverse(uint32_t base, uint32_t index);
 };

@@ -74,6 +74,17 @@ const float *RayTracer::renderFrame(const Camera *camera, uint32_t spp) {
     return transferImage();
 }
 
+void RayTracer::renderSamplesCameras(const std::vector<float> &blocks, uint32_t first_sample) {
+    check(rt_render_spp_cameras(ctx, blocks.data(), first_sample, (uint32_t)(blocks.size() / 12)));
+}
+
+const float *RayTracer::renderFrameCameras(const std::vector<float> &blocks) {
+    check(rt_clear(ctx));
+    renderSamplesCameras(blocks, 0);
+    check(rt_resolve(ctx));
+    return transferImage();
+}
+
 rt_adaptive_stats RayTracer::renderAdaptive(const Camera *camera, const rt_adaptive_params &params) {
     rt_adaptive_stats st{};
     check(rt_render_adaptive(ctx, camera->transferData(), &params, &st));

@@ -57,6 +57,11 @@ public:
     // native additions
     void renderSamples(const Camera *camera, uint32_t first_sample, uint32_t n_samples);  // fused, asynchronous
     const float *renderFrame(const Camera *camera, uint32_t spp);  // clear + fused + resolve + read back
+    // per-sample camera blocks (rt_render_spp_cameras, asynchronous): sample first_sample + j of every pixel through block j
+    // of `blocks` (n x 12 floats, e.g. Camera::sampleBlocks: pixel jitter, depth of field); adds to the accumulator like
+    // renderSamples.  renderFrameCameras: clear + that from sample 0 + resolve + read back
+    void renderSamplesCameras(const std::vector<float> &blocks, uint32_t first_sample);
+    const float *renderFrameCameras(const std::vector<float> &blocks);
     // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
     std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major

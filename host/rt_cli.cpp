@@ -6,7 +6,11 @@
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
 //              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
-//          [--aov PREFIX]
+//          [--aov PREFIX] [--aa] [--aperture R --focus D]
+// --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
+// --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
+// sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
+// --adaptive, whose samples share one camera; --denoise is allowed, its guides stay the unjittered camera's first hits.
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -57,7 +61,7 @@ static void usage() {
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
-                 "[--aov PREFIX]\n";
+                 "[--aov PREFIX] [--aa] [--aperture R --focus D]\n";
     std::exit(2);
 }
 
@@ -149,6 +153,8 @@ int main(int argc, char **argv) {
     uint32_t follow = 0;
     long max_chain = -1;   // (-1: RT_FEATURE_CHAIN_MAX)
     bool split_chains = false;
+    bool aa = false, focus_given = false;
+    float aperture = 0.0f, focus = 1.0f;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -190,6 +196,18 @@ int main(int argc, char **argv) {
         else if ((v = val("--follow"))) follow = parse_follow(v);
         else if ((v = val("--max-chain"))) max_chain = parse_int(v, 0, RT_FEATURE_CHAIN_MAX);
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
+        else if ((v = val("--aperture"))) {
+            char *end = nullptr;
+            aperture = std::strtof(v, &end);
+            if (!*v || *end || !(aperture > 0.0f) || !std::isfinite(aperture)) usage();
+        }
+        else if ((v = val("--focus"))) {
+            char *end = nullptr;
+            focus = std::strtof(v, &end);
+            if (!*v || *end || !(focus > 0.0f) || !std::isfinite(focus)) usage();
+            focus_given = true;
+        }
+        else if (a == "--aa") aa = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--variance-guided") variance_guided = true;
         else if (a == "--measured") measured = true;
@@ -206,6 +224,14 @@ int main(int argc, char **argv) {
     if (split_chains && !denoise) usage();
     if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
     if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
+    if ((aperture > 0.0f) != focus_given) usage();                         // a lens has a radius and a focus distance
+    const bool cameras = aa || aperture > 0.0f;
+    if (cameras && (progressive || adaptive)) {
+        std::cerr << "rt_cli: --aa and --aperture give every sample a camera of its own; --progressive and --adaptive trace "
+                     "all samples through one camera: use --spp" << std::endl;
+        return 2;
+    }
+    if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
         if (progressive) usage();
@@ -261,6 +287,8 @@ int main(int argc, char **argv) {
         tracer.render(&camera);
         for (int s = 1; s < spp; s++) tracer.renderAgain(&camera);
         img = tracer.transferImage();
+    } else if (cameras) {
+        img = tracer.renderFrameCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus));
     } else {
         img = tracer.renderFrame(&camera, (uint32_t)spp);
     }
@@ -272,7 +300,7 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back" << std::endl;
         if (!out_counts.empty()) write_counts(out_counts, tracer.sampleCounts(), w, h);
     } else {
-        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : "fused") << ": " << sec * 1e3
+        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 

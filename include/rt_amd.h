@@ -287,6 +287,29 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
 int rt_resolve(rt_context *ctx);
 
 /*
+ * Per-sample camera blocks (new): samples first_sample .. first_sample+n-1 of every owned pixel, sample first_sample+j
+ * traced from cameras[12*j .. 12*j+11] (host pointer, copied at the call).  The reference's `retrace` takes a camera block
+ * and a sample index per call and its host may move the camera between calls (src/raytracer.cpp:146-165), so this is, per
+ * pixel-sample, what the reference computes — with the host's camera a function of the sample index: pixel jitter
+ * (anti-aliasing), a lens (depth of field), a moving camera (motion blur).
+ *   - Sample first_sample+j of pixel (x, y) is bit for bit the radiance rt_trace_samples returns for (block j, x, y,
+ *     first_sample+j) under the selected arithmetic policy.
+ *   - The samples of a pixel are summed in rt_render_spp's fixed order — lane l of the pixel's g lanes adds its samples
+ *     l, l+g, ... one after the other, then the xor butterfly, g = 2^ceil(log2(min(n, 64))) — and the sum is added to the
+ *     linear accumulator, the count to its 4th channel.  With n identical blocks the accumulator therefore equals
+ *     rt_render_spp(block, first_sample, n)'s, bit for bit.
+ *   - A call of more than 512 samples runs as consecutive launches of 512, as rt_render_spp's does.
+ *   - Asynchronous on the context's stream.  The image, the sample counter, the feature records and pending look-ahead
+ *     frames stay as they are, as under rt_render_spp; so does a kept prefix (RT_OPT_PREFIX_CACHE): these launches use none of
+ *     its buffers.
+ *   - Sharded contexts, RT_OPT_MOMENTS, enabled counters, RT_OPT_MAX_THREADS_PER_LAUNCH and RT_OPT_ACCEL are honoured as by
+ *     rt_render_spp; no option changes a bit.  RT_OPT_PREFIX_SHARING, _TREE and _CACHE have nothing to act on: samples that
+ *     look through different cameras share no path prefix.
+ * RT_EINVAL: a NULL pointer, samples beyond RT_MAX_SAMPLE.  RT_ESTATE: no scene set.
+ */
+int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_sample, uint32_t n_samples);
+
+/*
  * Adaptive sampling (new): render until every decision block of block_w x block_h pixels has converged.
  * Round k (k = 0, 1, ...) traces samples k*batch .. k*batch+c-1, c = min(batch, max_spp - k*batch), of every pixel of
  * a still-active block, so a pixel whose count is n holds exactly samples 0 .. n-1 and each round adds, bit for bit,
@@ -758,6 +781,39 @@ int rt_debug_plan_samples(const rt_sample_facts *facts, rt_sample_plan *plan_out
 /* Test instrumentation: the facts and the plan of the context's last fused launch (its last slot range).  RT_EINVAL before
  * the first one. */
 int rt_debug_last_sample_plan(rt_context *ctx, rt_sample_facts *facts_out, rt_sample_plan *plan_out);
+
+/* What a camera launch's choice of kernel reads (one slot range of one launch of rt_render_spp_cameras); flags are 0 / 1. */
+typedef struct rt_camera_facts {
+    uint32_t count, glog2;              /* blocks (= samples per pixel) of the launch, log2 of the lanes per pixel */
+    uint32_t n;                         /* slots of the range */
+    uint32_t material_count, sphere_count, plane_count, lens_count, model_count;
+    uint32_t sphere_bvh, mesh_bvh;      /* the launch walks a sphere BVH / per-mesh BVHs */
+    uint32_t faces;                     /* triangles of all meshes together */
+    uint32_t cu_count;
+    uint32_t count_enabled, sample_queue, wave_fill, moments;
+} rt_camera_facts;
+
+#define RT_CAMERA_PLAN_FIXED 0u   /* pt_render<MODE_ACCUM, COUNT, ACCEL, CAMS = true> */
+#define RT_CAMERA_PLAN_QUEUE 1u   /* pt_samples_q<false, ACCEL, GEOM, WAVES, false, -1, CAM = true> */
+
+/* The kernel chosen for an rt_camera_facts and its launch geometry.  count, accel and moments as in rt_sample_plan; geom,
+ * waves, lds_face_f4 and lds_bytes belong to RT_CAMERA_PLAN_QUEUE (0 elsewhere).  A queue wave owns the owned, active pixels
+ * among pixels_per_wave consecutive slots, so grid_units = ceil(n / pixels_per_wave) exactly. */
+typedef struct rt_camera_plan {
+    uint32_t family;
+    uint32_t count, accel, geom, waves, moments;
+    uint32_t pixels_per_wave;           /* slots per wave (1 for RT_CAMERA_PLAN_FIXED) */
+    uint32_t lds_face_f4, lds_bytes;
+    uint32_t grid_units, block_size;
+} rt_camera_plan;
+
+/* Test instrumentation, no device needed: the plan rt_render_spp_cameras' launcher makes for `facts` — the launcher calls
+ * this very function.  RT_EINVAL: a NULL pointer, count 0 or above 512, glog2 above 6. */
+int rt_debug_plan_camera_samples(const rt_camera_facts *facts, rt_camera_plan *plan_out);
+
+/* Test instrumentation: the facts and the plan of the context's last camera launch (its last slot range).  RT_EINVAL before
+ * the first one. */
+int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 
 /* Test instrumentation: resident workgroups per compute unit the runtime reports for the headline sample-queue kernel
  * (one wave per workgroup) at `lds_bytes` of dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor; no kernel runs). */

@@ -247,6 +247,31 @@ class SamplePlan(_U32Record):
         "lds_bytes", "grid_units", "block_size")]
 
 
+class CameraFacts(_U32Record):
+    """rt_camera_facts: what the choice of kernel of an rt_render_spp_cameras launch reads"""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "count", "glog2", "n", "material_count", "sphere_count", "plane_count", "lens_count", "model_count", "sphere_bvh",
+        "mesh_bvh", "faces", "cu_count", "count_enabled", "sample_queue", "wave_fill", "moments")]
+
+
+CAMERA_PLAN_FIXED, CAMERA_PLAN_QUEUE = 0, 1   # rt_camera_plan.family
+
+
+class CameraPlan(_U32Record):
+    """rt_camera_plan: the camera launch's kernel and launch geometry"""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "family", "count", "accel", "geom", "waves", "moments", "pixels_per_wave", "lds_face_f4", "lds_bytes", "grid_units",
+        "block_size")]
+
+
+def camera_prototypes(lib):
+    """ctypes prototypes of rt_render_spp_cameras and its plan probes."""
+    vp, u32 = C.c_void_p, C.c_uint32
+    lib.rt_render_spp_cameras.argtypes = [vp, vp, u32, u32]
+    lib.rt_debug_plan_camera_samples.argtypes = [C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
+    lib.rt_debug_last_camera_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
+
+
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)
 LDS_MATERIALS, LDS_WINNERS, LDS_PLANES = 64, 64, 16
 

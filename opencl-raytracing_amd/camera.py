@@ -46,6 +46,19 @@ ZOOM_SPEED = f32(0.5)
 UP_DIR = np.array([0.0, -1.0, 0.0], dtype=f32)  # world up is -y, camera.cpp:23
 
 
+def radical_inverse(base, index):
+    """Van der Corput radical inverse of `index` in `base`, in double (rounded to float32 once, by the caller)."""
+    f, r, i = 1.0, 0.0, int(index)
+    while i > 0:
+        f /= base
+        r += f * (i % base)
+        i //= base
+    return r
+
+
+TWO_PI = f32(6.28318530717958647692)
+
+
 def _norm(v):
     # glm::normalize = v * inversesqrt(dot(v, v))
     return v * (f32(1) / f32(np.sqrt(f32(np.dot(v, v)))))
@@ -120,3 +133,56 @@ class Camera:
     def transferData(self):
         """float32[12]: position, lower_left_corner, horizontal, vertical (camera.cpp:94-110)."""
         return np.concatenate([self.position, self.lower_left_corner, self.horizontal, self.vertical]).astype(f32)
+
+    def sampleBlocks(self, n, first_sample=0, width=None, height=None, pixel_jitter=True, aperture=0.0, focus=1.0):
+        """float32[n, 12]: one camera block per sample first_sample .. first_sample + n - 1, for
+        RayTracer.renderSamplesCameras — pixel jitter (anti-aliasing) and / or a thin lens (depth of field).
+        Block j, in float32 and in this order, with i = first_sample + j + 1 the index into the Halton sequences:
+            hor' = F * horizontal, ver' = F * vertical                       (F = focus; only with aperture != 0)
+            off = a * (lx * u + ly * v)                                       (a = aperture; (lx, ly) the lens point)
+            position' = position + off
+            llc' = (F * llc + (dx / width) * hor' + (dy / height) * ver') - off
+        (dx, dy) = Halton(2, 3)(i) - 0.5, in [-0.5, 0.5)^2 of a pixel; (lx, ly) = sqrt(h5) * (cos, sin)(2 pi h7) with
+        (h5, h7) = Halton(5, 7)(i), a point of the unit disk (the host libm's cosf / sinf, as everywhere in this class).
+        The radical inverses are formed in double and rounded once.  A term that is switched off is not computed: without
+        jitter no dx / dy terms, with aperture 0 no `off` and F = 1 — with both off every block is transferData(), bit
+        for bit.  The index follows the SAMPLE index, so calls for samples 0.., 64.., 128.. continue one sequence.
+        The plane at distance `focus` along the view direction (w = 1 in the block's frame) stays where it is: points on
+        it are sharp, everything else is blurred over a disk of radius aperture * |1 - depth / focus|."""
+        n, first_sample = int(n), int(first_sample)
+        dof = float(aperture) != 0.0
+        if pixel_jitter and (width is None or height is None):
+            raise ValueError("pixel jitter needs the frame's width and height")
+        F, a = f32(focus), f32(aperture)
+        hor = F * self.horizontal if dof else self.horizontal
+        ver = F * self.vertical if dof else self.vertical
+        llc0 = F * self.lower_left_corner if dof else self.lower_left_corner
+        out = np.empty((n, 12), dtype=f32)
+        for j in range(n):
+            i = first_sample + j + 1
+            pos, llc = self.position, llc0
+            if pixel_jitter:
+                dx = f32(radical_inverse(2, i)) - f32(0.5)
+                dy = f32(radical_inverse(3, i)) - f32(0.5)
+                llc = llc + (dx / f32(width)) * hor
+                llc = llc + (dy / f32(height)) * ver
+            if dof:
+                rad = f32(np.sqrt(f32(radical_inverse(5, i))))
+                phi = TWO_PI * f32(radical_inverse(7, i))
+                lx, ly = rad * cosf(phi), rad * sinf(phi)
+                off = a * (lx * self.u + ly * self.v)
+                pos = pos + off
+                llc = llc - off
+            out[j] = np.concatenate([pos, llc, hor, ver]).astype(f32)
+        return out
+
+    @staticmethod
+    def sampleOffsets(n, first_sample=0):
+        """float32[n, 4]: (dx, dy, lx, ly) of sampleBlocks for samples first_sample .. first_sample + n - 1."""
+        out = np.empty((int(n), 4), dtype=f32)
+        for j in range(int(n)):
+            i = int(first_sample) + j + 1
+            rad = f32(np.sqrt(f32(radical_inverse(5, i))))
+            phi = TWO_PI * f32(radical_inverse(7, i))
+            out[j] = (f32(radical_inverse(2, i)) - f32(0.5), f32(radical_inverse(3, i)) - f32(0.5), rad * cosf(phi), rad * sinf(phi))
+        return out

@@ -935,14 +935,20 @@ PT_DEV V3 radiance(const Ctx &c, Ray r, uint32_t sample, uint32_t gx, uint32_t g
 }
 
 // :129-139, :500-505 — no pixel jitter
-PT_DEV Ray primary_ray(const float *cam, uint32_t x, uint32_t y, int w, int h) {
-    float s = (float)(int)x / (float)w;
-    float t = (float)(int)y / (float)h;
+// (in two parts: the pixel's frame coordinates (s, t) = (x / w, y / h) do not depend on the camera block, so the camera entry
+// of the sample queue forms them once per pixel at staging and only the second part per sample — the same operations)
+PT_DEV float primary_coord(uint32_t x, int w) { return (float)(int)x / (float)w; }
+PT_DEV Ray primary_ray_at(const float *cam, float s, float t) {
     Ray r;
     r.o = mk(cam[0], cam[1], cam[2]);
     V3 llc = mk(cam[3], cam[4], cam[5]), hor = mk(cam[6], cam[7], cam[8]), ver = mk(cam[9], cam[10], cam[11]);
     r.d = normalize(mad(ver, t, mad(hor, s, llc)));   // llc + s * hor + t * ver
     return r;
+}
+PT_DEV Ray primary_ray(const float *cam, uint32_t x, uint32_t y, int w, int h) {
+    float s = primary_coord(x, w);
+    float t = primary_coord(y, h);
+    return primary_ray_at(cam, s, t);
 }
 
 

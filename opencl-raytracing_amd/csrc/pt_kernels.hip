@@ -163,7 +163,10 @@ PT_DEV V3 retrace_step(V3 prev, V3 sample, uint32_t s) {
 //   MODE_ACCUM   accum += (sum, count)                      (rt_render_spp, prefix sharing off)
 //   MODE_TRACE   image = sqrt(radiance(sample first))        (`trace`,  raytracer.cl:496-510)
 //   MODE_RETRACE image = sqrt(mix(new, image², k/(k+1)))     (`retrace`, raytracer.cl:512-532)
-template <int MODE, bool COUNT, bool ACCEL>
+// CAMS (MODE_ACCUM only; rt_render_spp_cameras' fixed-lane kernel): sample first + j looks through block j of fp.cams instead of
+// fp.cam — the primary ray is formed per sample, everything else is the same code.  The other instantiations never read
+// the field.
+template <int MODE, bool COUNT, bool ACCEL, bool CAMS = false>
 __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
                                                  float4 *__restrict__ image, unsigned long long *counters) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
@@ -187,6 +190,7 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
         Ray r0 = primary_ray(fp.cam, x, y, fp.w, fp.h);
         for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
             if (COUNT) cn.c[CN_SAMPLES]++;
+            if (CAMS) r0 = primary_ray(fp.cams + 12u * (s - fp.first), x, y, fp.w, fp.h);
             const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, x, y);
             if (mom) moments_fold(lm, sum, rad);
             sum = sum + rad;
@@ -867,13 +871,72 @@ PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
     }
 }
 
+// ---- the queue's entry FROM THE CAMERA (pt_samples_q<…, CAM>; rt_render_spp_cameras) ---------------------------------------
+// Sample first + j of a pixel looks through camera block j of fp.cams, so the samples of a pixel share no path prefix:
+// there are no records, no live list and no trees.  A wave owns the owned, active pixels among `pixels_per_wave`
+// consecutive SLOTS of the launch's range (wave b: slot_begin + b·ppw …) — found and compacted inside the wave by one
+// ballot, so the launch needs no list kernel and touches none of the slot buffers (a kept prefix lies as it lay).  A wave
+// whose slots hold no such pixel (the slots of a partial tile outside the frame) leaves before anything is staged.
+// The queue's LDS layout is queue_stage's, so the sizing rules are shared; of a pixel's record region (80 bytes) the first
+// two floats hold its frame coordinates (s, t) = (x / w, y / h) — primary_ray's first part, formed here once per pixel.
+// Every lane of the wave calls queue_stage_cam after the ballot (it holds the wave's fence).
+PT_DEV WaveQueue queue_stage_cam(const DeviceScene &sc, const FrameParams &fp, bool owns, uint32_t x, uint32_t y,
+                                 unsigned long long owners, uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
+    float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
+    WaveQueue q;
+    q.rec = (LdsQueueF4)wave_lds;
+    q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
+    q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
+    q.npix = (uint32_t)__popcll(owners);
+    q.count = fp.count;
+    q.total = q.npix * q.count;
+    if (owns) {
+        const uint32_t k = lanes_below(owners);   // (< npix <= pixels_per_wave)
+        q.xy[k].x = x;
+        q.xy[k].y = y;
+        q.xy[k].bv = rnd_base_v(0u, x, y);
+        q.xy[k].bu = rnd_base_u(0u, x, y);
+        q.rec[QUEUE_REC_F4 * k].x = primary_coord(x, fp.w);
+        q.rec[QUEUE_REC_F4 * k].y = primary_coord(y, fp.h);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    q.inv_count = fp.inv_count;
+    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    return q;
+}
+// Queue entry idx → (pixel p, sample first + j): the primary ray through block j — the policy's own primary_ray, its second
+// part (primary_ray_at) on the staged coordinates — and the sample's part of the two table index sums.  The blocks are GATHERED from global memory here, at the refill — the lanes
+// of a refill hold consecutive entries, i.e. mostly consecutive j of one pixel, so a wave reads a contiguous stretch of the
+// table (48 bytes per lane) that every wave of the launch reads too: it lives in L2 / the vector L1.  In LDS the table of a
+// 512-sample launch would be 24 KiB per wave, four times the queue itself (about 6 KiB at 6 waves per SIMD).
+struct CameraEntry {
+    Ray r;
+    uint32_t bv, bu;
+};
+PT_DEV CameraEntry queue_fetch_cam(const WaveQueue &q, const FrameParams &fp, uint32_t idx) {
+    // (p = idx / count as queue_fetch forms it)
+    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t j = idx - p * q.count, sample = fp.first + j;
+    const LdsQueueF4 st = q.rec + QUEUE_REC_F4 * p;
+    CameraEntry e;
+    e.r = primary_ray_at(fp.cams + 12u * j, st->x, st->y);
+    e.bv = sample * 8049u + q.xy[p].bv;   // = rnd_base_v(sample, x, y)
+    e.bu = sample * 2683u + q.xy[p].bu;   // = rnd_base_u(sample, x, y)
+    return e;
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
 // kernel keeps 6 waves per SIMD.
 // COUNT_LOG2 = 6: the launch has exactly 64 samples per pixel and 64 lanes per pixel (fp.count == 64, fp.group_log2 == 6;
 // launch_fused picks it for <false, false, …> only) — the queue's index arithmetic and sums are written for that count.
-template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1>
+// CAM: the from-the-camera entry (rt_render_spp_cameras; never with COUNT, MOMENTS or a COUNT_LOG2): a refilled lane takes
+// the primary ray of its sample's own camera block, depth 0 and path colour (1, 1, 1), and — there is no interaction at
+// the camera — passes its first interaction step (`fresh`) and enters the loop at the nearest-hit step; from there the
+// body, queue_put and queue_sums are the code of the record-fed instantiations.  recs, live and live_count are NULL.
+template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1, bool CAM = false>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                     const uint32_t *__restrict__ live,
                                                     const uint32_t *__restrict__ live_count,
@@ -887,8 +950,19 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
     // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
     // anything is staged: no barrier, no sums, and only zeros to add to the counters.
-    uint32_t pix0 = 0;
-    const uint32_t npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    static_assert(!CAM || (!COUNT && !MOMENTS && COUNT_LOG2 < 0), "the camera entry has no counting, moment or count-specialised build");
+    uint32_t pix0 = 0, npix = 0;
+    uint32_t cam_x = 0, cam_y = 0;   // CAM: the pixel of this lane's slot, if the wave owns it
+    bool cam_owns = false;
+    unsigned long long cam_owners = 0;
+    if (CAM) {
+        const uint32_t slot = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
+        cam_owns = threadIdx.x < pixels_per_wave && slot < fp.slot_end && slot_to_pixel(fp, slot, cam_x, cam_y) && pixel_active(fp, cam_x, cam_y);
+        cam_owners = __ballot(cam_owns);
+        npix = (uint32_t)__popcll(cam_owners);
+    } else {
+        npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
+    }
     if (npix == 0u) return;
     float4 *s_mat = s_dyn;
     LaneCounters cn;
@@ -904,10 +978,12 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
+    const WaveQueue q = CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+                            : queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
     uint32_t next = 0;  // wave-uniform head of the queue
     bool active = false;
+    bool fresh = false;  // CAM: the lane stands at the camera — no interaction before its first nearest-hit search
     // Per-lane state carried from one iteration to the next, kept small (the kernel sits on its VGPR budget):
     // the hit POINT is not carried — the ray's origin is moved there as soon as the hit is known — and the
     // per-sample part of the table index sums is precomputed (bv, bu) instead of carrying sample, x and y.
@@ -932,6 +1008,20 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         // refill when enough lanes idle (or none is active): the refill step issues for the whole wave
         if (m && next < q.total && ((uint32_t)__popcll(m) >= PT_REFILL_MIN || m == ~0ull)) {
             uint32_t cand = next + lanes_below(m);
+            if (CAM) {
+                if (need && cand < q.total) {
+                    idx = cand;
+                    const CameraEntry e = queue_fetch_cam(q, fp, idx);
+                    bv = e.bv;
+                    bu = e.bu;
+                    depth = 0u;
+                    r = e.r;
+                    out = mk(1.0f, 1.0f, 1.0f);
+                    if (PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
+                    active = true;
+                    fresh = true;
+                }
+            } else
             if (need && cand < q.total) {
                 idx = cand;
                 const QueueEntry e = queue_fetch<COUNT_LOG2>(q, sc, fp, idx);
@@ -977,7 +1067,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         }
 #endif
         // ---- one material interaction for every active lane
-        if (active) {
+        if (CAM ? active && !fresh : active) {
             if (!PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
             Hit at;   // the vertex this interaction happens at: the ray's origin already stands on it
             at.p = r.o;
@@ -996,6 +1086,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 active = false;
             }
         }
+        if (CAM) fresh = false;
         PT_STAMP(c, 1);
         // ---- nearest hit for every lane still active; the table reads of the NEXT material
         // interaction are issued first (they depend on the ray direction only)
@@ -1050,7 +1141,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     if (threadIdx.x == 0 && q.npix)
         for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
 #endif
-    if (!COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
+    if (!CAM && !COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
     else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }
@@ -1902,6 +1993,115 @@ int launch_lookahead(rt_context *ctx, const float cam[12], uint32_t first, uint3
     return launch_fused_any(ctx, cam, first, count, group_log2_for(count), nullptr, nullptr, ring, nullptr);
 }
 
+// ---- per-sample camera blocks (rt_render_spp_cameras): facts (camera_facts, rt_context.hpp) → plan → launch ---------------
+// plan_camera_samples is THE place that decides what a slot range of a camera call runs — like plan_samples a pure function
+// of its facts (rt_debug_plan_camera_samples, tests/test_cameras_host.py).  The queue's sizing rules are plan_samples':
+// waves per SIMD by the scene's BVHs, pixels per wave by the LDS share and the wave-fill rule, a small scene's faces in LDS.
+//  * RT_CAMERA_PLAN_QUEUE: pt_samples_q<false, ACCEL, GEOM, WAVES, false, -1, true>, one wave per pixels_per_wave SLOTS — the
+//    grid is exact, ceil(n / pixels_per_wave).  A scene plan_samples would give the walk-slice kernel runs the (1, 2) row,
+//    its walks in place.
+//  * RT_CAMERA_PLAN_FIXED: pt_render<MODE_ACCUM, COUNT, ACCEL, true> — counting builds, RT_OPT_SAMPLE_QUEUE 0, and launches
+//    that keep sample moments (a MOMENTS row of the camera queue would be five more kernels for an option that is off
+//    by default; the fixed-lane kernel's moments are the ones rt_render_spp keeps with prefix sharing off).
+using CameraFacts = rt_camera_facts;
+using CameraPlan = rt_camera_plan;
+static CameraPlan plan_camera_samples(const CameraFacts &f) {
+    CameraPlan p = {};
+    const bool queue = f.sample_queue && f.count <= QUEUE_SLOTS && !f.count_enabled && !f.moments;
+    const bool accel = f.sphere_bvh || f.mesh_bvh;
+    const bool simple_geom = f.lens_count == 0 && f.model_count == 0;
+    const bool sphere_bvh_only = f.sphere_bvh && !f.mesh_bvh;
+    p.count = f.count_enabled;
+    p.accel = accel;
+    p.moments = f.moments;
+    if (!queue) {
+        p.family = RT_CAMERA_PLAN_FIXED;
+        p.pixels_per_wave = 1u;
+        p.block_size = 256u;
+        p.grid_units = (uint32_t)((((uint64_t)f.n << f.glog2) + 255u) / 256u);
+        return p;
+    }
+    p.family = RT_CAMERA_PLAN_QUEUE;
+    p.geom = !accel || sphere_bvh_only ? (simple_geom ? 0u : 1u) : 2u;
+    p.waves = !accel ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
+    uint32_t static_f4 = lds_static_used(f.material_count, f.sphere_count, f.plane_count);
+    const uint32_t want_units = (f.cu_count ? f.cu_count : 256u) * 4u * 6u * PT_UNITS_PER_WAVE_SLOT;
+    const uint32_t ppw_full = (64u + f.count - 1u) / f.count;
+    const uint32_t ppw_par = !f.wave_fill ? QUEUE_MAX_PIXELS : std::max(f.n / want_units, ppw_full);
+    const uint32_t ppw = std::min(queue_pixels_per_wave(f.count, p.waves, static_f4), ppw_par);
+    if (PT_FACE_MASK && !simple_geom && !f.mesh_bvh && f.faces > 0 && f.faces <= PT_LDS_FACE_CAP &&
+        queue_pixels_per_wave(f.count, p.waves, static_f4 + 3u * f.faces) >= ppw) {
+        p.lds_face_f4 = 3u * f.faces;
+        static_f4 += p.lds_face_f4;
+    }
+    p.pixels_per_wave = ppw;
+    p.block_size = 64u;
+    p.grid_units = (f.n + ppw - 1u) / ppw;
+    p.lds_bytes = static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(ppw, f.count);
+    return p;
+}
+
+static QueueKernel camera_queue_kernel(const CameraPlan &p) {   // the five geometry rows of queue_kernel; NULL: no such row
+    struct Row { uint32_t accel, geom, waves; QueueKernel k; };
+    static const Row rows[] = {
+        {0u, 0u, PT_Q_WAVES, pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>},
+        {0u, 1u, PT_Q_WAVES, pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>},
+        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false, -1, true>},
+        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false, -1, true>},
+        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false, -1, true>}};
+    for (const Row &r : rows)
+        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k;
+    return nullptr;
+}
+static RenderKernel camera_render_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
+    static const RenderKernel k[2][2] = {{pt_render<MODE_ACCUM, false, false, true>, pt_render<MODE_ACCUM, false, true, true>},
+                                         {pt_render<MODE_ACCUM, true, false, true>, pt_render<MODE_ACCUM, true, true, true>}};
+    return k[count][accel];
+}
+
+// One launch of a camera call: `count` blocks at d_cams.  cam0 (the first block) fills FrameParams::cam, which no camera
+// kernel reads.  Slot ranges as launch_render and launch_fused cut them (RT_OPT_MAX_THREADS_PER_LAUNCH).  Nothing here
+// reads or writes the slot buffers or the prefix cache; the staged scene block is the context's, refreshed as launch_fused
+// refreshes it.
+int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
+                   float4 *accum, float *m2) {
+    if (!d_cams || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
+    FrameParams fp = frame_params(ctx, cam0, first, count, glog2);
+    fp.m2 = m2;
+    fp.cams = d_cams;
+    const DeviceScene sc = device_scene(ctx);
+    const uint32_t slots = fp.slot_end;
+    if (slots == 0) return RT_OK;
+    refresh_stage_block(ctx, sc);
+    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
+    hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
+    HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
+    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
+        fp.slot_begin = b;
+        fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
+        const CameraFacts facts = camera_facts(ctx, sc, fp);
+        const CameraPlan plan = plan_camera_samples(facts);
+        fp.lds_face_f4 = plan.lds_face_f4;
+        if (plan.family == RT_CAMERA_PLAN_QUEUE) {
+            const QueueKernel kernel = camera_queue_kernel(plan);
+            if (!kernel) return fail(ctx, RT_ESTATE, "no camera instantiation of pt_samples_q for the plan");
+            hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
+                               (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,
+                               plan.pixels_per_wave);
+        } else {
+            hipLaunchKernelGGL(camera_render_kernel(plan.count != 0u, plan.accel != 0u), dim3(plan.grid_units), dim3(plan.block_size), 0,
+                               ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p);
+        }
+        ctx->cameras.last_facts = facts;
+        ctx->cameras.last_plan = plan;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
+    ctx->ev_count++;
+    return RT_OK;
+}
+
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
 // hitTriangle's unit normal, normalize(cross(edge1, edge2)) (raytracer.cl:285), depends on the face only: it is kept
 // in the face records (A, e1, e2, n).  Policy 0 computes it on the host (rt_amd.hip build_face_records: plain IEEE
@@ -2037,7 +2237,7 @@ const pt::KernelSet g_kernel_set = {
 #endif
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
-    ks_queue_pixels, ks_queue_occupancy, plan_samples};
+    ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples};
 
 }  // namespace
 

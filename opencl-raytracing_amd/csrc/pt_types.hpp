@@ -176,8 +176,17 @@ struct FrameParams {
     // look-ahead launches (rt_render_again under RT_OPT_LOOKAHEAD; NULL = an ordinary launch): instead of adding its samples
     // to the accumulator, a pixel starts from la_image[pix] and takes `count` retrace steps (samples first .. first+count-1
     // in order), the image after step j going to la_ring[j * w * h + pix] — frame-major, so a frame is handed out as one copy
+    // Per-sample camera blocks (rt_render_spp_cameras): count x 12 floats on the device, block j for sample first + j, read by
+    // the camera instantiations only (pt_render<…, CAMS>, pt_samples_q<…, CAM>).  The pointer SHARES la_image's eight bytes: a
+    // camera launch is never a look-ahead launch (la_ring == NULL, so nothing reads la_image), and the struct — the kernel
+    // argument of every shipped instantiation — keeps its size and every field its place.  (Appended as a field of its own
+    // it changed the scalar loads of the kernels that read m2 next to it: policy 0's pt_samples_q<true, true, 0, 6, true>
+    // went from 14 to 44 spilled VGPRs.)
     float4 *la_ring;
-    const float4 *la_image;
+    union {
+        const float4 *la_image;
+        const float *cams;
+    };
     // per-pixel sample moments (RT_OPT_MOMENTS; NULL = off): W x H floats beside the accumulator the launch adds to, the
     // centred second moment of each pixel's sample luminances (pt_moments.hpp).  Read in the kernels' epilogues only
     float *m2;

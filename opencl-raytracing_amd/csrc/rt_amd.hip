@@ -569,6 +569,9 @@ void rt_destroy(rt_context *ctx) {
             if (ctx->ev[i][k]) (void)hipEventDestroy(ctx->ev[i][k]);
     if (ctx->sample_grid.counts_ev) (void)hipEventDestroy(ctx->sample_grid.counts_ev);
     if (ctx->sample_grid.h_counts) (void)hipHostFree(ctx->sample_grid.h_counts);
+    for (hipEvent_t e : ctx->cameras.read)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->cameras.h_table) (void)hipHostFree(ctx->cameras.h_table);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -1022,6 +1025,50 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
         rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr, m2)
                                  : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c),
                                                           ctx->accum.p, nullptr, m2);
+        if (rc != RT_OK) return rc;
+        done += c;
+        ctx->accum_count += c;
+    }
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+// the context's camera tables (rt_context::Cameras), made on the first camera call
+int ensure_cameras(rt_context *ctx) {
+    rt_context::Cameras &cm = ctx->cameras;
+    if (cm.table.p) return RT_OK;
+    const size_t floats = (size_t)rt_context::Cameras::RING * RT_SPP_PER_LAUNCH * 12u;
+    if (!cm.h_table) HIP_TRY(ctx, hipHostMalloc((void **)&cm.h_table, floats * sizeof(float), hipHostMallocDefault));
+    for (hipEvent_t &e : cm.read)
+        if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(ctx, cm.table.alloc(floats));
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_sample, uint32_t n_samples) {
+    int rc = check_ready(ctx, cameras);
+    if (rc) return rc;
+    if (n_samples == 0) return RT_OK;
+    if ((uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
+        return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
+    rt_context::Cameras &cm = ctx->cameras;
+    // (launches of RT_SPP_PER_LAUNCH blocks, as rt_render_spp cuts its calls: the accumulator is the sum of their sums)
+    for (uint32_t done = 0; done < n_samples;) {
+        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
+        const uint32_t k = (uint32_t)(cm.launches % rt_context::Cameras::RING);
+        const size_t at = (size_t)k * RT_SPP_PER_LAUNCH * 12u;
+        if (cm.launches >= rt_context::Cameras::RING) HIP_TRY(ctx, hipEventSynchronize(cm.read[k]));   // (table k's last reader)
+        memcpy(cm.h_table + at, cameras + (size_t)done * 12u, (size_t)c * 12u * sizeof(float));
+        HIP_TRY(ctx, hipMemcpyAsync(cm.table.p + at, cm.h_table + at, (size_t)c * 12u * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        cm.launches++;
+        rc = ctx->ks->launch_cameras(ctx, cm.table.p + at, cm.h_table + at, first_sample + done, c, group_log2_for(c), ctx->accum.p,
+                                     ctx->moments.target());
+        HIP_TRY(ctx, hipEventRecord(cm.read[k], ctx->stream));
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
@@ -1847,6 +1894,20 @@ int rt_debug_last_sample_plan(rt_context *ctx, rt_sample_facts *facts_out, rt_sa
     if (ctx->sample_grid.last_plan.pixels_per_wave == 0) return fail(ctx, RT_EINVAL, "no fused launch yet");
     *facts_out = ctx->sample_grid.last_facts;
     *plan_out = ctx->sample_grid.last_plan;
+    return RT_OK;
+}
+
+int rt_debug_plan_camera_samples(const rt_camera_facts *facts, rt_camera_plan *plan_out) {
+    if (!facts || !plan_out || facts->count < 1u || facts->count > RT_SPP_PER_LAUNCH || facts->glog2 > 6u) return RT_EINVAL;
+    *plan_out = pt::kernel_set_a2()->plan_camera_samples(*facts);   // (host code: the same in every policy)
+    return RT_OK;
+}
+
+int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out) {
+    if (!ctx || !facts_out || !plan_out) return RT_EINVAL;
+    if (ctx->cameras.last_plan.block_size == 0) return fail(ctx, RT_EINVAL, "no camera launch yet");
+    *facts_out = ctx->cameras.last_facts;
+    *plan_out = ctx->cameras.last_plan;
     return RT_OK;
 }
 

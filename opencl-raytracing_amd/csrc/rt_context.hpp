@@ -275,6 +275,24 @@ struct rt_context {
         float *target() const { return on && valid ? m2.p : nullptr; }   // what a launch that adds to `accum` updates
     } moments;
 
+    // Per-sample camera blocks (rt_render_spp_cameras), made whole by the first such call and freed with the context.
+    // "Host pointer, copied at the call", and the call is asynchronous: a launch's blocks go through a table of their own in
+    // a ring of RING tables of RT_SPP_PER_LAUNCH blocks each — copied into the PINNED host table k at the call, from there
+    // to device table k on the stream, read by the launch's kernels, `read[k]` recorded behind them.  A launch that comes
+    // round to table k again waits (on the host) for read[k] first: four launches of 512 samples per pixel ahead of the
+    // device, which no caller reaches with the stream busy for milliseconds per launch.
+    struct Cameras {
+        static constexpr uint32_t RING = 4;
+        DevBuf<float> table;            // RING x RT_SPP_PER_LAUNCH x 12 floats
+        float *h_table = nullptr;       // pinned, the same shape
+        hipEvent_t read[RING] = {};
+        uint64_t launches = 0;          // launches that took a table (the next one takes table launches % RING)
+        // what the last launch was chosen from and what was chosen (plan_camera_samples, pt_kernels.hip); block_size 0: no
+        // launch yet (rt_debug_last_camera_plan)
+        rt_camera_facts last_facts = {};
+        rt_camera_plan last_plan = {};
+    } cameras;
+
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
 };
@@ -499,6 +517,28 @@ inline int learn_live_counts(rt_context *ctx, bool hit, const uint32_t *live_cou
     }
     *exact = hit && sg.exact && pc.counts_state == PC::COUNTS_KNOWN;
     return RT_OK;
+}
+
+// What plan_camera_samples reads, for the slot range fp holds (rt_render_spp_cameras).
+inline rt_camera_facts camera_facts(const rt_context *ctx, const DeviceScene &sc, const FrameParams &fp) {
+    rt_camera_facts f = {};
+    f.count = fp.count;
+    f.glog2 = fp.group_log2;
+    f.n = fp.slot_end - fp.slot_begin;
+    f.material_count = sc.material_count;
+    f.sphere_count = sc.sphere_count;
+    f.plane_count = sc.plane_count;
+    f.lens_count = sc.lens_count;
+    f.model_count = sc.model_count;
+    f.sphere_bvh = sc.bvh_node_count != 0;
+    f.mesh_bvh = sc.mesh_bvh_root != nullptr;
+    f.faces = ctx->h_faces.empty() ? 0u : (uint32_t)(ctx->h_faces.size() / 3u - 1u);   // (as sample_facts)
+    f.cu_count = ctx->cu_count > 0 ? (uint32_t)ctx->cu_count : 0u;
+    f.count_enabled = ctx->count_enabled;
+    f.sample_queue = ctx->sample_queue;
+    f.wave_fill = ctx->wave_fill;
+    f.moments = fp.m2 != nullptr;
+    return f;
 }
 
 inline uint32_t group_log2_for(uint32_t count) {

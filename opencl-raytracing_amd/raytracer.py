@@ -36,6 +36,7 @@ SYMBOLS = (
     "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy", "rt_debug_queue_sums",
     "rt_debug_plan_samples", "rt_debug_last_sample_plan",
+    "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -131,6 +132,7 @@ def load_library(path=LIB_PATH):
     _abi.lookahead_prototypes(lib)
     _abi.sample_grid_prototypes(lib)
     _abi.queue_sums_prototypes(lib)
+    _abi.camera_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -245,6 +247,23 @@ def plan_samples(**facts):
     if rc:
         raise RtError(rc, "rt_debug_plan_samples: invalid argument")
     return p.as_dict()
+
+
+def plan_camera_samples(**facts):
+    """The launch rt_render_spp_cameras' launcher plans for these facts (rt_debug_plan_camera_samples: the launcher's own
+    function; host-only, no device needed): the fields of _abi.CameraFacts (those left out are 0) → those of _abi.CameraPlan."""
+    f, p = _abi.CameraFacts(**facts), _abi.CameraPlan()
+    rc = load_library().rt_debug_plan_camera_samples(C.byref(f), C.byref(p))
+    if rc:
+        raise RtError(rc, "rt_debug_plan_camera_samples: invalid argument")
+    return p.as_dict()
+
+
+def _cam_blocks(blocks):
+    blocks = np.ascontiguousarray(blocks, dtype=np.float32)
+    if blocks.ndim != 2 or blocks.shape[1] != 12:
+        raise ValueError("camera blocks must be n x 12 floats")
+    return blocks
 
 
 class RayTracer:
@@ -366,6 +385,26 @@ class RayTracer:
     def renderSamples(self, camera, first_sample, n_samples):
         """Fused path: samples first..first+n-1 of every owned pixel in one launch (async)."""
         self._check(self._lib.rt_render_spp(self._ctx, _cam_block(camera).ctypes.data, first_sample, n_samples))
+
+    def renderSamplesCameras(self, blocks, first_sample=0):
+        """Samples first..first+n-1 of every owned pixel, sample first + j through camera block blocks[j] (n x 12 floats,
+        e.g. Camera.sampleBlocks: pixel jitter, depth of field; rt_render_spp_cameras, async).  Adds to the accumulator
+        like renderSamples; n identical blocks give renderSamples' bits."""
+        blocks = _cam_blocks(blocks)
+        self._check(self._lib.rt_render_spp_cameras(self._ctx, blocks.ctypes.data if len(blocks) else None, first_sample, len(blocks)))
+
+    def renderFrameCameras(self, blocks):
+        """clear + renderSamplesCameras(blocks, 0) + resolve + sync → gamma image (h,w,4)."""
+        self.clear()
+        self.renderSamplesCameras(blocks, 0)
+        self.resolve()
+        return self.transferImage()
+
+    def lastCameraPlan(self):
+        """(facts, plan) dicts of the last renderSamplesCameras launch (rt_debug_last_camera_plan)."""
+        f, p = _abi.CameraFacts(), _abi.CameraPlan()
+        self._check(self._lib.rt_debug_last_camera_plan(self._ctx, C.byref(f), C.byref(p)))
+        return f.as_dict(), p.as_dict()
 
     def resolve(self):
         self._check(self._lib.rt_resolve(self._ctx))
@@ -652,6 +691,7 @@ class RayTracer:
         return tuple(int(v) for v in out)
 
     planSamples = staticmethod(plan_samples)
+    planCameraSamples = staticmethod(plan_camera_samples)
 
     def lastSamplePlan(self):
         """(facts, plan) of the last fused launch's sample stage, as dicts of the fields of _abi.SampleFacts and
