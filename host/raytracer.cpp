@@ -107,6 +107,17 @@ void RayTracer::renderFeaturesChain(const Camera *camera, uint32_t follow, uint3
     check(rt_render_features_chain(ctx, camera->transferData(), &p));
 }
 
+void RayTracer::renderFeaturesCameras(const std::vector<float> &blocks, uint32_t follow, uint32_t max_chain) {
+    const rt_feature_chain_params p{follow, max_chain};
+    check(rt_render_features_cameras(ctx, blocks.empty() ? nullptr : blocks.data(), (uint32_t)(blocks.size() / 12), &p));
+}
+
+std::vector<float> RayTracer::featureCoverage() {
+    std::vector<float> c((size_t)width * height * 2);
+    check(rt_read_feature_coverage(ctx, c.data(), c.size() * sizeof(float)));
+    return c;
+}
+
 std::vector<rt_feature> RayTracer::features() {
     std::vector<rt_feature> f((size_t)width * height);
     check(rt_read_features(ctx, f.data(), f.size() * sizeof(rt_feature)));

@@ -73,6 +73,13 @@ public:
     // whose material type is in `follow` (RT_FOLLOW_* bits) are followed, at most max_chain of them; features() and the
     // denoisers with a null camera then work on these
     void renderFeaturesChain(const Camera *camera, uint32_t follow, uint32_t max_chain = RT_FEATURE_CHAIN_MAX);
+    // the guides of a renderFrameCameras frame (rt_render_features_cameras, asynchronous): the records of the n <= 64 camera
+    // blocks of `blocks` (n x 12 floats, e.g. Camera::sampleBlocks) reduced to one record per pixel — the dominant group's
+    // discrete fields, position / depth / normal / albedo averaged over the hit samples, RT_FEATURE_MIXED where the samples
+    // disagree; follow / max_chain as renderFeaturesChain (0, 0: first hits).  featureCoverage: W x H x (hit share,
+    // dominant share) of that call
+    void renderFeaturesCameras(const std::vector<float> &blocks, uint32_t follow = 0, uint32_t max_chain = 0);
+    std::vector<float> featureCoverage();
     // features for `camera` (unless it is null: then the last ones) + rt_denoise + read back into the image that
     // transferImage() / lastImage() return; the accumulator is left as it was
     const float *denoise(const Camera *camera, const rt_denoise_params &params);

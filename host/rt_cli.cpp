@@ -6,11 +6,15 @@
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
 //              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
-//          [--aov PREFIX] [--aa] [--aperture R --focus D]
+//          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
 // --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
 // --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
 // sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
-// --adaptive, whose samples share one camera; --denoise is allowed, its guides stay the unjittered camera's first hits.
+// --adaptive, whose samples share one camera; --denoise is allowed, its guides stay the unjittered camera's first hits
+// unless --aa-guides N (1 .. 64; with --aa or --aperture, and --denoise or --aov) asks for the guides that belong to such a
+// frame: the records of the run's first N sample cameras (its jitter, aperture and focus) reduced to one per pixel
+// (rt_render_features_cameras; --follow / --max-chain are honoured), which the filter and --aov then use; --aov also writes
+// PREFIX_coverage.pfm: per pixel (share of the N samples that hit, share in the dominant group, 0).
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -61,7 +65,7 @@ static void usage() {
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
-                 "[--aov PREFIX] [--aa] [--aperture R --focus D]\n";
+                 "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]\n";
     std::exit(2);
 }
 
@@ -155,6 +159,7 @@ int main(int argc, char **argv) {
     bool split_chains = false;
     bool aa = false, focus_given = false;
     float aperture = 0.0f, focus = 1.0f;
+    long aa_guides = 0;   // (0: the central, unjittered records)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -207,6 +212,7 @@ int main(int argc, char **argv) {
             if (!*v || *end || !(focus > 0.0f) || !std::isfinite(focus)) usage();
             focus_given = true;
         }
+        else if ((v = val("--aa-guides"))) aa_guides = parse_int(v, 1, RT_FEATURE_CAMERAS_MAX);
         else if (a == "--aa") aa = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--variance-guided") variance_guided = true;
@@ -232,6 +238,7 @@ int main(int argc, char **argv) {
         return 2;
     }
     if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
+    if (aa_guides && (!cameras || (!denoise && aov_prefix.empty()))) usage();   // guides of a per-sample-camera frame, for --denoise / --aov
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive) {
         if (progressive) usage();
@@ -304,7 +311,9 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 
-    if (follow) tracer.renderFeaturesChain(&camera, follow, (uint32_t)max_chain);
+    if (aa_guides) tracer.renderFeaturesCameras(camera.sampleBlocks((uint32_t)aa_guides, 0, w, h, aa, aperture, focus), follow,
+                                                follow ? (uint32_t)max_chain : 0u);
+    else if (follow) tracer.renderFeaturesChain(&camera, follow, (uint32_t)max_chain);
     else if (denoise || !aov_prefix.empty()) tracer.renderFeatures(&camera);
     if (denoise) {
         if (progressive) {   // the running mean of --progressive lives in the image: accumulate the same samples
@@ -316,6 +325,7 @@ int main(int argc, char **argv) {
         rt_denoise_variance_params vp{(uint32_t)dn_iterations, sigma_l, sigmas[1], sigmas[2], sigmas[3], dn_flags};
         auto d0 = std::chrono::steady_clock::now();
         img = measured ? tracer.denoiseMoments(nullptr, vp) : variance_guided ? tracer.denoiseVariance(nullptr, vp) : tracer.denoise(nullptr, dp);
+        if (aa_guides) std::cout << "guides: " << aa_guides << " sample cameras per pixel" << std::endl;
         if (follow)
             std::cout << "guides: chains through follow mask " << follow << ", at most " << max_chain << " vertices"
                       << (split_chains ? ", split" : "") << std::endl;
@@ -340,6 +350,15 @@ int main(int argc, char **argv) {
                 ch[3 * i + 2] = (f[i].flags & RT_FEATURE_CUT) ? 1.0f : 0.0f;
             }
             write_pfm(aov_prefix + "_chain.pfm", ch.data(), 3, 0, 3, w, h);
+        }
+        if (aa_guides) {
+            const std::vector<float> cv = tracer.featureCoverage();
+            std::vector<float> c3(f.size() * 3, 0.0f);
+            for (size_t i = 0; i < f.size(); i++) {
+                c3[3 * i] = cv[2 * i];
+                c3[3 * i + 1] = cv[2 * i + 1];
+            }
+            write_pfm(aov_prefix + "_coverage.pfm", c3.data(), 3, 0, 3, w, h);
         }
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);
         if (denoise && measured) {

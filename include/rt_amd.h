@@ -361,7 +361,8 @@ typedef struct rt_feature {
     uint32_t face;      /* face index inside the mesh for a mesh hit, else 0xFFFFFFFF                         */
     float u, v;         /* texture coordinates (mesh hits; 0 otherwise)                                       */
     uint32_t tex;       /* texture id (mesh hits; 0 otherwise)                                                */
-    uint32_t flags;     /* RT_FEATURE_HIT; after rt_render_features_chain also RT_FEATURE_CUT and the chain fields     */
+    uint32_t flags;     /* RT_FEATURE_HIT; after rt_render_features_chain also RT_FEATURE_CUT and the chain fields;
+                           after rt_render_features_cameras also RT_FEATURE_MIXED                            */
 } rt_feature;
 #define RT_FEATURE_HIT 1u
 
@@ -408,6 +409,53 @@ int rt_device_features(rt_context *ctx, void **d_features);
 typedef struct rt_feature_chain_params { uint32_t follow; uint32_t max_chain; } rt_feature_chain_params;
 int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_feature_chain_params *p);
 int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out);   /* host-only, no context */
+
+/*
+ * Feature records through per-sample cameras (new): the guides that belong to an rt_render_spp_cameras frame.  One call
+ * renders the feature records of n_cameras camera blocks per pixel (cameras[12*j .. 12*j+11], host pointer, copied at the
+ * call) and reduces them on the device to ONE record per pixel, in rt_feature's layout, plus a two-channel coverage buffer.
+ * Per-sample record: for pixel (x, y) and block j, r_j is bit for bit the record rt_render_features_chain(block j, p)
+ *   writes for that pixel under the selected arithmetic policy (p NULL = {0, 0}: rt_render_features' record).
+ * Key: key_j = (r_j.object, r_j.flags >> 8); the object is 0xFFFFFFFF on a miss, so misses with equal chain words form a
+ *   group too.
+ * Dominant group and representative: group the n samples by key.  The dominant group is the one with the most samples;
+ *   among equally large groups the one that contains the smallest j wins.  The representative j* is the smallest j inside
+ *   the dominant group, m the dominant group's size, c the number of samples with RT_FEATURE_HIT.
+ * Output record (it REPLACES the context's feature records, so rt_read_features, rt_device_features, the three denoisers
+ * and the AOV writers work on it unchanged):
+ *   object, material, face, u, v, tex, dir are r_j*'s values, bit for bit;
+ *   flags is r_j*'s flags, or'ed with RT_FEATURE_MIXED when m < n;
+ *   if r_j* is a miss, pos, t, normal, albedo hold r_j*'s miss values (0, +inf, 0, 0);
+ *   if r_j* is a hit, each of the ten floats of pos, t, normal, albedo is S / (float)c: S the sum over ALL hit samples,
+ *     whatever their group, taken by the xor butterfly of rt_render_spp over g = 2^ceil(log2 n) lanes — lane j holds sample
+ *     j's value, a lane whose sample missed or with j >= n holds +0.0f, offsets g/2, g/4, ..., 1 — and the division the
+ *     correctly rounded binary32 quotient under EVERY arithmetic policy.  t of a chain record is its path length, as
+ *     rt_render_features_chain defines it.
+ * Coverage buffer: W*H*2 floats, row-major, ((float)c / (float)n, (float)m / (float)n), correctly rounded: the anti-aliased
+ *   alpha and the purity of the discrete fields.
+ * Consequences: n_cameras == 1 gives rt_render_features_chain's record bit for bit and coverage (hit ? 1 : 0, 1); for
+ *   n_cameras a power of two, n identical blocks give that record too; hit == (t < inf) still holds; the denoisers' hard
+ *   hit / object / chain gates act on the dominant group, their distance terms on the footprint's mean.
+ * Why at most 64 blocks: one lane per sample and one pixel per lane group keep the reduction inside a wave; guides carry no
+ *   Monte-Carlo noise, only coverage, and 16 blocks are the intended use.
+ * Asynchronous on the context's stream.  The image, the accumulator, the sample counter, the moments, a kept prefix and
+ * pending look-ahead frames stay untouched, as under rt_render_features.  Unsharded contexts only.
+ * rt_read_feature_coverage (bytes = W*H*2*4) and rt_device_feature_coverage give RT_ESTATE until this call has run since the
+ * frame was (re)allocated, and again after a later rt_render_features / rt_render_features_chain: the coverage describes the
+ * records that lie in the buffer.
+ * RT_EINVAL: a NULL cameras or ctx, n_cameras 0 or above RT_FEATURE_CAMERAS_MAX, unknown follow bits, max_chain above
+ * RT_FEATURE_CHAIN_MAX, a sharded context, a wrong `bytes`.  RT_ESTATE: no scene set.  A failed call makes nothing.
+ * rt_debug_plan_feature_cameras (host-only, no context): the launcher's own plan for a width x height frame and n blocks,
+ * out = {log2 of the lanes per pixel, workgroups, threads per workgroup}.  RT_EINVAL: a size outside 1..RT_MAX_DIM, n outside
+ * 1..RT_FEATURE_CAMERAS_MAX, a NULL pointer.
+ */
+#define RT_FEATURE_CAMERAS_MAX 64u
+#define RT_FEATURE_MIXED 4u      /* flags bit 2: the pixel's samples fall into more than one group */
+int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras,
+                               const rt_feature_chain_params *p /* NULL = {0, 0}: first hits */);
+int rt_read_feature_coverage(rt_context *ctx, float *out, size_t bytes);   /* W*H*2 floats */
+int rt_device_feature_coverage(rt_context *ctx, void **d_out);
+int rt_debug_plan_feature_cameras(int width, int height, uint32_t n_cameras, uint32_t out[3]); /* host-only */
 
 /*
  * Edge-avoiding à-trous denoiser (new; the reference has no such entry point): Dammertz et al. 2010, "Edge-Avoiding

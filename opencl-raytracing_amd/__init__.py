@@ -8,9 +8,11 @@ from . import _abi, workloads  # noqa: F401
 from .camera import Camera  # noqa: F401
 from .raytracer import (ARITH_IEEE, ARITH_NAMES, ARITH_ROCM_OCL, ARITH_ROCM_OCL_NOCONTRACT, FOLLOW_ALL,  # noqa: F401
                         FOLLOW_DIELECTRIC, FOLLOW_REFLECTIVE, FOLLOW_REFRACTIVE, LIB_PATH, RayTracer, RtError, check_accel,
-                        feature_chain_signature, load_library, lookahead_plan, make_random_table, sample_units)
+                        feature_chain_signature, load_library, lookahead_plan, make_random_table, plan_feature_cameras,
+                        sample_units)
 from .scene import SceneCreator, SceneError  # noqa: F401
 
 __all__ = ["Camera", "RayTracer", "RtError", "SceneCreator", "SceneError", "workloads", "load_library",
-           "make_random_table", "lookahead_plan", "sample_units", "feature_chain_signature", "FOLLOW_REFLECTIVE",
+           "make_random_table", "lookahead_plan", "sample_units", "feature_chain_signature", "plan_feature_cameras",
+           "FOLLOW_REFLECTIVE",
            "FOLLOW_REFRACTIVE", "FOLLOW_DIELECTRIC", "FOLLOW_ALL", "LIB_PATH"]

@@ -121,6 +121,8 @@ FEATURE = np.dtype([("pos", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)),
 assert FEATURE.itemsize == 80
 FEATURE_HIT = 1
 FEATURE_CUT = 2             # rt_render_features_chain: the terminal has a followed type, max_chain was reached
+FEATURE_MIXED = 4           # rt_render_features_cameras: the pixel's samples fall into more than one (object, chain) group
+FEATURE_CAMERAS_MAX = 64    # RT_FEATURE_CAMERAS_MAX: camera blocks of one rt_render_features_cameras call
 FOLLOW_REFLECTIVE, FOLLOW_REFRACTIVE, FOLLOW_DIELECTRIC = 1, 2, 4   # RT_FOLLOW_*
 FOLLOW_NAMES = {"mirror": FOLLOW_REFLECTIVE, "glass": FOLLOW_REFRACTIVE, "dielectric": FOLLOW_DIELECTRIC}
 FEATURE_CHAIN_MAX = 29
@@ -270,6 +272,10 @@ def camera_prototypes(lib):
     lib.rt_render_spp_cameras.argtypes = [vp, vp, u32, u32]
     lib.rt_debug_plan_camera_samples.argtypes = [C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
     lib.rt_debug_last_camera_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
+    lib.rt_render_features_cameras.argtypes = [vp, vp, u32, C.POINTER(FeatureChainParams)]
+    lib.rt_read_feature_coverage.argtypes = [vp, vp, C.c_size_t]
+    lib.rt_device_feature_coverage.argtypes = [vp, C.POINTER(vp)]
+    lib.rt_debug_plan_feature_cameras.argtypes = [C.c_int, C.c_int, u32, C.POINTER(u32)]
 
 
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)
@@ -302,7 +308,9 @@ def split_features(rec):
             # (as flags & 0xFFFF0000), the cut flag, and flags >> 8 — the word RT_DENOISE_SPLIT_CHAINS compares
             "chain_length": ((rec["flags"] >> 8) & 31).astype(np.uint32),
             "chain_signature": (rec["flags"] & np.uint32(0xFFFF0000)).astype(np.uint32),
-            "cut": (rec["flags"] & FEATURE_CUT) != 0, "chain_word": (rec["flags"] >> 8).astype(np.uint32)}
+            "cut": (rec["flags"] & FEATURE_CUT) != 0, "chain_word": (rec["flags"] >> 8).astype(np.uint32),
+            # rt_render_features_cameras (False otherwise): the pixel's samples fall into more than one group
+            "mixed": (rec["flags"] & FEATURE_MIXED) != 0}
 
 
 def ptr(a):

@@ -1567,6 +1567,116 @@ __global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FramePa
     o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
 }
 
+// Feature records through per-sample cameras (rt_render_features_cameras): lane j < n of a pixel's g = 2^glog2 lanes (one
+// wave holds whole pixels) looks through block j of fp.cams and runs pt_features_chain's loop — the same search, scatter
+// and flags, duplicated here so that the single-camera kernel keeps its code — into five registers instead of memory.
+// No lane leaves before the cross-lane steps: a lane without a sample (j >= n, or a pixel past the frame) skips the
+// search under a branch and carries neutral values.  Then, per pixel:
+//   vote   every lane counts the samples that share its key (object, flags >> 8), reading lanes 0 .. n-1 of its group
+//          only; the maximum of (count << 6) | (63 - j) by the butterfly is (m, j*): the largest group, the smallest j
+//          among equally large ones, and the smallest j inside it;
+//   sums   pos, t, normal, albedo of the HIT samples of every group (a lane that missed or has no sample holds +0) by
+//          group_sum's tree (offsets g/2 .. 1), and the number of hit samples c the same way.
+// Lane j* writes the record: its own discrete fields and direction, RT_FEATURE_MIXED where m < n, the ten sums where it
+// hit (its miss values where it did not), and (c, m) as two uint32 into the coverage buffer.  No division here — under
+// policies 1 and 2 `/` is the 2.5-ulp expansion: pt_features_cameras_finish (rt_amd.hip) divides, for every policy alike.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features_cameras(DeviceScene sc, FrameParams fp, uint32_t follow, uint32_t max_chain,
+                                                           uint32_t n, uint32_t glog2, float4 *__restrict__ out,
+                                                           uint2 *__restrict__ cov) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t g = 1u << glog2;
+    const uint32_t pix = blockIdx.x * (256u >> glog2) + (threadIdx.x >> glog2), j = threadIdx.x & (g - 1u);
+    const bool in_frame = pix < (uint32_t)fp.w * (uint32_t)fp.h;
+    const float none = __uint_as_float(0xFFFFFFFFu);
+    // the record of a lane without a sample: a miss that no vote counts and no sum sees
+    float4 o0 = make_float4(0.0f, 0.0f, 0.0f, INFINITY), o1 = make_float4(0.0f, 0.0f, 0.0f, none);
+    float4 o2 = make_float4(0.0f, 0.0f, 0.0f, none), o3 = make_float4(0.0f, 0.0f, 0.0f, none);
+    float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (in_frame && j < n) {
+        const uint32_t x = pix % (uint32_t)fp.w, y = pix / (uint32_t)fp.w;
+        Ray r = primary_ray(fp.cams + 12u * j, x, y, fp.w, fp.h);
+        const V3 d0 = r.d;
+        float t_sum = 0.0f;
+        uint32_t len = 0u, sig = 0u;
+        bool terminal = false;
+        for (uint32_t k = 0u; k <= max_chain; k++) {   // (pt_features_chain's loop)
+            Nearest nb;
+            hit_primitives<false, ACCEL>(c, r, nb);
+            hit_models<false, ACCEL>(c, r, nb);
+            Hit h;
+            if (!hit_finish<false>(c, r, nb, h)) break;
+            int type;
+            float extra;
+            V3 col;
+            load_material(c, h.mat, type, extra, col);
+            t_sum = k == 0u ? nb.t : t_sum + nb.t;
+            const bool followed = (type == RT_REFLECTIVE && (follow & RT_FOLLOW_REFLECTIVE)) ||
+                                  (type == RT_REFRACTIVE && (follow & RT_FOLLOW_REFRACTIVE)) ||
+                                  (type == RT_DIELECTRIC && (follow & RT_FOLLOW_DIELECTRIC));
+            if (followed && len < max_chain) {
+                sig = pt::chain_signature_step(sig, nb.id);
+                len++;
+                Rnd rnd;  // mirror / glass by rayRefract's rule: no random numbers
+                rnd.v = mk(0.0f, 0.0f, 0.0f);
+                rnd.u = 0.0f;
+                V3 path = mk(1.0f, 1.0f, 1.0f);
+                scatter<false>(c, r, path, h, type == RT_DIELECTRIC ? RT_REFRACTIVE : type, extra, col, rnd);
+                continue;
+            }
+            if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
+            const bool mesh = (nb.id & K_MASK) == K_MESH;
+            const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
+            o0 = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
+            o1 = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
+            o2 = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
+            o3 = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
+            o4 = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
+            terminal = true;
+            break;
+        }
+        if (!terminal) {   // the chain left the scene
+            o3 = make_float4(d0.x, d0.y, d0.z, none);
+            o4.w = __uint_as_float((len << 8) | (sig & 0xFFFF0000u));
+        }
+    }
+    // ---- the vote: lanes 0 .. n-1 of the group all hold a sample (or none does, past the frame: nothing is written then)
+    const uint32_t flags = __float_as_uint(o4.w), key_o = __float_as_uint(o1.w), key_c = flags >> 8;
+    const uint32_t lane0 = (threadIdx.x & 63u) & ~(g - 1u);
+    uint32_t same = 0u;
+    for (uint32_t s = 0u; s < n; s++)
+        same += (__shfl(key_o, (int)(lane0 + s)) == key_o && __shfl(key_c, (int)(lane0 + s)) == key_c) ? 1u : 0u;
+    uint32_t best = j < n ? (same << 6) | (63u - j) : 0u;
+    const bool hit = (flags & RT_FEATURE_HIT) != 0u;
+    uint32_t hits = hit ? 1u : 0u;
+    float sum[10] = {hit ? o0.x : 0.0f, hit ? o0.y : 0.0f, hit ? o0.z : 0.0f, hit ? o0.w : 0.0f, hit ? o1.x : 0.0f,
+                     hit ? o1.y : 0.0f, hit ? o1.z : 0.0f, hit ? o2.x : 0.0f, hit ? o2.y : 0.0f, hit ? o2.z : 0.0f};
+    for (uint32_t off = g >> 1; off > 0u; off >>= 1) {
+        best = max(best, (uint32_t)__shfl_xor(best, off));
+        hits += __shfl_xor(hits, off);
+#pragma unroll
+        for (int k = 0; k < 10; k++) sum[k] += __shfl_xor(sum[k], off);
+    }
+    if (!in_frame || j != 63u - (best & 63u)) return;   // (past every cross-lane step)
+    const uint32_t m = best >> 6;
+    if (hit) {
+        o0 = make_float4(sum[0], sum[1], sum[2], sum[3]);
+        o1 = make_float4(sum[4], sum[5], sum[6], o1.w);
+        o2 = make_float4(sum[7], sum[8], sum[9], o2.w);
+    }
+    o4.w = __uint_as_float(flags | (m < n ? RT_FEATURE_MIXED : 0u));
+    float4 *o = out + 5 * (size_t)pix;
+    o[0] = o0;
+    o[1] = o1;
+    o[2] = o2;
+    o[3] = o3;
+    o[4] = o4;
+    cov[pix] = make_uint2(hits, m);
+}
+
 // ---- unit probes of the device routines (tests only; rt_debug_hit / rt_debug_material / rt_debug_div3) -----------
 // One work-item per record; the routines are the very ones the trace kernels inline (hit_primitives' sphere_t /
 // plane_t / lens_t, triangle_t, hit_scene + hit_finish, scatter), so a unit vector that matches the oracle here
@@ -2172,6 +2282,30 @@ int ks_launch_features_chain(rt_context *ctx, const FrameParams &fp, const Devic
     return RT_OK;
 }
 
+// rt_debug_plan_feature_cameras: one lane per sample, g = 2^ceil(log2 n) lanes per pixel, whole pixels per 256-thread
+// workgroup (at most 2^28 pixels of 4 .. 256 to a workgroup: the grid fits 32 bits)
+FeatureCamerasPlan ks_plan_feature_cameras(uint32_t pixels, uint32_t n) {
+    FeatureCamerasPlan p;
+    p.glog2 = 0u;
+    while ((1u << p.glog2) < n) p.glog2++;
+    const uint32_t per_wg = 256u >> p.glog2;
+    p.workgroups = (pixels + per_wg - 1u) / per_wg;
+    p.block_size = 256u;
+    return p;
+}
+
+int ks_launch_features_cameras(rt_context *ctx, FrameParams fp, const DeviceScene &sc, const float *d_cams, uint32_t n,
+                               uint32_t follow, uint32_t max_chain, rt_feature *d_out, uint2 *d_cov) {
+    if (!d_cams || n < 1u || n > RT_FEATURE_CAMERAS_MAX) return fail(ctx, RT_EINVAL, "a feature launch takes 1 .. %u camera blocks", RT_FEATURE_CAMERAS_MAX);
+    fp.cams = d_cams;   // (the union with la_image: la_ring is NULL, nothing reads la_image)
+    const FeatureCamerasPlan plan = ks_plan_feature_cameras((uint32_t)fp.w * (uint32_t)fp.h, n);
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features_cameras<true> : pt_features_cameras<false>, dim3(plan.workgroups),
+                       dim3(plan.block_size), 0, ctx->stream, sc, fp, follow, max_chain, n, plan.glog2, o, d_cov);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -2237,7 +2371,8 @@ const pt::KernelSet g_kernel_set = {
 #endif
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
-    ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples};
+    ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
+    ks_plan_feature_cameras};
 
 }  // namespace
 

@@ -6,6 +6,11 @@
 
 namespace pt {
 
+// the launch of pt_features_cameras (rt_debug_plan_feature_cameras' three words)
+struct FeatureCamerasPlan {
+    uint32_t glog2, workgroups, block_size;
+};
+
 struct KernelSet {
     int arith;             // RT_ARITH_* this set was compiled for
     const char *name;
@@ -57,6 +62,13 @@ struct KernelSet {
                           float4 *accum, float *m2);
     // rt_debug_plan_camera_samples: that launcher's choice of kernel and launch geometry — a pure function, no device
     rt_camera_plan (*plan_camera_samples)(const rt_camera_facts &facts);
+    // rt_render_features_cameras: pt_features_cameras, the records of n <= RT_FEATURE_CAMERAS_MAX blocks of d_cams (n x 12
+    // floats on the device) per pixel reduced to one record per pixel in d_out — the ten float sums undivided — and the
+    // counts (hit samples, dominant group) as two uint32 per pixel in d_cov; pt_features_cameras_finish (rt_amd.hip) divides
+    int (*launch_features_cameras)(rt_context *ctx, FrameParams fp, const DeviceScene &sc, const float *d_cams, uint32_t n,
+                                   uint32_t follow, uint32_t max_chain, rt_feature *d_out, uint2 *d_cov);
+    // rt_debug_plan_feature_cameras: that launcher's geometry for a frame of `pixels` pixels — a pure function, no device
+    FeatureCamerasPlan (*plan_feature_cameras)(uint32_t pixels, uint32_t n);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

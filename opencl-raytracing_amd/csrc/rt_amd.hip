@@ -63,6 +63,27 @@ __global__ __launch_bounds__(256) void pt_resolve(const float4 *__restrict__ acc
     image[i] = o;
 }
 
+// rt_render_features_cameras, behind pt_features_cameras (pt_kernels.hip): one work-item per pixel.  That kernel leaves the
+// ten floats of pos, t, normal, albedo of a hit record as SUMS over the pixel's hit samples and the coverage words as the
+// counts (c hit samples, m samples in the dominant group).  The quotients are taken HERE, in the translation unit that is
+// compiled with the correctly rounded divide whatever the arithmetic policy: S / (float)c in place, and the coverage
+// ((float)c / (float)n, (float)m / (float)n).
+__global__ __launch_bounds__(256) void pt_features_cameras_finish(float4 *__restrict__ rec, float2 *__restrict__ cov, uint32_t pixels,
+                                                                  uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= pixels) return;
+    const uint2 cm = reinterpret_cast<const uint2 *>(cov)[i];
+    float4 *r = rec + 5 * (size_t)i;
+    if (__float_as_uint(r[4].w) & RT_FEATURE_HIT) {
+        const float c = (float)cm.x;
+        const float4 a = r[0], b = r[1], d = r[2];
+        r[0] = make_float4(a.x / c, a.y / c, a.z / c, a.w / c);
+        r[1] = make_float4(b.x / c, b.y / c, b.z / c, b.w);
+        r[2] = make_float4(d.x / c, d.y / c, d.z / c, d.w);
+    }
+    cov[i] = make_float2((float)cm.x / (float)n, (float)cm.y / (float)n);
+}
+
 // Adaptive sampling (rt_render_adaptive), after each round: one wave per decision block, PT_MERGE_WAVES per workgroup.  A round has traced the active
 // blocks into `scratch`, which is zero everywhere else, so scratch = 0 + the launch's per-pixel sum exactly, and
 // accum + scratch is, bit for bit, what rt_render_spp of that launch would have made of accum.  Per pixel of an active
@@ -1249,6 +1270,7 @@ int render_features_with(rt_context *ctx, const float camera[12], int params_ok,
     const int rc = launch(fp, sc, f.records.p);
     if (rc != RT_OK) return rc;
     f.ready = true;
+    f.coverage_ready = false;   // (rt_render_features_cameras sets it: the coverage describes ITS records only)
     return RT_OK;
 }
 }  // namespace
@@ -1274,6 +1296,74 @@ int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_f
     return render_features_with(ctx, camera, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
         return ctx->ks->launch_features_chain(ctx, fp, sc, p->follow, p->max_chain, out);
     });
+}
+
+int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_feature_chain_params *p) {
+    const int rc = check_ready(ctx, cameras);
+    if (rc) return rc;
+    const rt_feature_chain_params first_hits = {0u, 0u};
+    if (!p) p = &first_hits;
+    int ok = RT_OK;
+    if (n_cameras < 1u || n_cameras > RT_FEATURE_CAMERAS_MAX)
+        ok = fail(ctx, RT_EINVAL, "%u camera blocks outside 1..%u", n_cameras, RT_FEATURE_CAMERAS_MAX);
+    else if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
+        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
+    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    // (cameras: the first block fills FrameParams::cam, which pt_features_cameras does not read)
+    const int done = render_features_with(ctx, cameras, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
+        rt_context::Features &f = ctx->features;
+        const size_t pixels = (size_t)ctx->width * ctx->height;
+        if (!f.coverage.p) HIP_TRY(ctx, f.coverage.alloc(pixels));
+        int r = ensure_cameras(ctx);
+        if (r != RT_OK) return r;
+        // the blocks go through table k of the ring, as a launch of rt_render_spp_cameras sends its own
+        rt_context::Cameras &cm = ctx->cameras;
+        const uint32_t k = (uint32_t)(cm.launches % rt_context::Cameras::RING);
+        const size_t at = (size_t)k * RT_SPP_PER_LAUNCH * 12u;
+        if (cm.launches >= rt_context::Cameras::RING) HIP_TRY(ctx, hipEventSynchronize(cm.read[k]));   // (table k's last reader)
+        memcpy(cm.h_table + at, cameras, (size_t)n_cameras * 12u * sizeof(float));
+        HIP_TRY(ctx, hipMemcpyAsync(cm.table.p + at, cm.h_table + at, (size_t)n_cameras * 12u * sizeof(float), hipMemcpyHostToDevice,
+                                    ctx->stream));
+        cm.launches++;
+        r = ctx->ks->launch_features_cameras(ctx, fp, sc, cm.table.p + at, n_cameras, p->follow, p->max_chain, out,
+                                             reinterpret_cast<uint2 *>(f.coverage.p));
+        if (r == RT_OK) {
+            hipLaunchKernelGGL(pt_features_cameras_finish, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), 0, ctx->stream,
+                               reinterpret_cast<float4 *>(out), f.coverage.p, (uint32_t)pixels, n_cameras);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) r = fail(ctx, RT_EHIP, "pt_features_cameras_finish: %s", hipGetErrorString(e));
+        }
+        HIP_TRY(ctx, hipEventRecord(cm.read[k], ctx->stream));
+        return r;
+    });
+    if (done == RT_OK) ctx->features.coverage_ready = true;
+    return done;
+}
+
+int rt_read_feature_coverage(rt_context *ctx, float *out, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const rt_context::Features &f = ctx->features;
+    return read_back(ctx, out, bytes, f.coverage.p, (size_t)ctx->width * ctx->height * sizeof(float2), "feature coverage",
+                     f.coverage_ready, "rt_render_features_cameras");
+}
+
+int rt_device_feature_coverage(rt_context *ctx, void **d_out) {
+    if (!ctx || !d_out) return RT_EINVAL;
+    if (!ctx->features.coverage_ready)
+        return fail(ctx, RT_ESTATE, "no rt_render_features_cameras call since the feature records were last written");
+    *d_out = ctx->features.coverage.p;
+    return RT_OK;
+}
+
+int rt_debug_plan_feature_cameras(int width, int height, uint32_t n_cameras, uint32_t out[3]) {
+    if (!out || width < 1 || width > RT_MAX_DIM || height < 1 || height > RT_MAX_DIM || n_cameras < 1u || n_cameras > RT_FEATURE_CAMERAS_MAX)
+        return fail(nullptr, RT_EINVAL, "rt_debug_plan_feature_cameras: a size outside 1..%d, a count outside 1..%u or a NULL pointer",
+                    RT_MAX_DIM, RT_FEATURE_CAMERAS_MAX);
+    const pt::FeatureCamerasPlan p = pt::kernel_set_a2()->plan_feature_cameras((uint32_t)width * (uint32_t)height, n_cameras);   // (host code: the same in every policy)
+    out[0] = p.glog2;
+    out[1] = p.workgroups;
+    out[2] = p.block_size;
+    return RT_OK;
 }
 
 int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out) {

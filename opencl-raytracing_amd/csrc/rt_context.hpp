@@ -251,6 +251,10 @@ struct rt_context {
     struct Features {
         DevBuf<rt_feature> records;     // W x H
         bool ready = false;             // written since the frame was (re)allocated
+        // rt_render_features_cameras, allocated on its first call: W x H x (hit share, dominant share) — two uint32 counts
+        // between pt_features_cameras and its finishing pass, two floats after it
+        DevBuf<float2> coverage;
+        bool coverage_ready = false;    // `coverage` describes the records that lie in `records`
     } features;
     // denoiser (rt_denoise), allocated on its first call: reset by alloc_frame and by a failed allocation
     struct Denoise {

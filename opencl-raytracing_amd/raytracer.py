@@ -37,6 +37,7 @@ SYMBOLS = (
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy", "rt_debug_queue_sums",
     "rt_debug_plan_samples", "rt_debug_last_sample_plan",
     "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
+    "rt_render_features_cameras", "rt_read_feature_coverage", "rt_device_feature_coverage", "rt_debug_plan_feature_cameras",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -259,6 +260,17 @@ def plan_camera_samples(**facts):
     return p.as_dict()
 
 
+def plan_feature_cameras(width, height, n):
+    """The launch rt_render_features_cameras plans for a width x height frame and n camera blocks
+    (rt_debug_plan_feature_cameras: the launcher's own function; host-only, no device needed) → (log2 of the lanes per
+    pixel, workgroups, threads per workgroup)."""
+    out = (C.c_uint32 * 3)()
+    rc = load_library().rt_debug_plan_feature_cameras(int(width), int(height), int(n), out)
+    if rc:
+        raise RtError(rc, "rt_debug_plan_feature_cameras: invalid argument")
+    return tuple(int(v) for v in out)
+
+
 def _cam_blocks(blocks):
     blocks = np.ascontiguousarray(blocks, dtype=np.float32)
     if blocks.ndim != 2 or blocks.shape[1] != 12:
@@ -460,6 +472,31 @@ class RayTracer:
         then work on these.  follow 0 or max_chain 0: renderFeatures."""
         p = _abi.FeatureChainParams(int(follow), int(max_chain))
         self._check(self._lib.rt_render_features_chain(self._ctx, _cam_block(camera).ctypes.data, C.byref(p)))
+
+    def renderFeaturesCameras(self, blocks, follow=0, max_chain=0):
+        """Feature records through per-sample cameras (rt_render_features_cameras, asynchronous): the records of the
+        n <= 64 camera blocks `blocks` (float32[n, 12], e.g. Camera.sampleBlocks — the guides that belong to a
+        renderFrameCameras frame) reduced to one record per pixel: the discrete fields of the dominant (object, chain)
+        group, position, depth, normal and albedo averaged over the hit samples, FEATURE_MIXED where the samples disagree.
+        `follow` / `max_chain` as renderFeaturesChain (0, 0: first hits).  Replaces the feature records and makes
+        featureCoverage()."""
+        blocks = _cam_blocks(blocks)
+        p = _abi.FeatureChainParams(int(follow), int(max_chain))
+        self._check(self._lib.rt_render_features_cameras(self._ctx, blocks.ctypes.data if len(blocks) else None, len(blocks),
+                                                         C.byref(p)))
+
+    def featureCoverage(self):
+        """The last renderFeaturesCameras call's coverage → (h, w, 2) float32: the share of the samples that hit (the
+        anti-aliased alpha) and the share in the dominant group (rt_read_feature_coverage)."""
+        out = np.empty((self.height, self.width, 2), dtype=np.float32)
+        self._check(self._lib.rt_read_feature_coverage(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def deviceFeatureCoverage(self):
+        """Device address of the W x H x 2 coverage floats (rt_device_feature_coverage)."""
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_feature_coverage(self._ctx, C.byref(p)))
+        return p.value
 
     def featureRecords(self):
         """The last renderFeatures / renderFeaturesChain call's records → (h, w) array of _abi.FEATURE."""
@@ -692,6 +729,7 @@ class RayTracer:
 
     planSamples = staticmethod(plan_samples)
     planCameraSamples = staticmethod(plan_camera_samples)
+    planFeatureCameras = staticmethod(plan_feature_cameras)
 
     def lastSamplePlan(self):
         """(facts, plan) of the last fused launch's sample stage, as dicts of the fields of _abi.SampleFacts and

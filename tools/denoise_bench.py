@@ -13,10 +13,16 @@ two stages of the fused 64-spp call (rt_stage_ms_history, median of --reps) with
 types followed, median of --reps), how many pixels have a chain, and per spp the RMSE of rt_denoise_variance guided by the
 first-hit records, by the chain records, and by the chain records with RT_DENOISE_SPLIT_CHAINS — on the whole frame and
 on the pixels with a chain — with the filter's device time without and with the flag.
+--aa-guides is about the guides of anti-aliased frames (rt_render_features_cameras): per scene the device time of that call
+at 16 blocks (median and min .. max of --reps), 16 x the single-camera rt_render_features time of the same run, and per
+sample count (jittered frames of 4 / 16 / 64 samples through rt_render_spp_cameras, truth a jittered --truth-spp frame) the
+RMSE of rt_denoise and rt_denoise_variance guided by the central records and by the 16-block records, on the whole frame
+and on the pixels with RT_FEATURE_MIXED; then a depth-of-field row (C2, aperture 0.05, focus 8).  With --profile-only it
+runs just the 16-block call --reps times per scene, and --trace FILE then prints the two kernels' times from such a run.
 --profile-only runs just the denoise (with --variance-guided: rt_denoise_variance), --reps times, for a `rocprofv3 --kernel-trace --stats` run; --trace FILE turns
 such a run's kernel_trace.csv into per-iteration times.
 
-    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided | --measured | --chain]
+    python tools/denoise_bench.py [--scenes c2,c3,c5] [--size 1920x1080] [--json out.json] [--sweep | --variance-guided | --measured | --chain | --aa-guides]
 """
 import argparse
 import csv
@@ -44,6 +50,22 @@ def per_iteration(trace, iterations):
     return [float(np.median(us[i::iterations])) for i in range(iterations)]
 
 
+# the cameras of the workloads (workloads.py): position, yaw, pitch — Camera.sampleBlocks needs the Camera, not its block
+POSES = {"c2": ((-8, -1, -8), 45.0, 0.0), "c3": ((-6, -2, -7), 40.0, 8.0), "c5": ((-7, 0, -7), 45.0, 8.0)}
+GUIDE_BLOCKS = 16
+
+
+def guide_kernels(trace):
+    """Times (us: median, min, max) of pt_features_cameras and pt_features_cameras_finish from a rocprofv3 kernel_trace.csv
+    of --aa-guides --profile-only runs, per kernel name."""
+    out = {}
+    for r in csv.DictReader(open(trace)):
+        if "pt_features_cameras" in r["Kernel_Name"]:
+            key = "pt_features_cameras_finish" if "finish" in r["Kernel_Name"] else r["Kernel_Name"].split("(")[0]
+            out.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    return {k: dict(n=len(v), median=float(np.median(v)), min=float(min(v)), max=float(max(v))) for k, v in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c2,c3,c5")
@@ -54,10 +76,14 @@ def main():
     ap.add_argument("--variance-guided", action="store_true")
     ap.add_argument("--measured", action="store_true")
     ap.add_argument("--chain", action="store_true")
+    ap.add_argument("--aa-guides", action="store_true")
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--trace", default=None)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    if a.trace and a.aa_guides:
+        print(json.dumps(guide_kernels(a.trace), indent=1))
+        return
     if a.trace:
         print(json.dumps({"pt_atrous_us_per_iteration": per_iteration(a.trace, D["iterations"])}))
         return
@@ -86,6 +112,57 @@ def main():
         t.denoiseOnDevice()
         if a.variance_guided:
             t.denoiseVarianceOnDevice()
+        if a.aa_guides:
+            pos, yaw, pitch = POSES[name]
+            cam = rt.Camera(60, np.float32(w) / np.float32(h), pos, yaw, pitch)
+            assert np.array_equal(cam.transferData(), wl.camera)
+            variants = [(name, 0.0)] + ([(name + " aperture 0.05 focus 8", 0.05)] if name == "c2" else [])
+            for label, aperture in variants:
+                def blocks(n):
+                    return cam.sampleBlocks(n, 0, w, h, True, aperture, 8.0)
+                guides = blocks(GUIDE_BLOCKS)
+                t.renderFeaturesCameras(guides)                   # warm-up (code object, coverage buffer, camera tables)
+                if a.profile_only:
+                    for _ in range(a.reps):
+                        t.renderFeaturesCameras(guides)
+                    t.sync()
+                    continue
+                ms_g = [timed(lambda: t.renderFeaturesCameras(guides)) for _ in range(a.reps)]
+                ms_1 = [timed(lambda: t.renderFeatures(wl.camera)) for _ in range(a.reps)]
+                t.renderFeaturesCameras(guides)
+                mixed_np = t.features()["mixed"]
+                mixed = torch.as_tensor(mixed_np, device="cuda")
+                t.clear()
+                t.renderSamplesCameras(blocks(a.truth_spp), 0)
+                t.resolve()
+                t.sync()
+                truth_aa = dev(t.deviceImage()).clone()
+
+                def rmse2(buf):
+                    t.sync()
+                    d2 = (dev(buf) - truth_aa) ** 2
+                    return float(torch.sqrt(d2.mean())), float(torch.sqrt(d2[mixed].mean()))
+
+                for spp in (4, 16, 64):
+                    t.clear()
+                    t.renderSamplesCameras(blocks(spp), 0)
+                    t.resolve()
+                    r = dict(scene=label, spp=spp, mixed=int(mixed_np.sum()), rmse_noisy=rmse2(t.deviceImage()),
+                             ms_guides=float(np.median(ms_g)), ms_guides_min=float(min(ms_g)), ms_guides_max=float(max(ms_g)),
+                             ms_features=float(np.median(ms_1)), ms_features_min=float(min(ms_1)), ms_features_max=float(max(ms_1)))
+                    for guide in ("central", "blocks"):
+                        if guide == "central":
+                            t.renderFeatures(wl.camera)
+                        else:
+                            t.renderFeaturesCameras(guides)
+                        t.denoiseOnDevice()
+                        r["rmse_denoise_" + guide] = rmse2(t.deviceDenoised())
+                        t.denoiseVarianceOnDevice()
+                        r["rmse_variance_" + guide] = rmse2(t.deviceDenoised())
+                    rows.append(r)
+            t.setStream(None)
+            t.close()
+            continue
         if a.profile_only:
             for _ in range(a.reps):
                 t.denoiseVarianceOnDevice() if a.variance_guided else t.denoiseOnDevice()
@@ -205,7 +282,26 @@ def main():
         t.close()
     if a.profile_only:
         return
-    if a.sweep:
+    if a.aa_guides:
+        print("| scene | MIXED pixels | rt_render_features_cameras, %d blocks: ms (min .. max) | rt_render_features ms (min .. max) | %d x that |"
+              % (GUIDE_BLOCKS, GUIDE_BLOCKS))
+        print("|---|---:|---:|---:|---:|")
+        for label in dict.fromkeys(r["scene"] for r in rows):
+            r = next(r for r in rows if r["scene"] == label)
+            print("| %s | %d | %.3f (%.3f .. %.3f) | %.3f (%.3f .. %.3f) | %.3f |" % (
+                label.upper(), r["mixed"], r["ms_guides"], r["ms_guides_min"], r["ms_guides_max"], r["ms_features"],
+                r["ms_features_min"], r["ms_features_max"], GUIDE_BLOCKS * r["ms_features"]))
+        print()
+        print("| scene | spp | pixels | RMSE noisy | rt_denoise, central guides | rt_denoise, %d-block guides | rt_denoise_variance, central | rt_denoise_variance, %d-block |"
+              % (GUIDE_BLOCKS, GUIDE_BLOCKS))
+        print("|---|---:|---|---:|---:|---:|---:|---:|")
+        for r in rows:
+            for k, what in ((0, "whole frame"), (1, "MIXED")):
+                print("| %s | %d | %s | %.4f | %.4f | %.4f | %.4f | %.4f |" % (
+                    r["scene"].upper(), r["spp"], what, r["rmse_noisy"][k], r["rmse_denoise_central"][k], r["rmse_denoise_blocks"][k],
+                    r["rmse_variance_central"][k], r["rmse_variance_blocks"][k]))
+        out = rows
+    elif a.sweep:
         by = {}
         for r in sweep:
             by.setdefault(tuple(r["sigma"]), []).append(r["rmse"] / r["noisy"])
