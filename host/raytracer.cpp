@@ -92,6 +92,13 @@ rt_adaptive_stats RayTracer::renderAdaptive(const Camera *camera, const rt_adapt
     return st;
 }
 
+rt_adaptive_stats RayTracer::renderAdaptiveCameras(const std::vector<float> &blocks, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive_cameras(ctx, blocks.empty() ? nullptr : blocks.data(), (uint32_t)(blocks.size() / 12), &params, &st));
+    transferImage();
+    return st;
+}
+
 std::vector<uint32_t> RayTracer::sampleCounts() {
     std::vector<uint32_t> c((size_t)width * height);
     check(rt_read_sample_counts(ctx, c.data(), c.size() * sizeof(uint32_t)));

@@ -64,6 +64,9 @@ public:
     const float *renderFrameCameras(const std::vector<float> &blocks);
     // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
+    // the same through per-sample camera blocks (rt_render_adaptive_cameras): sample j of every pixel through block j of
+    // `blocks` (params.max_spp x 12 floats, e.g. Camera::sampleBlocks)
+    rt_adaptive_stats renderAdaptiveCameras(const std::vector<float> &blocks, const rt_adaptive_params &params);
     std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major
     const float *lastImage() const { return pixels.data(); }  // what the last read-back returned
     // first-hit feature records of every pixel (rt_render_features, asynchronous) and their read-back

@@ -7,6 +7,7 @@
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
 //              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
+//          [--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 // --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
 // --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
 // sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
@@ -15,6 +16,10 @@
 // frame: the records of the run's first N sample cameras (its jitter, aperture and focus) reduced to one per pixel
 // (rt_render_features_cameras; --follow / --max-chain are honoured), which the filter and --aov then use; --aov also writes
 // PREFIX_coverage.pfm: per pixel (share of the N samples that hit, share in the dominant group, 0).
+// --adaptive-cameras THRESHOLD (with --aa or --aperture R --focus D; refused with --adaptive and --progressive) renders such
+// a frame adaptively (rt_render_adaptive_cameras): --adaptive's rounds, --batch, --min-spp, --spp (the maximum, default 1024)
+// and --counts, with sample j of every pixel through block j of the run's --spp sample cameras; --denoise, --aov and
+// --aa-guides work as with --spp.
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -65,7 +70,8 @@ static void usage() {
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
-                 "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]\n";
+                 "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
+                 "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]\n";
     std::exit(2);
 }
 
@@ -142,7 +148,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 0xC0FFEE;
     bool progressive = false;
     long lookahead = -1;   // (-1: the library's default)
-    bool adaptive = false, spp_given = false;
+    bool adaptive = false, adaptive_cameras = false, spp_given = false;
     float threshold = 0.0f;
     long batch = 0, min_spp = 0;
     std::string out_counts;
@@ -180,6 +186,12 @@ int main(int argc, char **argv) {
         else if ((v = val("--raw"))) out_raw = v;
         else if ((v = val("--device"))) device = std::atoi(v);
         else if ((v = val("--dump-scene"))) dump_scene = v;
+        else if ((v = val("--adaptive-cameras"))) {
+            char *end = nullptr;
+            threshold = std::strtof(v, &end);
+            if (!*v || *end || !(threshold >= 0.0f) || !std::isfinite(threshold)) usage();
+            adaptive_cameras = true;
+        }
         else if ((v = val("--adaptive"))) {
             char *end = nullptr;
             threshold = std::strtof(v, &end);
@@ -222,7 +234,8 @@ int main(int argc, char **argv) {
         else usage();
     }
     if (spp < 1 || w < 1 || h < 1) usage();
-    if (!adaptive && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
+    if (adaptive_cameras && (adaptive || progressive)) usage();            // one way to spend the samples
+    if (!adaptive && !adaptive_cameras && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
     if (!denoise && (dn_iterations || sigmas_given || variance_guided || sigma_l_given)) usage();   // denoise-only flags
     if ((sigma_l_given || measured) && !variance_guided) usage();
     if (follow && !denoise && aov_prefix.empty()) usage();                 // --follow guides --denoise and / or fills --aov
@@ -237,10 +250,11 @@ int main(int argc, char **argv) {
                      "all samples through one camera: use --spp" << std::endl;
         return 2;
     }
+    if (adaptive_cameras && !cameras) usage();                             // needs the per-sample cameras of --aa / --aperture
     if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
     if (aa_guides && (!cameras || (!denoise && aov_prefix.empty()))) usage();   // guides of a per-sample-camera frame, for --denoise / --aov
     if (!dn_iterations) dn_iterations = 5;
-    if (adaptive) {
+    if (adaptive || adaptive_cameras) {
         if (progressive) usage();
         if (!batch) batch = 64;
         if (!min_spp) min_spp = 2 * batch;
@@ -289,6 +303,10 @@ int main(int argc, char **argv) {
         rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
         st = tracer.renderAdaptive(&camera, p);
         img = tracer.lastImage();
+    } else if (adaptive_cameras) {
+        rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
+        st = tracer.renderAdaptiveCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus), p);
+        img = tracer.lastImage();
     } else if (progressive) {
         if (lookahead >= 0) tracer.setLookahead((int)lookahead);
         tracer.render(&camera);
@@ -300,8 +318,8 @@ int main(int argc, char **argv) {
         img = tracer.renderFrame(&camera, (uint32_t)spp);
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (adaptive) {
-        std::cout << w << "x" << h << " adaptive threshold " << threshold << " batch " << batch << " spp " << min_spp
+    if (adaptive || adaptive_cameras) {
+        std::cout << w << "x" << h << (adaptive_cameras ? " adaptive per-sample cameras threshold " : " adaptive threshold ") << threshold << " batch " << batch << " spp " << min_spp
                   << ".." << spp << ": " << st.rounds << " rounds, mean " << (double)st.pixel_samples / ((double)w * h)
                   << " spp, " << st.blocks_at_max << " of " << st.blocks << " blocks at max, " << sec * 1e3
                   << " ms incl. read-back" << std::endl;

@@ -343,6 +343,27 @@ int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes);
 int rt_read_block_error(rt_context *ctx, float *err, size_t bytes);
 
 /*
+ * Adaptive sampling through per-sample camera blocks (new): rt_render_adaptive for anti-aliased, defocused or moving
+ * frames.  `cameras` is a host pointer to n_cameras x 12 floats, copied during the call; n_cameras must equal
+ * p->max_spp: block j is the camera of sample j.  Round k traces samples k*batch .. k*batch+c-1 of every pixel of a
+ * still-active block through blocks k*batch .. k*batch+c-1, so a pixel whose count is n holds exactly samples 0 .. n-1
+ * through blocks 0 .. n-1 and each round adds, bit for bit, what rt_render_spp_cameras(cameras + 12*k*batch, k*batch, c)
+ * would have added to it.
+ *   - Parameters, estimator, stopping rule, rt_adaptive_stats, rt_read_sample_counts and rt_read_block_error are
+ *     rt_render_adaptive's.  With max_spp identical blocks the accumulator, the counts, the block errors and the stats
+ *     therefore equal rt_render_adaptive(block, p)'s, bit for bit.
+ *   - A self-contained clear + rounds + resolve like rt_render_adaptive: synchronous, unsharded contexts only; it starts the
+ *     sample moments when RT_OPT_MOMENTS is 1 and drops pending look-ahead frames.  The feature records and a kept prefix
+ *     (RT_OPT_PREFIX_CACHE) stay as they are: camera launches use none of the prefix buffers.
+ *   - Options as under rt_render_spp_cameras, none changes a bit: RT_OPT_SAMPLE_QUEUE 0, enabled counters and RT_OPT_MOMENTS 1
+ *     run the fixed-lane camera kernel; RT_OPT_ACCEL, RT_OPT_WAVE_FILL and RT_OPT_MAX_THREADS_PER_LAUNCH are honoured.
+ * RT_EINVAL: what rt_render_adaptive gives, a NULL `cameras`, n_cameras != max_spp.  RT_ESTATE: no scene set.  A failed
+ * call changes nothing.
+ */
+int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
+                               rt_adaptive_stats *out);
+
+/*
  * First-hit feature buffers (new; the reference has no such entry point).  One record per pixel of the frame,
  * row-major W x H in the layout of rt_read_image: the pixel's primary ray (no jitter, raytracer.cl:500-505, so one
  * first hit per pixel) through the same nearest-hit search and winner rebuild as the trace kernels, under the

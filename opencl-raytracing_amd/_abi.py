@@ -89,6 +89,7 @@ def adaptive_prototypes(lib):
     lib.rt_render_adaptive.argtypes = [vp, vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
     lib.rt_read_sample_counts.argtypes = [vp, vp, sz]
     lib.rt_read_block_error.argtypes = [vp, vp, sz]
+    lib.rt_render_adaptive_cameras.argtypes = [vp, vp, C.c_uint32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
 
 
 def block_error_reference(accum, half, block_w, block_h):

@@ -2172,11 +2172,13 @@ static RenderKernel camera_render_kernel(bool count, bool accel) {   // [COUNT][
 // One launch of a camera call: `count` blocks at d_cams.  cam0 (the first block) fills FrameParams::cam, which no camera
 // kernel reads.  Slot ranges as launch_render and launch_fused cut them (RT_OPT_MAX_THREADS_PER_LAUNCH).  Nothing here
 // reads or writes the slot buffers or the prefix cache; the staged scene block is the context's, refreshed as launch_fused
-// refreshes it.
+// refreshes it.  mask != NULL (rt_render_adaptive_cameras): only the pixels of active decision blocks are traced — the camera
+// kernels test pixel_active where they take ownership of a slot; the plan and the grid are those of the unmasked launch.
 int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
-                   float4 *accum, float *m2) {
+                   float4 *accum, const BlockMask *mask, float *m2) {
     if (!d_cams || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
     FrameParams fp = frame_params(ctx, cam0, first, count, glog2);
+    apply_mask(fp, mask);
     fp.m2 = m2;
     fp.cams = d_cams;
     const DeviceScene sc = device_scene(ctx);

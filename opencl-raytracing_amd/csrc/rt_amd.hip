@@ -1066,6 +1066,30 @@ int ensure_cameras(rt_context *ctx) {
     HIP_TRY(ctx, cm.table.alloc(floats));
     return RT_OK;
 }
+
+// One launch's blocks on their way to the device: `c` <= RT_SPP_PER_LAUNCH blocks go into table k of the ring — after the
+// table's last reader, through the pinned host table, onto the stream.  The launch then reads `d` (cam0: `h`), and
+// camera_table_read records its kernels as the table's reader.  Every call that sends camera blocks goes through these two.
+struct CameraTable {
+    uint32_t k;
+    const float *d, *h;
+};
+int camera_table_send(rt_context *ctx, const float *blocks, uint32_t c, CameraTable *t) {
+    rt_context::Cameras &cm = ctx->cameras;
+    t->k = (uint32_t)(cm.launches % rt_context::Cameras::RING);
+    const size_t at = (size_t)t->k * RT_SPP_PER_LAUNCH * 12u;
+    if (cm.launches >= rt_context::Cameras::RING) HIP_TRY(ctx, hipEventSynchronize(cm.read[t->k]));   // (table k's last reader)
+    memcpy(cm.h_table + at, blocks, (size_t)c * 12u * sizeof(float));
+    HIP_TRY(ctx, hipMemcpyAsync(cm.table.p + at, cm.h_table + at, (size_t)c * 12u * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    cm.launches++;
+    t->d = cm.table.p + at;
+    t->h = cm.h_table + at;
+    return RT_OK;
+}
+int camera_table_read(rt_context *ctx, const CameraTable &t) {
+    HIP_TRY(ctx, hipEventRecord(ctx->cameras.read[t.k], ctx->stream));
+    return RT_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -1077,19 +1101,15 @@ int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_
         return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
-    rt_context::Cameras &cm = ctx->cameras;
     // (launches of RT_SPP_PER_LAUNCH blocks, as rt_render_spp cuts its calls: the accumulator is the sum of their sums)
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        const uint32_t k = (uint32_t)(cm.launches % rt_context::Cameras::RING);
-        const size_t at = (size_t)k * RT_SPP_PER_LAUNCH * 12u;
-        if (cm.launches >= rt_context::Cameras::RING) HIP_TRY(ctx, hipEventSynchronize(cm.read[k]));   // (table k's last reader)
-        memcpy(cm.h_table + at, cameras + (size_t)done * 12u, (size_t)c * 12u * sizeof(float));
-        HIP_TRY(ctx, hipMemcpyAsync(cm.table.p + at, cm.h_table + at, (size_t)c * 12u * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        cm.launches++;
-        rc = ctx->ks->launch_cameras(ctx, cm.table.p + at, cm.h_table + at, first_sample + done, c, group_log2_for(c), ctx->accum.p,
+        CameraTable tb;
+        if ((rc = camera_table_send(ctx, cameras + (size_t)done * 12u, c, &tb)) != RT_OK) return rc;
+        rc = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr,
                                      ctx->moments.target());
-        HIP_TRY(ctx, hipEventRecord(cm.read[k], ctx->stream));
+        const int rd = camera_table_read(ctx, tb);
+        if (rd != RT_OK) return rd;
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
@@ -1144,9 +1164,11 @@ int log2_pow2(uint32_t v) {
 }  // namespace
 }  // extern "C++"
 
-int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
-    int rc = check_ready(ctx, camera);
-    if (rc) return rc;
+extern "C++" {
+namespace {
+
+// The parameter rules of both adaptive calls (after check_ready): RT_OK, or an RT_* code recorded on the context.
+int check_adaptive(rt_context *ctx, const rt_adaptive_params *p, const rt_adaptive_stats *out, int *bwl, int *bhl) {
     if (!p || !out) return fail(ctx, RT_EINVAL, "adaptive parameters / stats are NULL");
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "adaptive rendering of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
     if (p->batch < 1 || p->batch > RT_SPP_PER_LAUNCH)
@@ -1157,10 +1179,19 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
         return fail(ctx, RT_EINVAL, "max_spp %u outside min_spp %u .. %u", p->max_spp, p->min_spp, RT_MAX_SAMPLE + 1u);
     if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold))
         return fail(ctx, RT_EINVAL, "threshold must be finite and >= 0");
-    const int bwl = log2_pow2(p->block_w), bhl = log2_pow2(p->block_h);
-    if (p->block_w < 1 || p->block_h < 1 || p->block_w > 256 || p->block_h > 256 || bwl < 0 || bhl < 0)
+    *bwl = log2_pow2(p->block_w), *bhl = log2_pow2(p->block_h);
+    if (p->block_w < 1 || p->block_h < 1 || p->block_w > 256 || p->block_h > 256 || *bwl < 0 || *bhl < 0)
         return fail(ctx, RT_EINVAL, "block %ux%u: sides must be powers of two in 1..256", p->block_w, p->block_h);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+// The round loop of both adaptive calls, the parameters checked (bwl, bhl: check_adaptive's): buffers, clear, rounds —
+// launch, pt_adaptive_merge, the stats read back, the stop test — and the resolve.  `launch_round(first, c, scratch, mask,
+// m2_scratch)` adds samples first .. first+c-1 of every pixel of an active block to `scratch` (and their moments to
+// m2_scratch, NULL without RT_OPT_MOMENTS): the one thing in which the two calls differ.
+template <class LaunchRound>
+int adaptive_rounds(rt_context *ctx, const rt_adaptive_params *p, int bwl, int bhl, rt_adaptive_stats *out, LaunchRound launch_round) {
+    int rc;
     const uint32_t bx = ((uint32_t)ctx->width + p->block_w - 1) >> bwl, by = ((uint32_t)ctx->height + p->block_h - 1) >> bhl;
     const uint32_t blocks = bx * by;
     if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
@@ -1198,10 +1229,7 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     for (uint32_t k = 0;; k++) {
         const uint32_t first = k * p->batch;
         const uint32_t c = std::min(p->batch, p->max_spp - first);
-        rc = ctx->prefix_sharing
-                 ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), a.scratch.p, &mask, m2_scratch)
-                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), a.scratch.p, &mask, m2_scratch);
-        if (rc != RT_OK) return rc;
+        if ((rc = launch_round(first, c, a.scratch.p, &mask, m2_scratch)) != RT_OK) return rc;
         mp.round = k;
         mp.count = first + c;
         HIP_TRY(ctx, hipMemsetAsync(a.stats.p, 0, st_bytes, ctx->stream));
@@ -1229,6 +1257,42 @@ int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptiv
     out->blocks = blocks;
     out->blocks_at_max = (uint32_t)at_max;
     return RT_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
+    int rc = check_ready(ctx, camera), bwl = 0, bhl = 0;
+    if (rc) return rc;
+    if ((rc = check_adaptive(ctx, p, out, &bwl, &bhl)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return adaptive_rounds(ctx, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
+        return ctx->prefix_sharing
+                   ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch)
+                   : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+    });
+}
+
+int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
+                               rt_adaptive_stats *out) {
+    int rc = check_ready(ctx, cameras), bwl = 0, bhl = 0;
+    if (rc) return rc;
+    if ((rc = check_adaptive(ctx, p, out, &bwl, &bhl)) != RT_OK) return rc;
+    if (n_cameras != p->max_spp)
+        return fail(ctx, RT_EINVAL, "%u camera blocks for max_spp %u: block j is the camera of sample j", n_cameras, p->max_spp);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
+    // (a round ends in a stream synchronisation, so the ring's wait returns at once: the tables go the way of
+    // rt_render_spp_cameras' all the same)
+    return adaptive_rounds(ctx, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
+        CameraTable tb;
+        int r = camera_table_send(ctx, cameras + (size_t)first * 12u, c, &tb);
+        if (r != RT_OK) return r;
+        r = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+        const int rd = camera_table_read(ctx, tb);
+        return rd != RT_OK ? rd : r;
+    });
 }
 
 int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
@@ -1317,15 +1381,9 @@ int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n
         int r = ensure_cameras(ctx);
         if (r != RT_OK) return r;
         // the blocks go through table k of the ring, as a launch of rt_render_spp_cameras sends its own
-        rt_context::Cameras &cm = ctx->cameras;
-        const uint32_t k = (uint32_t)(cm.launches % rt_context::Cameras::RING);
-        const size_t at = (size_t)k * RT_SPP_PER_LAUNCH * 12u;
-        if (cm.launches >= rt_context::Cameras::RING) HIP_TRY(ctx, hipEventSynchronize(cm.read[k]));   // (table k's last reader)
-        memcpy(cm.h_table + at, cameras, (size_t)n_cameras * 12u * sizeof(float));
-        HIP_TRY(ctx, hipMemcpyAsync(cm.table.p + at, cm.h_table + at, (size_t)n_cameras * 12u * sizeof(float), hipMemcpyHostToDevice,
-                                    ctx->stream));
-        cm.launches++;
-        r = ctx->ks->launch_features_cameras(ctx, fp, sc, cm.table.p + at, n_cameras, p->follow, p->max_chain, out,
+        CameraTable tb;
+        if ((r = camera_table_send(ctx, cameras, n_cameras, &tb)) != RT_OK) return r;
+        r = ctx->ks->launch_features_cameras(ctx, fp, sc, tb.d, n_cameras, p->follow, p->max_chain, out,
                                              reinterpret_cast<uint2 *>(f.coverage.p));
         if (r == RT_OK) {
             hipLaunchKernelGGL(pt_features_cameras_finish, dim3((uint32_t)((pixels + 255u) / 256u)), dim3(256), 0, ctx->stream,
@@ -1333,8 +1391,8 @@ int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) r = fail(ctx, RT_EHIP, "pt_features_cameras_finish: %s", hipGetErrorString(e));
         }
-        HIP_TRY(ctx, hipEventRecord(cm.read[k], ctx->stream));
-        return r;
+        const int rd = camera_table_read(ctx, tb);
+        return rd != RT_OK ? rd : r;
     });
     if (done == RT_OK) ctx->features.coverage_ready = true;
     return done;

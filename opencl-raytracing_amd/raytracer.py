@@ -38,6 +38,7 @@ SYMBOLS = (
     "rt_debug_plan_samples", "rt_debug_last_sample_plan",
     "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
     "rt_render_features_cameras", "rt_read_feature_coverage", "rt_device_feature_coverage", "rt_debug_plan_feature_cameras",
+    "rt_render_adaptive_cameras",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -444,6 +445,19 @@ class RayTracer:
         p = _abi.AdaptiveParams(int(batch), int(min_spp), int(max_spp), float(threshold), int(block[0]), int(block[1]))
         st = _abi.AdaptiveStats()
         self._check(self._lib.rt_render_adaptive(self._ctx, _cam_block(camera).ctypes.data, C.byref(p), C.byref(st)))
+        self._adaptive_block = (int(block[0]), int(block[1]))
+        return st.as_dict()
+
+    def renderAdaptiveCameras(self, blocks, threshold, batch=64, min_spp=128, block=(8, 8)):
+        """Adaptive frame through per-sample camera blocks (rt_render_adaptive_cameras): renderAdaptive with sample j of
+        every pixel looking through blocks[j] (float32[max_spp, 12], e.g. Camera.sampleBlocks — pixel jitter, depth of
+        field); max_spp = len(blocks).  Each round adds what renderSamplesCameras(blocks[first:first + c], first) adds;
+        identical blocks give renderAdaptive's bits.  → the stats dict renderAdaptive returns."""
+        blocks = _cam_blocks(blocks)
+        p = _abi.AdaptiveParams(int(batch), int(min_spp), len(blocks), float(threshold), int(block[0]), int(block[1]))
+        st = _abi.AdaptiveStats()
+        self._check(self._lib.rt_render_adaptive_cameras(self._ctx, blocks.ctypes.data if len(blocks) else None, len(blocks),
+                                                         C.byref(p), C.byref(st)))
         self._adaptive_block = (int(block[0]), int(block[1]))
         return st.as_dict()
 
