@@ -805,10 +805,13 @@ PT_DEV V3 texture_rgb(const DeviceScene &sc, float s, float t, uint32_t tex_id) 
     int W = sc.tex_w, H = sc.tex_h;
     int layer = tex_id < (uint32_t)sc.tex_layers ? (int)tex_id : 0;
     float u = s * sc.tex_wf - 0.5f, v = t * sc.tex_hf - 0.5f;
+    // the texel coordinate is clamped to [-1, W] BEFORE floor (NaN counts as -1): outside the image both taps are the
+    // edge texel and the weight is 0, so the colour is constant there and a huge uv cannot make inf - inf
+    u = u >= -1.0f ? (u > sc.tex_wf ? sc.tex_wf : u) : -1.0f;
+    v = v >= -1.0f ? (v > sc.tex_hf ? sc.tex_hf : v) : -1.0f;
     float fu = floorf(u), fv = floorf(v);
     float a = u - fu, b = v - fv;
-    int i0 = (fu >= -1.0f && fu <= 1.0e9f) ? (int)fu : 0;
-    int j0 = (fv >= -1.0f && fv <= 1.0e9f) ? (int)fv : 0;
+    int i0 = (int)fu, j0 = (int)fv;
     int i1 = clampi(i0 + 1, 0, W - 1), j1 = clampi(j0 + 1, 0, H - 1);
     i0 = clampi(i0, 0, W - 1);
     j0 = clampi(j0, 0, H - 1);

@@ -341,10 +341,12 @@ static v3 texture_rgb(const world_t *wd, float s, float t, uint32_t tex_id) {
     int W = wd->tw, H = wd->th;
     int layer = clampi((int)rintf((float)tex_id), 0, wd->layers - 1);
     float u = s * (float)W - 0.5f, v = t * (float)H - 0.5f;
+    /* clamped to [-1, W] before floor, NaN counts as -1 */
+    u = u >= -1.0f ? (u > (float)W ? (float)W : u) : -1.0f;
+    v = v >= -1.0f ? (v > (float)H ? (float)H : v) : -1.0f;
     float fu = floorf(u), fv = floorf(v);
     float a = u - fu, b = v - fv;
-    int i0 = (fu >= -1.0f && fu <= 1.0e9f) ? (int)fu : 0;
-    int j0 = (fv >= -1.0f && fv <= 1.0e9f) ? (int)fv : 0;
+    int i0 = (int)fu, j0 = (int)fv;
     int i1 = clampi(i0 + 1, 0, W - 1), j1 = clampi(j0 + 1, 0, H - 1);
     i0 = clampi(i0, 0, W - 1);
     j0 = clampi(j0, 0, H - 1);

@@ -171,11 +171,13 @@ float4 cl_read_imagef_2da(HostImage *im, void *, float4 c) {
     int layer = clampi((int)__builtin_rintf(c.z), 0, im->layers - 1);
     float u = c.x * (float)im->w - 0.5f;
     float v = c.y * (float)im->h - 0.5f;
+    // clamped to [-1, W] before floor, NaN counts as -1: a constant edge outside the image, and
+    // (int) never sees a NaN or a huge coordinate
+    u = u >= -1.0f ? (u > (float)im->w ? (float)im->w : u) : -1.0f;
+    v = v >= -1.0f ? (v > (float)im->h ? (float)im->h : v) : -1.0f;
     float fu = __builtin_floorf(u), fv = __builtin_floorf(v);
     float a = u - fu, b = v - fv;
-    // NaN / huge coordinates: (int) of those is undefined, pin them to texel 0
-    int i0 = (fu >= -1.0f && fu <= 1.0e9f) ? (int)fu : 0;
-    int j0 = (fv >= -1.0f && fv <= 1.0e9f) ? (int)fv : 0;
+    int i0 = (int)fu, j0 = (int)fv;
     int i1 = clampi(i0 + 1, 0, im->w - 1), j1 = clampi(j0 + 1, 0, im->h - 1);
     i0 = clampi(i0, 0, im->w - 1);
     j0 = clampi(j0, 0, im->h - 1);

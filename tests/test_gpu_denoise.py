@@ -63,11 +63,14 @@ def texel(scene, u, v, tex):
     T = scene.textures
     layers, H, W = T.shape[:3]
     layer = np.where(tex < layers, tex, 0)
-    uu, vv = (u * f(W) - f(0.5)).astype(f), (v * f(H) - f(0.5)).astype(f)
+    # the texel coordinate, clamped to [-1, W] before floor, NaN counts as -1
+    with np.errstate(invalid="ignore", over="ignore"):
+        uu, vv = (u * f(W) - f(0.5)).astype(f), (v * f(H) - f(0.5)).astype(f)
+        uu = np.where(uu >= -1, np.where(uu > f(W), f(W), uu), f(-1)).astype(f)
+        vv = np.where(vv >= -1, np.where(vv > f(H), f(H), vv), f(-1)).astype(f)
     fu, fv = np.floor(uu), np.floor(vv)
     a, b = (uu - fu).astype(f), (vv - fv).astype(f)
-    i0 = np.where((fu >= -1) & (fu <= 1e9), fu, 0).astype(np.int64)
-    j0 = np.where((fv >= -1) & (fv <= 1e9), fv, 0).astype(np.int64)
+    i0, j0 = fu.astype(np.int64), fv.astype(np.int64)
     i1, j1 = np.clip(i0 + 1, 0, W - 1), np.clip(j0 + 1, 0, H - 1)
     i0, j0 = np.clip(i0, 0, W - 1), np.clip(j0, 0, H - 1)
     t00, t10, t01, t11 = (T[layer, jj, ii, :3] for jj, ii in ((j0, i0), (j0, i1), (j1, i0), (j1, i1)))
