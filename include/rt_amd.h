@@ -701,12 +701,21 @@ int rt_enable_counters(rt_context *ctx, int enable);
 int rt_reset_counters(rt_context *ctx);
 int rt_get_counters(rt_context *ctx, rt_counters *out);
 
-/* Host-only self-check (no device, no context): builds the sphere BVH and the per-mesh BVHs
- * exactly as rt_set_scene does and verifies their invariants — every primitive in exactly one
- * leaf and inside its boxes, child boxes inside parent boxes, split axes and skip links (both
- * walks are threaded), the walk visiting every leaf exactly once in all eight direction octants,
- * smallest-face indices, normal cones, edge bounds.  stats = {sphere nodes, sphere leaves,
- * sphere depth, mesh nodes, mesh leaves, mesh depth, meshes with a BVH, 0}. */
+/* Host-only self-check (no device, no context): validates and prepares the scene through the very
+ * code rt_set_scene uploads from and verifies the invariants of the prepared arrays — every
+ * primitive in exactly one leaf and inside the box of every node above it, split axes and skip
+ * links (both walks are threaded), the walk visiting every leaf exactly once in all eight direction
+ * octants (mesh trees: as built and through the collapsed links of the packed nodes), smallest-face
+ * indices, normal cones, edge bounds, the packed nodes' fields rounded to the safe side, the sphere
+ * tree's device arrays, the walk jobs.  Where rt_set_scene builds no tree (a non-finite sphere, the
+ * size gates) none is reported.  A scene rt_set_scene would reject gives the same code, the message
+ * in `err`.  stats = {sphere nodes, sphere leaves, sphere depth, mesh nodes, mesh leaves, mesh
+ * depth, meshes with a BVH, digest}; digest = FNV-1a-64 over the raw bytes of what rt_set_scene
+ * uploads or keeps for arithmetic policy 0, each array preceded by its element count as a
+ * little-endian uint64: face bases, face records, packed mesh nodes, leaf faces, leaf face indices,
+ * mesh roots, walk jobs, sphere boxes, sphere links, sphere leaf indices, then eleven 32-bit words
+ * (BVH node count, centre bounds lo[3] hi[3], largest radius, mesh BVHs in use, textures in use,
+ * largest texture id). */
 int rt_debug_check_accel(const rt_scene_desc *scene, uint64_t stats[8], char *err, size_t err_len);
 
 /* Diagnostics of the sphere search since the last reset (counting build only):

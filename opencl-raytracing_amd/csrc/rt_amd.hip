@@ -1,5 +1,5 @@
-// rt_amd.hip — host side of librt_amd.so (include/rt_amd.h), gfx950 only: the C ABI, scene upload, the builders of
-// the acceleration structures and the kernels that carry none of the reference's arithmetic (resolve, pack, unpack).
+// rt_amd.hip — host side of librt_amd.so (include/rt_amd.h), gfx950 only: the C ABI, scene upload (what is uploaded is
+// computed by scene_prep.hpp) and the kernels that carry none of the reference's arithmetic (resolve, pack, unpack).
 // The path-tracing kernels live in pt_kernels.hip, compiled once per arithmetic policy (pt_arith.hpp); this file
 // picks a policy's launchers at run time (RT_OPT_ARITH).  The denoisers and their kernels live in rt_denoise.hip.
 //
@@ -23,10 +23,13 @@
 #include "pt_kernels.hpp"
 #include "pt_moments.hpp"
 #include "pt_chain.hpp"
-#include "mesh_bvh_build.hpp"
+#include "scene_prep.hpp"
 
 using namespace pt;
 using namespace rtamd;
+using namespace scene_prep;
+
+static_assert(MESH_ROOT_NONE == PT_MESH_BVH_NONE, "scene_prep.hpp and pt_types.hpp name the same \"no BVH\" root");
 
 // =============================== policy-free kernels ===============================
 
@@ -210,180 +213,6 @@ void make_table(uint64_t seed, float *out) {
             }
         }
     }
-}
-
-// Sphere BVH (see hit_spheres_bvh): binned surface-area-heuristic splits (16 bins per axis over the
-// centroids; median split when no bin boundary separates them), leaves of <= 4 spheres; children
-// are allocated in adjacent pairs (left at an even index, lower coordinates along the split axis),
-// every node records its split axis and, per direction octant, the node that follows its subtree in the
-// near-before-far order of that octant (the walk is threaded: no stack, no way back up).
-#ifndef SPHERE_BVH_LEAF
-#define SPHERE_BVH_LEAF 4  // spheres per leaf (<= 7)
-#endif
-#define BVH_END 0x0FFFFFFFu
-#define BVH_ROOT 1u
-struct BvhBuild {
-    const rt_sphere *sph;
-    std::vector<uint32_t> order;
-    std::vector<float4> nodes;   // 4 per node: (lo, A) (hi, B) and the eight skip links (pt_device.hpp hit_spheres_bvh)
-    std::vector<float4> leaf_sph;
-    std::vector<uint32_t> leaf_idx;
-
-    void bounds(uint32_t b, uint32_t e, float lo[3], float hi[3]) const {
-        for (int k = 0; k < 3; k++) { lo[k] = INFINITY; hi[k] = -INFINITY; }
-        for (uint32_t i = b; i < e; i++) {
-            const rt_sphere &s = sph[order[i]];
-            const float c[3] = {s.pos.x, s.pos.y, s.pos.z};
-            float r = std::fabs(s.r);
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::fmin(lo[k], c[k] - r);
-                hi[k] = std::fmax(hi[k], c[k] + r);
-            }
-        }
-    }
-    // skip[o]: the node that follows this subtree for a ray of direction octant o (bit k of o: d_k < 0), whose walk
-    // enters the nearer child of every inner node first; BVH_END after the last one
-    void fill(uint32_t me, const uint32_t skip[8], uint32_t b, uint32_t e, uint32_t depth = 0) {
-        float lo[3], hi[3];
-        bounds(b, e, lo, hi);
-        uint32_t A = 0, B;
-        if (e - b <= SPHERE_BVH_LEAF) {
-            uint32_t first = (uint32_t)leaf_sph.size();
-            for (uint32_t i = b; i < e; i++) {
-                const rt_sphere &s = sph[order[i]];
-                volatile float r2 = s.r * s.r;
-                leaf_sph.push_back(make_float4(s.pos.x, s.pos.y, s.pos.z, r2));
-                leaf_idx.push_back(order[i]);
-            }
-            B = 0x80000000u | ((e - b) << 28) | first;
-        } else {
-            float clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (uint32_t i = b; i < e; i++) {
-                const rt_sphere &s = sph[order[i]];
-                const float c[3] = {s.pos.x, s.pos.y, s.pos.z};
-                for (int k = 0; k < 3; k++) { clo[k] = std::fmin(clo[k], c[k]); chi[k] = std::fmax(chi[k], c[k]); }
-            }
-            int ax = 0;
-            for (int k = 1; k < 3; k++) if (chi[k] - clo[k] > chi[ax] - clo[ax]) ax = k;
-            uint32_t mid = b + (e - b) / 2;
-            const rt_sphere *sp = sph;
-            // binned SAH: cost(split) = area(L)·|L| + area(R)·|R| over 15 boundaries × 3 axes
-            constexpr int NB = 16;
-            double best_cost = INFINITY;
-            int best_ax = -1, best_bin = -1;
-            for (int k = 0; k < 3 && depth < 32u; k++) {   // (median splits from level 32 on bound the depth)
-                float ext = chi[k] - clo[k];
-                if (!(ext > 0.0f)) continue;
-                struct Bin { float lo[3], hi[3]; uint32_t n; } bins[NB];
-                for (auto &bn : bins) { for (int q = 0; q < 3; q++) { bn.lo[q] = INFINITY; bn.hi[q] = -INFINITY; } bn.n = 0; }
-                for (uint32_t i = b; i < e; i++) {
-                    const rt_sphere &s = sph[order[i]];
-                    const float c[3] = {s.pos.x, s.pos.y, s.pos.z};
-                    int bi = (int)((c[k] - clo[k]) / ext * NB);
-                    bi = bi < 0 ? 0 : (bi >= NB ? NB - 1 : bi);
-                    float r = std::fabs(s.r);
-                    for (int q = 0; q < 3; q++) { bins[bi].lo[q] = std::fmin(bins[bi].lo[q], c[q] - r); bins[bi].hi[q] = std::fmax(bins[bi].hi[q], c[q] + r); }
-                    bins[bi].n++;
-                }
-                auto area = [](const float *l, const float *h) {
-                    double dx = (double)h[0] - l[0], dy = (double)h[1] - l[1], dz = (double)h[2] - l[2];
-                    return dx < 0 ? 0.0 : 2.0 * (dx * dy + dy * dz + dz * dx);
-                };
-                double right_cost[NB];
-                float rl[3] = {INFINITY, INFINITY, INFINITY}, rh[3] = {-INFINITY, -INFINITY, -INFINITY};
-                uint32_t rn = 0;
-                for (int j = NB - 1; j > 0; j--) {
-                    for (int q = 0; q < 3; q++) { rl[q] = std::fmin(rl[q], bins[j].lo[q]); rh[q] = std::fmax(rh[q], bins[j].hi[q]); }
-                    rn += bins[j].n;
-                    right_cost[j] = rn ? area(rl, rh) * rn : INFINITY;
-                }
-                float ll[3] = {INFINITY, INFINITY, INFINITY}, lh[3] = {-INFINITY, -INFINITY, -INFINITY};
-                uint32_t ln = 0;
-                for (int j = 0; j < NB - 1; j++) {
-                    for (int q = 0; q < 3; q++) { ll[q] = std::fmin(ll[q], bins[j].lo[q]); lh[q] = std::fmax(lh[q], bins[j].hi[q]); }
-                    ln += bins[j].n;
-                    if (ln == 0 || ln == e - b) continue;
-                    double cost = area(ll, lh) * ln + right_cost[j + 1];
-                    if (cost < best_cost) { best_cost = cost; best_ax = k; best_bin = j; }
-                }
-            }
-            if (best_ax >= 0) {
-                ax = best_ax;
-                float ext = chi[ax] - clo[ax], base = clo[ax];
-                int bb = best_bin;
-                auto it = std::partition(order.begin() + b, order.begin() + e, [sp, ax, ext, base, bb](uint32_t i) {
-                    const float *ci = &sp[i].pos.x;
-                    int bi = (int)((ci[ax] - base) / ext * NB);
-                    bi = bi < 0 ? 0 : (bi >= NB ? NB - 1 : bi);
-                    return bi <= bb;
-                });
-                mid = (uint32_t)(it - order.begin());
-            }
-            if (best_ax < 0 || mid == b || mid == e) {  // coincident centroids: median split by index
-                mid = b + (e - b) / 2;
-                std::nth_element(order.begin() + b, order.begin() + mid, order.begin() + e, [sp, ax](uint32_t i, uint32_t j) {
-                    const float *ci = &sp[i].pos.x, *cj = &sp[j].pos.x;
-                    return ci[ax] < cj[ax] || (ci[ax] == cj[ax] && i < j);
-                });
-            }
-            uint32_t left = (uint32_t)(nodes.size() / 4);  // even: the root is node 1 and pairs follow, each in one 64-byte stretch
-            nodes.resize(nodes.size() + 8);
-            A = (uint32_t)ax << 28;
-            B = left;
-            uint32_t skip_l[8], skip_r[8];
-            for (uint32_t o = 0; o < 8; o++) {   // the walk enters child B + ((o >> ax) & 1) first, its sibling next
-                bool right_first = ((o >> ax) & 1u) != 0;
-                skip_l[o] = right_first ? skip[o] : left + 1u;
-                skip_r[o] = right_first ? left : skip[o];
-            }
-            fill(left, skip_l, b, mid, depth + 1u);
-            fill(left + 1, skip_r, mid, e, depth + 1u);
-        }
-        float bc[3], bh[3];
-        bvh_centre_half(lo, hi, bc, bh);
-        nodes[4 * (size_t)me] = make_float4(bc[0], bc[1], bc[2], 0.0f);
-        nodes[4 * (size_t)me + 1] = make_float4(bh[0], bh[1], bh[2], 0.0f);
-        memcpy(&nodes[4 * (size_t)me].w, &A, 4);
-        memcpy(&nodes[4 * (size_t)me + 1].w, &B, 4);
-        memcpy(&nodes[4 * (size_t)me + 2], skip, 32);
-    }
-    void build(uint32_t b, uint32_t e) {
-        nodes.assign(8, make_float4(0.0f, 0.0f, 0.0f, 0.0f));   // node 0 is padding, the root is node BVH_ROOT
-        const uint32_t end[8] = {BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END};
-        fill(BVH_ROOT, end, b, e);
-    }
-};
-
-// per-face records (see DeviceScene::faces): the same binary32 operations hitTriangle performs.
-// base[m] = first record of mesh m; fr = 3 float4 per face + one dummy record.
-bool build_face_records(const rt_scene_desc *d, std::vector<uint32_t> &base, std::vector<float4> &fr) {
-    base.assign(d->mesh_count ? d->mesh_count : 1, 0u);
-    size_t total = 0;
-    for (uint32_t m = 0; m < d->mesh_count; m++) { base[m] = (uint32_t)total; total += d->meshes[m].face_count; }
-    if (total >= (1ull << 31)) return false;
-    fr.assign(3 * (total + 1), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    for (uint32_t m = 0; m < d->mesh_count; m++) {
-        const rt_mesh &me = d->meshes[m];
-        for (uint32_t f = 0; f < me.face_count; f++) {
-            const uint32_t *ib = d->indices + me.index_anchor + 3u * f;
-            const rt_float3 &A = d->vertices[me.vertex_anchor + ib[0]], &B = d->vertices[me.vertex_anchor + ib[1]],
-                            &C = d->vertices[me.vertex_anchor + ib[2]];
-            volatile float e1x = B.x - A.x, e1y = B.y - A.y, e1z = B.z - A.z;
-            volatile float e2x = C.x - A.x, e2y = C.y - A.y, e2z = C.z - A.z;
-            volatile float p1 = e1y * e2z, p2 = e1z * e2y, p3 = e1z * e2x, p4 = e1x * e2z, p5 = e1x * e2y, p6 = e1y * e2x;
-            volatile float cx = p1 - p2, cy = p3 - p4, cz = p5 - p6;          // cross(e1, e2)
-            volatile float xx = cx * cx, yy = cy * cy, zz = cz * cz;
-            volatile float s2 = xx + yy;
-            volatile float s3 = s2 + zz;                                        // dot = (x*x + y*y) + z*z
-            volatile float len = std::sqrt((float)s3);
-            volatile float nx = cx / len, ny = cy / len, nz = cz / len;          // normalize
-            float4 *q = &fr[3 * ((size_t)base[m] + f)];
-            q[0] = make_float4(A.x, A.y, A.z, e1x);
-            q[1] = make_float4(e1y, e1z, e2x, e2y);
-            q[2] = make_float4(e2z, nx, ny, nz);
-        }
-    }
-    return true;
 }
 
 }  // namespace
@@ -620,167 +449,54 @@ int rt_set_scene(rt_context *ctx, const rt_scene_desc *d) {
     if (!ctx) return RT_EINVAL;
     if (!d) return fail(ctx, RT_EINVAL, "scene is NULL");
     ctx->prefix_changed();
-    ctx->walk_jobs.release();
-    struct { const void *p; uint32_t n; const char *name; } arrs[] = {
-        {d->materials, d->material_count, "materials"}, {d->spheres, d->sphere_count, "spheres"},
-        {d->planes, d->plane_count, "planes"}, {d->lenses, d->lens_count, "lenses"},
-        {d->vertices, d->vertex_count, "vertices"}, {d->uvs, d->uv_count, "uvs"},
-        {d->indices, d->index_count, "indices"}, {d->meshes, d->mesh_count, "meshes"},
-        {d->models, d->model_count, "models"}};
-    for (auto &a : arrs)
-        if (a.n && !a.p) return fail(ctx, RT_EINVAL, "%s: count %u but NULL pointer", a.name, a.n);
-    if (d->uv_count != 0 && d->uv_count != d->vertex_count)
-        return fail(ctx, RT_EINVAL, "uv_count (%u) must be 0 or vertex_count (%u)", d->uv_count, d->vertex_count);
-    // validate every index the kernels dereference
-    for (uint32_t i = 0; i < d->material_count; i++)
-        if (d->materials[i].type < 0 || d->materials[i].type > RT_LIGHT)
-            return fail(ctx, RT_EINVAL, "material %u has unknown type %d", i, d->materials[i].type);
-    for (uint32_t i = 0; i < d->sphere_count; i++)
-        if (d->spheres[i].mat_ID >= d->material_count) return fail(ctx, RT_ERANGE, "sphere %u: material %u does not exist", i, d->spheres[i].mat_ID);
-    for (uint32_t i = 0; i < d->plane_count; i++)
-        if (d->planes[i].mat_ID >= d->material_count) return fail(ctx, RT_ERANGE, "plane %u: material %u does not exist", i, d->planes[i].mat_ID);
-    for (uint32_t i = 0; i < d->lens_count; i++)
-        if (d->lenses[i].mat_ID >= d->material_count) return fail(ctx, RT_ERANGE, "lens %u: material %u does not exist", i, d->lenses[i].mat_ID);
-    bool uses_tex = false;
-    uint32_t max_tex = 0;
-    for (uint32_t i = 0; i < d->model_count; i++) {
-        const rt_model &mo = d->models[i];
-        if (mo.mat_ID >= d->material_count) return fail(ctx, RT_ERANGE, "model %u: material %u does not exist", i, mo.mat_ID);
-        if ((uint64_t)mo.mesh_anchor + mo.mesh_count > d->mesh_count) return fail(ctx, RT_ERANGE, "model %u: meshes [%u,+%u) outside the mesh array (%u)", i, mo.mesh_anchor, mo.mesh_count, d->mesh_count);
-        bool textured = d->materials[mo.mat_ID].type == RT_TEXTURED;
-        for (uint32_t k = 0; k < mo.mesh_count; k++) {
-            const rt_mesh &me = d->meshes[mo.mesh_anchor + k];
-            if (textured) {
-                uses_tex = true;
-                if (me.texture_ID > max_tex) max_tex = me.texture_ID;
-            }
-        }
-    }
-    for (uint32_t i = 0; i < d->mesh_count; i++) {
-        const rt_mesh &me = d->meshes[i];
-        if ((uint64_t)me.index_anchor + 3ull * me.face_count > d->index_count)
-            return fail(ctx, RT_ERANGE, "mesh %u: indices [%u,+3*%u) outside the index array (%u)", i, me.index_anchor, me.face_count, d->index_count);
-        for (uint64_t k = 0; k < 3ull * me.face_count; k++)
-            if ((uint64_t)me.vertex_anchor + d->indices[me.index_anchor + k] >= d->vertex_count)
-                return fail(ctx, RT_ERANGE, "mesh %u: vertex index %u (+anchor %u) outside the vertex array (%u)", i, d->indices[me.index_anchor + k], me.vertex_anchor, d->vertex_count);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->have_scene = false;
-    // (behind the materials: room for the staged scene block, rt_context::StageBlock)
-    HIP_TRY(ctx, ctx->materials.upload(d->materials, d->material_count,
-                                       lds_static_used(d->material_count, d->sphere_count, d->plane_count) * sizeof(float4)));
-    ctx->stage_block.generation = ~0ull;
-    HIP_TRY(ctx, ctx->spheres.upload(d->spheres, d->sphere_count));
-    ctx->h_spheres.assign(d->spheres, d->spheres + d->sphere_count);   // the test records follow in apply_arith()
-    ctx->h_bvh_idx.clear();
     {
-        std::vector<uint32_t> base;
-        std::vector<float4> fr;
-        if (!build_face_records(d, base, fr)) return fail(ctx, RT_EINVAL, "too many faces");
-        HIP_TRY(ctx, ctx->mesh_face_base.upload(base.data(), d->mesh_count));
-        // per-mesh BVHs for the "first front-facing hit in face order" rule (pt_mesh_bvh.hpp)
-        std::vector<float4> nodes, lfaces;
-        std::vector<uint32_t> lidx, roots(d->mesh_count ? d->mesh_count : 1, PT_MESH_BVH_NONE);
-        ctx->have_mesh_bvh = false;
-        for (uint32_t m = 0; m < d->mesh_count; m++) {
-            if (d->meshes[m].face_count < MESH_BVH_MIN_FACES || d->meshes[m].face_count >= (1u << 27)) continue;
-            MeshBvhBuilder mb;
-            mb.rec = &fr[3 * (size_t)base[m]];
-            mb.n_faces = d->meshes[m].face_count;
-            mb.nodes = &nodes;
-            mb.leaf_faces = &lfaces;
-            mb.leaf_idx = &lidx;
-            roots[m] = mb.build();
-            ctx->have_mesh_bvh = true;
+        PreparedScene ps;
+        std::string err;
+        if (int rc = prepare_scene(*d, ps, err)) return fail(ctx, rc, "%s", err.c_str());
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->have_scene = false;
+        // (behind the materials: room for the staged scene block, rt_context::StageBlock)
+        HIP_TRY(ctx, ctx->materials.upload(d->materials, d->material_count,
+                                           lds_static_used(d->material_count, d->sphere_count, d->plane_count) * sizeof(float4)));
+        ctx->stage_block.generation = ~0ull;
+        HIP_TRY(ctx, ctx->spheres.upload(d->spheres, d->sphere_count));
+        ctx->h_spheres.assign(d->spheres, d->spheres + d->sphere_count);   // the test records follow in apply_arith()
+        HIP_TRY(ctx, ctx->mesh_face_base.upload(ps.face_base.data(), ps.face_base.size()));
+        HIP_TRY(ctx, ctx->mbvh_nodes.upload(ps.mesh_packed.data(), ps.mesh_packed.size()));
+        ctx->have_mesh_bvh = ps.have_mesh_bvh;
+        HIP_TRY(ctx, ctx->mbvh_face_idx.upload(ps.leaf_face_idx.data(), ps.leaf_face_idx.size()));
+        HIP_TRY(ctx, ctx->mesh_bvh_root.upload(ps.mesh_roots.data(), ps.mesh_roots.size()));
+        ctx->walk_jobs.release();
+        if (!ps.walk_jobs.empty()) HIP_TRY(ctx, ctx->walk_jobs.upload(ps.walk_jobs.data(), ps.walk_jobs.size()));
+        ctx->bvh_node_count = ps.bvh_node_count;
+        if (!ps.sphere_nodes.empty()) {   // (without a tree the arrays and bounds of the last one stay, unused: bvh_node_count is 0)
+            HIP_TRY(ctx, ctx->bvh_nodes.upload(ps.sphere_boxes.data(), ps.sphere_boxes.size()));
+            HIP_TRY(ctx, ctx->bvh_links.upload(ps.sphere_links.data(), ps.sphere_links.size()));
+            HIP_TRY(ctx, ctx->bvh_idx.upload(ps.sphere_leaf_idx.data(), ps.sphere_leaf_idx.size()));
+            ctx->bvh_rmax = ps.bvh_rmax;
+            for (int k = 0; k < 3; k++) { ctx->bvh_lo[k] = ps.bvh_lo[k]; ctx->bvh_hi[k] = ps.bvh_hi[k]; }
         }
-        // the walks address these arrays with 32-bit byte offsets (at32): everything below 4 GiB, node indices below 2^26
-        if (nodes.size() / 4 >= (1u << 26) || lidx.size() >= (1u << 26)) ctx->have_mesh_bvh = false;
-        if (nodes.empty()) nodes.resize(4, make_float4(0, 0, 0, 0));
-        if (lfaces.empty()) lfaces.resize(3, make_float4(0, 0, 0, 0));
-        {   // device layout: 48 bytes per node (mesh_node_pack), wide-cone inner nodes spliced out of the links
-            std::vector<uint8_t> is_root(nodes.size() / 4, 0);
-            for (uint32_t m = 0; m < d->mesh_count; m++) if (roots[m] != PT_MESH_BVH_NONE && roots[m] < is_root.size()) is_root[roots[m]] = 1;
-            mesh_collapse_links(nodes, is_root);
-            std::vector<float4> packed(nodes.size() / 4 * 3);
-            for (size_t n = 0; n < nodes.size() / 4; n++) mesh_node_pack(&nodes[4 * n], &packed[3 * n]);
-            HIP_TRY(ctx, ctx->mbvh_nodes.upload(packed.data(), packed.size()));
+        HIP_TRY(ctx, ctx->planes.upload(d->planes, d->plane_count));
+        HIP_TRY(ctx, ctx->lenses.upload(d->lenses, d->lens_count));
+        HIP_TRY(ctx, ctx->vertices.upload(d->vertices, d->vertex_count));
+        if (d->uv_count) HIP_TRY(ctx, ctx->uvs.upload(d->uvs, d->uv_count));
+        else {
+            std::vector<rt_float2> zeros(d->vertex_count ? d->vertex_count : 1, rt_float2{0.0f, 0.0f});
+            HIP_TRY(ctx, ctx->uvs.upload(zeros.data(), d->vertex_count));
         }
-        ctx->h_faces.swap(fr);            // uploaded by apply_arith(): the normals depend on the arithmetic policy
-        ctx->h_mbvh_faces.swap(lfaces);
-        HIP_TRY(ctx, ctx->mbvh_face_idx.upload(lidx.data(), lidx.size()));
-        HIP_TRY(ctx, ctx->mesh_bvh_root.upload(roots.data(), d->mesh_count));
-        std::vector<uint2> jobs;
-        bool all_bvh = ctx->have_mesh_bvh && d->model_count > 0;
-        for (uint32_t mo = 0; mo < d->model_count && all_bvh; mo++)
-            for (uint32_t k = 0; k < d->models[mo].mesh_count && all_bvh; k++) {
-                uint32_t mi = d->models[mo].mesh_anchor + k;
-                all_bvh = mi < d->mesh_count && roots[mi] != PT_MESH_BVH_NONE;
-                jobs.push_back(make_uint2(mi, d->models[mo].mat_ID));
-            }
-        if (all_bvh && !jobs.empty() && jobs.size() < (1u << 16)) HIP_TRY(ctx, ctx->walk_jobs.upload(jobs.data(), jobs.size()));
-    }
-    ctx->bvh_node_count = 0;
-    if (d->sphere_count > 0 && d->sphere_count < (1u << 24)) {   // (32-bit byte offsets into the node / link / leaf arrays: at32; a node's links are 128 bytes)
-        bool finite = true;
-        for (uint32_t i = 0; i < d->sphere_count && finite; i++)
-            finite = std::isfinite(d->spheres[i].pos.x) && std::isfinite(d->spheres[i].pos.y) &&
-                     std::isfinite(d->spheres[i].pos.z) && std::isfinite(d->spheres[i].r);
-        if (finite) {  // non-finite spheres: no BVH, the brute-force loop handles them as the reference does
-            BvhBuild bb;
-            bb.sph = d->spheres;
-            bb.order.resize(d->sphere_count);
-            for (uint32_t i = 0; i < d->sphere_count; i++) bb.order[i] = i;
-            bb.build(0, d->sphere_count);
-            {   // device layout (hit_spheres_bvh): (centre, B) in 16 bytes; per octant (skip | axis << 28, half extent) in 16 bytes
-                std::vector<float4> boxes(bb.nodes.size() / 4), links(bb.nodes.size() * 2);
-                for (size_t n = 0; n < bb.nodes.size() / 4; n++) {
-                    boxes[n] = bb.nodes[4 * n];
-                    boxes[n].w = bb.nodes[4 * n + 1].w;
-                    uint32_t A, s8[8];
-                    memcpy(&A, &bb.nodes[4 * n].w, 4);
-                    memcpy(s8, &bb.nodes[4 * n + 2], 32);
-                    for (int o = 0; o < 8; o++) {
-                        const uint32_t w = s8[o] | (A & 0x30000000u);
-                        float4 &l = links[8 * n + o];
-                        l = make_float4(0.0f, bb.nodes[4 * n + 1].x, bb.nodes[4 * n + 1].y, bb.nodes[4 * n + 1].z);
-                        memcpy(&l.x, &w, 4);
-                    }
-                }
-                HIP_TRY(ctx, ctx->bvh_nodes.upload(boxes.data(), boxes.size()));
-                HIP_TRY(ctx, ctx->bvh_links.upload(links.data(), links.size()));
-            }
-            HIP_TRY(ctx, ctx->bvh_idx.upload(bb.leaf_idx.data(), bb.leaf_idx.size()));
-            ctx->h_bvh_idx = bb.leaf_idx;   // the leaf records (centre, r*r or r) follow in apply_arith()
-            // the walk addresses the link array with the 32-bit byte offset node << 7 and leaf slots with slot << 4
-            // (at32): a degenerate set whose tree outgrows that takes the brute-force loop
-            ctx->bvh_node_count = (bb.nodes.size() / 4 < (1u << 25) && bb.leaf_sph.size() < (1u << 28)) ? (uint32_t)(bb.nodes.size() / 4) : 0u;
-            ctx->bvh_rmax = 0;
-            for (int k = 0; k < 3; k++) { ctx->bvh_lo[k] = INFINITY; ctx->bvh_hi[k] = -INFINITY; }
-            for (uint32_t i = 0; i < d->sphere_count; i++) {
-                const float c[3] = {d->spheres[i].pos.x, d->spheres[i].pos.y, d->spheres[i].pos.z};
-                for (int k = 0; k < 3; k++) { ctx->bvh_lo[k] = std::fmin(ctx->bvh_lo[k], c[k]); ctx->bvh_hi[k] = std::fmax(ctx->bvh_hi[k], c[k]); }
-                ctx->bvh_rmax = std::fmax(ctx->bvh_rmax, std::fabs(d->spheres[i].r));
-            }
-        }
-    }
-    HIP_TRY(ctx, ctx->planes.upload(d->planes, d->plane_count));
-    HIP_TRY(ctx, ctx->lenses.upload(d->lenses, d->lens_count));
-    HIP_TRY(ctx, ctx->vertices.upload(d->vertices, d->vertex_count));
-    if (d->uv_count) HIP_TRY(ctx, ctx->uvs.upload(d->uvs, d->uv_count));
-    else {
-        std::vector<rt_float2> zeros(d->vertex_count ? d->vertex_count : 1, rt_float2{0.0f, 0.0f});
-        HIP_TRY(ctx, ctx->uvs.upload(zeros.data(), d->vertex_count));
-    }
-    HIP_TRY(ctx, ctx->indices.upload(d->indices, d->index_count));
-    HIP_TRY(ctx, ctx->meshes.upload(d->meshes, d->mesh_count));
-    HIP_TRY(ctx, ctx->models.upload(d->models, d->model_count));
-    ctx->scene_uses_textures = uses_tex;
-    ctx->max_texture_id = max_tex;
-    {
-        int rc = apply_arith(ctx);
-        if (rc != RT_OK) return rc;
-    }
+        HIP_TRY(ctx, ctx->indices.upload(d->indices, d->index_count));
+        HIP_TRY(ctx, ctx->meshes.upload(d->meshes, d->mesh_count));
+        HIP_TRY(ctx, ctx->models.upload(d->models, d->model_count));
+        ctx->scene_uses_textures = ps.uses_tex;
+        ctx->max_texture_id = ps.max_tex;
+        // what depends on the arithmetic policy is uploaded by apply_arith() from these: the spheres' and the leaves' test
+        // records, the face records and the leaf faces with their normals
+        ctx->h_bvh_idx.swap(ps.sphere_leaf_idx);
+        ctx->h_faces.swap(ps.faces);
+        ctx->h_mbvh_faces.swap(ps.leaf_faces);
+    }   // (the upload sources are freed before apply_arith() allocates its records: the host's peak is the builders')
+    if (int rc = apply_arith(ctx)) return rc;
     ctx->have_scene = true;
     ctx->sample_counter = 0;
     return RT_OK;
@@ -1536,280 +1252,16 @@ int rt_enable_counters(rt_context *ctx, int enable) {
     return RT_OK;
 }
 
-// ---- host-only self-check of the acceleration structures ------------------------------------
-extern "C++" {
-namespace {
-struct BvhWalkStats { uint64_t nodes = 0, leaves = 0, prims = 0, max_depth = 0; };
-
-// walk the sphere tree the way the kernel does for direction octant `oct` with every box "hit": nearer child
-// after an inner node, the octant's skip link after a leaf
-std::string host_walk_octant(const std::vector<float4> &nodes, uint32_t oct, std::vector<uint32_t> &leaf_visits, BvhWalkStats &st) {
-    uint32_t n_nodes = (uint32_t)(nodes.size() / 4), cur = BVH_ROOT;
-    for (uint64_t guard = 0; cur != BVH_END; guard++) {
-        if (guard > (uint64_t)n_nodes + 8) return "walk does not terminate";
-        if (cur >= n_nodes) return "node index out of range";
-        uint32_t A, B, sk[8];
-        memcpy(&A, &nodes[4 * (size_t)cur].w, 4);
-        memcpy(&B, &nodes[4 * (size_t)cur + 1].w, 4);
-        memcpy(sk, &nodes[4 * (size_t)cur + 2], 32);
-        st.nodes++;
-        if (B & 0x80000000u) {
-            uint32_t first = B & 0x0FFFFFFFu, cnt = (B >> 28) & 7u;
-            st.leaves++;
-            for (uint32_t k = 0; k < cnt; k++) {
-                if (first + k >= leaf_visits.size()) return "leaf slot out of range";
-                leaf_visits[first + k]++;
-            }
-            cur = sk[oct];
-        } else {
-            if (((A >> 28) & 3u) > 2) return "bad split axis";
-            if (B & 1u) return "left child at an odd index";
-            cur = B + ((oct >> ((A >> 28) & 3u)) & 1u);
-        }
-    }
-    return "";
-}
-
-// recursive structural check of the sphere tree: child boxes inside the parent's, the eight skip links, depth
-std::string host_check_sphere_tree(const std::vector<float4> &nodes, uint32_t me, uint32_t parent, const uint32_t skip[8],
-                                   bool is_root, uint32_t depth, BvhWalkStats &st) {
-    const float4 &lo = nodes[4 * (size_t)me], &hi = nodes[4 * (size_t)me + 1];
-    uint32_t A, B, sk[8];
-    memcpy(&A, &lo.w, 4);
-    memcpy(&B, &hi.w, 4);
-    memcpy(sk, &nodes[4 * (size_t)me + 2], 32);
-    for (int o = 0; o < 8; o++) if (sk[o] != skip[o]) return "wrong skip link";
-    st.max_depth = std::max<uint64_t>(st.max_depth, depth);
-    if (depth > 60) return "tree deeper than 60 levels";
-    (void)parent; (void)is_root;   // (boxes: every primitive is checked against the box of EVERY node above it, see rt_debug_check_accel)
-    if (B & 0x80000000u) return "";
-    uint32_t ax = (A >> 28) & 3u, sl[8], sr[8];
-    for (uint32_t o = 0; o < 8; o++) {
-        bool right_first = ((o >> ax) & 1u) != 0;
-        sl[o] = right_first ? skip[o] : B + 1u;
-        sr[o] = right_first ? B : skip[o];
-    }
-    std::string e = host_check_sphere_tree(nodes, B, me, sl, false, depth + 1, st);
-    if (e.empty()) e = host_check_sphere_tree(nodes, B + 1u, me, sr, false, depth + 1, st);
-    return e;
-}
-
-// the mesh trees are threaded (pt_mesh_bvh.hpp): follow "left child after an inner node, skip link after a leaf"
-std::string host_walk_threaded(const std::vector<float4> &nodes, uint32_t root, std::vector<uint32_t> &leaf_visits, BvhWalkStats &st) {
-    uint32_t n_nodes = (uint32_t)(nodes.size() / 4), cur = root;
-    for (uint64_t guard = 0; cur != 0x0FFFFFFFu; guard++) {
-        if (guard > (uint64_t)n_nodes + 8) return "walk does not terminate";
-        if (cur >= n_nodes) return "node index out of range";
-        uint32_t A, B;
-        memcpy(&A, &nodes[4 * (size_t)cur].w, 4);
-        memcpy(&B, &nodes[4 * (size_t)cur + 1].w, 4);
-        st.nodes++;
-        if (B & 0x80000000u) {
-            uint32_t first = B & 0x0FFFFFFFu, cnt = (B >> 28) & 7u;
-            st.leaves++;
-            for (uint32_t k = 0; k < cnt; k++) {
-                if (first + k >= leaf_visits.size()) return "leaf slot out of range";
-                leaf_visits[first + k]++;
-            }
-            cur = A & 0x0FFFFFFFu;
-        } else {
-            cur = B;
-        }
-    }
-    return "";
-}
-
-// recursive structural check of a threaded tree: child boxes inside the parent's, skip links, depth
-std::string host_check_threaded(const std::vector<float4> &nodes, uint32_t me, uint32_t parent, uint32_t skip, bool is_root,
-                                uint32_t depth, BvhWalkStats &st) {
-    const float4 &lo = nodes[4 * (size_t)me], &hi = nodes[4 * (size_t)me + 1];
-    uint32_t A, B;
-    memcpy(&A, &lo.w, 4);
-    memcpy(&B, &hi.w, 4);
-    if ((A & 0x0FFFFFFFu) != skip) return "wrong skip link";
-    st.max_depth = std::max<uint64_t>(st.max_depth, depth);
-    if (depth > 60) return "tree deeper than 60 levels";
-    (void)parent; (void)is_root;   // (boxes: every primitive is checked against the box of EVERY node above it, see rt_debug_check_accel)
-    if (B & 0x80000000u) return "";
-    uint32_t right;   // = the left child's skip link
-    memcpy(&right, &nodes[4 * (size_t)B].w, 4);
-    right &= 0x0FFFFFFFu;
-    if (right >= nodes.size() / 4) return "left child's skip link out of range";
-    std::string e = host_check_threaded(nodes, B, me, right, false, depth + 1, st);
-    if (e.empty()) e = host_check_threaded(nodes, right, me, skip, false, depth + 1, st);
-    return e;
-}
-
-}  // namespace
-}  // extern "C++"
-
+// host-only self-check of the acceleration structures: the prepared scene rt_set_scene would upload (scene_prep.hpp)
 int rt_debug_check_accel(const rt_scene_desc *d, uint64_t stats[8], char *err, size_t err_len) {
-    auto bad = [&](const std::string &m) {
-        if (err && err_len) snprintf(err, err_len, "%s", m.c_str());
-        return RT_EINVAL;
-    };
     if (!d || !stats) return RT_EINVAL;
     memset(stats, 0, 8 * sizeof(uint64_t));
-    // ---- sphere BVH
-    if (d->sphere_count) {
-        BvhBuild bb;
-        bb.sph = d->spheres;
-        bb.order.resize(d->sphere_count);
-        for (uint32_t i = 0; i < d->sphere_count; i++) bb.order[i] = i;
-        bb.build(0, d->sphere_count);
-        BvhWalkStats st;
-        const uint32_t end[8] = {BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END, BVH_END};
-        std::string e = host_check_sphere_tree(bb.nodes, BVH_ROOT, BVH_ROOT, end, true, 0, st);
-        if (!e.empty()) return bad("sphere bvh: " + e);
-        for (uint32_t oct = 0; oct < 8; oct++) {
-            std::vector<uint32_t> visits(bb.leaf_idx.size(), 0);
-            BvhWalkStats w;
-            e = host_walk_octant(bb.nodes, oct, visits, w);
-            if (!e.empty()) return bad("sphere bvh: " + e);
-            for (uint32_t v : visits) if (v != 1) return bad("sphere bvh: a leaf slot is not visited exactly once");
-            st.nodes = w.nodes; st.leaves = w.leaves;
-        }
-        std::vector<uint32_t> seen(d->sphere_count, 0);
-        if (bb.leaf_idx.size() != d->sphere_count) return bad("sphere bvh: leaf slot count != sphere count");
-        for (uint32_t i : bb.leaf_idx) { if (i >= d->sphere_count || seen[i]++) return bad("sphere bvh: sphere missing or duplicated"); }
-        // every sphere inside the box (centre ± half extent) of its leaf and of every node above it
-        std::function<std::string(uint32_t, std::vector<uint32_t> &)> gather = [&](uint32_t n, std::vector<uint32_t> &sph) -> std::string {
-            uint32_t B;
-            memcpy(&B, &bb.nodes[4 * (size_t)n + 1].w, 4);
-            if (B & 0x80000000u) {
-                uint32_t first = B & 0x0FFFFFFFu, cnt = (B >> 28) & 7u;
-                for (uint32_t k = 0; k < cnt; k++) sph.push_back(bb.leaf_idx[first + k]);
-            } else {
-                for (uint32_t k = 0; k < 2; k++) {
-                    std::vector<uint32_t> sub;
-                    std::string er = gather(B + k, sub);
-                    if (!er.empty()) return er;
-                    sph.insert(sph.end(), sub.begin(), sub.end());
-                }
-            }
-            const float4 &c = bb.nodes[4 * (size_t)n], &h = bb.nodes[4 * (size_t)n + 1];
-            for (uint32_t i : sph) {
-                const rt_sphere &sp = d->spheres[i];
-                const float r = std::fabs(sp.r), p[3] = {sp.pos.x, sp.pos.y, sp.pos.z};
-                for (int k = 0; k < 3; k++) {   // (the sphere's extent in binary32, as BvhBuild::bounds forms it)
-                    const double lo = (double)(&c.x)[k] - (double)(&h.x)[k], hi = (double)(&c.x)[k] + (double)(&h.x)[k];
-                    const float slo = p[k] - r, shi = p[k] + r;
-                    if ((double)slo < lo || (double)shi > hi) return std::string("sphere outside the box of a node above it");
-                }
-            }
-            return "";
-        };
-        {
-            std::vector<uint32_t> all;
-            e = gather(BVH_ROOT, all);
-            if (!e.empty()) return bad("sphere bvh: " + e);
-        }
-        stats[0] = st.nodes; stats[1] = st.leaves; stats[2] = st.max_depth;
-    }
-    // ---- mesh BVHs
-    std::vector<uint32_t> base;
-    std::vector<float4> fr;
-    if (!build_face_records(d, base, fr)) return bad("too many faces");
-    for (uint32_t m = 0; m < d->mesh_count; m++) {
-        uint32_t nf = d->meshes[m].face_count;
-        if (nf < MESH_BVH_MIN_FACES) continue;
-        std::vector<float4> nodes, lfaces;
-        std::vector<uint32_t> lidx;
-        MeshBvhBuilder mb;
-        mb.rec = &fr[3 * (size_t)base[m]];
-        mb.n_faces = nf;
-        mb.nodes = &nodes;
-        mb.leaf_faces = &lfaces;
-        mb.leaf_idx = &lidx;
-        uint32_t root = mb.build();
-        BvhWalkStats st;
-        std::string e = host_check_threaded(nodes, root, root, 0x0FFFFFFFu, true, 0, st);
-        if (!e.empty()) return bad("mesh bvh: " + e);
-        {
-            std::vector<uint32_t> visits(lidx.size(), 0);
-            BvhWalkStats w;
-            e = host_walk_threaded(nodes, root, visits, w);
-            if (!e.empty()) return bad("mesh bvh: " + e);
-            for (uint32_t v : visits) if (v != 1) return bad("mesh bvh: a leaf slot is not visited exactly once");
-            st.nodes = w.nodes; st.leaves = w.leaves;
-        }
-        {   // the links the device walks (wide-cone inner nodes spliced out): still every leaf exactly once
-            std::vector<float4> dev = nodes;
-            std::vector<uint8_t> is_root(dev.size() / 4, 0);
-            is_root[root] = 1;
-            mesh_collapse_links(dev, is_root);
-            std::vector<uint32_t> visits(lidx.size(), 0);
-            BvhWalkStats w;
-            e = host_walk_threaded(dev, root, visits, w);
-            if (!e.empty()) return bad("mesh bvh (collapsed links): " + e);
-            for (uint32_t v : visits) if (v != 1) return bad("mesh bvh (collapsed links): a leaf slot is not visited exactly once");
-        }
-        if (lidx.size() != nf) return bad("mesh bvh: leaf slot count != face count");
-        std::vector<uint32_t> seen(nf, 0);
-        for (uint32_t i : lidx) { if (i >= nf || seen[i]++) return bad("mesh bvh: face missing or duplicated"); }
-        // per node: min face, normal cone, edge and quality bounds, faces inside leaf boxes — from the leaves up
-        std::function<std::string(uint32_t, std::vector<uint32_t> &)> collect = [&](uint32_t n, std::vector<uint32_t> &faces) -> std::string {
-            uint32_t B;
-            memcpy(&B, &nodes[4 * (size_t)n + 1].w, 4);
-            if (B & 0x80000000u) {
-                uint32_t first = B & 0x0FFFFFFFu, cnt = (B >> 28) & 7u;
-                for (uint32_t k = 0; k < cnt; k++) faces.push_back(lidx[first + k]);
-            } else {
-                uint32_t right;
-                memcpy(&right, &nodes[4 * (size_t)B].w, 4);
-                for (uint32_t k = 0; k < 2; k++) {
-                    std::vector<uint32_t> sub;
-                    std::string er = collect(k ? (right & 0x0FFFFFFFu) : B, sub);
-                    if (!er.empty()) return er;
-                    faces.insert(faces.end(), sub.begin(), sub.end());
-                }
-            }
-            const float4 &lo = nodes[4 * (size_t)n], &hi = nodes[4 * (size_t)n + 1], &cone = nodes[4 * (size_t)n + 2], &ex = nodes[4 * (size_t)n + 3];
-            uint32_t min_face;
-            memcpy(&min_face, &ex.y, 4);
-            uint32_t true_min = 0xFFFFFFFFu;
-            for (uint32_t f : faces) {
-                true_min = std::min(true_min, f);
-                const float4 *q = mb.rec + 3 * (size_t)f;
-                double A[3] = {q[0].x, q[0].y, q[0].z}, e1[3] = {q[0].w, q[1].x, q[1].y}, e2[3] = {q[1].z, q[1].w, q[2].x};
-                for (int k = 0; k < 3; k++) {   // (lo, hi here: the node's centre and half extent)
-                    const double l = (double)(&lo.x)[k] - (double)(&hi.x)[k], h = (double)(&lo.x)[k] + (double)(&hi.x)[k];
-                    double p[3] = {A[k], A[k] + e1[k], A[k] + e2[k]};
-                    for (double v : p) if (v < l || v > h) return std::string("face outside its node box");
-                }
-                double nl = std::sqrt((double)q[2].y * q[2].y + (double)q[2].z * q[2].z + (double)q[2].w * q[2].w);
-                if (std::isfinite(nl) && nl > 0.5 && ex.w > 0.0f) {
-                    double dt = (cone.x * q[2].y + cone.y * q[2].z + cone.z * q[2].w) / nl;
-                    double cos_a = cone.w, sin_a = ex.x;
-                    // the face normal must lie inside the cone (cos/sin describe the half angle; 0/1 = hemisphere or wider)
-                    if (!(cos_a == 0.0 && sin_a == 1.0) && dt < cos_a - 1e-5) return std::string("face normal outside the node's cone");
-                }
-                double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
-                if (l1 > ex.z * 1.0001 || l2 > ex.z * 1.0001) return std::string("edge longer than the node's bound");
-            }
-            if (true_min != min_face) return std::string("wrong smallest face index");
-            return "";
-        };
-        std::vector<uint32_t> all;
-        e = collect(root, all);
-        if (!e.empty()) return bad("mesh bvh: " + e);
-        // the device's 48-byte form of every node (mesh_node_pack): binary16 fields rounded to the safe side
-        for (size_t n = root; n < nodes.size() / 4; n++) {
-            const float4 *nd = &nodes[4 * n];
-            float4 pk[3];
-            mesh_node_pack(nd, pk);
-            uint32_t p[3];
-            memcpy(p, &pk[2], 12);
-            const float hx = bvh_half_value(p[0] & 0xFFFFu), hy = bvh_half_value(p[0] >> 16), hz = bvh_half_value(p[1] & 0xFFFFu);
-            const float sn = bvh_half_value(p[1] >> 16), em = bvh_half_value(p[2] & 0xFFFFu), q = bvh_half_value(p[2] >> 16);
-            if (!(hx >= nd[1].x && hy >= nd[1].y && hz >= nd[1].z)) return bad("mesh bvh: packed half extent below the node's");
-            if (!(sn >= nd[3].x) || !(em >= nd[3].z) || !(q <= nd[3].w)) return bad("mesh bvh: packed cone / edge / quality on the wrong side");
-            if (memcmp(&pk[0], &nd[0], 16) || memcmp(&pk[1], &nd[2], 12) || memcmp(&pk[1].w, &nd[1].w, 4) || memcmp(&pk[2].w, &nd[3].y, 4))
-                return bad("mesh bvh: packed node differs in an unpacked field");
-        }
-        stats[3] += st.nodes; stats[4] += st.leaves; stats[5] = std::max(stats[5], st.max_depth); stats[6]++;
-    }
-    return RT_OK;
+    PreparedScene ps;
+    std::string msg;
+    int rc = prepare_scene(*d, ps, msg);
+    if (rc == RT_OK) rc = check_prepared(*d, ps, stats, msg);
+    if (rc != RT_OK && err && err_len) snprintf(err, err_len, "%s", msg.c_str());
+    return rc;
 }
 
 extern "C++" {

@@ -1,5 +1,5 @@
 // rt_context.hpp — the context behind the C ABI (include/rt_amd.h) and the helpers every translation unit of
-// librt_amd.so shares: rt_amd.hip (host side: C ABI, scene upload, BVH builders, policy-free kernels), rt_denoise.hip
+// librt_amd.so shares: rt_amd.hip (host side: C ABI, scene upload from scene_prep.hpp, policy-free kernels), rt_denoise.hip
 // (the denoisers, policy-free) and pt_kernels.hip (the path-tracing kernels and their launchers, compiled once per
 // arithmetic policy).
 #pragma once

@@ -142,8 +142,10 @@ def load_library(path=LIB_PATH):
 
 
 def check_accel(scene):
-    """Host-only self-check of the BVHs rt_set_scene would build for `scene` (no device needed).
-    → stats dict; raises RtError with the violated invariant."""
+    """Host-only self-check of what rt_set_scene would upload for `scene` (no device needed): the scene is validated
+    and prepared as rt_set_scene does it, and the invariants of the prepared structures are verified.
+    → stats dict ("digest": FNV-1a-64 of the prepared arrays); raises RtError with the validation error or the
+    violated invariant."""
     lib = load_library()
     d = scene.desc()
     stats = (C.c_uint64 * 8)()
@@ -151,7 +153,7 @@ def check_accel(scene):
     rc = lib.rt_debug_check_accel(C.byref(d), stats, err, 256)
     if rc:
         raise RtError(rc, err.value.decode() or "accel check failed")
-    keys = ("sphere_nodes", "sphere_leaves", "sphere_depth", "mesh_nodes", "mesh_leaves", "mesh_depth", "meshes")
+    keys = ("sphere_nodes", "sphere_leaves", "sphere_depth", "mesh_nodes", "mesh_leaves", "mesh_depth", "meshes", "digest")
     return dict(zip(keys, [int(v) for v in stats]))
 
 
