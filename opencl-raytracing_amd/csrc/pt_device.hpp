@@ -73,7 +73,13 @@ PT_DEV LdsV4 lds_ptr(const float4 *generic) { return (LdsV4)generic; }
 
 struct Ctx {
     const DeviceScene &sc;
-    LdsV4 lmat;  // LDS: [2i] = (r,g,b,extra), [2i+1].x = type bits; nullptr → read global
+    // The three table pointers double as "is it staged?" (nullptr → read global) — which is only sound for a table that does
+    // not stand at LDS address 0: that address IS this address space's nullptr, so the table that opens a workgroup's LDS
+    // (the materials; the winners or planes where the sets before them are over their caps) reads as absent whatever was
+    // staged.  The instantiations that ask BY_COUNT (has_materials & co. below) never look at the pointers' null state, and
+    // there the value 0 is a valid table.  Every other kernel still asks the pointer and reads such a table from global memory:
+    // same values, more work (open items).
+    LdsV4 lmat;  // LDS: [2i] = (r,g,b,extra), [2i+1].x = type bits; nullptr → read global (see above)
     LaneCounters *cn;
     LdsV4 lwin = nullptr;  // LDS winner records of small sphere sets (stage_materials), or nullptr
     LdsV4 lpln = nullptr;  // LDS (normal, mat) of small plane sets, or nullptr
@@ -143,8 +149,20 @@ PT_DEV LdsV4 staged_planes(const DeviceScene &sc, const float4 *lds) {
     return lds_pln_n(sc.plane_count) ? lds_ptr(lds + lds_mat_n(sc.material_count) + lds_win_n(sc.sphere_count)) : (LdsV4) nullptr;
 }
 
+// Is the table staged?  BY_COUNT (pt_samples_q without counters and without a BVH walk, PT_TABLES_BY_COUNT) asks the rule that
+// staged it — lds_*_n of the scene's counts, a scalar compare of launch constants — where every other kernel asks the
+// pointer.  The two differ for a table that opens the workgroup's LDS: LDS address 0 IS the null pointer of that address
+// space, so the pointer calls the queue kernel's material table absent and every lane reads the global records instead.
+template <bool BY_COUNT>
+PT_DEV bool has_materials(const Ctx &c) { return BY_COUNT ? lds_mat_n(c.sc.material_count) != 0u : c.lmat != nullptr; }
+template <bool BY_COUNT>
+PT_DEV bool has_winners(const Ctx &c) { return BY_COUNT ? lds_win_n(c.sc.sphere_count) != 0u : c.lwin != nullptr; }
+template <bool BY_COUNT>
+PT_DEV bool has_planes(const Ctx &c) { return BY_COUNT ? lds_pln_n(c.sc.plane_count) != 0u : c.lpln != nullptr; }
+
+template <bool BY_COUNT = false>
 PT_DEV void load_material(const Ctx &c, uint32_t id, int &type, float &extra, V3 &col) {
-    if (c.lmat) {
+    if (has_materials<BY_COUNT>(c)) {
         float4 a = lds_ld(c.lmat, 2 * id);
         type = __float_as_int(lds_ld(c.lmat, 2 * id + 1).x);
         extra = a.w;
@@ -692,7 +710,7 @@ PT_DEV void hit_models(const Ctx &c, const Ray &r, Nearest &nb) {
 }
 
 // SIMPLE = true: the winner can only be a sphere or a plane (no lens / mesh code)
-template <bool COUNT, bool SIMPLE = false>
+template <bool COUNT, bool SIMPLE = false, bool BY_COUNT = false>
 PT_DEV bool hit_finish(const Ctx &c, const Ray &r, const Nearest &nb, Hit &hit) {
     const DeviceScene &sc = c.sc;
     const float best_t = nb.t;
@@ -715,7 +733,7 @@ PT_DEV bool hit_finish(const Ctx &c, const Ray &r, const Nearest &nb, Hit &hit) 
     hit.tex = 0;
     if (kind == K_PLANE) {
         V3 n;
-        if (c.lpln) {
+        if (has_planes<BY_COUNT>(c)) {
             float4 w = lds_ld(c.lpln, idx);
             n = xyz(w);
             hit.mat = __float_as_uint(w.w);
@@ -742,7 +760,7 @@ PT_DEV bool hit_finish(const Ctx &c, const Ray &r, const Nearest &nb, Hit &hit) 
         V3 centre;
         float rad;
         if (SIMPLE || kind == K_SPHERE) {
-            if (c.lwin) {
+            if (has_winners<BY_COUNT>(c)) {
                 float4 w = lds_ld(c.lwin, 2 * idx);
                 centre = xyz(w);
                 rad = w.w;
@@ -839,10 +857,11 @@ struct GlassTerms {
     V3 n;
     float ratio, cai, r0;
 };
+template <bool BY_COUNT = false>
 PT_DEV GlassTerms glass_terms(const Ctx &c, V3 d, V3 hn, uint32_t mat, float extra) {
     // 1/extra and Schlick's r0² per material: from the workgroup's LDS table when there is one
     float inv_extra, r0_extra, r0_inv;
-    if (c.lmat) {
+    if (has_materials<BY_COUNT>(c)) {
         float4 x = lds_ld(c.lmat, 2 * mat + 1);
         inv_extra = x.y; r0_extra = x.z; r0_inv = x.w;
     } else {
@@ -867,7 +886,7 @@ PT_DEV GlassTerms glass_terms(const Ctx &c, V3 d, V3 hn, uint32_t mat, float ext
 PT_DEV float glass_disc(const GlassTerms &g) { return nmad(g.ratio * g.ratio, nmad(g.cai, g.cai, 1.0f), 1.0f); }   // 1 - ratio * ratio * (1 - cai * cai)   (:381,:424)
 
 // FAST: the glass refraction's square root and the shared tail's normalize in their tagged forms (pt_arith.hpp)
-template <bool COUNT, bool FAST = false>
+template <bool COUNT, bool FAST = false, bool BY_COUNT = false>
 PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float extra, V3 col, const Rnd &rnd,
                     bool set_origin = true) {
     V3 v;
@@ -881,7 +900,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
         v = nmad(h.n, k, r.d);   // dir - 2 dot(dir, n) * n
         out = out * extra;  // :366 — only for t_reflective
     } else if (type == RT_REFRACTIVE || type == RT_DIELECTRIC) {
-        const GlassTerms g = glass_terms(c, r.d, h.n, h.mat, extra);
+        const GlassTerms g = glass_terms<BY_COUNT>(c, r.d, h.n, h.mat, extra);
         const V3 n = g.n;
         const float ratio = g.ratio, cai = g.cai;
         bool want = true;

@@ -587,6 +587,10 @@ struct WaveQueue {
 #ifndef PT_STAGE_COPY
 #define PT_STAGE_COPY 1      // pt_samples_q<false, false, …> copies the scene's LDS tables from the context's block
 #endif
+// What a wave issues per iteration of the sample loop and the result does not need (profiles/r20_experiments.md):
+#ifndef PT_TABLES_BY_COUNT
+#define PT_TABLES_BY_COUNT 1 // pt_samples_q<false, false, …>: "is the table staged?" is asked of the scene's counts, not of the LDS pointer
+#endif
 
 // queue_stage's slot → (x, y).  slot_to_pixel divides the tile index by fp.tiles_x, a launch constant, with the generic
 // uint32 division (about 25 VALU instructions).  An unsharded frame (world == 1, so rank == 0 and t = slot >> tpix_log2)
@@ -947,6 +951,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     // (pt_device.hpp sphere_take): this kernel without counters and without a BVH walk only — every other kernel, and
     // every other instantiation of this one, keeps the untagged code.
     constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
+    // The presence of the staged tables by count (pt_device.hpp has_materials): the instantiations that copy the staged block, in every policy.
+    constexpr bool BY_COUNT = PT_TABLES_BY_COUNT && !COUNT && !ACCEL;
     // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
     // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
     // anything is staged: no barrier, no sums, and only zeros to add to the counters.
@@ -1078,8 +1084,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             int type;
             float extra;
             V3 mcol;
-            load_material(c, hmat, type, extra, mcol);   // type and extra_data are not carried: one LDS read each
-            scatter<COUNT, FAST>(c, r, out, at, type, extra, col, rnd, false);
+            load_material<BY_COUNT>(c, hmat, type, extra, mcol);   // type and extra_data are not carried: one LDS read each
+            scatter<COUNT, FAST, BY_COUNT>(c, r, out, at, type, extra, col, rnd, false);
             depth++;
             if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
                 queue_put(q, idx, out);
@@ -1098,7 +1104,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             Nearest nb;
             hit_primitives<COUNT, ACCEL, GEOM != 0, FAST>(c, r, nb);
             if (GEOM != 0) hit_models<COUNT, GEOM == 2>(c, r, nb);
-            if (!hit_finish<COUNT, GEOM == 0>(c, r, nb, h)) {
+            if (!hit_finish<COUNT, GEOM == 0, BY_COUNT>(c, r, nb, h)) {
                 res = mk(0.0f, 0.0f, 0.0f);
                 done = true;
             } else {
@@ -1110,7 +1116,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 hmat = h.mat;
                 int type;
                 float extra;
-                load_material(c, h.mat, type, extra, col);
+                load_material<BY_COUNT>(c, h.mat, type, extra, col);
                 if (type == RT_LIGHT) {
                     res = vmin(out, col);
                     done = true;
