@@ -78,6 +78,10 @@ void RayTracer::renderSamplesCameras(const std::vector<float> &blocks, uint32_t 
     check(rt_render_spp_cameras(ctx, blocks.data(), first_sample, (uint32_t)(blocks.size() / 12)));
 }
 
+void RayTracer::renderAgainCameras(const std::vector<float> &blocks) {
+    check(rt_render_again_cameras(ctx, blocks.data(), (uint32_t)(blocks.size() / 12)));
+}
+
 const float *RayTracer::renderFrameCameras(const std::vector<float> &blocks) {
     check(rt_clear(ctx));
     renderSamplesCameras(blocks, 0);

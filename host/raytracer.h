@@ -62,6 +62,10 @@ public:
     // renderSamples.  renderFrameCameras: clear + that from sample 0 + resolve + read back
     void renderSamplesCameras(const std::vector<float> &blocks, uint32_t first_sample);
     const float *renderFrameCameras(const std::vector<float> &blocks);
+    // renderAgain through a cyclic schedule of camera blocks (rt_render_again_cameras): the call that makes sample s looks
+    // through block s mod n of `blocks` (n x 12 floats) — renderAgain's bits for that block, served from look-ahead batches
+    // while the calls repeat one table
+    void renderAgainCameras(const std::vector<float> &blocks);
     // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
     // the same through per-sample camera blocks (rt_render_adaptive_cameras): sample j of every pixel through block j of

@@ -8,6 +8,7 @@
 //              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
 //          [--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
+//          [--progressive-cameras [--lookahead N]]
 // --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
 // --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
 // sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
@@ -20,6 +21,10 @@
 // a frame adaptively (rt_render_adaptive_cameras): --adaptive's rounds, --batch, --min-spp, --spp (the maximum, default 1024)
 // and --counts, with sample j of every pixel through block j of the run's --spp sample cameras; --denoise, --aov and
 // --aa-guides work as with --spp.
+// --progressive-cameras (with --aa or --aperture R --focus D; refused with --progressive, --adaptive, --adaptive-cameras and
+// --denoise) renders such a frame like the interactive app: render(block 0) + (spp - 1) x renderAgainCameras(table), the
+// table being the run's first min(spp, 4096) sample cameras, sample s through block s mod that (rt_render_again_cameras);
+// --lookahead N is accepted with it, and the image is the same whatever N.
 // --progressive renders like the interactive app (render + spp-1 × renderAgain, one launch
 // per sample, or with look-ahead — --lookahead N, 0 or 2 .. 64, default the library's 16 — one fused launch per N samples
 // whose frames the calls hand out: the same image either way); the default is the fused path (all samples in one launch).  --adaptive renders
@@ -66,7 +71,7 @@ static void check_rc(int rc) {
 
 static void usage() {
     std::cerr << "usage: rt_cli --scene FILE [--size WxH] [--spp N] [--camera=x,y,z,yaw,pitch] [--fov DEG] "
-                 "[--seed N] [--progressive [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
+                 "[--seed N] [--progressive [--lookahead N]] [--progressive-cameras [--lookahead N]] [--out F.tga] [--pfm F.pfm] [--raw F.f32] [--device N] "
                  "[--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
@@ -146,7 +151,7 @@ int main(int argc, char **argv) {
     int w = 1200, h = 800, spp = 16, device = 0, fov = 60;  // the reference's window is 1200x800 (main.cpp:9-12)
     float cam[5] = {0, 0, 0, 0, 0};
     unsigned long long seed = 0xC0FFEE;
-    bool progressive = false;
+    bool progressive = false, progressive_cameras = false;
     long lookahead = -1;   // (-1: the library's default)
     bool adaptive = false, adaptive_cameras = false, spp_given = false;
     float threshold = 0.0f;
@@ -231,6 +236,7 @@ int main(int argc, char **argv) {
         else if (a == "--measured") measured = true;
         else if (a == "--split-chains") split_chains = true;
         else if (a == "--progressive") progressive = true;
+        else if (a == "--progressive-cameras") progressive_cameras = true;
         else usage();
     }
     if (spp < 1 || w < 1 || h < 1) usage();
@@ -242,7 +248,8 @@ int main(int argc, char **argv) {
     if ((max_chain >= 0 || split_chains) && !follow) usage();
     if (split_chains && !denoise) usage();
     if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
-    if (!progressive && lookahead >= 0) usage();                           // progressive-only flag
+    if (progressive_cameras && (progressive || adaptive || adaptive_cameras || denoise)) usage();   // one way to spend the samples; the running mean lives in the image
+    if (!progressive && !progressive_cameras && lookahead >= 0) usage();   // progressive-only flag
     if ((aperture > 0.0f) != focus_given) usage();                         // a lens has a radius and a focus distance
     const bool cameras = aa || aperture > 0.0f;
     if (cameras && (progressive || adaptive)) {
@@ -250,7 +257,7 @@ int main(int argc, char **argv) {
                      "all samples through one camera: use --spp" << std::endl;
         return 2;
     }
-    if (adaptive_cameras && !cameras) usage();                             // needs the per-sample cameras of --aa / --aperture
+    if ((adaptive_cameras || progressive_cameras) && !cameras) usage();    // need the per-sample cameras of --aa / --aperture
     if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
     if (aa_guides && (!cameras || (!denoise && aov_prefix.empty()))) usage();   // guides of a per-sample-camera frame, for --denoise / --aov
     if (!dn_iterations) dn_iterations = 5;
@@ -312,6 +319,12 @@ int main(int argc, char **argv) {
         tracer.render(&camera);
         for (int s = 1; s < spp; s++) tracer.renderAgain(&camera);
         img = tracer.transferImage();
+    } else if (progressive_cameras) {
+        if (lookahead >= 0) tracer.setLookahead((int)lookahead);
+        const std::vector<float> table = camera.sampleBlocks((uint32_t)std::min<long>(spp, (long)RT_AGAIN_CAMERAS_MAX), 0, w, h, aa, aperture, focus);
+        check_rc(rt_render(tracer.context(), table.data()));
+        for (int s = 1; s < spp; s++) tracer.renderAgainCameras(table);
+        img = tracer.transferImage();
     } else if (cameras) {
         img = tracer.renderFrameCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus));
     } else {
@@ -325,7 +338,7 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back" << std::endl;
         if (!out_counts.empty()) write_counts(out_counts, tracer.sampleCounts(), w, h);
     } else {
-        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
+        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : progressive_cameras ? "progressive per-sample cameras" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 

@@ -310,6 +310,32 @@ int rt_resolve(rt_context *ctx);
 int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_sample, uint32_t n_samples);
 
 /*
+ * Progressive anti-aliasing (new): rt_render_again through a CYCLIC SCHEDULE of camera blocks.  `cameras` is a host pointer to
+ * n_cameras x 12 floats, copied during the call; the call that makes sample s = sample_counter + 1 looks through block
+ * s mod n_cameras (a caller who starts with rt_render(ctx, cameras) has sample 0 through block 0).
+ *   - The image, the sample counter and every other piece of state after the call are, bit for bit, what
+ *     rt_render_again(ctx, cameras + 12 * (s % n_cameras)) leaves with RT_OPT_LOOKAHEAD 0.  Synchronous; one entry in the
+ *     event history per call.  The accumulator, the feature records, the sample moments and a kept prefix stay untouched.
+ *   - Look-ahead through the table: the context keeps a copy of the table of the previous rt_render_again_cameras call.  A
+ *     call whose table equals it (n_cameras and every bit), with no batch pending and RT_OPT_LOOKAHEAD = K >= 2, traces the
+ *     next K' = rt_lookahead_plan(w, h, K, sample_counter) samples in ONE camera launch — sample s + j through block
+ *     (s + j) mod n_cameras — and leaves K' images in the ring; this call and the next K' - 1 equal calls hand them out as
+ *     rt_render_again does.  The first call with a new table runs the direct kernel and is remembered, so a caller who
+ *     changes the table on every call never pays for a batch.
+ *   - Pending frames are dropped by everything that drops them for rt_render_again, by a table that differs in any bit or
+ *     in n_cameras, and by a plain rt_render_again between two table calls; a pending plain batch is dropped by this call,
+ *     and a plain rt_render_again that follows a table call repeats no plain call and runs direct.
+ *   - The direct kernel (same bits) also runs with counters enabled, on a sharded context, with RT_OPT_SAMPLE_QUEUE 0, where
+ *     RT_OPT_MAX_THREADS_PER_LAUNCH splits the frame into several slot ranges, and where K' < 2.  RT_OPT_PREFIX_SHARING does
+ *     not matter (camera launches share no prefix), nor does RT_OPT_MOMENTS (the compat path keeps no moments).
+ *   - rt_lookahead_stats counts these batches, served calls, direct calls and discarded frames with rt_render_again's.
+ * RT_EINVAL: a NULL pointer, n_cameras 0 or above RT_AGAIN_CAMERAS_MAX, the sample counter at RT_MAX_SAMPLE.  RT_ESTATE: no
+ * scene set.  A failed call changes nothing.
+ */
+#define RT_AGAIN_CAMERAS_MAX 4096u
+int rt_render_again_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras);
+
+/*
  * Adaptive sampling (new): render until every decision block of block_w x block_h pixels has converged.
  * Round k (k = 0, 1, ...) traces samples k*batch .. k*batch+c-1, c = min(batch, max_spp - k*batch), of every pixel of
  * a still-active block, so a pixel whose count is n holds exactly samples 0 .. n-1 and each round adds, bit for bit,
@@ -787,7 +813,8 @@ int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses);
 
 /* Look-ahead (RT_OPT_LOOKAHEAD) since rt_create: `batches` look-ahead launches; `served` rt_render_again calls whose image
  * came from a look-ahead frame (the launching call included); `direct` rt_render_again calls that ran the direct kernel;
- * `discarded` frames computed and dropped before a call could hand them out. */
+ * `discarded` frames computed and dropped before a call could hand them out.  rt_render_again_cameras calls count with
+ * rt_render_again's. */
 int rt_lookahead_stats(rt_context *ctx, uint64_t *batches, uint64_t *served, uint64_t *direct, uint64_t *discarded);
 
 /* Host-only (no device, no context): the number of samples the look-ahead launch of an rt_render_again call would trace

@@ -258,6 +258,7 @@ class CameraFacts(_U32Record):
 
 
 CAMERA_PLAN_FIXED, CAMERA_PLAN_QUEUE = 0, 1   # rt_camera_plan.family
+AGAIN_CAMERAS_MAX = 4096                      # RT_AGAIN_CAMERAS_MAX: blocks of an rt_render_again_cameras table
 
 
 class CameraPlan(_U32Record):
@@ -271,6 +272,7 @@ def camera_prototypes(lib):
     """ctypes prototypes of rt_render_spp_cameras and its plan probes."""
     vp, u32 = C.c_void_p, C.c_uint32
     lib.rt_render_spp_cameras.argtypes = [vp, vp, u32, u32]
+    lib.rt_render_again_cameras.argtypes = [vp, vp, u32]
     lib.rt_debug_plan_camera_samples.argtypes = [C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
     lib.rt_debug_last_camera_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
     lib.rt_render_features_cameras.argtypes = [vp, vp, u32, C.POINTER(FeatureChainParams)]

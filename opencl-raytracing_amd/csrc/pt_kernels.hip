@@ -855,8 +855,15 @@ PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__rest
 // p' (a wave owns at most QUEUE_MAX_PIXELS = 16 of them): the chain of a channel is sequential by definition, and the four
 // lanes of a pixel store its 16 bytes of a frame with one instruction (channel 3 is the alpha of 1).
 // Every lane of the wave calls it.
+// CAM (a look-ahead launch of the camera entry, rt_render_again_cameras): fp.cams holds the eight bytes la_image would, so
+// the start image comes from the RING — the host has copied the image as it lies into frame 0 before the launch, and the
+// lane takes its channel from there before its own loop overwrites that element (the same lane owns (pixel, channel) for
+// the read and for every write, and no other wave owns the pixel).  Everything after that read is the same code.
 static_assert(QUEUE_MAX_PIXELS * 4u <= 64u, "queue_replay maps (pixel, channel) to the wave's lanes");
+template <bool CAM = false>
 PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
+    static_assert(!CAM || !PT_RING_PIXEL_MAJOR, "the camera look-ahead's start image is frame 0 of a frame-major ring (one contiguous "
+                                                "device copy of the image); the pixel-major A/B layout has no such frame");
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const uint32_t lane = threadIdx.x, ch = lane & 3u;
@@ -865,8 +872,8 @@ PT_DEV void queue_replay(const WaveQueue &q, const FrameParams &fp) {
         const uint32_t p = pb + (lane >> 2);
         if (p >= q.npix) continue;
         const size_t pix = (size_t)q.xy[p].y * fp.w + q.xy[p].x;
-        float prev = reinterpret_cast<const float *>(fp.la_image)[4u * pix + ch];
         float *out = reinterpret_cast<float *>(fp.la_ring) + ch;
+        float prev = CAM ? out[4u * ring_at(fp, pix, 0u)] : reinterpret_cast<const float *>(fp.la_image)[4u * pix + ch];
         const LdsF32 sl = q.slot + 3u * (p * q.count) + (alpha ? 0u : ch);
         for (uint32_t j = 0; j < q.count; j++) {
             prev = retrace_step1(prev, 0.0f + sl[3u * j], fp.first + j);
@@ -940,217 +947,21 @@ PT_DEV CameraEntry queue_fetch_cam(const WaveQueue &q, const FrameParams &fp, ui
 // the primary ray of its sample's own camera block, depth 0 and path colour (1, 1, 1), and — there is no interaction at
 // the camera — passes its first interaction step (`fresh`) and enters the loop at the nearest-hit step; from there the
 // body, queue_put and queue_sums are the code of the record-fed instantiations.  recs, live and live_count are NULL.
-template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1, bool CAM = false>
-__global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
-                                                    const uint32_t *__restrict__ live,
-                                                    const uint32_t *__restrict__ live_count,
-                                                    float4 *__restrict__ accum, unsigned long long *counters,
-                                                    uint32_t pixels_per_wave) {
-    extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
-    // The tagged forms of sqrt and normalize (pt_arith.hpp) and the sphere scan that compares inside the root block
-    // (pt_device.hpp sphere_take): this kernel without counters and without a BVH walk only — every other kernel, and
-    // every other instantiation of this one, keeps the untagged code.
-    constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
-    // The presence of the staged tables by count (pt_device.hpp has_materials): the instantiations that copy the staged block, in every policy.
-    constexpr bool BY_COUNT = PT_TABLES_BY_COUNT && !COUNT && !ACCEL;
-    // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
-    // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
-    // anything is staged: no barrier, no sums, and only zeros to add to the counters.
-    static_assert(!CAM || (!COUNT && !MOMENTS && COUNT_LOG2 < 0), "the camera entry has no counting, moment or count-specialised build");
-    uint32_t pix0 = 0, npix = 0;
-    uint32_t cam_x = 0, cam_y = 0;   // CAM: the pixel of this lane's slot, if the wave owns it
-    bool cam_owns = false;
-    unsigned long long cam_owners = 0;
-    if (CAM) {
-        const uint32_t slot = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
-        cam_owns = threadIdx.x < pixels_per_wave && slot < fp.slot_end && slot_to_pixel(fp, slot, cam_x, cam_y) && pixel_active(fp, cam_x, cam_y);
-        cam_owners = __ballot(cam_owns);
-        npix = (uint32_t)__popcll(cam_owners);
-    } else {
-        npix = live_take(fp, live_count, blockIdx.x, pixels_per_wave, pix0);
-    }
-    if (npix == 0u) return;
-    float4 *s_mat = s_dyn;
-    LaneCounters cn;
-    if (COUNT) zero_counters(cn);
-    // (without counters and without a BVH walk: the tables by copy from the context's staged block — launch_fused built it)
-    Ctx c{sc, PT_STAGE_COPY && !COUNT && !ACCEL ? stage_materials_copy(sc, s_mat) : stage_materials(sc, s_mat), &cn};
-    c.lwin = staged_winners(sc, s_mat);
-    c.lpln = staged_planes(sc, s_mat);
-    if (GEOM != 0 && fp.lds_face_f4) {   // the face records of a scene of a few small meshes (hit_models' candidate loop)
-        float4 *s_faces = s_dyn + queue_faces_f4(sc);
-        for (uint32_t i = threadIdx.x; i < fp.lds_face_f4; i += blockDim.x) s_faces[i] = sc.faces[i];
-        __syncthreads();
-        c.lfaces = lds_ptr(s_faces);
-    }
-
-    const WaveQueue q = CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
-                            : queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
-
-    uint32_t next = 0;  // wave-uniform head of the queue
-    bool active = false;
-    bool fresh = false;  // CAM: the lane stands at the camera — no interaction before its first nearest-hit search
-    // Per-lane state carried from one iteration to the next, kept small (the kernel sits on its VGPR budget):
-    // the hit POINT is not carried — the ray's origin is moved there as soon as the hit is known — and the
-    // per-sample part of the table index sums is precomputed (bv, bu) instead of carrying sample, x and y.
-    uint32_t idx = 0, depth = 0, bv = 0, bu = 0;
-    V3 col = mk(0.0f, 0.0f, 0.0f), out = mk(0.0f, 0.0f, 0.0f);   // col: material colour or texel of the hit
-    Ray r;
-    r.o = r.d = mk(0.0f, 0.0f, 0.0f);
-    V3 hn = mk(0.0f, 0.0f, 0.0f);   // normal and material of the hit the next interaction happens at
-    uint32_t hmat = 0;
-    Rnd rnd;
-    rnd.v = mk(0.0f, 0.0f, 0.0f);
-    rnd.u = 0.0f;
-
-#if PT_STAMPS
-    c.st_last = __builtin_amdgcn_s_memtime();
-#endif
-    while (true) {
-        PT_STAMP(c, 5);
-        // ---- refill idle lanes from the queue
-        bool need = !active;
-        unsigned long long m = __ballot(need);
-        // refill when enough lanes idle (or none is active): the refill step issues for the whole wave
-        if (m && next < q.total && ((uint32_t)__popcll(m) >= PT_REFILL_MIN || m == ~0ull)) {
-            uint32_t cand = next + lanes_below(m);
-            if (CAM) {
-                if (need && cand < q.total) {
-                    idx = cand;
-                    const CameraEntry e = queue_fetch_cam(q, fp, idx);
-                    bv = e.bv;
-                    bu = e.bu;
-                    depth = 0u;
-                    r = e.r;
-                    out = mk(1.0f, 1.0f, 1.0f);
-                    if (PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-                    active = true;
-                    fresh = true;
-                }
-            } else
-            if (need && cand < q.total) {
-                idx = cand;
-                const QueueEntry e = queue_fetch<COUNT_LOG2>(q, sc, fp, idx);
-                bv = e.bv;
-                bu = e.bu;
-                if (COUNT) cn.c[CN_SAMPLES]++;
-                // the state of an idle lane is dead: it takes the record whatever its kind, so that the registers are
-                // written in place (a final colour's lane stays idle and its state is never read)
-                depth = (e.bits >> 8) & 0xFFu;   // (type and extra_data of the record are the material's: re-read below)
-                hn = xyz(e.q1);
-                r.o = xyz(e.q0);
-                r.d = xyz(e.q2);
-                hmat = __float_as_uint(e.q2.w);
-                out = xyz(e.q3);
-                col = xyz(e.q4);
-                if ((e.bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
-                    queue_put(q, idx, out);
-                } else {
-                    if (PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-                    active = true;
-                }
-            }
-            next += (uint32_t)__popcll(m);
-        }
-        if (!__any(active) && next >= q.total) break;
-        PT_STAMP(c, 0);
-#ifdef PT_EXP_PAD  // timing experiment (tools/pad_experiment.sh): PT_EXP_PAD extra full-rate VALU instructions per iteration
-                   // (v_or_b32 x, x, x on a live register: no new VGPR; PT_EXP_PAD_NOP: operand-free v_nop instead).  An
-                   // issue-bound loop slows down by their issue time, a latency-bound one does not (profiles/r03_experiments.md)
-#define PT_STR2(x) #x
-#define PT_STR(x) PT_STR2(x)
-#ifdef PT_EXP_PAD_NOP
-        asm volatile(".rept " PT_STR(PT_EXP_PAD) "\n\tv_nop\n\t.endr");
-#else
-        asm volatile(".rept " PT_STR(PT_EXP_PAD) "\n\tv_or_b32 %0, %0, %0\n\t.endr" : "+v"(idx));
-#endif
-#endif
-#ifdef PT_QSTAT  // diagnostic: lane-iterations used / offered (read through rt_get_debug_counters on a BVH-free scene)
-        if (COUNT && __any(active)) {   // (an iteration that only refilled final colours is not offered)
-            uint32_t na = (uint32_t)__popcll(__ballot(active));
-            if (threadIdx.x == 0) cn.c[CN_DBG_BVH_NODES] += na;
-            if (threadIdx.x == 0) cn.c[CN_DBG_BVH_TESTS] += 64u;
-        }
-#endif
-        // ---- one material interaction for every active lane
-        if (CAM ? active && !fresh : active) {
-            if (!PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-            Hit at;   // the vertex this interaction happens at: the ray's origin already stands on it
-            at.p = r.o;
-            at.n = hn;
-            at.u = at.v = 0.0f;
-            at.tex = 0;
-            at.mat = hmat;
-            int type;
-            float extra;
-            V3 mcol;
-            load_material<BY_COUNT>(c, hmat, type, extra, mcol);   // type and extra_data are not carried: one LDS read each
-            scatter<COUNT, FAST, BY_COUNT>(c, r, out, at, type, extra, col, rnd, false);
-            depth++;
-            if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
-                queue_put(q, idx, out);
-                active = false;
-            }
-        }
-        if (CAM) fresh = false;
-        PT_STAMP(c, 1);
-        // ---- nearest hit for every lane still active; the table reads of the NEXT material
-        // interaction are issued first (they depend on the ray direction only)
-        if (active) {
-            if (PT_RNG_PREFETCH == 1) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-            V3 res;
-            bool done = false;
-            Hit h;   // (every field is written by hit_finish on a hit, and read only then)
-            Nearest nb;
-            hit_primitives<COUNT, ACCEL, GEOM != 0, FAST>(c, r, nb);
-            if (GEOM != 0) hit_models<COUNT, GEOM == 2>(c, r, nb);
-            if (!hit_finish<COUNT, GEOM == 0, BY_COUNT>(c, r, nb, h)) {
-                res = mk(0.0f, 0.0f, 0.0f);
-                done = true;
-            } else {
-                if (COUNT) cn.c[CN_H_BOUNCE]++;
-                // the next interaction happens here (for a light the lane retires below and this state is dead):
-                // written in the branch that computed it, so that the registers are updated in place
-                r.o = h.p;
-                hn = h.n;
-                hmat = h.mat;
-                int type;
-                float extra;
-                load_material<BY_COUNT>(c, h.mat, type, extra, col);
-                if (type == RT_LIGHT) {
-                    res = vmin(out, col);
-                    done = true;
-                } else if (type == RT_TEXTURED) {
-                    if (COUNT) cn.c[CN_N_TEXFETCH]++;
-                    float tu = h.u, tv = h.v;
-                    // (GEOM 0: hit_finish leaves u = v = 0 and layer 0, constants — the texel's address arithmetic, four
-                    // 64-bit addresses and four weights, was lifted to the kernel's entry and carried through the loop in
-                    // 11 VGPRs, for a branch C2 never takes; opaque to the optimiser, the same operations stay in here)
-                    // (Nothing but the compiler's present cost model keeps LICM from lifting the asm together with what hangs
-                    // on it — it is not volatile and its inputs are loop-invariant: tools/isa_stats.py shows it, as a GEOM 0
-                    // kernel back at 71 VGPRs.)
-                    if (PT_TEXEL_LAZY && GEOM == 0 && !COUNT && !ACCEL) asm("" : "+v"(tu), "+v"(tv));
-                    col = texture_rgb(c.sc, tu, tv, h.tex);
-                }
-            }
-            if (done) {
-                queue_put(q, idx, res);
-                active = false;
-            } else if (PT_RNG_PREFETCH == 2) {
-                // this lane WILL interact next iteration: its table reads fly during the refill step
-                rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-            }
-        }
-        PT_STAMP(c, 4);
-    }
-#if PT_STAMPS
-    if (threadIdx.x == 0 && q.npix)
-        for (int k = 0; k < 6; k++) atomicAdd(&counters[(size_t)COUNTER_REPLICAS * COUNTER_STRIDE + k], c.st[k]);
-#endif
-    if (!CAM && !COUNT && !MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never a counting one, never with moments)
-    else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2>(q, fp, accum);
-    flush_counters<COUNT>(cn, counters, 1);
-}
+// The kernel's text is csrc/pt_samples_q_kernel.hpp, included twice below: as pt_samples_q, and as
+// pt_samples_q_la<GEOM, WAVES> — CAM_LA, the LOOK-AHEAD form of the camera entry's ACCEL rows (rt_render_again_cameras), which
+// ends in queue_replay<true> instead of queue_sums.  The two CAM rows without a BVH walk carry the wave-uniform branch on
+// fp.la_ring that the record-fed kernels carry — it costs them neither a register nor scratch.  The three ACCEL rows sit on
+// the 96-VGPR budget of their five waves, and there the branch cost the (ACCEL, GEOM 2) row scratch under the ROCm-OpenCL
+// policies (8 -> 12 bytes, 3 -> 6 / 4 spilled VGPRs): these rows carry no branch and their look-ahead form is a kernel
+// of its own, chosen by the host.  (A second kernel around a shared __device__ body, and an eighth template parameter, were
+// both tried: the first moved scalar instructions in a dozen instantiations, the second renames every one of them.  Two
+// inclusions of one text leave every other kernel's code as it was — DESIGN.md, "Progressive anti-aliasing".)
+#define PT_Q_LOOKAHEAD_FORM 0
+#include "pt_samples_q_kernel.hpp"
+#undef PT_Q_LOOKAHEAD_FORM
+#define PT_Q_LOOKAHEAD_FORM 1
+#include "pt_samples_q_kernel.hpp"
+#undef PT_Q_LOOKAHEAD_FORM
 
 // The context's staged scene block (rt_context::StageBlock): stage_materials' tables by stage_materials' loops, compiled
 // in this translation unit — the divisions are the policy's.  One workgroup.
@@ -1436,7 +1247,7 @@ __global__ __launch_bounds__(64, MULTI ? PT_W_WAVES_MULTI : PT_W_WAVES) void pt_
         for (int k = 0; k < 12; k++) atomicAdd(&wstat[k], v[k]);
     }
 #endif
-    if (!MOMENTS && fp.la_ring) queue_replay(q, fp);   // (wave-uniform: a look-ahead launch; never with moments)
+    if (!MOMENTS && fp.la_ring) queue_replay<false>(q, fp);   // (wave-uniform: a look-ahead launch; never with moments)
     else queue_sums<MOMENTS, true>(q, fp, accum);
 }
 
@@ -2157,16 +1968,18 @@ static CameraPlan plan_camera_samples(const CameraFacts &f) {
     return p;
 }
 
-static QueueKernel camera_queue_kernel(const CameraPlan &p) {   // the five geometry rows of queue_kernel; NULL: no such row
-    struct Row { uint32_t accel, geom, waves; QueueKernel k; };
+// the five geometry rows of queue_kernel; lookahead: the rows without a BVH walk branch on fp.la_ring themselves, the ACCEL
+// rows have pt_samples_q_la; NULL: no such row
+static QueueKernel camera_queue_kernel(const CameraPlan &p, bool lookahead) {
+    struct Row { uint32_t accel, geom, waves; QueueKernel k[2]; };
     static const Row rows[] = {
-        {0u, 0u, PT_Q_WAVES, pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>},
-        {0u, 1u, PT_Q_WAVES, pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>},
-        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false, -1, true>},
-        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false, -1, true>},
-        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false, -1, true>}};
+        {0u, 0u, PT_Q_WAVES, {pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>, pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>}},
+        {0u, 1u, PT_Q_WAVES, {pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>, pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>}},
+        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, {pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false, -1, true>, pt_samples_q_la<0, PT_Q_WAVES_SPHERE_BVH>}},
+        {1u, 1u, PT_Q_WAVES_ACCEL, {pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false, -1, true>, pt_samples_q_la<1, PT_Q_WAVES_ACCEL>}},
+        {1u, 2u, PT_Q_WAVES_ACCEL, {pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false, -1, true>, pt_samples_q_la<2, PT_Q_WAVES_ACCEL>}}};
     for (const Row &r : rows)
-        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k;
+        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k[lookahead];
     return nullptr;
 }
 static RenderKernel camera_render_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
@@ -2180,13 +1993,21 @@ static RenderKernel camera_render_kernel(bool count, bool accel) {   // [COUNT][
 // reads or writes the slot buffers or the prefix cache; the staged scene block is the context's, refreshed as launch_fused
 // refreshes it.  mask != NULL (rt_render_adaptive_cameras): only the pixels of active decision blocks are traced — the camera
 // kernels test pixel_active where they take ownership of a slot; the plan and the grid are those of the unmasked launch.
+// ring != NULL: a LOOK-AHEAD launch (rt_render_again_cameras, RT_OPT_LOOKAHEAD) — the queue family only, accum, mask and m2
+// NULL: the `count` samples become `count` frames of the ring (queue_replay<true>), whose frame 0 holds the image as it lies
+// (the caller copied it there on the stream), and the accumulator is not touched.  The facts carry moments = 0.
 int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
-                   float4 *accum, const BlockMask *mask, float *m2) {
+                   float4 *accum, const BlockMask *mask, float *m2, float4 *ring) {
     if (!d_cams || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
     FrameParams fp = frame_params(ctx, cam0, first, count, glog2);
     apply_mask(fp, mask);
     fp.m2 = m2;
     fp.cams = d_cams;
+    if (ring) {
+        if (!lookahead_ok(ctx, fp, accum, mask, m2) || plan_camera_samples(camera_facts(ctx, device_scene(ctx), fp)).family != RT_CAMERA_PLAN_QUEUE)
+            return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
+        fp.la_ring = ring;   // (la_image's bytes hold `cams`: the start image is the ring's frame 0)
+    }
     const DeviceScene sc = device_scene(ctx);
     const uint32_t slots = fp.slot_end;
     if (slots == 0) return RT_OK;
@@ -2202,7 +2023,7 @@ int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], u
         const CameraPlan plan = plan_camera_samples(facts);
         fp.lds_face_f4 = plan.lds_face_f4;
         if (plan.family == RT_CAMERA_PLAN_QUEUE) {
-            const QueueKernel kernel = camera_queue_kernel(plan);
+            const QueueKernel kernel = camera_queue_kernel(plan, ring != nullptr);
             if (!kernel) return fail(ctx, RT_ESTATE, "no camera instantiation of pt_samples_q for the plan");
             hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
                                (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,

@@ -58,9 +58,11 @@ struct KernelSet {
     // rt_render_spp_cameras: samples first .. first+count-1 (count <= RT_SPP_PER_LAUNCH) of every owned pixel, sample first + j
     // through block j of d_cams (count x 12 floats on the device), summed in launch_fused's order and added to `accum`
     // (updating `m2`): the from-the-camera sample queue, or pt_render<MODE_ACCUM, …, CAMS> where plan_camera_samples says so;
-    // mask != NULL (rt_render_adaptive_cameras): the pixels of active decision blocks only, as launch_fused / launch_render
+    // mask != NULL (rt_render_adaptive_cameras): the pixels of active decision blocks only, as launch_fused / launch_render;
+    // ring != NULL (rt_render_again_cameras): a look-ahead launch — accum, mask and m2 NULL, the queue family only, the image
+    // after sample first + j into frame j of `ring`, whose frame 0 holds the start image when the launch begins
     int (*launch_cameras)(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
-                          float4 *accum, const BlockMask *mask, float *m2);
+                          float4 *accum, const BlockMask *mask, float *m2, float4 *ring);
     // rt_debug_plan_camera_samples: that launcher's choice of kernel and launch geometry — a pure function, no device
     rt_camera_plan (*plan_camera_samples)(const rt_camera_facts &facts);
     // rt_render_features_cameras: pt_features_cameras, the records of n <= RT_FEATURE_CAMERAS_MAX blocks of d_cams (n x 12

@@ -177,9 +177,12 @@ struct FrameParams {
     // to the accumulator, a pixel starts from la_image[pix] and takes `count` retrace steps (samples first .. first+count-1
     // in order), the image after step j going to la_ring[j * w * h + pix] — frame-major, so a frame is handed out as one copy
     // Per-sample camera blocks (rt_render_spp_cameras): count x 12 floats on the device, block j for sample first + j, read by
-    // the camera instantiations only (pt_render<…, CAMS>, pt_samples_q<…, CAM>).  The pointer SHARES la_image's eight bytes: a
-    // camera launch is never a look-ahead launch (la_ring == NULL, so nothing reads la_image), and the struct — the kernel
-    // argument of every shipped instantiation — keeps its size and every field its place.  (Appended as a field of its own
+    // the camera instantiations only (pt_render<…, CAMS>, pt_samples_q<…, CAM>).  The pointer SHARES la_image's eight bytes: no
+    // camera kernel reads la_image, and the struct — the kernel argument of every shipped instantiation — keeps its size and
+    // every field its place.  A camera launch that IS a look-ahead launch (rt_render_again_cameras: la_ring != NULL) finds its
+    // start image in the ring instead: the host copies the image as it lies into frame 0 on the stream before the launch, and
+    // the lane that owns (pixel, channel) reads la_ring[pix] before its own loop overwrites it (queue_replay<true>); the
+    // ring keeps its size, frame-major only.  (Appended as a field of its own
     // it changed the scalar loads of the kernels that read m2 next to it: policy 0's pt_samples_q<true, true, 0, 6, true>
     // went from 14 to 44 spilled VGPRs.)
     float4 *la_ring;

@@ -586,28 +586,81 @@ uint32_t lookahead_frames(int w, int h, int k, uint32_t sample_counter) {
     return n >= 2u ? (uint32_t)n : 0u;
 }
 
-// The batch this rt_render_again call may start (0: the direct path): the call must repeat the previous call's camera,
-// the context must be one a look-ahead launch can serve (launch_fused_any), and the ring must exist.
-uint32_t lookahead_batch(rt_context *ctx, const uint32_t cam_bits[12]) {
+// The ring holds kp frames of this frame size — allocated for as many as any batch of this size and option can have.
+// false: it cannot be had (not an error: the direct path).
+bool lookahead_ring(rt_context *ctx, uint32_t kp) {
     rt_context::Lookahead &la = ctx->lookahead;
-    if (!la.have_last_cam || memcmp(la.last_cam, cam_bits, sizeof la.last_cam) != 0) return 0u;
-    if (ctx->count_enabled || ctx->world != 1 || !ctx->prefix_sharing || !ctx->sample_queue) return 0u;
+    if (la.ring_frames >= kp) return true;
+    if (la.ring_failed) return false;
+    const uint32_t frames = lookahead_frames(ctx->width, ctx->height, la.k, 0u);
+    la.ring_frames = 0;
+    if (la.ring.alloc((size_t)frames * ctx->width * ctx->height) != hipSuccess) {
+        (void)hipGetLastError();
+        la.ring_failed = true;
+        return false;
+    }
+    la.ring_frames = frames;
+    return true;
+}
+
+// The batch a call that repeats the previous call's camera (rt_render_again) or table (rt_render_again_cameras) may start
+// (0: the direct path): the context must be one a look-ahead launch can serve (lookahead_ok, pt_kernels.hip), and the ring
+// must exist.  Camera launches share no prefix: RT_OPT_PREFIX_SHARING matters to the plain call only.
+uint32_t lookahead_batch_any(rt_context *ctx, bool cameras) {
+    rt_context::Lookahead &la = ctx->lookahead;
+    if (ctx->count_enabled || ctx->world != 1 || (!cameras && !ctx->prefix_sharing) || !ctx->sample_queue) return 0u;
     uint32_t kp = 0;
     if (rt_lookahead_plan(ctx->width, ctx->height, la.k, ctx->sample_counter, &kp) != RT_OK || kp < 2u) return 0u;
     if ((ctx->max_threads_per_launch >> group_log2_for(kp)) < shard_of(ctx, 0, 1).slots) return 0u;   // several slot ranges
-    if (la.ring_frames < kp) {
-        if (la.ring_failed) return 0u;
-        // (as many frames as any batch of this frame size and option can have)
-        const uint32_t frames = lookahead_frames(ctx->width, ctx->height, la.k, 0u);
-        la.ring_frames = 0;
-        if (la.ring.alloc((size_t)frames * ctx->width * ctx->height) != hipSuccess) {   // not an error: the direct path
-            (void)hipGetLastError();
-            la.ring_failed = true;
-            return 0u;
-        }
-        la.ring_frames = frames;
+    return lookahead_ring(ctx, kp) ? kp : 0u;
+}
+uint32_t lookahead_batch(rt_context *ctx, const uint32_t cam_bits[12]) {
+    const rt_context::Lookahead &la = ctx->lookahead;
+    if (!la.have_last_cam || memcmp(la.last_cam, cam_bits, sizeof la.last_cam) != 0) return 0u;
+    return lookahead_batch_any(ctx, false);
+}
+
+// a batch of kp frames has just been launched for the samples behind the counter
+void lookahead_begin(rt_context *ctx, uint32_t kp, bool table) {
+    rt_context::Lookahead &la = ctx->lookahead;
+    la.batches++;
+    la.pending = la.batch_frames = kp;
+    la.next_frame = 0;
+    la.next_sample = ctx->sample_counter + 1u;
+    la.key_generation = ctx->prefix_cache.generation;   // (after the launch: ensure_slots may have bumped it)
+    la.key_epoch = ctx->image_epoch;
+    la.key_is_table = table;
+}
+
+// Hands the next pending frame out: device copy into the image, then synchronise.  timed: the call has its entry in the
+// event history already (it launched the batch).
+int lookahead_hand_out(rt_context *ctx, bool timed) {
+    rt_context::Lookahead &la = ctx->lookahead;
+    const size_t frame_px = (size_t)ctx->width * ctx->height;
+    hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
+    if (!timed) {
+        HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
     }
-    return kp;
+#if PT_RING_PIXEL_MAJOR   // (A/B variant: a pixel's frames lie side by side, the hand-out gathers one of them)
+    hipLaunchKernelGGL(pt_ring_handout, dim3((unsigned)((frame_px + 255) / 256)), dim3(256), 0, ctx->stream, la.ring.p, ctx->image.p,
+                       frame_px, la.batch_frames, la.next_frame);
+    HIP_TRY(ctx, hipGetLastError());
+#else
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->image.p, la.ring.p + (size_t)la.next_frame * frame_px, frame_px * sizeof(float4),
+                                hipMemcpyDeviceToDevice, ctx->stream));
+#endif
+    if (!timed) {
+        HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
+        ctx->ev_count++;
+    }
+    la.pending--;
+    la.next_frame++;
+    la.next_sample++;
+    la.served++;
+    ctx->sample_counter++;  // src/raytracer.cpp:147
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 void remember_camera(rt_context *ctx, const float camera[12]) {
@@ -663,50 +716,20 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     uint32_t cam_bits[12];
     memcpy(cam_bits, camera, sizeof cam_bits);
     lookahead_validate(ctx);
-    if (la.pending && memcmp(la.key_cam, cam_bits, sizeof cam_bits) != 0) lookahead_drop(ctx);
-    const size_t frame_px = (size_t)ctx->width * ctx->height;
+    if (la.pending && (la.key_is_table || memcmp(la.key_cam, cam_bits, sizeof cam_bits) != 0)) lookahead_drop(ctx);
+    la.have_last_table = false;   // (a plain call between two table calls: the next table call repeats none)
     bool timed = false;   // the call has its entry in the event history
     if (!la.pending) {
         const uint32_t kp = lookahead_batch(ctx, cam_bits);
         if (kp) {
             if ((rc = ctx->ks->launch_lookahead(ctx, camera, ctx->sample_counter + 1u, kp, la.ring.p)) != RT_OK) return rc;
             timed = true;
-            la.batches++;
-            la.pending = la.batch_frames = kp;
-            la.next_frame = 0;
-            la.next_sample = ctx->sample_counter + 1u;
-            la.key_generation = ctx->prefix_cache.generation;   // (after the launch: ensure_slots may have bumped it)
-            la.key_epoch = ctx->image_epoch;
+            lookahead_begin(ctx, kp, false);
             memcpy(la.key_cam, cam_bits, sizeof cam_bits);
         }
     }
     remember_camera(ctx, camera);
-    if (la.pending) {   // hand the next frame out
-        hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
-        if (!timed) {
-            HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
-            HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
-        }
-#if PT_RING_PIXEL_MAJOR   // (A/B variant: a pixel's frames lie side by side, the hand-out gathers one of them)
-        hipLaunchKernelGGL(pt_ring_handout, dim3((unsigned)((frame_px + 255) / 256)), dim3(256), 0, ctx->stream, la.ring.p, ctx->image.p,
-                           frame_px, la.batch_frames, la.next_frame);
-        HIP_TRY(ctx, hipGetLastError());
-#else
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->image.p, la.ring.p + (size_t)la.next_frame * frame_px, frame_px * sizeof(float4),
-                                    hipMemcpyDeviceToDevice, ctx->stream));
-#endif
-        if (!timed) {
-            HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
-            ctx->ev_count++;
-        }
-        la.pending--;
-        la.next_frame++;
-        la.next_sample++;
-        la.served++;
-        ctx->sample_counter++;  // src/raytracer.cpp:147
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return RT_OK;
-    }
+    if (la.pending) return lookahead_hand_out(ctx, timed);
     ctx->image_epoch++;
     la.direct++;
     ctx->sample_counter++;  // src/raytracer.cpp:147
@@ -823,13 +846,63 @@ int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_
         CameraTable tb;
         if ((rc = camera_table_send(ctx, cameras + (size_t)done * 12u, c, &tb)) != RT_OK) return rc;
         rc = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr,
-                                     ctx->moments.target());
+                                     ctx->moments.target(), nullptr);
         const int rd = camera_table_read(ctx, tb);
         if (rd != RT_OK) return rd;
         if (rc != RT_OK) return rc;
         done += c;
         ctx->accum_count += c;
     }
+    return RT_OK;
+}
+
+int rt_render_again_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras) {
+    if (!ctx) return RT_EINVAL;
+    if (!cameras) return fail(ctx, RT_EINVAL, "camera table is NULL");
+    if (n_cameras == 0u || n_cameras > RT_AGAIN_CAMERAS_MAX) return fail(ctx, RT_EINVAL, "a camera table holds 1 .. %u blocks", RT_AGAIN_CAMERAS_MAX);
+    int rc = check_ready(ctx, cameras);
+    if (rc) return rc;
+    if (ctx->sample_counter >= RT_MAX_SAMPLE) return fail(ctx, RT_EINVAL, "sample counter limit %u reached", RT_MAX_SAMPLE);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // rt_render_again's look-ahead rule over the table: sample s looks through block s mod n_cameras, so while the calls
+    // repeat one table the next samples' blocks are known, and one camera launch computes the images after them.
+    rt_context::Lookahead &la = ctx->lookahead;
+    const uint32_t s = ctx->sample_counter + 1u;
+    const size_t words = (size_t)n_cameras * 12u;
+    const bool same = la.have_last_table && la.last_table.size() == words && memcmp(la.last_table.data(), cameras, words * sizeof(uint32_t)) == 0;
+    lookahead_validate(ctx);
+    if (la.pending && (!la.key_is_table || !same)) lookahead_drop(ctx);
+    bool timed = false;   // the call has its entry in the event history
+    if (!la.pending && same) {
+        const uint32_t kp = lookahead_batch_any(ctx, true);
+        if (kp) {
+            if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
+            std::vector<float> blocks((size_t)kp * 12u);   // the batch's blocks: (s + j) mod n_cameras
+            for (uint32_t j = 0; j < kp; j++) memcpy(&blocks[12u * j], cameras + 12u * (size_t)((s + j) % n_cameras), 12u * sizeof(float));
+            // the start image: frame 0 of the ring (FrameParams::cams holds la_image's bytes)
+            HIP_TRY(ctx, hipMemcpyAsync(la.ring.p, ctx->image.p, (size_t)ctx->width * ctx->height * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+            CameraTable tb;
+            if ((rc = camera_table_send(ctx, blocks.data(), kp, &tb)) != RT_OK) return rc;
+            rc = ctx->ks->launch_cameras(ctx, tb.d, tb.h, s, kp, group_log2_for(kp), nullptr, nullptr, nullptr, la.ring.p);
+            const int rd = camera_table_read(ctx, tb);
+            if (rd != RT_OK) return rd;
+            if (rc != RT_OK) return rc;
+            timed = true;
+            lookahead_begin(ctx, kp, true);
+        }
+    }
+    if (!same) {
+        la.last_table.resize(words);
+        memcpy(la.last_table.data(), cameras, words * sizeof(uint32_t));
+        la.have_last_table = true;
+    }
+    la.have_last_cam = false;   // (a plain rt_render_again after this call repeats no plain call)
+    if (la.pending) return lookahead_hand_out(ctx, timed);
+    ctx->image_epoch++;
+    la.direct++;
+    ctx->sample_counter++;
+    if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, cameras + 12u * (size_t)(s % n_cameras), ctx->sample_counter, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 
@@ -1005,7 +1078,7 @@ int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n
         CameraTable tb;
         int r = camera_table_send(ctx, cameras + (size_t)first * 12u, c, &tb);
         if (r != RT_OK) return r;
-        r = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+        r = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first, c, group_log2_for(c), scratch, mask, m2_scratch, nullptr);
         const int rd = camera_table_read(ctx, tb);
         return rd != RT_OK ? rd : r;
     });

@@ -221,6 +221,13 @@ struct rt_context {
         uint32_t key_cam[12] = {};
         bool have_last_cam = false;     // the camera block of the previous rt_render / rt_render_again call
         uint32_t last_cam[12] = {};
+        // rt_render_again_cameras: the same rule over a cyclic TABLE of blocks.  `last_table` is the host copy of the table
+        // the previous such call was given (n x 12 words; dropped by a plain rt_render_again, which in turn finds no
+        // `last_cam` after a table call); a batch launched by a table call is keyed by that table (`key_is_table`, key_cam
+        // unused) and handed out to table calls only.
+        bool have_last_table = false;
+        std::vector<uint32_t> last_table;
+        bool key_is_table = false;
         uint64_t batches = 0, served = 0, direct = 0, discarded = 0;   // rt_lookahead_stats
     } lookahead;
     uint64_t image_epoch = 0;

@@ -38,7 +38,7 @@ SYMBOLS = (
     "rt_debug_plan_samples", "rt_debug_last_sample_plan",
     "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
     "rt_render_features_cameras", "rt_read_feature_coverage", "rt_device_feature_coverage", "rt_debug_plan_feature_cameras",
-    "rt_render_adaptive_cameras",
+    "rt_render_adaptive_cameras", "rt_render_again_cameras",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -387,6 +387,14 @@ class RayTracer:
 
     def renderAgain(self, camera):
         self._check(self._lib.rt_render_again(self._ctx, _cam_block(camera).ctypes.data))
+
+    def renderAgainCameras(self, blocks):
+        """renderAgain through a cyclic schedule of camera blocks (n x 12 floats, e.g. Camera.sampleBlocks: progressive
+        anti-aliasing, depth of field; rt_render_again_cameras): the call that makes sample s looks through
+        blocks[s % n].  Same bits as renderAgain(blocks[s % n]); while the calls repeat one table, RT_OPT_LOOKAHEAD
+        serves them from one camera launch per batch."""
+        blocks = _cam_blocks(blocks)
+        self._check(self._lib.rt_render_again_cameras(self._ctx, blocks.ctypes.data if len(blocks) else None, len(blocks)))
 
     @property
     def sample_counter(self):
