@@ -207,15 +207,42 @@ PT_DEV Rnd fetch_rnd(const float *__restrict__ table, V3 dir, uint32_t s_seed, u
 // s_seed·2683 + gx·3931 + gy = depth·2683 + bu   in uint32 arithmetic (the sums stay below 2^32, see above).
 PT_DEV uint32_t rnd_base_v(uint32_t sample, uint32_t gx, uint32_t gy) { return (sample * 2683u + gx * 3931u + gy * 2504u) * 3u; }
 PT_DEV uint32_t rnd_base_u(uint32_t sample, uint32_t gx, uint32_t gy) { return sample * 2683u + gx * 3931u + gy; }
+// The two reads apart, `hsh` = dir_hash of the incoming direction: randomVec's three floats and random's one.
+PT_DEV V3 fetch_rnd_v(const float *__restrict__ table, uint32_t hsh, uint32_t depth, uint32_t bv) {
+    uint32_t iv = (hsh + bv + depth * 8049u) % RT_RANDOM_BUFFER_SIZE;
+    const float *t = table + iv;
+    return mk(t[0], t[1], t[2]);
+}
+PT_DEV float fetch_rnd_u(const float *__restrict__ table, uint32_t hsh, uint32_t depth, uint32_t bu) {
+    uint32_t iu = (hsh + bu + depth * 2683u) % RT_RANDOM_BUFFER_SIZE;
+    return table[3 * RT_RANDOM_BUFFER_SIZE + iu];
+}
 PT_DEV Rnd fetch_rnd_b(const float *__restrict__ table, V3 dir, uint32_t depth, uint32_t bv, uint32_t bu) {
     uint32_t hsh = dir_hash(dir);
-    uint32_t iv = (hsh + bv + depth * 8049u) % RT_RANDOM_BUFFER_SIZE;
-    uint32_t iu = (hsh + bu + depth * 2683u) % RT_RANDOM_BUFFER_SIZE;
-    const float *t = table + iv;
     Rnd r;
-    r.v = mk(t[0], t[1], t[2]);
-    r.u = table[3 * RT_RANDOM_BUFFER_SIZE + iu];
+    r.v = fetch_rnd_v(table, hsh, depth, bv);
+    r.u = fetch_rnd_u(table, hsh, depth, bu);
     return r;
+}
+// What scatter() reads of the two at a material of this type: randomVec in the diffuse / textured arm, random at
+// t_dielectric, nothing at a mirror or a refractive surface.
+PT_DEV bool rnd_needs_v(int type) { return type == RT_DIFFUSE || type == RT_TEXTURED; }
+PT_DEV bool rnd_needs_u(int type) { return type == RT_DIELECTRIC; }
+// The same table entries as fetch_rnd_b, but only those the interaction at a material of `type` reads (PT_RND_BY_USE,
+// pt_samples_q): the hash and each index sum are formed, and each gather is issued, only in a wave that has a lane
+// that uses it — both tests are wave-uniform, so a wave without glass never forms random's index.  What is not read
+// stays as it was in `rnd`; scatter() does not look at it.  Every lane that is active here calls it.
+PT_DEV void fetch_rnd_by_use(Rnd &rnd, const float *__restrict__ table, V3 dir, int type, uint32_t depth, uint32_t bv, uint32_t bu) {
+    const bool need_v = rnd_needs_v(type), need_u = rnd_needs_u(type);
+    if (__any(need_v || need_u)) {
+        uint32_t hsh = dir_hash(dir);
+        if (__any(need_v)) {
+            if (need_v) rnd.v = fetch_rnd_v(table, hsh, depth, bv);
+        }
+        if (__any(need_u)) {
+            if (need_u) rnd.u = fetch_rnd_u(table, hsh, depth, bu);
+        }
+    }
 }
 
 // ---- nearest-hit search --------------------------------------------------------

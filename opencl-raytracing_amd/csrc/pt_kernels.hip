@@ -591,6 +591,9 @@ struct WaveQueue {
 #ifndef PT_TABLES_BY_COUNT
 #define PT_TABLES_BY_COUNT 1 // pt_samples_q<false, false, …>: "is the table staged?" is asked of the scene's counts, not of the LDS pointer
 #endif
+#ifndef PT_RND_BY_USE
+#define PT_RND_BY_USE 1      // pt_samples_q<false, false, 0, …> without CAM: an interaction gathers only the table entries its material reads (profiles/r22_experiments.md)
+#endif
 
 // queue_stage's slot → (x, y).  slot_to_pixel divides the tile index by fp.tiles_x, a launch constant, with the generic
 // uint32 division (about 25 VALU instructions).  An unsharded frame (world == 1, so rank == 0 and t = slot >> tpix_log2)

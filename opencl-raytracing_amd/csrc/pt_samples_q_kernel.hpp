@@ -28,6 +28,12 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
     // The presence of the staged tables by count (pt_device.hpp has_materials): the instantiations that copy the staged block, in every policy.
     constexpr bool BY_COUNT = PT_TABLES_BY_COUNT && !COUNT && !ACCEL;
+    // The table gathers by use (pt_device.hpp fetch_rnd_by_use): a lane reads randomVec's entry at a diffuse or textured vertex,
+    // random's at a dielectric one, nothing at a mirror or a refractive one.  The same family, without the camera rows and
+    // without meshes: GEOM 1 sits on its budget of 80 VGPRs and spills under policy 0 with the gathers in branches of their
+    // own, and C3 gained nothing from them (profiles/r22_experiments.md).  The type that decides it is carried from where it
+    // was last known (htype below), so the gathers do not wait for an LDS read.
+    constexpr bool BY_USE = PT_RND_BY_USE && !PT_RNG_PREFETCH && !COUNT && !ACCEL && !CAM && GEOM == 0;
     // The wave's share of the live list first (two counters, read through the scalar cache): a wave that owns no pixel —
     // the launch is sized for "every pixel is live" unless the host knows better (launch_fused) — leaves here, before
     // anything is staged: no barrier, no sums, and only zeros to add to the counters.
@@ -74,6 +80,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     r.o = r.d = mk(0.0f, 0.0f, 0.0f);
     V3 hn = mk(0.0f, 0.0f, 0.0f);   // normal and material of the hit the next interaction happens at
     uint32_t hmat = 0;
+    uint32_t htype = 0;   // BY_USE: the type of that material (the hit section has read it for the light test; a record holds it)
     Rnd rnd;
     rnd.v = mk(0.0f, 0.0f, 0.0f);
     rnd.u = 0.0f;
@@ -116,6 +123,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 r.o = xyz(e.q0);
                 r.d = xyz(e.q2);
                 hmat = __float_as_uint(e.q2.w);
+                if (BY_USE) htype = e.bits >> 16;   // (a vertex record holds its material's type, trace_branch)
                 out = xyz(e.q3);
                 col = xyz(e.q4);
                 if ((e.bits & 0xFFu) == REC_FINAL) {  // a leaf of a tree, or count is not a multiple of g
@@ -149,7 +157,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
 #endif
         // ---- one material interaction for every active lane
         if (CAM ? active && !fresh : active) {
-            if (!PT_RNG_PREFETCH) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
+            if (!PT_RNG_PREFETCH && !BY_USE) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
             Hit at;   // the vertex this interaction happens at: the ray's origin already stands on it
             at.p = r.o;
             at.n = hn;
@@ -159,7 +167,9 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             int type;
             float extra;
             V3 mcol;
-            load_material<BY_COUNT>(c, hmat, type, extra, mcol);   // type and extra_data are not carried: one LDS read each
+            if (BY_USE) fetch_rnd_by_use(rnd, sc.table, r.d, (int)htype, depth, bv, bu);
+            load_material<BY_COUNT>(c, hmat, type, extra, mcol);   // extra_data is not carried, nor the type without BY_USE: one LDS read each
+            if (BY_USE) type = (int)htype;   // (the same value, and the type's LDS read goes)
             scatter<COUNT, FAST, BY_COUNT>(c, r, out, at, type, extra, col, rnd, false);
             depth++;
             if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
@@ -192,6 +202,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 int type;
                 float extra;
                 load_material<BY_COUNT>(c, h.mat, type, extra, col);
+                if (BY_USE) htype = (uint32_t)type;
                 if (type == RT_LIGHT) {
                     res = vmin(out, col);
                     done = true;
