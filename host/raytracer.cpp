@@ -103,6 +103,26 @@ rt_adaptive_stats RayTracer::renderAdaptiveCameras(const std::vector<float> &blo
     return st;
 }
 
+rt_adaptive_stats RayTracer::renderAdaptiveVariance(const Camera *camera, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive_variance(ctx, camera->transferData(), &params, &st));
+    transferImage();
+    return st;
+}
+
+rt_adaptive_stats RayTracer::renderAdaptiveVarianceCameras(const std::vector<float> &blocks, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive_variance_cameras(ctx, blocks.empty() ? nullptr : blocks.data(), (uint32_t)(blocks.size() / 12), &params, &st));
+    transferImage();
+    return st;
+}
+
+std::vector<float> RayTracer::pixelError() {
+    std::vector<float> e((size_t)width * height);
+    check(rt_read_pixel_error(ctx, e.data(), e.size() * sizeof(float)));
+    return e;
+}
+
 std::vector<uint32_t> RayTracer::sampleCounts() {
     std::vector<uint32_t> c((size_t)width * height);
     check(rt_read_sample_counts(ctx, c.data(), c.size() * sizeof(uint32_t)));

@@ -71,6 +71,11 @@ public:
     // the same through per-sample camera blocks (rt_render_adaptive_cameras): sample j of every pixel through block j of
     // `blocks` (params.max_spp x 12 floats, e.g. Camera::sampleBlocks)
     rt_adaptive_stats renderAdaptiveCameras(const std::vector<float> &blocks, const rt_adaptive_params &params);
+    // both under the variance-driven stopping rule (rt_render_adaptive_variance, ..._variance_cameras): setMoments(true)
+    // first; pixelError() reads the W x H standard errors the rule decided on
+    rt_adaptive_stats renderAdaptiveVariance(const Camera *camera, const rt_adaptive_params &params);
+    rt_adaptive_stats renderAdaptiveVarianceCameras(const std::vector<float> &blocks, const rt_adaptive_params &params);
+    std::vector<float> pixelError();
     std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major
     const float *lastImage() const { return pixels.data(); }  // what the last read-back returned
     // first-hit feature records of every pixel (rt_render_features, asynchronous) and their read-back

@@ -4,6 +4,7 @@
 //          --camera=-8,-1,-8,45,0 [--fov 60] [--seed 12648430] [--progressive [--lookahead N]]
 //          [--out frame.tga] [--pfm frame.pfm] [--raw frame.f32] [--device 0]
 //          [--adaptive THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
+//          [--adaptive-rule dammertz|variance]
 //          [--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]]]
 //              [--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]]
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
@@ -21,6 +22,11 @@
 // a frame adaptively (rt_render_adaptive_cameras): --adaptive's rounds, --batch, --min-spp, --spp (the maximum, default 1024)
 // and --counts, with sample j of every pixel through block j of the run's --spp sample cameras; --denoise, --aov and
 // --aa-guides work as with --spp.
+// --adaptive-rule variance (with --adaptive or --adaptive-cameras; default dammertz) stops a block by the standard error of
+// its pixels' means, measured from the per-pixel sample moments (rt_render_adaptive_variance, ..._variance_cameras): the
+// moments are switched on before anything is accumulated, --min-spp may then equal --batch (default batch, at least 2), and
+// --aov also writes PREFIX_error.pfm, the pixel errors the rule decided on; --denoise --variance-guided --measured filters
+// on the same moments.
 // --progressive-cameras (with --aa or --aperture R --focus D; refused with --progressive, --adaptive, --adaptive-cameras and
 // --denoise) renders such a frame like the interactive app: render(block 0) + (spp - 1) x renderAgainCameras(table), the
 // table being the run's first min(spp, 4096) sample cameras, sample s through block s mod that (rt_render_again_cameras);
@@ -76,7 +82,8 @@ static void usage() {
                  "[--denoise [--denoise-iterations N] [--sigma c,n,x,a] [--variance-guided [--sigma-luminance S] [--measured]] "
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
-                 "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]\n";
+                 "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
+                 "[--adaptive-rule dammertz|variance]\n";
     std::exit(2);
 }
 
@@ -153,7 +160,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 0xC0FFEE;
     bool progressive = false, progressive_cameras = false;
     long lookahead = -1;   // (-1: the library's default)
-    bool adaptive = false, adaptive_cameras = false, spp_given = false;
+    bool adaptive = false, adaptive_cameras = false, spp_given = false, rule_given = false, rule_variance = false;
     float threshold = 0.0f;
     long batch = 0, min_spp = 0;
     std::string out_counts;
@@ -191,6 +198,12 @@ int main(int argc, char **argv) {
         else if ((v = val("--raw"))) out_raw = v;
         else if ((v = val("--device"))) device = std::atoi(v);
         else if ((v = val("--dump-scene"))) dump_scene = v;
+        else if ((v = val("--adaptive-rule"))) {
+            const std::string r = v;
+            if (r != "dammertz" && r != "variance") usage();
+            rule_given = true;
+            rule_variance = r == "variance";
+        }
         else if ((v = val("--adaptive-cameras"))) {
             char *end = nullptr;
             threshold = std::strtof(v, &end);
@@ -241,7 +254,7 @@ int main(int argc, char **argv) {
     }
     if (spp < 1 || w < 1 || h < 1) usage();
     if (adaptive_cameras && (adaptive || progressive)) usage();            // one way to spend the samples
-    if (!adaptive && !adaptive_cameras && (batch || min_spp || !out_counts.empty())) usage();   // adaptive-only flags
+    if (!adaptive && !adaptive_cameras && (batch || min_spp || !out_counts.empty() || rule_given)) usage();   // adaptive-only flags
     if (!denoise && (dn_iterations || sigmas_given || variance_guided || sigma_l_given)) usage();   // denoise-only flags
     if ((sigma_l_given || measured) && !variance_guided) usage();
     if (follow && !denoise && aov_prefix.empty()) usage();                 // --follow guides --denoise and / or fills --aov
@@ -264,9 +277,9 @@ int main(int argc, char **argv) {
     if (adaptive || adaptive_cameras) {
         if (progressive) usage();
         if (!batch) batch = 64;
-        if (!min_spp) min_spp = 2 * batch;
+        if (!min_spp) min_spp = rule_variance ? std::max(batch, 2L) : 2 * batch;
         if (!spp_given) spp = 1024;
-        if (min_spp < 2 * batch || min_spp % batch || spp < min_spp || spp > (long)RT_MAX_SAMPLE + 1) usage();
+        if (min_spp < (rule_variance ? std::max(batch, 2L) : 2 * batch) || min_spp % batch || spp < min_spp || spp > (long)RT_MAX_SAMPLE + 1) usage();
     }
 
     Camera camera(fov, (float)w / (float)h, rth::vec3(cam[0], cam[1], cam[2]), cam[3], cam[4]);
@@ -301,18 +314,19 @@ int main(int argc, char **argv) {
         return f ? 0 : 1;
     }
     RayTracer tracer(w, h, "kernels/raytracer.cl", scene_path, device, seed);
-    if (measured) tracer.setMoments(true);   // before anything is accumulated: every path below starts with a clear
+    if (measured || rule_variance) tracer.setMoments(true);   // before anything is accumulated: every path below starts with a clear
 
     auto t0 = std::chrono::steady_clock::now();
     const float *img;
     rt_adaptive_stats st{};
     if (adaptive) {
         rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
-        st = tracer.renderAdaptive(&camera, p);
+        st = rule_variance ? tracer.renderAdaptiveVariance(&camera, p) : tracer.renderAdaptive(&camera, p);
         img = tracer.lastImage();
     } else if (adaptive_cameras) {
         rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
-        st = tracer.renderAdaptiveCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus), p);
+        const std::vector<float> blocks = camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus);
+        st = rule_variance ? tracer.renderAdaptiveVarianceCameras(blocks, p) : tracer.renderAdaptiveCameras(blocks, p);
         img = tracer.lastImage();
     } else if (progressive) {
         if (lookahead >= 0) tracer.setLookahead((int)lookahead);
@@ -332,7 +346,7 @@ int main(int argc, char **argv) {
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (adaptive || adaptive_cameras) {
-        std::cout << w << "x" << h << (adaptive_cameras ? " adaptive per-sample cameras threshold " : " adaptive threshold ") << threshold << " batch " << batch << " spp " << min_spp
+        std::cout << w << "x" << h << (adaptive_cameras ? " adaptive per-sample cameras threshold " : " adaptive threshold ") << threshold << (rule_variance ? " (variance rule)" : "") << " batch " << batch << " spp " << min_spp
                   << ".." << spp << ": " << st.rounds << " rounds, mean " << (double)st.pixel_samples / ((double)w * h)
                   << " spp, " << st.blocks_at_max << " of " << st.blocks << " blocks at max, " << sec * 1e3
                   << " ms incl. read-back" << std::endl;
@@ -391,6 +405,7 @@ int main(int argc, char **argv) {
             }
             write_pfm(aov_prefix + "_coverage.pfm", c3.data(), 3, 0, 3, w, h);
         }
+        if (rule_variance) write_pfm(aov_prefix + "_error.pfm", tracer.pixelError().data(), 1, 0, 1, w, h);
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);
         if (denoise && measured) {
             const std::vector<float> m2 = tracer.moments();

@@ -364,7 +364,7 @@ typedef struct rt_adaptive_stats {
 int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out);
 /* Per-pixel sample counts (accum.w) of the accumulator: W*H uint32, row-major; bytes = W*H*4. */
 int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes);
-/* Block errors of the last rt_render_adaptive call, ceil(W/block_w) * ceil(H/block_h) floats, row-major; a block
+/* Block errors of the last adaptive call (of either stopping rule), ceil(W/block_w) * ceil(H/block_h) floats, row-major; a block
  * holds its error after the last round it was traced in.  RT_ESTATE before the first call / after rt_resize. */
 int rt_read_block_error(rt_context *ctx, float *err, size_t bytes);
 
@@ -388,6 +388,40 @@ int rt_read_block_error(rt_context *ctx, float *err, size_t bytes);
  */
 int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
                                rt_adaptive_stats *out);
+
+/*
+ * Adaptive sampling with a stopping rule driven by MEASURED variance (new): rt_render_adaptive and
+ * rt_render_adaptive_cameras with the standard error of every pixel's mean, taken from the sample moments, in place of the
+ * half-buffer estimate.  RT_OPT_MOMENTS must be 1: the calls do not switch it on.
+ *   - The rounds are rt_render_adaptive's (rt_render_adaptive_cameras' for the cameras form, n_cameras == max_spp): round
+ *     k traces samples k*batch .. k*batch+c-1 of every pixel of a still-active block, so every pixel holds, bit for bit,
+ *     the accumulator of the fixed-count frame with its own count.  A self-contained clear + rounds + resolve, synchronous,
+ *     unsharded contexts only; rt_adaptive_stats means the same; rt_read_sample_counts and rt_read_block_error serve it.
+ *   - Estimator.  After a round, for a pixel with n = accum.w samples, I = accum.rgb / n, L = l(I) (the luminance of
+ *     rt_denoise_variance) and M2 its merged moment (rt_moments_merge, taken in before the round's sums are added):
+ *       e_p = sqrt(M2 / (n (n - 1))) / sqrt(L),   0 where n < 2, L <= 0 or M2 <= 0
+ *     — the standard error of the pixel's mean luminance over the root of that mean.  By the delta method e_p / 2 is the
+ *     standard error of the displayed (sqrt-space) luminance: that is what `threshold` means, and it does not depend on
+ *     `batch`.  A block's error is the mean e_p of its in-frame pixels.  Division and square root are correctly rounded
+ *     whatever the arithmetic policy.
+ *   - A block stays active while its count < min_spp, or while (threshold == 0 or its error >= threshold) and its count <
+ *     max_spp.  Decisions are taken from round 0 on.  The block errors and the pixel errors hold the values of the last
+ *     round a block was traced in.
+ *   - Parameters: batch 1 .. 512; min_spp a multiple of batch, >= batch and >= 2 (no half buffer exists, so there is no
+ *     2 * batch rule); max_spp in min_spp .. RT_MAX_SAMPLE + 1; threshold finite and >= 0; blocks as rt_render_adaptive's.
+ *   - Afterwards the moments are valid, so rt_denoise_moments can follow directly.  The half buffer of the Dammertz rule is
+ *     neither read nor written, and a context that only ever uses this rule never allocates it.
+ * rt_read_pixel_error: the W*H pixel errors, row-major; bytes = W*H*4.  rt_device_pixel_error: their device address.  Both
+ * give RT_ESTATE unless the last completed adaptive call since the frame was (re)allocated was one of these two: a later
+ * rt_render_adaptive / rt_render_adaptive_cameras or rt_resize invalidates them.
+ * RT_ESTATE: RT_OPT_MOMENTS is 0; no scene set.  RT_EINVAL: everything else rt_render_adaptive / rt_render_adaptive_cameras
+ * refuse, a sharded context included.  A failed call changes nothing.
+ */
+int rt_render_adaptive_variance(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out);
+int rt_render_adaptive_variance_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras,
+                                        const rt_adaptive_params *p, rt_adaptive_stats *out);
+int rt_read_pixel_error(rt_context *ctx, float *err, size_t bytes);      /* W*H floats, row-major */
+int rt_device_pixel_error(rt_context *ctx, void **d_err);
 
 /*
  * First-hit feature buffers (new; the reference has no such entry point).  One record per pixel of the frame,
@@ -587,10 +621,11 @@ int rt_device_variance(rt_context *ctx, int which, void **d_out);
  * Per-pixel sample moments (new; RT_OPT_MOMENTS) and the variance-guided filter on MEASURED variance.
  * With l(c) the luminance above and s_0 .. s_(n-1) the samples a pixel's accumulator holds (n = accum.w), the moment
  * buffer keeps M2_p = sum_j (l(s_j) - m_p)^2, m_p = sum_j l(s_j) / n: one float per pixel, W x H, row-major.
- * The moments become VALID at rt_clear and at the start of rt_render_adaptive while RT_OPT_MOMENTS is 1 (both zero them
- * on the stream); they become invalid when the option's value changes and after rt_resize.  While they are valid,
- * every call that adds to the accumulator — rt_render_spp and rt_render_adaptive, on every path they can take — updates
- * them; rt_render, rt_render_again and its look-ahead launches never touch them.  While they are invalid nothing
+ * The moments become VALID at rt_clear and at the start of rt_render_adaptive, rt_render_adaptive_cameras,
+ * rt_render_adaptive_variance and rt_render_adaptive_variance_cameras while RT_OPT_MOMENTS is 1 (all zero them on the
+ * stream); they become invalid when the option's value changes and after rt_resize.  While they are valid, every call
+ * that adds to the accumulator — rt_render_spp and the adaptive calls, on every path they can take — updates them (the
+ * two variance-rule calls also READ them, to decide when a block stops); rt_render, rt_render_again and its look-ahead launches never touch them.  While they are invalid nothing
  * writes the buffer, and rt_read_moments, rt_device_moments and rt_denoise_moments give RT_ESTATE.
  * Two partial states (n, RGB sum S, M2) of a pixel are combined in ONE place, by the pairwise update of Chan, Golub &
  * LeVeque 1979 — rt_moments_merge, the very function the kernels call:
@@ -700,7 +735,8 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
                                            kernels' epilogue, 4 more bytes per pixel).  Any other value: RT_EINVAL.  Unsharded
                                            contexts only: setting 1 on a context with world > 1, and rt_set_shard to world > 1
                                            while it is 1, give RT_EINVAL.  A change of value invalidates the moments until the next
-                                           rt_clear / rt_render_adaptive.  Image and accumulator: the same bit for bit        */
+                                           rt_clear / rt_render_adaptive.  rt_render_adaptive_variance(_cameras) need 1 and give
+                                           RT_ESTATE otherwise.  Image and accumulator: the same bit for bit                  */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's

@@ -90,6 +90,10 @@ def adaptive_prototypes(lib):
     lib.rt_read_sample_counts.argtypes = [vp, vp, sz]
     lib.rt_read_block_error.argtypes = [vp, vp, sz]
     lib.rt_render_adaptive_cameras.argtypes = [vp, vp, C.c_uint32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_render_adaptive_variance.argtypes = [vp, vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_render_adaptive_variance_cameras.argtypes = [vp, vp, C.c_uint32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_read_pixel_error.argtypes = [vp, vp, sz]
+    lib.rt_device_pixel_error.argtypes = [vp, C.POINTER(vp)]
 
 
 def block_error_reference(accum, half, block_w, block_h):

@@ -171,6 +171,66 @@ __global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge(MergePa
     }
 }
 
+// The same pass for the variance-driven rule (rt_render_adaptive_variance): the shape, the pixel order, the butterfly and the
+// stats rows are pt_adaptive_merge's, the moments are always kept (m2 != NULL), and no half buffer exists.  Per pixel of
+// an active block: (accum, m2) takes (scratch, m2_scratch) in with the merge rule BEFORE accum += scratch, both scratches
+// are zeroed, and with n = accum.w, L = l(accum.rgb / n) the pixel error — the standard error of the pixel's mean luminance
+// over the root of that mean — is sqrt(M2 / (n (n - 1))) / sqrt(L), 0 where n < 2, L <= 0 or M2 <= 0.  It is written for
+// every such pixel in every round, so pixel_err and block_err hold the values of the last round a block was traced in,
+// and lane 0 decides from round 0 on.
+__global__ __launch_bounds__(64 * PT_MERGE_WAVES) void pt_adaptive_merge_variance(MergeParams mp, float4 *__restrict__ accum,
+                                                        float4 *__restrict__ scratch, uint32_t *__restrict__ active,
+                                                        float *__restrict__ block_err, unsigned long long *__restrict__ stats,
+                                                        float *__restrict__ m2, float *__restrict__ m2_scratch,
+                                                        float *__restrict__ pixel_err) {
+    const uint32_t b = blockIdx.x * PT_MERGE_WAVES + (threadIdx.x >> 6);
+    if (b >= mp.blocks || active[b] == 0u) return;   // (uniform over the wave; no workgroup barrier follows)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t bw = 1u << mp.bw_log2, area = bw << mp.bh_log2;
+    const uint32_t x0 = (b % mp.blocks_x) << mp.bw_log2, y0 = (b / mp.blocks_x) << mp.bh_log2;
+    float esum = 0.0f;
+    uint32_t npx = 0u;
+    for (uint32_t i = lane; i < area; i += 64u) {
+        const uint32_t x = x0 + (i & (bw - 1u)), y = y0 + (i >> mp.bw_log2);
+        if (x >= mp.w || y >= mp.h) continue;
+        const size_t p = (size_t)y * mp.w + x;
+        const float4 s = scratch[p];
+        float4 m = accum[p];
+        const float mm = moments_merge(m.w, m.x, m.y, m.z, m2[p], s.w, s.x, s.y, s.z, m2_scratch[p]);
+        m2[p] = mm;
+        m2_scratch[p] = 0.0f;
+        m.x += s.x; m.y += s.y; m.z += s.z; m.w += s.w;
+        accum[p] = m;
+        scratch[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        npx++;
+        float e = 0.0f;
+        if (m.w >= 2.0f) {
+            const float lum = moments_lum(m.x / m.w, m.y / m.w, m.z / m.w);
+            if (lum > 0.0f && mm > 0.0f) e = sqrtf(mm / (m.w * (m.w - 1.0f))) / sqrtf(lum);
+        }
+        pixel_err[p] = e;
+        esum += e;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        esum += __shfl_xor(esum, off);
+        npx += __shfl_xor(npx, off);
+    }
+    if (lane != 0u) return;
+    const float err = esum / (float)npx;
+    block_err[b] = err;
+    const bool unconverged = mp.threshold == 0.0f || !(err < mp.threshold);
+    const bool next = mp.count < mp.max_spp && (mp.count < mp.min_spp || unconverged);
+    active[b] = next ? 1u : 0u;
+    stats += (size_t)(b % PT_MERGE_REPLICAS) * PT_MERGE_STRIDE;
+    if (next) {
+        atomicAdd(&stats[0], 1ull);
+    } else {
+        if (mp.count >= mp.max_spp && unconverged) atomicAdd(&stats[1], 1ull);
+        atomicAdd(&stats[2], (unsigned long long)npx * mp.count);
+    }
+}
+
 // ================================== host side ==================================
 
 namespace {
@@ -932,7 +992,6 @@ int ensure_adaptive(rt_context *ctx, size_t blocks) {
     a = {};
     const size_t px = (size_t)ctx->width * ctx->height;
     hipError_t e = a.scratch.alloc(px);
-    if (e == hipSuccess) e = a.half.alloc(px);
     if (e == hipSuccess) e = a.block_active.alloc(blocks);
     if (e == hipSuccess) e = a.block_err.alloc(blocks);
     if (e == hipSuccess) e = a.stats.alloc(PT_MERGE_REPLICAS * PT_MERGE_STRIDE);
@@ -956,13 +1015,22 @@ int log2_pow2(uint32_t v) {
 extern "C++" {
 namespace {
 
-// The parameter rules of both adaptive calls (after check_ready): RT_OK, or an RT_* code recorded on the context.
-int check_adaptive(rt_context *ctx, const rt_adaptive_params *p, const rt_adaptive_stats *out, int *bwl, int *bhl) {
+// The two stopping rules: Dammertz' half-buffer estimate (rt_render_adaptive, rt_render_adaptive_cameras) and the standard
+// error of each pixel's mean, measured by the sample moments (rt_render_adaptive_variance, ..._variance_cameras)
+enum AdaptiveRule { RULE_DAMMERTZ, RULE_VARIANCE };
+
+// The parameter rules of the adaptive calls (after check_ready): RT_OK, or an RT_* code recorded on the context.
+int check_adaptive(rt_context *ctx, AdaptiveRule rule, const rt_adaptive_params *p, const rt_adaptive_stats *out, int *bwl, int *bhl) {
     if (!p || !out) return fail(ctx, RT_EINVAL, "adaptive parameters / stats are NULL");
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "adaptive rendering of a sharded context (rank %d of %d)", ctx->rank, ctx->world);
+    if (rule == RULE_VARIANCE && !ctx->moments.on)
+        return fail(ctx, RT_ESTATE, "the variance-driven stopping rule reads the sample moments: set RT_OPT_MOMENTS to 1 first");
     if (p->batch < 1 || p->batch > RT_SPP_PER_LAUNCH)
         return fail(ctx, RT_EINVAL, "batch %u outside 1..%u", p->batch, RT_SPP_PER_LAUNCH);
-    if (p->min_spp < 2 * p->batch || p->min_spp % p->batch)
+    if (rule == RULE_VARIANCE) {   // (no half buffer, so one round can decide; a standard error needs two samples)
+        if (p->min_spp < std::max(p->batch, 2u) || p->min_spp % p->batch)
+            return fail(ctx, RT_EINVAL, "min_spp %u must be a multiple of batch %u, at least it and at least 2", p->min_spp, p->batch);
+    } else if (p->min_spp < 2 * p->batch || p->min_spp % p->batch)
         return fail(ctx, RT_EINVAL, "min_spp %u must be a multiple of batch %u and at least twice it", p->min_spp, p->batch);
     if (p->max_spp < p->min_spp || p->max_spp > RT_MAX_SAMPLE + 1u)
         return fail(ctx, RT_EINVAL, "max_spp %u outside min_spp %u .. %u", p->max_spp, p->min_spp, RT_MAX_SAMPLE + 1u);
@@ -974,26 +1042,33 @@ int check_adaptive(rt_context *ctx, const rt_adaptive_params *p, const rt_adapti
     return RT_OK;
 }
 
-// The round loop of both adaptive calls, the parameters checked (bwl, bhl: check_adaptive's): buffers, clear, rounds —
-// launch, pt_adaptive_merge, the stats read back, the stop test — and the resolve.  `launch_round(first, c, scratch, mask,
-// m2_scratch)` adds samples first .. first+c-1 of every pixel of an active block to `scratch` (and their moments to
-// m2_scratch, NULL without RT_OPT_MOMENTS): the one thing in which the two calls differ.
+// The round loop of the adaptive calls, the parameters checked (bwl, bhl: check_adaptive's): buffers, clear, rounds —
+// launch, the rule's merge kernel, the stats read back, the stop test — and the resolve.  `launch_round(first, c, scratch,
+// mask, m2_scratch)` adds samples first .. first+c-1 of every pixel of an active block to `scratch` (and their moments to
+// m2_scratch, NULL without RT_OPT_MOMENTS): the one thing in which the two calls of a rule differ.  The rules differ in
+// the merge kernel and in the buffer beside the accumulator: `half` (Dammertz) or `pixel_err` (variance; the moments are on).
 template <class LaunchRound>
-int adaptive_rounds(rt_context *ctx, const rt_adaptive_params *p, int bwl, int bhl, rt_adaptive_stats *out, LaunchRound launch_round) {
+int adaptive_rounds(rt_context *ctx, AdaptiveRule rule, const rt_adaptive_params *p, int bwl, int bhl, rt_adaptive_stats *out,
+                    LaunchRound launch_round) {
     int rc;
     const uint32_t bx = ((uint32_t)ctx->width + p->block_w - 1) >> bwl, by = ((uint32_t)ctx->height + p->block_h - 1) >> bhl;
     const uint32_t blocks = bx * by;
     if ((rc = ensure_adaptive(ctx, blocks)) != RT_OK) return rc;
     rt_context::Adaptive &a = ctx->adaptive;
     a.blocks = 0;
+    a.variance = false;
+    const size_t px = (size_t)ctx->width * ctx->height;
+    if (rule == RULE_DAMMERTZ && !a.half.p) HIP_TRY(ctx, a.half.alloc(px));
+    if (rule == RULE_VARIANCE && !a.pixel_err.p) HIP_TRY(ctx, a.pixel_err.alloc(px));
     // sample moments (RT_OPT_MOMENTS): the rounds leave theirs in a scratch of its own, made once the option is on
     const bool mom = ctx->moments.on;
-    if (mom && !a.m2_scratch.p) HIP_TRY(ctx, a.m2_scratch.alloc((size_t)ctx->width * ctx->height));
+    if (mom && !a.m2_scratch.p) HIP_TRY(ctx, a.m2_scratch.alloc(px));
     ctx->image_epoch++;   // (the call ends in a resolve)
-    const size_t bytes = (size_t)ctx->width * ctx->height * sizeof(float4);
+    const size_t bytes = px * sizeof(float4);
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, bytes, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.scratch.p, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(a.half.p, 0, bytes, ctx->stream));
+    if (rule == RULE_DAMMERTZ) HIP_TRY(ctx, hipMemsetAsync(a.half.p, 0, bytes, ctx->stream));
+    else HIP_TRY(ctx, hipMemsetAsync(a.pixel_err.p, 0, bytes / 4, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.block_active.p, 0xFF, blocks * sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.block_err.p, 0, blocks * sizeof(float), ctx->stream));
     ctx->accum_count = 0;
@@ -1022,9 +1097,13 @@ int adaptive_rounds(rt_context *ctx, const rt_adaptive_params *p, int bwl, int b
         mp.round = k;
         mp.count = first + c;
         HIP_TRY(ctx, hipMemsetAsync(a.stats.p, 0, st_bytes, ctx->stream));
-        hipLaunchKernelGGL(pt_adaptive_merge, dim3((blocks + PT_MERGE_WAVES - 1) / PT_MERGE_WAVES), dim3(64 * PT_MERGE_WAVES), 0,
-                           ctx->stream, mp, ctx->accum.p, a.half.p, a.scratch.p, a.block_active.p, a.block_err.p, a.stats.p,
-                           m2, m2_scratch);
+        const dim3 grid((blocks + PT_MERGE_WAVES - 1) / PT_MERGE_WAVES), wg(64 * PT_MERGE_WAVES);
+        if (rule == RULE_DAMMERTZ)
+            hipLaunchKernelGGL(pt_adaptive_merge, grid, wg, 0, ctx->stream, mp, ctx->accum.p, a.half.p, a.scratch.p, a.block_active.p,
+                               a.block_err.p, a.stats.p, m2, m2_scratch);
+        else
+            hipLaunchKernelGGL(pt_adaptive_merge_variance, grid, wg, 0, ctx->stream, mp, ctx->accum.p, a.scratch.p, a.block_active.p,
+                               a.block_err.p, a.stats.p, m2, m2_scratch, a.pixel_err.p);
         HIP_TRY(ctx, hipGetLastError());
         rounds++;
         ctx->accum_count = first + c;
@@ -1041,6 +1120,7 @@ int adaptive_rounds(rt_context *ctx, const rt_adaptive_params *p, int bwl, int b
     if ((rc = resolve_into(ctx, 0)) != RT_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     a.blocks = blocks;
+    a.variance = rule == RULE_VARIANCE;
     out->rounds = rounds;
     out->pixel_samples = pixel_samples;
     out->blocks = blocks;
@@ -1051,30 +1131,35 @@ int adaptive_rounds(rt_context *ctx, const rt_adaptive_params *p, int bwl, int b
 }  // namespace
 }  // extern "C++"
 
-int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
+extern "C++" {
+namespace {
+
+// rt_render_adaptive / rt_render_adaptive_variance: every sample through one camera
+int render_adaptive(rt_context *ctx, AdaptiveRule rule, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
     int rc = check_ready(ctx, camera), bwl = 0, bhl = 0;
     if (rc) return rc;
-    if ((rc = check_adaptive(ctx, p, out, &bwl, &bhl)) != RT_OK) return rc;
+    if ((rc = check_adaptive(ctx, rule, p, out, &bwl, &bhl)) != RT_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return adaptive_rounds(ctx, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
+    return adaptive_rounds(ctx, rule, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
         return ctx->prefix_sharing
                    ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch)
                    : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch);
     });
 }
 
-int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
-                               rt_adaptive_stats *out) {
+// rt_render_adaptive_cameras / rt_render_adaptive_variance_cameras: sample j through block j
+int render_adaptive_cameras(rt_context *ctx, AdaptiveRule rule, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
+                            rt_adaptive_stats *out) {
     int rc = check_ready(ctx, cameras), bwl = 0, bhl = 0;
     if (rc) return rc;
-    if ((rc = check_adaptive(ctx, p, out, &bwl, &bhl)) != RT_OK) return rc;
+    if ((rc = check_adaptive(ctx, rule, p, out, &bwl, &bhl)) != RT_OK) return rc;
     if (n_cameras != p->max_spp)
         return fail(ctx, RT_EINVAL, "%u camera blocks for max_spp %u: block j is the camera of sample j", n_cameras, p->max_spp);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
     // (a round ends in a stream synchronisation, so the ring's wait returns at once: the tables go the way of
     // rt_render_spp_cameras' all the same)
-    return adaptive_rounds(ctx, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
+    return adaptive_rounds(ctx, rule, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
         CameraTable tb;
         int r = camera_table_send(ctx, cameras + (size_t)first * 12u, c, &tb);
         if (r != RT_OK) return r;
@@ -1082,6 +1167,27 @@ int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n
         const int rd = camera_table_read(ctx, tb);
         return rd != RT_OK ? rd : r;
     });
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rt_render_adaptive(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
+    return render_adaptive(ctx, RULE_DAMMERTZ, camera, p, out);
+}
+
+int rt_render_adaptive_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
+                               rt_adaptive_stats *out) {
+    return render_adaptive_cameras(ctx, RULE_DAMMERTZ, cameras, n_cameras, p, out);
+}
+
+int rt_render_adaptive_variance(rt_context *ctx, const float camera[12], const rt_adaptive_params *p, rt_adaptive_stats *out) {
+    return render_adaptive(ctx, RULE_VARIANCE, camera, p, out);
+}
+
+int rt_render_adaptive_variance_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
+                                        rt_adaptive_stats *out) {
+    return render_adaptive_cameras(ctx, RULE_VARIANCE, cameras, n_cameras, p, out);
 }
 
 int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
@@ -1101,6 +1207,25 @@ int rt_read_block_error(rt_context *ctx, float *err, size_t bytes) {
     const rt_context::Adaptive &a = ctx->adaptive;
     if (!a.blocks) return fail(ctx, RT_ESTATE, "no rt_render_adaptive call since the frame was (re)allocated");
     return read_back(ctx, err, bytes, a.block_err.p, a.blocks * sizeof(float), "block error");
+}
+
+int rt_read_pixel_error(rt_context *ctx, float *err, size_t bytes) {
+    if (!ctx) return RT_EINVAL;
+    const rt_context::Adaptive &a = ctx->adaptive;
+    const size_t need = (size_t)ctx->width * ctx->height * sizeof(float);
+    if (!err || bytes != need) return fail(ctx, RT_EINVAL, "pixel error buffer must be %zu bytes", need);
+    if (!a.blocks || !a.variance)
+        return fail(ctx, RT_ESTATE, "the last adaptive call on this frame was not rt_render_adaptive_variance(_cameras)");
+    return read_back(ctx, err, bytes, a.pixel_err.p, need, "pixel error");
+}
+
+int rt_device_pixel_error(rt_context *ctx, void **d_err) {
+    if (!ctx || !d_err) return RT_EINVAL;
+    const rt_context::Adaptive &a = ctx->adaptive;
+    if (!a.blocks || !a.variance)
+        return fail(ctx, RT_ESTATE, "the last adaptive call on this frame was not rt_render_adaptive_variance(_cameras)");
+    *d_err = a.pixel_err.p;
+    return RT_OK;
 }
 
 // ---- feature buffers (the denoisers that read them: rt_denoise.hip) ---------------------------------------------------

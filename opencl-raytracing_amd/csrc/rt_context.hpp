@@ -246,13 +246,15 @@ struct rt_context {
     // alloc_frame and by a failed allocation
     struct Adaptive {
         DevBuf<float4> scratch;         // W x H: the current round's sums (zero outside it)
-        DevBuf<float4> half;            // W x H: the sums of the even rounds
+        DevBuf<float4> half;            // W x H: the sums of the even rounds; made by the first call of the Dammertz rule
         DevBuf<uint32_t> block_active;  // per decision block: traced by the next round
         DevBuf<float> block_err;        // per decision block: its error after the last round it was traced in
         DevBuf<unsigned long long> stats;   // pt_adaptive_merge's counter rows (rt_amd.hip)
         DevBuf<float> m2_scratch;       // W x H: the current round's moments (zero outside it); only with RT_OPT_MOMENTS 1
+        DevBuf<float> pixel_err;        // W x H: rt_render_adaptive_variance's pixel errors; made by the first call of that rule
         size_t block_capacity = 0;
         uint32_t blocks = 0;            // blocks of the last completed rt_render_adaptive call (0: none)
+        bool variance = false;          // that call was of the variance rule: pixel_err describes the frame
     } adaptive;
     // first-hit features (rt_render_features), allocated on its first call: reset by alloc_frame
     struct Features {

@@ -39,6 +39,7 @@ SYMBOLS = (
     "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
     "rt_render_features_cameras", "rt_read_feature_coverage", "rt_device_feature_coverage", "rt_debug_plan_feature_cameras",
     "rt_render_adaptive_cameras", "rt_render_again_cameras",
+    "rt_render_adaptive_variance", "rt_render_adaptive_variance_cameras", "rt_read_pixel_error", "rt_device_pixel_error",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -471,6 +472,43 @@ class RayTracer:
         self._adaptive_block = (int(block[0]), int(block[1]))
         return st.as_dict()
 
+    def renderAdaptiveVariance(self, camera, threshold, batch=16, min_spp=32, max_spp=1024, block=(8, 8)):
+        """Adaptive frame under the variance-driven stopping rule (rt_render_adaptive_variance): renderAdaptive's rounds,
+        but a block stops once the mean over its pixels of sqrt(M2 / (n (n - 1))) / sqrt(luminance) — the standard error
+        of the pixel's mean, measured from its own samples — is below `threshold` (after at least min_spp samples, which
+        may equal batch; decisions from round 0 on).  Needs OPT_MOMENTS 1; denoiseMoments can follow directly.
+        → the stats dict renderAdaptive returns; pixelError() and blockError() read the estimates."""
+        p = _abi.AdaptiveParams(int(batch), int(min_spp), int(max_spp), float(threshold), int(block[0]), int(block[1]))
+        st = _abi.AdaptiveStats()
+        self._check(self._lib.rt_render_adaptive_variance(self._ctx, _cam_block(camera).ctypes.data, C.byref(p), C.byref(st)))
+        self._adaptive_block = (int(block[0]), int(block[1]))
+        return st.as_dict()
+
+    def renderAdaptiveVarianceCameras(self, blocks, threshold, batch=16, min_spp=32, block=(8, 8)):
+        """renderAdaptiveVariance through per-sample camera blocks (rt_render_adaptive_variance_cameras): sample j of every
+        pixel looks through blocks[j] (float32[max_spp, 12]); max_spp = len(blocks).  Identical blocks give
+        renderAdaptiveVariance's bits.  → the stats dict renderAdaptive returns."""
+        blocks = _cam_blocks(blocks)
+        p = _abi.AdaptiveParams(int(batch), int(min_spp), len(blocks), float(threshold), int(block[0]), int(block[1]))
+        st = _abi.AdaptiveStats()
+        self._check(self._lib.rt_render_adaptive_variance_cameras(self._ctx, blocks.ctypes.data if len(blocks) else None,
+                                                                  len(blocks), C.byref(p), C.byref(st)))
+        self._adaptive_block = (int(block[0]), int(block[1]))
+        return st.as_dict()
+
+    def pixelError(self):
+        """Pixel errors of the last renderAdaptiveVariance(Cameras) call (rt_read_pixel_error): each pixel's value after
+        the last round its block was traced in → (h, w) float32."""
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self._lib.rt_read_pixel_error(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def devicePixelError(self):
+        """Device address of the W x H floats of pixelError() (rt_device_pixel_error)."""
+        p = C.c_void_p()
+        self._check(self._lib.rt_device_pixel_error(self._ctx, C.byref(p)))
+        return p.value
+
     def sampleCounts(self):
         """Per-pixel sample counts of the accumulator → (h, w) uint32."""
         out = np.empty((self.height, self.width), dtype=np.uint32)
@@ -478,7 +516,7 @@ class RayTracer:
         return out
 
     def blockError(self):
-        """Block errors of the last renderAdaptive call → (ceil(h/bh), ceil(w/bw)) float32."""
+        """Block errors of the last adaptive call, of either stopping rule → (ceil(h/bh), ceil(w/bw)) float32."""
         bw, bh = getattr(self, "_adaptive_block", (8, 8))
         out = np.empty((-(-self.height // bh), -(-self.width // bw)), dtype=np.float32)
         self._check(self._lib.rt_read_block_error(self._ctx, out.ctypes.data, out.nbytes))

@@ -13,6 +13,19 @@ and the adaptive runs are renderAdaptiveCameras frames — the thresholds and th
 themselves.  The configurations alternate inside each of --rounds rounds (default 5) and the times are reported as
 median (min .. max).  Per adaptive run the record also holds every round's launch time (the device events round each
 round's camera launch, kernelMsHistory) beside the share of the decision blocks that round traced.
+
+--rule variance compares the two stopping rules (DESIGN.md "Variance-driven stopping rule") at EQUAL pixel-sample budgets:
+for each --thresholds value the Dammertz frame (renderAdaptive) is rendered, then the variance rule's threshold is found by
+bisection so that renderAdaptiveVariance spends the same pixel samples within 2 %, and for both the gamma RMSE against the
+--truth-spp frame, the pixel samples, the rounds and the whole call's time (median (min .. max) of --runs) are reported;
+the sample moments are on for both, batch / min_spp / max_spp are shared.  It ends with the cameras form at threshold 0
+(every block in every round, --cameras-spp jittered samples): renderAdaptiveCameras without and with moments and
+renderAdaptiveVarianceCameras — what the fixed-lane camera kernel the moments ask for costs.
+The merge kernels' own time per round comes from a kernel trace:
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/adaptive_bench.py --rule variance --merge-rounds 20
+renders 20 two-round threshold-0 frames per rule and scene (every block active in round 0 and in round 1), and
+    python tools/adaptive_bench.py --merge-trace DIR/.../*_kernel_trace.csv
+prints per merge kernel and round the median (min .. max) of its dispatches.
 """
 import argparse
 import json
@@ -42,6 +55,122 @@ def jitter_blocks(block, n, width, height):
 def spread(v):
     v = sorted(v)
     return "%.1f (%.1f .. %.1f)" % (v[len(v) // 2], v[0], v[-1])
+
+
+def merge_trace_main(path):
+    """--merge-trace: per merge kernel and round (the dispatches of a two-round frame alternate) its time in a rocprofv3 trace."""
+    import csv
+    rows = [r for r in csv.DictReader(open(path)) if "pt_adaptive_merge" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    by = {}
+    for r in rows:
+        name = "pt_adaptive_merge_variance" if "pt_adaptive_merge_variance" in r["Kernel_Name"] else "pt_adaptive_merge"
+        grid = r.get("Grid_Size_X", r.get("Grid_Size", "?"))
+        by.setdefault((name, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    print("| kernel | grid (work-items) | round | dispatches | us: median (min .. max) |")
+    print("|---|---:|---:|---:|---:|")
+    for (name, grid), us in sorted(by.items()):
+        for k in (0, 1):
+            v = sorted(us[k::2])
+            if v:
+                print("| %s | %s | %d | %d | %.1f (%.1f .. %.1f) |" % (name, grid, k, len(v), v[len(v) // 2], v[0], v[-1]))
+
+
+def rule_main(a):
+    """--rule variance: the two stopping rules at equal pixel-sample budgets."""
+    import torch
+    w, h = (int(v) for v in a.size.split("x"))
+    rows, cam_rows = [], []
+    for name in a.scenes.split(","):
+        wl = rt.workloads.get(name, width=w, height=h)
+        t = rt.RayTracer(w, h, scene=wl.scene, seed=rt.workloads.SEED)
+        t.setArith(2 if a.policy is None else a.policy)
+        stream = torch.cuda.Stream()
+        t.setStream(stream.cuda_stream)
+        kw = dict(batch=a.batch, min_spp=a.min_spp, max_spp=a.max_spp)
+        calls = {"dammertz": lambda thr: t.renderAdaptive(wl.camera, thr, **kw),
+                 "variance": lambda thr: t.renderAdaptiveVariance(wl.camera, thr, **kw)}
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            r = fn()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1), r
+
+        t.setOption(t.OPT_MOMENTS, 1)
+        t.renderFrameOnDevice(wl.camera, 64)   # warm-up (code objects, LDS sizing, buffers)
+        if a.merge_rounds:
+            two = dict(batch=a.batch, min_spp=2 * a.batch, max_spp=2 * a.batch)
+            for _ in range(a.merge_rounds):
+                t.renderAdaptive(wl.camera, 0.0, **two)
+                t.renderAdaptiveVariance(wl.camera, 0.0, **two)
+            t.setStream(None)
+            t.close()
+            continue
+        for c in calls.values():
+            c(0.05)
+        truth = t.renderFrame(wl.camera, a.truth_spp)[..., :3].astype(np.float64)
+
+        def measure(rule, thr, against=None):
+            ms, st = [], None
+            for _ in range(a.runs):
+                m, st = timed(lambda: calls[rule](thr))
+                ms.append(m)
+            img = t.transferImage()[..., :3].astype(np.float64)
+            rec = dict(scene=name, rule=rule, threshold=thr, ms=ms, pixel_samples=st["pixel_samples"],
+                       mean_spp=st["pixel_samples"] / float(w * h), rounds=st["rounds"], blocks_at_max=st["blocks_at_max"],
+                       blocks=st["blocks"], rmse=float(np.sqrt(((img - truth) ** 2).mean())))
+            if against:
+                rec["budget_ratio"] = st["pixel_samples"] / float(against)
+            return rec
+
+        for thr in (float(v) for v in a.thresholds.split(",")):
+            d = measure("dammertz", thr)
+            lo, hi = 1e-5, 10.0          # the samples fall as the threshold rises: bisect its logarithm
+            for _ in range(24):
+                mid = float(np.sqrt(lo * hi))
+                ps = calls["variance"](mid)["pixel_samples"]
+                if abs(ps / float(d["pixel_samples"]) - 1.0) <= 0.005:
+                    break
+                lo, hi = (mid, hi) if ps > d["pixel_samples"] else (lo, mid)
+            rows += [d, measure("variance", mid, against=d["pixel_samples"])]
+
+        # the cameras form at threshold 0: equal work, so the difference is the camera kernel the moments select (and the merge)
+        blocks = jitter_blocks(wl.camera, a.cameras_spp, w, h)
+        ckw = dict(batch=a.batch, min_spp=2 * a.batch)
+        forms = [("renderAdaptiveCameras, moments off", 0, lambda: t.renderAdaptiveCameras(blocks, 0.0, **ckw)),
+                 ("renderAdaptiveCameras, moments on", 1, lambda: t.renderAdaptiveCameras(blocks, 0.0, **ckw)),
+                 ("renderAdaptiveVarianceCameras", 1, lambda: t.renderAdaptiveVarianceCameras(blocks, 0.0, **ckw))]
+        recs = [dict(scene=name, form=f[0], ms=[]) for f in forms]
+        for rnd in range(a.runs + 1):             # (the first pass warms the camera tables and code objects up)
+            for f, r in zip(forms, recs):
+                t.setOption(t.OPT_MOMENTS, f[1])
+                ms, st = timed(f[2])
+                if rnd:
+                    r["ms"].append(ms)
+                r.update(rounds=st["rounds"], family=t.lastCameraPlan()[1]["family"])
+        cam_rows += recs
+        t.setStream(None)
+        t.close()
+    if a.merge_rounds:
+        return
+    print("| scene | rule | threshold | ms: median (min .. max) of %d | pixel samples | vs Dammertz | mean spp | rounds | at max | RMSE (gamma) |" % a.runs)
+    print("|---|---|---:|---:|---:|---:|---:|---:|---:|---:|")
+    for r in rows:
+        print("| %s | %s | %.5g | %s | %d | %s | %.1f | %d | %d of %d | %.5f |" %
+              (r["scene"], r["rule"], r["threshold"], spread(r["ms"]), r["pixel_samples"],
+               "%+.2f %%" % (100 * (r["budget_ratio"] - 1)) if "budget_ratio" in r else "", r["mean_spp"], r["rounds"],
+               r["blocks_at_max"], r["blocks"], r["rmse"]))
+    print()
+    print("| scene | cameras form, threshold 0, %d samples | camera kernel family | rounds | ms: median (min .. max) of %d |" % (a.cameras_spp, a.runs))
+    print("|---|---|---:|---:|---:|")
+    for r in cam_rows:
+        print("| %s | %s | %d | %d | %s |" % (r["scene"], r["form"], r["family"], r["rounds"], spread(r["ms"])))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(rules=rows, cameras=cam_rows), f, indent=1)
 
 
 def cameras_main(a):
@@ -142,7 +271,18 @@ def main():
     ap.add_argument("--cameras", action="store_true", help="anti-aliased frames: per-sample cameras (see the module text)")
     ap.add_argument("--rounds", type=int, default=5, help="--cameras: repeats, the configurations alternating inside each")
     ap.add_argument("--policy", type=int, default=None, help="--cameras: arithmetic policy (default: the tracer's)")
+    ap.add_argument("--rule", choices=("dammertz", "variance"), default="dammertz",
+                    help="variance: compare the two stopping rules at equal pixel-sample budgets (see the module text)")
+    ap.add_argument("--runs", type=int, default=3, help="--rule variance: timed repeats of every configuration")
+    ap.add_argument("--cameras-spp", type=int, default=256, help="--rule variance: samples of the cameras-form comparison")
+    ap.add_argument("--merge-rounds", type=int, default=0,
+                    help="--rule variance: only render this many two-round threshold-0 frames per rule, for a kernel trace")
+    ap.add_argument("--merge-trace", default=None, help="summarise the merge kernels of a rocprofv3 kernel-trace CSV and exit")
     a = ap.parse_args()
+    if a.merge_trace:
+        return merge_trace_main(a.merge_trace)
+    if a.rule == "variance":
+        return rule_main(a)
     if a.cameras:
         return cameras_main(a)
     import torch
