@@ -78,6 +78,25 @@ void RayTracer::renderSamplesCameras(const std::vector<float> &blocks, uint32_t 
     check(rt_render_spp_cameras(ctx, blocks.data(), first_sample, (uint32_t)(blocks.size() / 12)));
 }
 
+void RayTracer::uploadRays(const std::vector<rt_ray> &batch) { check(rt_upload_rays(ctx, batch.data(), batch.size())); }
+
+void RayTracer::renderRays(uint32_t first_sample, uint32_t n_samples) {
+    check(rt_render_rays(ctx, nullptr, (size_t)width * height, first_sample, n_samples, nullptr));
+}
+
+void RayTracer::renderFeaturesRays(uint32_t follow, uint32_t max_chain) {
+    const rt_feature_chain_params p{follow, max_chain};
+    check(rt_render_features_rays(ctx, nullptr, (size_t)width * height, &p));
+}
+
+const float *RayTracer::renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp) {
+    uploadRays(batch);
+    check(rt_clear(ctx));
+    renderRays(0, spp);
+    check(rt_resolve(ctx));
+    return transferImage();
+}
+
 void RayTracer::renderAgainCameras(const std::vector<float> &blocks) {
     check(rt_render_again_cameras(ctx, blocks.data(), (uint32_t)(blocks.size() / 12)));
 }

@@ -66,6 +66,15 @@ public:
     // through block s mod n of `blocks` (n x 12 floats) — renderAgain's bits for that block, served from look-ahead batches
     // while the calls repeat one table
     void renderAgainCameras(const std::vector<float> &blocks);
+    // caller-supplied rays (rt_upload_rays, rt_render_rays, rt_render_features_rays; host/rays.h makes panoramas, fisheye and
+    // orthographic views and cube maps): uploadRays copies a batch into the context's ray buffer; renderRays traces samples
+    // first_sample .. +n_samples-1 of the uploaded rays into the accumulator (the batch holds w x h rays, ray i = pixel i),
+    // asynchronously like renderSamples; renderFeaturesRays writes the feature records that belong to such a frame, so that
+    // denoise(nullptr, ...) works on it
+    void uploadRays(const std::vector<rt_ray> &batch);
+    void renderRays(uint32_t first_sample, uint32_t n_samples);
+    void renderFeaturesRays(uint32_t follow = 0, uint32_t max_chain = 0);
+    const float *renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp);  // upload + clear + renderRays + resolve + read back
     // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
     // the same through per-sample camera blocks (rt_render_adaptive_cameras): sample j of every pixel through block j of

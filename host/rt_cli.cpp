@@ -10,6 +10,13 @@
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
 //          [--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--progressive-cameras [--lookahead N]]
+//          [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E]]
+// --projection renders --spp samples through caller-supplied rays instead of the pinhole camera (host/rays.h →
+// rt_upload_rays + rt_render_rays into the accumulator): an equirectangular panorama about --camera's position and yaw, an
+// equidistant fisheye of --fov-deg degrees (default 180) or an orthographic view --extent world units wide (default 10)
+// along --camera's direction.  It goes with --spp, --denoise (plain or --variance-guided, with or without --follow), --aov
+// and the image outputs — the guides then come from rt_render_features_rays — and is refused with every other way to spend
+// the samples (--progressive, --adaptive, --aa, --aperture, ...) and with --measured.
 // --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
 // --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
 // sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
@@ -67,6 +74,7 @@
 #include <vector>
 
 #include "raytracer.h"
+#include "rays.h"
 
 static void check_rc(int rc) {
     if (rc) {
@@ -83,7 +91,7 @@ static void usage() {
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--adaptive-rule dammertz|variance]\n";
+                 "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E]]\n";
     std::exit(2);
 }
 
@@ -178,6 +186,9 @@ int main(int argc, char **argv) {
     bool aa = false, focus_given = false;
     float aperture = 0.0f, focus = 1.0f;
     long aa_guides = 0;   // (0: the central, unjittered records)
+    std::string projection;
+    float fov_deg = 180.0f, extent = 10.0f;
+    bool fov_deg_given = false, extent_given = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -242,6 +253,22 @@ int main(int argc, char **argv) {
             if (!*v || *end || !(focus > 0.0f) || !std::isfinite(focus)) usage();
             focus_given = true;
         }
+        else if ((v = val("--projection"))) {
+            projection = v;
+            if (projection != "equirect" && projection != "fisheye" && projection != "ortho") usage();
+        }
+        else if ((v = val("--fov-deg"))) {
+            char *end = nullptr;
+            fov_deg = std::strtof(v, &end);
+            if (!*v || *end || !(fov_deg > 0.0f) || !(fov_deg <= 360.0f)) usage();
+            fov_deg_given = true;
+        }
+        else if ((v = val("--extent"))) {
+            char *end = nullptr;
+            extent = std::strtof(v, &end);
+            if (!*v || *end || !(extent > 0.0f) || !std::isfinite(extent)) usage();
+            extent_given = true;
+        }
         else if ((v = val("--aa-guides"))) aa_guides = parse_int(v, 1, RT_FEATURE_CAMERAS_MAX);
         else if (a == "--aa") aa = true;
         else if (a == "--denoise") denoise = true;
@@ -273,6 +300,10 @@ int main(int argc, char **argv) {
     if ((adaptive_cameras || progressive_cameras) && !cameras) usage();    // need the per-sample cameras of --aa / --aperture
     if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
     if (aa_guides && (!cameras || (!denoise && aov_prefix.empty()))) usage();   // guides of a per-sample-camera frame, for --denoise / --aov
+    const bool rays_frame = !projection.empty();
+    if (rays_frame && (cameras || progressive || progressive_cameras || adaptive || adaptive_cameras || measured)) usage();   // one way to spend the samples
+    if (fov_deg_given && projection != "fisheye") usage();
+    if (extent_given && projection != "ortho") usage();
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive || adaptive_cameras) {
         if (progressive) usage();
@@ -339,6 +370,12 @@ int main(int argc, char **argv) {
         check_rc(rt_render(tracer.context(), table.data()));
         for (int s = 1; s < spp; s++) tracer.renderAgainCameras(table);
         img = tracer.transferImage();
+    } else if (rays_frame) {
+        const float pos[3] = {cam[0], cam[1], cam[2]};
+        img = tracer.renderFrameRays(projection == "equirect" ? rays::equirect(pos, w, h, cam[3])
+                                     : projection == "fisheye" ? rays::fisheye(pos, w, h, fov_deg, cam[3], cam[4])
+                                                               : rays::orthographic(pos, w, h, extent, cam[3], cam[4]),
+                                     (uint32_t)spp);
     } else if (cameras) {
         img = tracer.renderFrameCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus));
     } else {
@@ -352,11 +389,12 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back" << std::endl;
         if (!out_counts.empty()) write_counts(out_counts, tracer.sampleCounts(), w, h);
     } else {
-        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : progressive_cameras ? "progressive per-sample cameras" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
+        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : progressive_cameras ? "progressive per-sample cameras" : rays_frame ? "caller-supplied rays" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 
-    if (aa_guides) tracer.renderFeaturesCameras(camera.sampleBlocks((uint32_t)aa_guides, 0, w, h, aa, aperture, focus), follow,
+    if (rays_frame) { if (denoise || !aov_prefix.empty()) tracer.renderFeaturesRays(follow, follow ? (uint32_t)max_chain : 0u); }
+    else if (aa_guides) tracer.renderFeaturesCameras(camera.sampleBlocks((uint32_t)aa_guides, 0, w, h, aa, aperture, focus), follow,
                                                 follow ? (uint32_t)max_chain : 0u);
     else if (follow) tracer.renderFeaturesChain(&camera, follow, (uint32_t)max_chain);
     else if (denoise || !aov_prefix.empty()) tracer.renderFeatures(&camera);

@@ -310,6 +310,57 @@ int rt_resolve(rt_context *ctx);
 int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_sample, uint32_t n_samples);
 
 /*
+ * Caller-supplied rays (new): paths that start at rays the caller computed — an equirectangular panorama, a fisheye or
+ * orthographic view, a cube-map probe, a bake from surface points, a radiance query along arbitrary rays — instead of at a
+ * pinhole camera block.
+ *   o      the origin.
+ *   d      the direction, used AS GIVEN and not normalised (the reference leaves refracted directions unnormalised too: the
+ *          hit routines take any length).
+ *   x, y   the ray's random stream: they take the values the pixel coordinates take in the table index.
+ * The contract is stated for finite components, a non-zero d and x, y < RT_MAX_DIM.  The library does not validate device
+ * data; every table index is reduced mod RT_RANDOM_BUFFER_SIZE in 32 bits, so any 32-bit id is memory-safe.
+ */
+typedef struct rt_ray {
+    float o[3];
+    uint32_t x;
+    float d[3];
+    uint32_t y;
+}
+#if defined(__GNUC__) || defined(__clang__)
+__attribute__((aligned(16)))
+#endif
+rt_ray;
+
+#define RT_MAX_RAYS (1u << 28)   /* rays of one rt_render_rays call */
+
+/* Copies n rays (host pointer) into the context's own ray buffer, on the context's stream.  The buffer grows on demand and
+ * survives rt_resize and a scene change.  RT_EINVAL: a NULL pointer, n 0 or above RT_MAX_RAYS. */
+int rt_upload_rays(rt_context *ctx, const rt_ray *host, size_t n);
+/* Device address of the uploaded rays and their count (NULL and 0 before the first upload). */
+int rt_device_rays(rt_context *ctx, void **d_rays, size_t *n);
+
+/*
+ * Samples first_sample .. first_sample+n_samples-1 of ray i, for every i < n_rays.  d_rays: n_rays rt_ray records on the
+ * device, 16-byte aligned (NULL: the uploaded rays, of which there must be at least n_rays); d_accum: n_rays x 4 floats on
+ * the device (NULL: the context's accumulator, and then n_rays == W*H, ray i being pixel i, row-major).
+ *   - Sample s of ray i is, bit for bit under the selected arithmetic policy, the radiance rt_trace_samples returns for a
+ *     camera whose primary ray at pixel (x_i, y_i) has exactly these origin and direction bits.
+ *   - The samples of a ray are summed in rt_render_spp's fixed order — lane l of the ray's g lanes adds its samples l, l+g, ...
+ *     one after the other, then the xor butterfly — and the sum is ADDED to d_accum[i], the count to its 4th channel: the
+ *     caller zeroes the buffer, consecutive calls add.  More than 512 samples run as launches of 512, as elsewhere.
+ *   - Asynchronous on the context's stream (the caller orders its own writes of d_rays / d_accum before it).
+ *   - With d_accum NULL rt_clear, rt_resolve, rt_read_image / rt_read_linear, the denoisers and RT_OPT_MOMENTS work on the frame
+ *     unchanged; the sample moments are updated exactly as rt_render_spp_cameras updates them.  An external d_accum keeps none.
+ *   - The image, the sample counter, the feature records, a kept prefix and pending look-ahead frames stay untouched, as
+ *     under rt_render_spp_cameras.  Enabled counters, RT_OPT_SAMPLE_QUEUE, RT_OPT_ACCEL, RT_OPT_WAVE_FILL and
+ *     RT_OPT_MAX_THREADS_PER_LAUNCH are honoured; none changes a bit.  The prefix options have nothing to act on.
+ * RT_EINVAL: n_rays 0 or above RT_MAX_RAYS, samples beyond RT_MAX_SAMPLE, NULL d_rays with fewer than n_rays rays uploaded,
+ * NULL d_accum with n_rays != W*H, a sharded context (the caller shards a batch itself).  RT_ESTATE: no scene set.  A failed
+ * call changes nothing.
+ */
+int rt_render_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t first_sample, uint32_t n_samples, void *d_accum);
+
+/*
  * Progressive anti-aliasing (new): rt_render_again through a CYCLIC SCHEDULE of camera blocks.  `cameras` is a host pointer to
  * n_cameras x 12 floats, copied during the call; the call that makes sample s = sample_counter + 1 looks through block
  * s mod n_cameras (a caller who starts with rt_render(ctx, cameras) has sample 0 through block 0).
@@ -489,6 +540,16 @@ int rt_device_features(rt_context *ctx, void **d_features);
 #define RT_FEATURE_CHAIN_SIGNATURE(flags) ((flags) & 0xFFFF0000u)   /* == signature & 0xFFFF0000 */
 typedef struct rt_feature_chain_params { uint32_t follow; uint32_t max_chain; } rt_feature_chain_params;
 int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_feature_chain_params *p);
+
+/*
+ * Feature records for caller-supplied rays (new): the guides that belong to an rt_render_rays frame.  d_rays: n_rays == W*H
+ * rt_ray records on the device (NULL: the uploaded rays), ray i being pixel i, row-major; p NULL = first hits.  Record i is,
+ * bit for bit, what rt_render_features_chain writes for a camera whose primary ray at that pixel has these origin and
+ * direction bits; `dir` is the direction as given.  The call replaces the context's feature records, so the denoisers work
+ * on a panorama.  State rules and errors as rt_render_features_chain, plus RT_EINVAL for n_rays != W*H and for NULL d_rays
+ * with fewer than n_rays rays uploaded.
+ */
+int rt_render_features_rays(rt_context *ctx, const void *d_rays, size_t n_rays, const rt_feature_chain_params *p);
 int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out);   /* host-only, no context */
 
 /*
@@ -955,6 +1016,11 @@ int rt_debug_plan_camera_samples(const rt_camera_facts *facts, rt_camera_plan *p
 /* Test instrumentation: the facts and the plan of the context's last camera launch (its last slot range).  RT_EINVAL before
  * the first one. */
 int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
+
+/* Test instrumentation: the facts (n = the rays of the range) and the plan of the context's last ray launch (rt_render_rays,
+ * its last slot range) — rt_render_spp_cameras' planner, the one rt_debug_plan_camera_samples calls.  RT_EINVAL before the
+ * first one. */
+int rt_debug_last_ray_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 
 /* Test instrumentation: resident workgroups per compute unit the runtime reports for the headline sample-queue kernel
  * (one wave per workgroup) at `lds_bytes` of dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor; no kernel runs). */

@@ -285,6 +285,59 @@ def camera_prototypes(lib):
     lib.rt_debug_plan_feature_cameras.argtypes = [C.c_int, C.c_int, u32, C.POINTER(u32)]
 
 
+# rt_ray (rt_render_rays): origin, random-stream x, direction (used as given), random-stream y — 32 bytes, two float4
+RAY = np.dtype([("o", "<f4", (3,)), ("x", "<u4"), ("d", "<f4", (3,)), ("y", "<u4")])
+assert RAY.itemsize == 32
+MAX_RAYS = 1 << 28          # RT_MAX_RAYS
+
+
+def check_rays(t):
+    """A ray batch as renderRays takes it on the device: a torch tensor of shape (n, 8), float32, contiguous, on a GPU,
+    holding rt_ray bits (RAY: the ids are the float words 3 and 7 reinterpreted).  Raises ValueError otherwise, before any
+    library call; needs no device.  → n."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("rays must be a torch tensor on the device (upload a numpy batch with uploadRays)")
+    if t.dtype != torch.float32:
+        raise ValueError("rays must be float32 (rt_ray bits), not %s" % t.dtype)
+    if t.dim() != 2 or t.shape[1] != 8:
+        raise ValueError("rays must have shape (n, 8), not %s" % (tuple(t.shape),))
+    if t.shape[0] < 1 or t.shape[0] > MAX_RAYS:
+        raise ValueError("a ray batch holds 1 .. 2^28 rays, not %d" % t.shape[0])
+    if not t.is_contiguous():
+        raise ValueError("rays must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError("rays must live on the device, not on %s" % t.device)
+    return int(t.shape[0])
+
+
+def check_ray_target(t, n):
+    """The external target of renderRays: a torch (n, 4) float32 contiguous device tensor.  ValueError otherwise."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("out must be a torch tensor on the device")
+    if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, 4):
+        raise ValueError("out must be float32 of shape (%d, 4), not %s %s" % (n, t.dtype, tuple(t.shape)))
+    if not t.is_contiguous() or t.device.type != "cuda":
+        raise ValueError("out must be a contiguous device tensor")
+
+
+def ray_prototypes(lib):
+    """ctypes prototypes of the caller-supplied-ray entry points (rt_render_rays & co.)."""
+    vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
+    lib.rt_upload_rays.argtypes = [vp, vp, sz]
+    lib.rt_device_rays.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    lib.rt_render_rays.argtypes = [vp, vp, sz, u32, u32, vp]
+    lib.rt_render_features_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams)]
+    lib.rt_debug_last_ray_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
+
+
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)
 LDS_MATERIALS, LDS_WINNERS, LDS_PLANES = 64, 64, 16
 

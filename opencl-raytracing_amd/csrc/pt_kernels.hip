@@ -214,6 +214,50 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
     flush_counters<COUNT>(cn, counters, 1);
 }
 
+// Caller-supplied rays, fixed lanes (rt_render_rays with counters on, RT_OPT_SAMPLE_QUEUE 0 or sample moments — as
+// plan_camera_samples decides): pt_render<MODE_ACCUM>'s shape with slot i of the launch's range = ray i of fp.rays.  Lane l of
+// the ray's g lanes traces samples first+l, first+l+g, … of the given ray — used as given, not normalised — under the
+// random stream (ray.x, ray.y); the g partial sums meet in the same butterfly and lane 0 adds to accum[i] (and m2[i]).
+template <bool COUNT, bool ACCEL>
+__global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
+                                                      unsigned long long *counters) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    LaneCounters cn;
+    if (COUNT) zero_counters(cn);
+    Ctx c{sc, stage_materials(sc, s_mat), &cn};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t g = 1u << fp.group_log2;
+    const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
+    const uint32_t lane = tid & (g - 1u);
+    const bool valid = index < fp.slot_end;
+
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const bool mom = fp.m2 != nullptr;   // (uniform)
+    LaneMoments lm{0.0f, 0.0f};
+    if (valid) {
+        const float4 ro = fp.rays[2u * (size_t)index], rd = fp.rays[2u * (size_t)index + 1u];
+        Ray r0;
+        r0.o = mk(ro.x, ro.y, ro.z);
+        r0.d = mk(rd.x, rd.y, rd.z);
+        const uint32_t rx = __float_as_uint(ro.w), ry = __float_as_uint(rd.w);
+        for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
+            if (COUNT) cn.c[CN_SAMPLES]++;
+            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, rx, ry);
+            if (mom) moments_fold(lm, sum, rad);
+            sum = sum + rad;
+        }
+    }
+    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
+    if (valid && lane == 0) {
+        if (mom) moments_update(accum, fp.m2, (size_t)index, sum, fp.count, lm.m2);
+        accumulate(accum, (size_t)index, sum, fp.count);
+    }
+    flush_counters<COUNT>(cn, counters, 1);
+}
+
 // Fused path, stage 1: one work-item per owned PIXEL traces the sample-invariant
 // prefix of the pixel's paths (pt_device.hpp "shared deterministic prefix").
 // A pixel whose paths never meet a random event (sky, direct light, mirror /
@@ -940,6 +984,56 @@ PT_DEV CameraEntry queue_fetch_cam(const WaveQueue &q, const FrameParams &fp, ui
     return e;
 }
 
+// ---- the queue's entry FROM A RAY BUFFER (pt_samples_q_rays; rt_render_rays) -----------------------------------------------
+// The camera entry with the primary ray given instead of formed: slot i of the launch's range IS ray i of fp.rays (no tiles,
+// no shard, no mask), a wave owns the slots below slot_end among its `pixels_per_wave` consecutive ones, and a ray's `count`
+// samples are the queue entries of one "pixel".  The LDS layout is queue_stage's once more, so the sizing rules stay shared:
+//   coordinates   (x: the ray index, y: 0, rnd_base_v(0, ray.x, ray.y), rnd_base_u(0, ray.x, ray.y)) — queue_sums forms
+//                 y · fp.w + x = the ray index with its code unchanged, and the random stream is the one the ray names;
+//   record        of the 80 bytes the first two float4 hold the ray as it lies in the buffer, (o, x bits) and (d, y bits):
+//                 two 16-byte loads per ray at staging, two 12-byte LDS reads per refill, no camera block, no normalize.
+// Every lane of the wave calls queue_stage_rays after the ballot (it holds the wave's fence).
+PT_DEV WaveQueue queue_stage_rays(const DeviceScene &sc, const FrameParams &fp, bool owns, uint32_t index,
+                                  unsigned long long owners, uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
+    float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
+    WaveQueue q;
+    q.rec = (LdsQueueF4)wave_lds;
+    q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
+    q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
+    q.npix = (uint32_t)__popcll(owners);
+    q.count = fp.count;
+    q.total = q.npix * q.count;
+    if (owns) {
+        const uint32_t k = lanes_below(owners);   // (< npix <= pixels_per_wave)
+        const float4 ro = fp.rays[2u * (size_t)index], rd = fp.rays[2u * (size_t)index + 1u];
+        const uint32_t rx = __float_as_uint(ro.w), ry = __float_as_uint(rd.w);
+        q.xy[k].x = index;
+        q.xy[k].y = 0u;
+        q.xy[k].bv = rnd_base_v(0u, rx, ry);
+        q.xy[k].bu = rnd_base_u(0u, rx, ry);
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k) = v4f{ro.x, ro.y, ro.z, ro.w};        // (whole, as queue_stage writes a record part)
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k + 1u) = v4f{rd.x, rd.y, rd.z, rd.w};
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    q.inv_count = fp.inv_count;
+    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    return q;
+}
+// Queue entry idx → (ray p, sample first + j): the staged ray as it was given, and the sample's part of the two index sums.
+PT_DEV CameraEntry queue_fetch_rays(const WaveQueue &q, const FrameParams &fp, uint32_t idx) {
+    // (p = idx / count as queue_fetch forms it)
+    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t sample = fp.first + (idx - p * q.count);
+    const LdsQueueF4 st = q.rec + QUEUE_REC_F4 * p;
+    CameraEntry e;
+    e.r.o = mk(st[0].x, st[0].y, st[0].z);
+    e.r.d = mk(st[1].x, st[1].y, st[1].z);
+    e.bv = sample * 8049u + q.xy[p].bv;   // = rnd_base_v(sample, ray.x, ray.y)
+    e.bu = sample * 2683u + q.xy[p].bu;   // = rnd_base_u(sample, ray.x, ray.y)
+    return e;
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
@@ -963,6 +1057,11 @@ PT_DEV CameraEntry queue_fetch_cam(const WaveQueue &q, const FrameParams &fp, ui
 #include "pt_samples_q_kernel.hpp"
 #undef PT_Q_LOOKAHEAD_FORM
 #define PT_Q_LOOKAHEAD_FORM 1
+#include "pt_samples_q_kernel.hpp"
+#undef PT_Q_LOOKAHEAD_FORM
+// … and a third time as pt_samples_q_rays<ACCEL, GEOM, WAVES>, the camera entry fed from a ray buffer (rt_render_rays;
+// queue_stage_rays above): a kernel of its own for the same reason — the existing instantiations keep their code.
+#define PT_Q_LOOKAHEAD_FORM 2
 #include "pt_samples_q_kernel.hpp"
 #undef PT_Q_LOOKAHEAD_FORM
 
@@ -1379,6 +1478,69 @@ __global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FramePa
         return;
     }
     // the chain left the scene (a terminal exists whenever the loop runs out: its last pass cannot follow)
+    const float none = __uint_as_float(0xFFFFFFFFu);
+    o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+    o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
+    o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
+    o[3] = make_float4(d0.x, d0.y, d0.z, none);
+    o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
+}
+
+// Feature records for caller-supplied rays (rt_render_features_rays): pt_features_chain's loop — the same search, scatter
+// and flags, duplicated here so that the camera kernel keeps its code — with record i's primary ray read from ray i of the
+// buffer (n rays = the frame's pixels, row-major).  `dir` is the direction as given.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features_rays(DeviceScene sc, const float4 *__restrict__ rays, uint32_t n, uint32_t follow,
+                                                        uint32_t max_chain, float4 *__restrict__ out) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2u * (size_t)i], rd = rays[2u * (size_t)i + 1u];
+    Ray r;
+    r.o = mk(ro.x, ro.y, ro.z);
+    r.d = mk(rd.x, rd.y, rd.z);
+    const V3 d0 = r.d;
+    float4 *o = out + 5 * (size_t)i;
+    float t_sum = 0.0f;
+    uint32_t len = 0u, sig = 0u;
+    for (uint32_t k = 0u; k <= max_chain; k++) {   // (pt_features_chain's loop)
+        Nearest nb;
+        hit_primitives<false, ACCEL>(c, r, nb);
+        hit_models<false, ACCEL>(c, r, nb);
+        Hit h;
+        if (!hit_finish<false>(c, r, nb, h)) break;
+        int type;
+        float extra;
+        V3 col;
+        load_material(c, h.mat, type, extra, col);
+        t_sum = k == 0u ? nb.t : t_sum + nb.t;
+        const bool followed = (type == RT_REFLECTIVE && (follow & RT_FOLLOW_REFLECTIVE)) ||
+                              (type == RT_REFRACTIVE && (follow & RT_FOLLOW_REFRACTIVE)) ||
+                              (type == RT_DIELECTRIC && (follow & RT_FOLLOW_DIELECTRIC));
+        if (followed && len < max_chain) {
+            sig = pt::chain_signature_step(sig, nb.id);
+            len++;
+            Rnd none;  // mirror / glass by rayRefract's rule: no random numbers
+            none.v = mk(0.0f, 0.0f, 0.0f);
+            none.u = 0.0f;
+            V3 path = mk(1.0f, 1.0f, 1.0f);   // (the path colour is not needed)
+            scatter<false>(c, r, path, h, type == RT_DIELECTRIC ? RT_REFRACTIVE : type, extra, col, none);
+            continue;
+        }
+        if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
+        const bool mesh = (nb.id & K_MASK) == K_MESH;
+        const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
+        o[0] = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
+        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
+        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
+        o[3] = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
+        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
+        return;
+    }
+    // the chain left the scene
     const float none = __uint_as_float(0xFFFFFFFFu);
     o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
     o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
@@ -2044,6 +2206,72 @@ int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], u
     return RT_OK;
 }
 
+// ---- caller-supplied rays (rt_render_rays): the camera launch with a ray buffer in place of the camera blocks ---------------
+// The facts are camera_facts with n = the slots (= rays) of the range and the plan is plan_camera_samples' — one planner, the
+// same sizing rules; the rows are camera_queue_kernel's five, in the ray form of the kernel text.
+static QueueKernel ray_queue_kernel(const CameraPlan &p) {
+    struct Row { uint32_t accel, geom, waves; QueueKernel k; };
+    static const Row rows[] = {
+        {0u, 0u, PT_Q_WAVES, pt_samples_q_rays<false, 0, PT_Q_WAVES>},
+        {0u, 1u, PT_Q_WAVES, pt_samples_q_rays<false, 1, PT_Q_WAVES>},
+        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q_rays<true, 0, PT_Q_WAVES_SPHERE_BVH>},
+        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 1, PT_Q_WAVES_ACCEL>},
+        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 2, PT_Q_WAVES_ACCEL>}};
+    for (const Row &r : rows)
+        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k;
+    return nullptr;
+}
+typedef void (*RayRenderKernel)(DeviceScene, FrameParams, float4 *, unsigned long long *);
+static RayRenderKernel ray_render_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
+    static const RayRenderKernel k[2][2] = {{pt_render_rays<false, false>, pt_render_rays<false, true>},
+                                            {pt_render_rays<true, false>, pt_render_rays<true, true>}};
+    return k[count][accel];
+}
+
+// One launch of a ray call: samples first .. first+count-1 of rays 0 .. n-1 at d_rays, the sums added to accum[i] (and
+// m2[i]).  The event pair, the slot ranges (RT_OPT_MAX_THREADS_PER_LAUNCH) and the staged scene block as launch_cameras has
+// them; the frame parameters carry the context's frame, of which the ray kernels read nothing but what queue_sums
+// multiplies by the row 0.  Nothing here reads or writes the slot buffers or the prefix cache.
+int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                float *m2) {
+    if (!d_rays || !accum || n < 1u || n > (1u << 28) || count < 1u || count > RT_SPP_PER_LAUNCH)
+        return fail(ctx, RT_EINVAL, "a ray launch takes 1 .. 2^28 rays and 1 .. %u samples", RT_SPP_PER_LAUNCH);
+    const float cam0[12] = {};
+    FrameParams fp = frame_params(ctx, cam0, first, count, glog2, 0, 1);   // (unsharded: slot = ray index)
+    fp.m2 = m2;
+    fp.rays = reinterpret_cast<const float4 *>(d_rays);
+    const DeviceScene sc = device_scene(ctx);
+    const uint32_t slots = (uint32_t)n;
+    refresh_stage_block(ctx, sc);
+    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
+    hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
+    HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
+    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
+        fp.slot_begin = b;
+        fp.slot_end = slots - b > slots_per_launch ? b + slots_per_launch : slots;
+        const CameraFacts facts = camera_facts(ctx, sc, fp);
+        const CameraPlan plan = plan_camera_samples(facts);
+        fp.lds_face_f4 = plan.lds_face_f4;
+        if (plan.family == RT_CAMERA_PLAN_QUEUE) {
+            const QueueKernel kernel = ray_queue_kernel(plan);
+            if (!kernel) return fail(ctx, RT_ESTATE, "no ray instantiation of pt_samples_q for the plan");
+            hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
+                               (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,
+                               plan.pixels_per_wave);
+        } else {
+            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u), dim3(plan.grid_units), dim3(plan.block_size), 0,
+                               ctx->stream, sc, fp, accum, ctx->counters.p);
+        }
+        ctx->rays.last_facts = facts;
+        ctx->rays.last_plan = plan;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
+    ctx->ev_count++;
+    return RT_OK;
+}
+
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
 // hitTriangle's unit normal, normalize(cross(edge1, edge2)) (raytracer.cl:285), depends on the face only: it is kept
 // in the face records (A, e1, e2, n).  Policy 0 computes it on the host (rt_amd.hip build_face_records: plain IEEE
@@ -2138,6 +2366,17 @@ int ks_launch_features_cameras(rt_context *ctx, FrameParams fp, const DeviceScen
     return RT_OK;
 }
 
+// rt_render_features_rays: pt_features_rays, one record per ray (n = the frame's pixels) into d_out
+int ks_launch_features_rays(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow, uint32_t max_chain,
+                            rt_feature *d_out) {
+    if (!d_rays || n < 1u) return fail(ctx, RT_EINVAL, "a feature launch over rays needs a ray buffer");
+    float4 *o = reinterpret_cast<float4 *>(d_out);
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features_rays<true> : pt_features_rays<false>, dim3((n + 255u) / 256u), dim3(256), 0,
+                       ctx->stream, sc, reinterpret_cast<const float4 *>(d_rays), n, follow, max_chain, o);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -2204,7 +2443,7 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays};
 
 }  // namespace
 

@@ -72,6 +72,14 @@ struct KernelSet {
                                    uint32_t follow, uint32_t max_chain, rt_feature *d_out, uint2 *d_cov);
     // rt_debug_plan_feature_cameras: that launcher's geometry for a frame of `pixels` pixels — a pure function, no device
     FeatureCamerasPlan (*plan_feature_cameras)(uint32_t pixels, uint32_t n);
+    // rt_render_rays: samples first .. first+count-1 (count <= RT_SPP_PER_LAUNCH) of the n <= 2^28 rays at d_rays (rt_ray
+    // records on the device), ray i's sum added to accum[i] (updating m2[i]; NULL = no moments): the sample queue's ray
+    // entry, or pt_render_rays where plan_camera_samples says fixed lanes; facts and plan go to rt_context::Rays
+    int (*launch_rays)(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                       float *m2);
+    // rt_render_features_rays: pt_features_rays, pt_features_chain's record for each of the n rays at d_rays into d_out
+    int (*launch_features_rays)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow,
+                                uint32_t max_chain, rt_feature *d_out);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

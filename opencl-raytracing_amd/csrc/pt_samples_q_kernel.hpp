@@ -2,15 +2,26 @@
 // FORM of the kernel, inside the policy's namespace, with PT_Q_LOOKAHEAD_FORM defined:
 //   0  pt_samples_q<COUNT, ACCEL, GEOM, WAVES, MOMENTS, COUNT_LOG2, CAM>, every instantiation there was
 //   1  pt_samples_q_la<GEOM, WAVES>: the look-ahead form of the camera entry's ACCEL rows (CAM_LA; see pt_kernels.hip)
-// No include guard: it is meant to be read twice.
-#if PT_Q_LOOKAHEAD_FORM
+//   2  pt_samples_q_rays<ACCEL, GEOM, WAVES>: the camera entry fed from a ray buffer (RAYS; rt_render_rays) — the slots ARE
+//      the ray indices, the staged record holds the ray itself, and a refill gathers no camera block and normalises nothing
+// No include guard: it is meant to be read once per form.
+#if PT_Q_LOOKAHEAD_FORM == 2
+template <bool ACCEL, int GEOM, int WAVES>
+__global__ __launch_bounds__(64, WAVES) void pt_samples_q_rays(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
+                                                         const uint32_t *__restrict__ live,
+                                                         const uint32_t *__restrict__ live_count,
+                                                         float4 *__restrict__ accum, unsigned long long *counters,
+                                                         uint32_t pixels_per_wave) {
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true;
+    constexpr int COUNT_LOG2 = -1;
+#elif PT_Q_LOOKAHEAD_FORM == 1
 template <int GEOM, int WAVES>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q_la(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                        const uint32_t *__restrict__ live,
                                                        const uint32_t *__restrict__ live_count,
                                                        float4 *__restrict__ accum, unsigned long long *counters,
                                                        uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true;
+    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true, RAYS = false;
     constexpr int COUNT_LOG2 = -1;
 #else
 template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1, bool CAM = false>
@@ -19,7 +30,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                                                     const uint32_t *__restrict__ live_count,
                                                     float4 *__restrict__ accum, unsigned long long *counters,
                                                     uint32_t pixels_per_wave) {
-    constexpr bool CAM_LA = false;
+    constexpr bool CAM_LA = false, RAYS = false;
 #endif
     extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
     // The tagged forms of sqrt and normalize (pt_arith.hpp) and the sphere scan that compares inside the root block
@@ -27,7 +38,9 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     // every other instantiation of this one, keeps the untagged code.
     constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
     // The presence of the staged tables by count (pt_device.hpp has_materials): the instantiations that copy the staged block, in every policy.
-    constexpr bool BY_COUNT = PT_TABLES_BY_COUNT && !COUNT && !ACCEL;
+    // (the ray form was written after that A/B was settled: it takes the settled form whatever the switch says, so the
+    // switch keeps changing exactly the instantiations it changed — tests/test_loop_terms_host.py)
+    constexpr bool BY_COUNT = (PT_TABLES_BY_COUNT || RAYS) && !COUNT && !ACCEL;
     // The table gathers by use (pt_device.hpp fetch_rnd_by_use): a lane reads randomVec's entry at a diffuse or textured vertex,
     // random's at a dielectric one, nothing at a mirror or a refractive one.  The same family, without the camera rows and
     // without meshes: GEOM 1 sits on its budget of 80 VGPRs and spills under policy 0 with the gathers in branches of their
@@ -42,7 +55,12 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     uint32_t cam_x = 0, cam_y = 0;   // CAM: the pixel of this lane's slot, if the wave owns it
     bool cam_owns = false;
     unsigned long long cam_owners = 0;
-    if (CAM) {
+    if (RAYS) {   // (slot = ray index: no tiles, no mask; cam_x carries it)
+        cam_x = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
+        cam_owns = threadIdx.x < pixels_per_wave && cam_x < fp.slot_end;
+        cam_owners = __ballot(cam_owns);
+        npix = (uint32_t)__popcll(cam_owners);
+    } else if (CAM) {
         const uint32_t slot = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
         cam_owns = threadIdx.x < pixels_per_wave && slot < fp.slot_end && slot_to_pixel(fp, slot, cam_x, cam_y) && pixel_active(fp, cam_x, cam_y);
         cam_owners = __ballot(cam_owns);
@@ -65,7 +83,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+    const WaveQueue q = RAYS ? queue_stage_rays(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+                      : CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                             : queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
     uint32_t next = 0;  // wave-uniform head of the queue
@@ -99,7 +118,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             if (CAM) {
                 if (need && cand < q.total) {
                     idx = cand;
-                    const CameraEntry e = queue_fetch_cam(q, fp, idx);
+                    const CameraEntry e = RAYS ? queue_fetch_rays(q, fp, idx) : queue_fetch_cam(q, fp, idx);
                     bv = e.bv;
                     bu = e.bu;
                     depth = 0u;
@@ -236,7 +255,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     static_assert(!CAM_LA || (CAM && ACCEL), "the look-ahead kernels of the camera entry's ACCEL rows");
     // (wave-uniform: a look-ahead launch; never a counting one, never with moments; of the camera rows those without a BVH walk)
     constexpr bool LA_BRANCH = CAM ? !ACCEL : !COUNT && !MOMENTS;
-    if (CAM_LA || (LA_BRANCH && fp.la_ring)) queue_replay<CAM>(q, fp);
+    if (CAM_LA || (!RAYS && LA_BRANCH && fp.la_ring)) queue_replay<CAM>(q, fp);   // (a ray launch is never a look-ahead launch)
     else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }

@@ -185,10 +185,14 @@ struct FrameParams {
     // ring keeps its size, frame-major only.  (Appended as a field of its own
     // it changed the scalar loads of the kernels that read m2 next to it: policy 0's pt_samples_q<true, true, 0, 6, true>
     // went from 14 to 44 spilled VGPRs.)
+    // Caller-supplied rays (rt_render_rays): the launch's ray buffer, two float4 per rt_ray — (o.xyz, x bits), (d.xyz, y bits)
+    // — shares the same eight bytes for the same reason: a ray launch (pt_samples_q_rays, pt_render_rays) reads neither
+    // la_image nor cams, is never a look-ahead launch, and no other kernel reads `rays`.
     float4 *la_ring;
     union {
         const float4 *la_image;
         const float *cams;
+        const float4 *rays;
     };
     // per-pixel sample moments (RT_OPT_MOMENTS; NULL = off): W x H floats beside the accumulator the launch adds to, the
     // centred second moment of each pixel's sample luminances (pt_moments.hpp).  Read in the kernels' epilogues only

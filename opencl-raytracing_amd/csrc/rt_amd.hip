@@ -916,6 +916,80 @@ int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_
     return RT_OK;
 }
 
+// ---- caller-supplied rays ------------------------------------------------------------------------------------------------
+static_assert(sizeof(rt_ray) == 32 && alignof(rt_ray) == 16, "an rt_ray is two float4: (o, x bits), (d, y bits)");
+
+int rt_upload_rays(rt_context *ctx, const rt_ray *host, size_t n) {
+    if (!ctx) return RT_EINVAL;
+    if (!host || n == 0 || n > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "rt_upload_rays takes 1 .. %u rays", RT_MAX_RAYS);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rt_context::Rays &ry = ctx->rays;
+    if (n > ry.buf.n) {   // grow: a new array first, so that a failed allocation leaves the old rays as they were
+        DevBuf<rt_ray> grown;
+        if (grown.alloc(n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_EHIP, "no device memory for %zu rays", n);
+        }
+        ry.buf = std::move(grown);   // (the old array is freed here: hipFree waits for the launches that read it)
+        ry.count = 0;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ry.buf.p, host, n * sizeof(rt_ray), hipMemcpyHostToDevice, ctx->stream));
+    ry.count = n;
+    return RT_OK;
+}
+
+int rt_device_rays(rt_context *ctx, void **d_rays, size_t *n) {
+    if (!ctx || !d_rays || !n) return RT_EINVAL;
+    *d_rays = ctx->rays.count ? ctx->rays.buf.p : nullptr;
+    *n = ctx->rays.count;
+    return RT_OK;
+}
+
+extern "C++" {
+namespace {
+const float k_no_camera[12] = {};   // a ray call has no camera block: check_ready's other rules apply
+// the ray buffer of a ray call: the caller's, or the uploaded rays (at least n_rays of them); NULL + a recorded RT_EINVAL
+const void *ray_source(rt_context *ctx, const void *d_rays, size_t n_rays) {
+    if (d_rays) {
+        if ((uintptr_t)d_rays % alignof(rt_ray)) { (void)fail(ctx, RT_EINVAL, "d_rays is not 16-byte aligned"); return nullptr; }
+        return d_rays;
+    }
+    if (ctx->rays.count < n_rays) {
+        (void)fail(ctx, RT_EINVAL, "%zu rays asked for, %zu uploaded (rt_upload_rays)", n_rays, ctx->rays.count);
+        return nullptr;
+    }
+    return ctx->rays.buf.p;
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_render_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t first_sample, uint32_t n_samples, void *d_accum) {
+    int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "rays on a sharded context (rank %d of %d): shard the batch instead", ctx->rank, ctx->world);
+    if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "rt_render_rays takes 1 .. %u rays", RT_MAX_RAYS);
+    if (n_samples && (uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
+        return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
+    if (!d_accum && n_rays != (size_t)ctx->width * ctx->height)
+        return fail(ctx, RT_EINVAL, "%zu rays into the accumulator of a %d x %d frame", n_rays, ctx->width, ctx->height);
+    if (d_accum && (uintptr_t)d_accum % sizeof(float4)) return fail(ctx, RT_EINVAL, "d_accum is not 16-byte aligned");
+    const void *rays = ray_source(ctx, d_rays, n_rays);
+    if (!rays) return RT_EINVAL;
+    if (n_samples == 0) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float4 *accum = d_accum ? static_cast<float4 *>(d_accum) : ctx->accum.p;
+    // (launches of RT_SPP_PER_LAUNCH samples, as rt_render_spp cuts its calls: the target holds the sum of their sums)
+    for (uint32_t done = 0; done < n_samples;) {
+        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
+        rc = ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum,
+                                  d_accum ? nullptr : ctx->moments.target());
+        if (rc != RT_OK) return rc;
+        done += c;
+        if (!d_accum) ctx->accum_count += c;
+    }
+    return RT_OK;
+}
+
 int rt_render_again_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras) {
     if (!ctx) return RT_EINVAL;
     if (!cameras) return fail(ctx, RT_EINVAL, "camera table is NULL");
@@ -1273,6 +1347,24 @@ int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_f
     else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
     return render_features_with(ctx, camera, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
         return ctx->ks->launch_features_chain(ctx, fp, sc, p->follow, p->max_chain, out);
+    });
+}
+
+int rt_render_features_rays(rt_context *ctx, const void *d_rays, size_t n_rays, const rt_feature_chain_params *p) {
+    const int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    const rt_feature_chain_params first_hits = {0u, 0u};
+    if (!p) p = &first_hits;
+    int ok = RT_OK;
+    const void *rays = nullptr;
+    if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
+        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
+    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    else if (n_rays != (size_t)ctx->width * ctx->height)
+        ok = fail(ctx, RT_EINVAL, "%zu rays for the feature records of a %d x %d frame", n_rays, ctx->width, ctx->height);
+    else if (!(rays = ray_source(ctx, d_rays, n_rays))) ok = RT_EINVAL;
+    return render_features_with(ctx, k_no_camera, ok, [&](const FrameParams &, const DeviceScene &sc, rt_feature *out) {
+        return ctx->ks->launch_features_rays(ctx, sc, rays, (uint32_t)n_rays, p->follow, p->max_chain, out);
     });
 }
 
@@ -1706,6 +1798,14 @@ int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_ca
     if (ctx->cameras.last_plan.block_size == 0) return fail(ctx, RT_EINVAL, "no camera launch yet");
     *facts_out = ctx->cameras.last_facts;
     *plan_out = ctx->cameras.last_plan;
+    return RT_OK;
+}
+
+int rt_debug_last_ray_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out) {
+    if (!ctx || !facts_out || !plan_out) return RT_EINVAL;
+    if (ctx->rays.last_plan.block_size == 0) return fail(ctx, RT_EINVAL, "no ray launch yet");
+    *facts_out = ctx->rays.last_facts;
+    *plan_out = ctx->rays.last_plan;
     return RT_OK;
 }
 

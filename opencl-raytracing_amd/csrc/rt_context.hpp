@@ -306,6 +306,18 @@ struct rt_context {
         rt_camera_plan last_plan = {};
     } cameras;
 
+    // Caller-supplied rays (rt_upload_rays, rt_render_rays): the context's own ray buffer — `count` rays uploaded, room for
+    // buf.n; grown on demand (the old array is freed by DevBuf, which waits for the device), never touched by alloc_frame or
+    // rt_set_scene: rays belong to neither a frame size nor a scene — freed with the context.
+    struct Rays {
+        DevBuf<rt_ray> buf;
+        size_t count = 0;
+        // what the last ray launch was chosen from and what was chosen (plan_camera_samples with n = the range's rays);
+        // block_size 0: no launch yet (rt_debug_last_ray_plan)
+        rt_camera_facts last_facts = {};
+        rt_camera_plan last_plan = {};
+    } rays;
+
     int rank = 0, world = 1, tile_w_log2 = 3, tile_h_log2 = 3;
     uint32_t max_threads_per_launch = 1u << 30;
 };

@@ -40,6 +40,7 @@ SYMBOLS = (
     "rt_render_features_cameras", "rt_read_feature_coverage", "rt_device_feature_coverage", "rt_debug_plan_feature_cameras",
     "rt_render_adaptive_cameras", "rt_render_again_cameras",
     "rt_render_adaptive_variance", "rt_render_adaptive_variance_cameras", "rt_read_pixel_error", "rt_device_pixel_error",
+    "rt_upload_rays", "rt_device_rays", "rt_render_rays", "rt_render_features_rays", "rt_debug_last_ray_plan",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -136,6 +137,7 @@ def load_library(path=LIB_PATH):
     _abi.sample_grid_prototypes(lib)
     _abi.queue_sums_prototypes(lib)
     _abi.camera_prototypes(lib)
+    _abi.ray_prototypes(lib)
     if lib.rt_abi_version() != _abi.RT_ABI_VERSION:
         raise OSError("librt_amd.so ABI %d != expected %d" % (lib.rt_abi_version(), _abi.RT_ABI_VERSION))
     _lib = lib
@@ -428,6 +430,65 @@ class RayTracer:
         """(facts, plan) dicts of the last renderSamplesCameras launch (rt_debug_last_camera_plan)."""
         f, p = _abi.CameraFacts(), _abi.CameraPlan()
         self._check(self._lib.rt_debug_last_camera_plan(self._ctx, C.byref(f), C.byref(p)))
+        return f.as_dict(), p.as_dict()
+
+    # -- caller-supplied rays ---------------------------------------------------------------
+    def uploadRays(self, rays):
+        """Copies a host batch of rays — an _abi.RAY array (rays.pack_rays and the generators of rays.py make them), or
+        (n, 8) float32 holding the same bits — into the context's own ray buffer (rt_upload_rays); renderRays(None, ...)
+        and renderFeaturesRays(None) then trace them.  → n."""
+        rays = np.asarray(rays)
+        if rays.dtype == _abi.RAY:
+            rays = np.ascontiguousarray(rays).reshape(-1)
+        elif rays.dtype == np.float32 and rays.ndim == 2 and rays.shape[1] == 8:
+            rays = np.ascontiguousarray(rays)
+        else:
+            raise ValueError("rays must be an _abi.RAY array or (n, 8) float32")
+        n = len(rays)
+        self._check(self._lib.rt_upload_rays(self._ctx, rays.ctypes.data if n else None, n))
+        return n
+
+    def deviceRays(self):
+        """(device address, count) of the uploaded rays (rt_device_rays)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.rt_device_rays(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, int(n.value)
+
+    def _ray_args(self, rays):
+        """→ (device pointer or None, n, what must stay alive until the call has been enqueued)"""
+        if rays is None:
+            return None, self.deviceRays()[1], None
+        if isinstance(rays, np.ndarray):
+            return None, self.uploadRays(rays), None
+        n = _abi.check_rays(rays)
+        return C.c_void_p(rays.data_ptr()), n, rays
+
+    def renderRays(self, rays, first_sample, n_samples, out=None):
+        """Samples first..first+n-1 of every ray of the batch (rt_render_rays, asynchronous on the context's stream).
+        `rays`: a torch device tensor (n, 8) float32 holding rt_ray bits, read in place; None: the uploaded rays; a
+        numpy batch is uploaded first.  `out`: a torch device tensor (n, 4) float32 the sums and counts are ADDED to, in
+        place; None: the accumulator (n == w * h, ray i = pixel i), after which resolve, the denoisers and the moments
+        work as for a camera frame.  Work queued on another stream that writes `rays` / `out` is the caller's to order."""
+        ptr, n, _keep = self._ray_args(rays)
+        target = None
+        if out is not None:
+            _abi.check_ray_target(out, n)
+            target = C.c_void_p(out.data_ptr())
+        self._check(self._lib.rt_render_rays(self._ctx, ptr, n, int(first_sample), int(n_samples), target))
+
+    def renderFeaturesRays(self, rays, follow=0, max_chain=0):
+        """Feature records for a w * h batch of rays, ray i = pixel i (rt_render_features_rays, asynchronous): what
+        renderFeaturesChain writes for a camera with these primary rays (follow 0: first hits).  `rays` as renderRays.
+        Replaces the feature records: the denoisers then work on a frame made by renderRays."""
+        ptr, n, _keep = self._ray_args(rays)
+        p = _abi.FeatureChainParams(int(follow), int(max_chain))
+        self._check(self._lib.rt_render_features_rays(self._ctx, ptr, n, C.byref(p)))
+
+    def lastRayPlan(self):
+        """(facts, plan) dicts of the last renderRays launch (rt_debug_last_ray_plan): the camera planner's, with
+        n = the rays of the launch's last range."""
+        f, p = _abi.CameraFacts(), _abi.CameraPlan()
+        self._check(self._lib.rt_debug_last_ray_plan(self._ctx, C.byref(f), C.byref(p)))
         return f.as_dict(), p.as_dict()
 
     def resolve(self):
