@@ -130,3 +130,17 @@ std::vector<float> Camera::sampleBlocks(uint32_t n, uint32_t first_sample, int w
     }
     return out;
 }
+
+std::vector<float> Camera::sampleOffsets(uint32_t n, uint32_t first_sample) {
+    std::vector<float> out((size_t)n * 4);
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t i = first_sample + j + 1u;
+        const float rad = std::sqrt((float)radicalInverse(5, i));
+        const float phi = 6.28318530717958647692f * (float)radicalInverse(7, i);
+        out[(size_t)j * 4] = (float)radicalInverse(2, i) - 0.5f;
+        out[(size_t)j * 4 + 1] = (float)radicalInverse(3, i) - 0.5f;
+        out[(size_t)j * 4 + 2] = rad * std::cos(phi);
+        out[(size_t)j * 4 + 3] = rad * std::sin(phi);
+    }
+    return out;
+}

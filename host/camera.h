@@ -50,6 +50,9 @@ public:
     // every block is transferData().  The same arithmetic as camera.py's sampleBlocks, bit for bit.
     std::vector<float> sampleBlocks(uint32_t n, uint32_t first_sample, int width, int height, bool pixel_jitter = true,
                                     float aperture = 0.0f, float focus = 1.0f) const;
+    // n x 4 floats: (dx, dy, lx, ly) of sampleBlocks for samples first_sample .. first_sample + n - 1 (camera.py's
+    // sampleOffsets): the pixel offsets and lens points of rays::ray_sets
+    static std::vector<float> sampleOffsets(uint32_t n, uint32_t first_sample = 0);
     // van der Corput radical inverse of `index` in `base`
     static double radicalInverse(uint32_t base, uint32_t index);
 };

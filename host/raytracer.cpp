@@ -97,6 +97,18 @@ const float *RayTracer::renderFrameRays(const std::vector<rt_ray> &batch, uint32
     return transferImage();
 }
 
+void RayTracer::renderRaySets(uint32_t set_size, uint32_t first_sample, uint32_t n_samples) {
+    check(rt_render_ray_sets(ctx, nullptr, (size_t)width * height, set_size, first_sample, n_samples, nullptr));
+}
+
+const float *RayTracer::renderFrameRaySets(const std::vector<rt_ray> &sets, uint32_t set_size, uint32_t spp) {
+    uploadRays(sets);
+    check(rt_clear(ctx));
+    renderRaySets(set_size, 0, spp);
+    check(rt_resolve(ctx));
+    return transferImage();
+}
+
 void RayTracer::renderAgainCameras(const std::vector<float> &blocks) {
     check(rt_render_again_cameras(ctx, blocks.data(), (uint32_t)(blocks.size() / 12)));
 }

@@ -75,6 +75,10 @@ public:
     void renderRays(uint32_t first_sample, uint32_t n_samples);
     void renderFeaturesRays(uint32_t follow = 0, uint32_t max_chain = 0);
     const float *renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp);  // upload + clear + renderRays + resolve + read back
+    // ray sets (rt_render_ray_sets; rays::ray_sets makes them): the uploaded records are w x h sets of set_size records,
+    // ray-major, and sample s of pixel i starts at record s mod set_size of its set — anti-aliasing for any projection
+    void renderRaySets(uint32_t set_size, uint32_t first_sample, uint32_t n_samples);
+    const float *renderFrameRaySets(const std::vector<rt_ray> &sets, uint32_t set_size, uint32_t spp);  // upload + clear + renderRaySets + resolve + read back
     // adaptive frame (rt_render_adaptive) + read back like renderFrame; the image is then transferImage()'s
     rt_adaptive_stats renderAdaptive(const Camera *camera, const rt_adaptive_params &params);
     // the same through per-sample camera blocks (rt_render_adaptive_cameras): sample j of every pixel through block j of

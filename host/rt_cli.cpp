@@ -10,13 +10,16 @@
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
 //          [--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--progressive-cameras [--lookahead N]]
-//          [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E]]
+//          [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K]]
 // --projection renders --spp samples through caller-supplied rays instead of the pinhole camera (host/rays.h →
 // rt_upload_rays + rt_render_rays into the accumulator): an equirectangular panorama about --camera's position and yaw, an
 // equidistant fisheye of --fov-deg degrees (default 180) or an orthographic view --extent world units wide (default 10)
 // along --camera's direction.  It goes with --spp, --denoise (plain or --variance-guided, with or without --follow), --aov
 // and the image outputs — the guides then come from rt_render_features_rays — and is refused with every other way to spend
 // the samples (--progressive, --adaptive, --aa, --aperture, ...) and with --measured.
+// --ray-sets K (1 .. RT_RAY_SET_MAX, only with --projection) anti-aliases such a frame: K records per pixel, jittered inside
+// the pixel by the Halton points of Camera::sampleOffsets(K) (rays::ray_sets), sample s through record s mod K
+// (rt_render_ray_sets); the guides of --denoise / --aov still come from the central rays.
 // --aa jitters every sample's primary rays inside their pixels (Halton points, Camera::sampleBlocks) and --aperture R
 // --focus D looks through a thin lens of radius R focused at distance D along the view direction: one camera block per
 // sample, traced by rt_render_spp_cameras.  Both go with --spp (the fused path) and are refused with --progressive and
@@ -91,7 +94,7 @@ static void usage() {
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E]]\n";
+                 "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K]]\n";
     std::exit(2);
 }
 
@@ -189,6 +192,7 @@ int main(int argc, char **argv) {
     std::string projection;
     float fov_deg = 180.0f, extent = 10.0f;
     bool fov_deg_given = false, extent_given = false;
+    long ray_set = 0;   // (0: one record per pixel)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -269,6 +273,7 @@ int main(int argc, char **argv) {
             if (!*v || *end || !(extent > 0.0f) || !std::isfinite(extent)) usage();
             extent_given = true;
         }
+        else if ((v = val("--ray-sets"))) ray_set = parse_int(v, 1, RT_RAY_SET_MAX);
         else if ((v = val("--aa-guides"))) aa_guides = parse_int(v, 1, RT_FEATURE_CAMERAS_MAX);
         else if (a == "--aa") aa = true;
         else if (a == "--denoise") denoise = true;
@@ -303,6 +308,7 @@ int main(int argc, char **argv) {
     const bool rays_frame = !projection.empty();
     if (rays_frame && (cameras || progressive || progressive_cameras || adaptive || adaptive_cameras || measured)) usage();   // one way to spend the samples
     if (fov_deg_given && projection != "fisheye") usage();
+    if (ray_set && !rays_frame) usage();   // ray sets belong to a projection (--aa is the pinhole camera's)
     if (extent_given && projection != "ortho") usage();
     if (!dn_iterations) dn_iterations = 5;
     if (adaptive || adaptive_cameras) {
@@ -372,10 +378,17 @@ int main(int argc, char **argv) {
         img = tracer.transferImage();
     } else if (rays_frame) {
         const float pos[3] = {cam[0], cam[1], cam[2]};
-        img = tracer.renderFrameRays(projection == "equirect" ? rays::equirect(pos, w, h, cam[3])
-                                     : projection == "fisheye" ? rays::fisheye(pos, w, h, fov_deg, cam[3], cam[4])
-                                                               : rays::orthographic(pos, w, h, extent, cam[3], cam[4]),
-                                     (uint32_t)spp);
+        auto generate = [&](rays::Offset off) {
+            return projection == "equirect" ? rays::equirect(pos, w, h, cam[3], off)
+                   : projection == "fisheye" ? rays::fisheye(pos, w, h, fov_deg, cam[3], cam[4], off)
+                                             : rays::orthographic(pos, w, h, extent, cam[3], cam[4], off);
+        };
+        if (ray_set) {
+            img = tracer.renderFrameRaySets(rays::ray_sets(generate, Camera::sampleOffsets((uint32_t)ray_set)), (uint32_t)ray_set, (uint32_t)spp);
+            if (denoise || !aov_prefix.empty()) tracer.uploadRays(generate(rays::Offset{}));   // the guides' central rays
+        } else {
+            img = tracer.renderFrameRays(generate(rays::Offset{}), (uint32_t)spp);
+        }
     } else if (cameras) {
         img = tracer.renderFrameCameras(camera.sampleBlocks((uint32_t)spp, 0, w, h, aa, aperture, focus));
     } else {
@@ -389,7 +402,7 @@ int main(int argc, char **argv) {
                   << " ms incl. read-back" << std::endl;
         if (!out_counts.empty()) write_counts(out_counts, tracer.sampleCounts(), w, h);
     } else {
-        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : progressive_cameras ? "progressive per-sample cameras" : rays_frame ? "caller-supplied rays" : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
+        std::cout << w << "x" << h << " " << spp << " spp " << (progressive ? "progressive" : progressive_cameras ? "progressive per-sample cameras" : rays_frame ? (ray_set ? "caller-supplied ray sets" : "caller-supplied rays") : cameras ? "per-sample cameras" : "fused") << ": " << sec * 1e3
                   << " ms incl. read-back, " << (double)w * h * spp / sec / 1e6 << " Msamples/s" << std::endl;
     }
 

@@ -361,6 +361,36 @@ int rt_device_rays(rt_context *ctx, void **d_rays, size_t *n);
 int rt_render_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t first_sample, uint32_t n_samples, void *d_accum);
 
 /*
+ * Ray sets (new): anti-aliasing and depth of field for caller-supplied rays — rt_render_rays with a SET of set_size records
+ * per ray instead of one, so that every sample of a ray can have its own origin and direction (a jittered panorama, a lens
+ * in front of a fisheye), as rt_render_spp_cameras gives every sample of a pinhole frame its own camera block.
+ * d_rays: n_rays x set_size rt_ray records on the device, 16-byte aligned and RAY-MAJOR: the set of ray i is records
+ * i*set_size .. i*set_size + set_size-1, and sample s (the absolute sample index) of ray i starts at record
+ * i*set_size + (s mod set_size) — rt_render_again_cameras' cyclic rule, under which a call cut into launches needs no offset.
+ * (Ray-major because the lanes of a queue refill hold consecutive samples of one ray: they read one contiguous stretch of
+ * 32-byte records; sample-major they would stand n_rays * 32 bytes apart.)
+ *   - Sample s of ray i is, bit for bit under the selected arithmetic policy, the radiance rt_render_rays traces for that
+ *     single record at sample s: the record's own origin, its own direction used as given, its own (x, y) random-stream ids.
+ *     Every record is a full rt_ray.
+ *   - The samples of a ray are summed in rt_render_spp's fixed order and ADDED to d_accum[i], the count to its 4th channel
+ *     (d_accum NULL: the context's accumulator, and then n_rays == W*H; rt_resolve, the three denoisers and RT_OPT_MOMENTS work
+ *     unchanged).  More than 512 samples run as launches of 512.  So set_size 1 is rt_render_rays bit for bit, a set of
+ *     identical records is too, and sets built from the primary rays of camera blocks are rt_render_spp_cameras of those blocks.
+ *   - d_rays NULL: the uploaded records (rt_upload_rays), of which there must be at least n_rays*set_size.
+ *   - Asynchronous on the context's stream.  The image, the sample counter, the feature records, a kept prefix and pending
+ *     look-ahead frames stay untouched.  Counters, RT_OPT_SAMPLE_QUEUE, RT_OPT_ACCEL, RT_OPT_WAVE_FILL,
+ *     RT_OPT_MAX_THREADS_PER_LAUNCH and RT_OPT_MOMENTS are honoured exactly as by rt_render_rays; none changes a bit.
+ *   - Record addresses are formed in 64 bits.  rt_debug_last_ray_plan also reports these launches.
+ *   - Memory: a record is 32 bytes, so 1080p x 16 records is 1.06 GB.  Calls add: a large sample count can be rendered in
+ *     chunks over one reused buffer (refill it between the calls, in stream order).
+ * RT_EINVAL: everything rt_render_rays refuses (a sharded context included), set_size 0 or above RT_RAY_SET_MAX,
+ * n_rays*set_size above 2^31.  RT_ESTATE: no scene set.  A failed call changes nothing.
+ */
+#define RT_RAY_SET_MAX 4096u
+int rt_render_ray_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, uint32_t first_sample,
+                       uint32_t n_samples, void *d_accum);
+
+/*
  * Progressive anti-aliasing (new): rt_render_again through a CYCLIC SCHEDULE of camera blocks.  `cameras` is a host pointer to
  * n_cameras x 12 floats, copied during the call; the call that makes sample s = sample_counter + 1 looks through block
  * s mod n_cameras (a caller who starts with rt_render(ctx, cameras) has sample 0 through block 0).
@@ -1017,8 +1047,8 @@ int rt_debug_plan_camera_samples(const rt_camera_facts *facts, rt_camera_plan *p
  * the first one. */
 int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 
-/* Test instrumentation: the facts (n = the rays of the range) and the plan of the context's last ray launch (rt_render_rays,
- * its last slot range) — rt_render_spp_cameras' planner, the one rt_debug_plan_camera_samples calls.  RT_EINVAL before the
+/* Test instrumentation: the facts (n = the rays of the range) and the plan of the context's last ray launch (rt_render_rays or
+ * rt_render_ray_sets, its last slot range) — rt_render_spp_cameras' planner, the one rt_debug_plan_camera_samples calls.  RT_EINVAL before the
  * first one. */
 int rt_debug_last_ray_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 

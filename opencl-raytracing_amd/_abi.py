@@ -314,6 +314,40 @@ def check_rays(t):
     return int(t.shape[0])
 
 
+RAY_SET_MAX = 4096          # RT_RAY_SET_MAX
+MAX_RAY_RECORDS = 1 << 31   # n_rays * set_size of one rt_render_ray_sets call
+
+
+def check_ray_sets(t, set_size):
+    """Ray sets as renderRaySets takes them on the device: a torch tensor of shape (n_rays * set_size, 8) or
+    (n_rays, set_size, 8), float32, contiguous, on a GPU, holding rt_ray bits ray-major (the set of ray i is records
+    i * set_size .. + set_size - 1).  Raises ValueError otherwise, before any library call; needs no device.  → n_rays."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    k = int(set_size)
+    if not 1 <= k <= RAY_SET_MAX:
+        raise ValueError("a ray set holds 1 .. %d records, not %d" % (RAY_SET_MAX, k))
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("ray sets must be a torch tensor on the device (upload a numpy batch with uploadRays)")
+    if t.dtype != torch.float32:
+        raise ValueError("ray sets must be float32 (rt_ray bits), not %s" % t.dtype)
+    if t.dim() == 3 and t.shape[1] == k and t.shape[2] == 8:
+        n = int(t.shape[0])
+    elif t.dim() == 2 and t.shape[1] == 8 and t.shape[0] % k == 0:
+        n = int(t.shape[0]) // k
+    else:
+        raise ValueError("ray sets of %d must have shape (n * %d, 8) or (n, %d, 8), not %s" % (k, k, k, tuple(t.shape)))
+    if n < 1 or n > MAX_RAYS or n * k > MAX_RAY_RECORDS:
+        raise ValueError("ray sets hold 1 .. 2^28 rays and at most 2^31 records, not %d x %d" % (n, k))
+    if not t.is_contiguous():
+        raise ValueError("ray sets must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError("ray sets must live on the device, not on %s" % t.device)
+    return n
+
+
 def check_ray_target(t, n):
     """The external target of renderRays: a torch (n, 4) float32 contiguous device tensor.  ValueError otherwise."""
     try:
@@ -334,6 +368,7 @@ def ray_prototypes(lib):
     lib.rt_upload_rays.argtypes = [vp, vp, sz]
     lib.rt_device_rays.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     lib.rt_render_rays.argtypes = [vp, vp, sz, u32, u32, vp]
+    lib.rt_render_ray_sets.argtypes = [vp, vp, sz, u32, u32, u32, vp]
     lib.rt_render_features_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams)]
     lib.rt_debug_last_ray_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
 

@@ -1034,6 +1034,62 @@ PT_DEV CameraEntry queue_fetch_rays(const WaveQueue &q, const FrameParams &fp, u
     return e;
 }
 
+// ---- the queue's entry FROM RAY SETS (pt_samples_q_raysets; rt_render_ray_sets) --------------------------------------------
+// The ray entry with a SET of set_size records per ray, ray-major: sample s of ray i starts at record i · set_size +
+// (s mod set_size) of fp.rays — its own origin, direction and random-stream ids.  Nothing of a ray can be staged once per
+// slot, so staging writes the ray index alone (queue_sums reads x and y, nothing else) and a refill loads its record from
+// global memory, as queue_fetch_cam gathers its block: the lanes of a refill hold consecutive samples of one ray, i.e. one
+// contiguous stretch of 32-byte records.  Unlike the camera table a record is read by one lane only — it comes from HBM.
+// The set size travels in fp.cam, of which a ray launch reads nothing else: cam[0] holds its bits, cam[1] its reciprocal
+// (the IEEE quotient 1 / set_size computed on the host, as inv_count is).
+PT_DEV WaveQueue queue_stage_raysets(const DeviceScene &sc, const FrameParams &fp, bool owns, uint32_t index,
+                                     unsigned long long owners, uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
+    float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
+    WaveQueue q;
+    q.rec = (LdsQueueF4)wave_lds;
+    q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
+    q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
+    q.npix = (uint32_t)__popcll(owners);
+    q.count = fp.count;
+    q.total = q.npix * q.count;
+    if (owns) {
+        const uint32_t k = lanes_below(owners);   // (< npix <= pixels_per_wave)
+        q.xy[k].x = index;
+        q.xy[k].y = 0u;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    q.inv_count = fp.inv_count;
+    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    return q;
+}
+// s mod set_size for s <= RT_MAX_SAMPLE and set_size <= RT_RAY_SET_MAX without an integer division: the quotient is
+// floor((s + 0.5) · (1 / set_size)) in float — s + 0.5 is exact, the true quotient (s + 0.5) / set_size stands at least
+// 0.5 / set_size from every integer, and the two roundings move the product by less than 2^-22 · 2^16 / set_size =
+// 0.016 / set_size.  (tests/test_ray_sets_host.py walks the whole domain.)
+PT_DEV uint32_t ray_set_member(const FrameParams &fp, uint32_t sample) {
+    const uint32_t set_size = __float_as_uint(fp.cam[0]);
+    return sample - (uint32_t)(((float)sample + 0.5f) * fp.cam[1]) * set_size;
+}
+// the two float4 of record `member` of ray `index`'s set; the record index stays below 2^31 and is formed in 64 bits
+PT_DEV const float4 *ray_set_record(const FrameParams &fp, uint32_t index, uint32_t member) {
+    return fp.rays + 2u * ((size_t)index * __float_as_uint(fp.cam[0]) + member);
+}
+// Queue entry idx → (ray p, sample first + j): the sample's own record, and both index sums in full from the record's ids.
+PT_DEV CameraEntry queue_fetch_raysets(const WaveQueue &q, const FrameParams &fp, uint32_t idx) {
+    // (p = idx / count as queue_fetch forms it)
+    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t sample = fp.first + (idx - p * q.count);
+    const float4 *rec = ray_set_record(fp, q.xy[p].x, ray_set_member(fp, sample));
+    const float4 ro = rec[0], rd = rec[1];   // (non-temporal loads were tried: no gain, profiles/r24_experiments.md)
+    CameraEntry e;
+    e.r.o = mk(ro.x, ro.y, ro.z);
+    e.r.d = mk(rd.x, rd.y, rd.z);
+    e.bv = rnd_base_v(sample, __float_as_uint(ro.w), __float_as_uint(rd.w));
+    e.bu = rnd_base_u(sample, __float_as_uint(ro.w), __float_as_uint(rd.w));
+    return e;
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
@@ -1064,6 +1120,54 @@ PT_DEV CameraEntry queue_fetch_rays(const WaveQueue &q, const FrameParams &fp, u
 #define PT_Q_LOOKAHEAD_FORM 2
 #include "pt_samples_q_kernel.hpp"
 #undef PT_Q_LOOKAHEAD_FORM
+// … and a fourth time as pt_samples_q_raysets<ACCEL, GEOM, WAVES>, the ray form with a set of records per ray
+// (rt_render_ray_sets; queue_stage_raysets above).
+#define PT_Q_LOOKAHEAD_FORM 3
+#include "pt_samples_q_kernel.hpp"
+#undef PT_Q_LOOKAHEAD_FORM
+
+// Ray sets, fixed lanes (rt_render_ray_sets with counters on, RT_OPT_SAMPLE_QUEUE 0 or sample moments): pt_render_rays with
+// the record loaded INSIDE the sample loop — sample s of ray i starts at record s mod set_size of the ray's set.  A sibling
+// kernel, so that pt_render_rays keeps its name and its code.
+template <bool COUNT, bool ACCEL>
+__global__ __launch_bounds__(256) void pt_render_raysets(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
+                                                         unsigned long long *counters) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    LaneCounters cn;
+    if (COUNT) zero_counters(cn);
+    Ctx c{sc, stage_materials(sc, s_mat), &cn};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t g = 1u << fp.group_log2;
+    const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
+    const uint32_t lane = tid & (g - 1u);
+    const bool valid = index < fp.slot_end;
+
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const bool mom = fp.m2 != nullptr;   // (uniform)
+    LaneMoments lm{0.0f, 0.0f};
+    if (valid) {
+        for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
+            if (COUNT) cn.c[CN_SAMPLES]++;
+            const float4 *rec = ray_set_record(fp, index, ray_set_member(fp, s));
+            const float4 ro = rec[0], rd = rec[1];
+            Ray r0;
+            r0.o = mk(ro.x, ro.y, ro.z);
+            r0.d = mk(rd.x, rd.y, rd.z);
+            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, __float_as_uint(ro.w), __float_as_uint(rd.w));
+            if (mom) moments_fold(lm, sum, rad);
+            sum = sum + rad;
+        }
+    }
+    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
+    if (valid && lane == 0) {
+        if (mom) moments_update(accum, fp.m2, (size_t)index, sum, fp.count, lm.m2);
+        accumulate(accum, (size_t)index, sum, fp.count);
+    }
+    flush_counters<COUNT>(cn, counters, 1);
+}
 
 // The context's staged scene block (rt_context::StageBlock): stage_materials' tables by stage_materials' loops, compiled
 // in this translation unit — the divisions are the policy's.  One workgroup.
@@ -2209,34 +2313,47 @@ int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], u
 // ---- caller-supplied rays (rt_render_rays): the camera launch with a ray buffer in place of the camera blocks ---------------
 // The facts are camera_facts with n = the slots (= rays) of the range and the plan is plan_camera_samples' — one planner, the
 // same sizing rules; the rows are camera_queue_kernel's five, in the ray form of the kernel text.
-static QueueKernel ray_queue_kernel(const CameraPlan &p) {
-    struct Row { uint32_t accel, geom, waves; QueueKernel k; };
+// (sets: the rows of pt_samples_q_raysets, rt_render_ray_sets)
+static QueueKernel ray_queue_kernel(const CameraPlan &p, bool sets) {
+    struct Row { uint32_t accel, geom, waves; QueueKernel k, k_sets; };
     static const Row rows[] = {
-        {0u, 0u, PT_Q_WAVES, pt_samples_q_rays<false, 0, PT_Q_WAVES>},
-        {0u, 1u, PT_Q_WAVES, pt_samples_q_rays<false, 1, PT_Q_WAVES>},
-        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q_rays<true, 0, PT_Q_WAVES_SPHERE_BVH>},
-        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 1, PT_Q_WAVES_ACCEL>},
-        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 2, PT_Q_WAVES_ACCEL>}};
+        {0u, 0u, PT_Q_WAVES, pt_samples_q_rays<false, 0, PT_Q_WAVES>, pt_samples_q_raysets<false, 0, PT_Q_WAVES>},
+        {0u, 1u, PT_Q_WAVES, pt_samples_q_rays<false, 1, PT_Q_WAVES>, pt_samples_q_raysets<false, 1, PT_Q_WAVES>},
+        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q_rays<true, 0, PT_Q_WAVES_SPHERE_BVH>, pt_samples_q_raysets<true, 0, PT_Q_WAVES_SPHERE_BVH>},
+        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 1, PT_Q_WAVES_ACCEL>, pt_samples_q_raysets<true, 1, PT_Q_WAVES_ACCEL>},
+        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 2, PT_Q_WAVES_ACCEL>, pt_samples_q_raysets<true, 2, PT_Q_WAVES_ACCEL>}};
     for (const Row &r : rows)
-        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k;
+        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return sets ? r.k_sets : r.k;
     return nullptr;
 }
 typedef void (*RayRenderKernel)(DeviceScene, FrameParams, float4 *, unsigned long long *);
-static RayRenderKernel ray_render_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
+static RayRenderKernel ray_render_kernel(bool count, bool accel, bool sets) {   // [COUNT][ACCEL]
     static const RayRenderKernel k[2][2] = {{pt_render_rays<false, false>, pt_render_rays<false, true>},
                                             {pt_render_rays<true, false>, pt_render_rays<true, true>}};
-    return k[count][accel];
+    static const RayRenderKernel k_sets[2][2] = {{pt_render_raysets<false, false>, pt_render_raysets<false, true>},
+                                                 {pt_render_raysets<true, false>, pt_render_raysets<true, true>}};
+    return sets ? k_sets[count][accel] : k[count][accel];
 }
 
 // One launch of a ray call: samples first .. first+count-1 of rays 0 .. n-1 at d_rays, the sums added to accum[i] (and
 // m2[i]).  The event pair, the slot ranges (RT_OPT_MAX_THREADS_PER_LAUNCH) and the staged scene block as launch_cameras has
 // them; the frame parameters carry the context's frame, of which the ray kernels read nothing but what queue_sums
 // multiplies by the row 0.  Nothing here reads or writes the slot buffers or the prefix cache.
-int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                float *m2) {
+// set_size 0: one record per ray (rt_render_rays).  1 .. RT_RAY_SET_MAX: d_rays holds n sets of that many records, ray-major
+// (rt_render_ray_sets), and the launch runs the sets form of the same rows; the set size and its reciprocal travel in the
+// camera block's first two words (queue_stage_raysets).
+static int launch_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count,
+                               uint32_t glog2, float4 *accum, float *m2) {
     if (!d_rays || !accum || n < 1u || n > (1u << 28) || count < 1u || count > RT_SPP_PER_LAUNCH)
         return fail(ctx, RT_EINVAL, "a ray launch takes 1 .. 2^28 rays and 1 .. %u samples", RT_SPP_PER_LAUNCH);
-    const float cam0[12] = {};
+    if (set_size > RT_RAY_SET_MAX || (uint64_t)n * set_size > (1ull << 31))
+        return fail(ctx, RT_EINVAL, "a ray-set launch takes sets of 1 .. %u records, 2^31 records in all", RT_RAY_SET_MAX);
+    const bool sets = set_size != 0u;
+    float cam0[12] = {};
+    if (sets) {
+        memcpy(&cam0[0], &set_size, sizeof(uint32_t));
+        cam0[1] = 1.0f / (float)set_size;
+    }
     FrameParams fp = frame_params(ctx, cam0, first, count, glog2, 0, 1);   // (unsharded: slot = ray index)
     fp.m2 = m2;
     fp.rays = reinterpret_cast<const float4 *>(d_rays);
@@ -2254,13 +2371,13 @@ int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, u
         const CameraPlan plan = plan_camera_samples(facts);
         fp.lds_face_f4 = plan.lds_face_f4;
         if (plan.family == RT_CAMERA_PLAN_QUEUE) {
-            const QueueKernel kernel = ray_queue_kernel(plan);
+            const QueueKernel kernel = ray_queue_kernel(plan, sets);
             if (!kernel) return fail(ctx, RT_ESTATE, "no ray instantiation of pt_samples_q for the plan");
             hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
                                (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,
                                plan.pixels_per_wave);
         } else {
-            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u), dim3(plan.grid_units), dim3(plan.block_size), 0,
+            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u, sets), dim3(plan.grid_units), dim3(plan.block_size), 0,
                                ctx->stream, sc, fp, accum, ctx->counters.p);
         }
         ctx->rays.last_facts = facts;
@@ -2270,6 +2387,15 @@ int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, u
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
     ctx->ev_count++;
     return RT_OK;
+}
+int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                float *m2) {
+    return launch_rays_or_sets(ctx, d_rays, n, 0u, first, count, glog2, accum, m2);
+}
+int launch_ray_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
+                    float4 *accum, float *m2) {
+    if (set_size < 1u) return fail(ctx, RT_EINVAL, "a ray set holds at least one record");
+    return launch_rays_or_sets(ctx, d_rays, n, set_size, first, count, glog2, accum, m2);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
@@ -2443,7 +2569,7 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, launch_ray_sets};
 
 }  // namespace
 

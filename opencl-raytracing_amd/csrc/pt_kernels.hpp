@@ -80,6 +80,10 @@ struct KernelSet {
     // rt_render_features_rays: pt_features_rays, pt_features_chain's record for each of the n rays at d_rays into d_out
     int (*launch_features_rays)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow,
                                 uint32_t max_chain, rt_feature *d_out);
+    // rt_render_ray_sets: launch_rays with n sets of set_size (1 .. RT_RAY_SET_MAX) records at d_rays, ray-major; sample s of
+    // ray i starts at record i * set_size + s % set_size: pt_samples_q_raysets, or pt_render_raysets for fixed lanes
+    int (*launch_ray_sets)(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count,
+                           uint32_t glog2, float4 *accum, float *m2);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

@@ -4,15 +4,26 @@
 //   1  pt_samples_q_la<GEOM, WAVES>: the look-ahead form of the camera entry's ACCEL rows (CAM_LA; see pt_kernels.hip)
 //   2  pt_samples_q_rays<ACCEL, GEOM, WAVES>: the camera entry fed from a ray buffer (RAYS; rt_render_rays) — the slots ARE
 //      the ray indices, the staged record holds the ray itself, and a refill gathers no camera block and normalises nothing
+//   3  pt_samples_q_raysets<ACCEL, GEOM, WAVES>: the ray form with a SET of records per ray (SETS; rt_render_ray_sets) —
+//      nothing of a ray is staged but its index, and a refill loads the record of its own sample from global memory
 // No include guard: it is meant to be read once per form.
-#if PT_Q_LOOKAHEAD_FORM == 2
+#if PT_Q_LOOKAHEAD_FORM == 3
+template <bool ACCEL, int GEOM, int WAVES>
+__global__ __launch_bounds__(64, WAVES) void pt_samples_q_raysets(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
+                                                            const uint32_t *__restrict__ live,
+                                                            const uint32_t *__restrict__ live_count,
+                                                            float4 *__restrict__ accum, unsigned long long *counters,
+                                                            uint32_t pixels_per_wave) {
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = true;
+    constexpr int COUNT_LOG2 = -1;
+#elif PT_Q_LOOKAHEAD_FORM == 2
 template <bool ACCEL, int GEOM, int WAVES>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q_rays(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                          const uint32_t *__restrict__ live,
                                                          const uint32_t *__restrict__ live_count,
                                                          float4 *__restrict__ accum, unsigned long long *counters,
                                                          uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true;
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = false;
     constexpr int COUNT_LOG2 = -1;
 #elif PT_Q_LOOKAHEAD_FORM == 1
 template <int GEOM, int WAVES>
@@ -21,7 +32,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q_la(DeviceScene sc, Fra
                                                        const uint32_t *__restrict__ live_count,
                                                        float4 *__restrict__ accum, unsigned long long *counters,
                                                        uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true, RAYS = false;
+    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true, RAYS = false, SETS = false;
     constexpr int COUNT_LOG2 = -1;
 #else
 template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1, bool CAM = false>
@@ -30,7 +41,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                                                     const uint32_t *__restrict__ live_count,
                                                     float4 *__restrict__ accum, unsigned long long *counters,
                                                     uint32_t pixels_per_wave) {
-    constexpr bool CAM_LA = false, RAYS = false;
+    constexpr bool CAM_LA = false, RAYS = false, SETS = false;
 #endif
     extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
     // The tagged forms of sqrt and normalize (pt_arith.hpp) and the sphere scan that compares inside the root block
@@ -83,7 +94,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = RAYS ? queue_stage_rays(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+    const WaveQueue q = SETS ? queue_stage_raysets(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+                      : RAYS ? queue_stage_rays(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                       : CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                             : queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
 
@@ -118,7 +130,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             if (CAM) {
                 if (need && cand < q.total) {
                     idx = cand;
-                    const CameraEntry e = RAYS ? queue_fetch_rays(q, fp, idx) : queue_fetch_cam(q, fp, idx);
+                    const CameraEntry e = SETS ? queue_fetch_raysets(q, fp, idx) : RAYS ? queue_fetch_rays(q, fp, idx) : queue_fetch_cam(q, fp, idx);
                     bv = e.bv;
                     bu = e.bu;
                     depth = 0u;

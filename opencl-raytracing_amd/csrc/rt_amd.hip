@@ -963,31 +963,51 @@ const void *ray_source(rt_context *ctx, const void *d_rays, size_t n_rays) {
 }  // namespace
 }  // extern "C++"
 
-int rt_render_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t first_sample, uint32_t n_samples, void *d_accum) {
+extern "C++" {
+namespace {
+// rt_render_rays (set_size 0) and rt_render_ray_sets (set_size 1 .. RT_RAY_SET_MAX): one set of checks, one launch loop
+int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, bool sets, uint32_t first_sample,
+                        uint32_t n_samples, void *d_accum) {
     int rc = check_ready(ctx, k_no_camera);
     if (rc) return rc;
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "rays on a sharded context (rank %d of %d): shard the batch instead", ctx->rank, ctx->world);
-    if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "rt_render_rays takes 1 .. %u rays", RT_MAX_RAYS);
+    if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "%s takes 1 .. %u rays", sets ? "rt_render_ray_sets" : "rt_render_rays", RT_MAX_RAYS);
+    if (sets && (set_size == 0 || set_size > RT_RAY_SET_MAX)) return fail(ctx, RT_EINVAL, "a ray set holds 1 .. %u records, not %u", RT_RAY_SET_MAX, set_size);
+    const size_t records = sets ? n_rays * set_size : n_rays;   // (<= 2^28 * 2^12: no overflow)
+    if (records > ((size_t)1 << 31)) return fail(ctx, RT_EINVAL, "%zu rays x %u records exceed 2^31 records", n_rays, set_size);
     if (n_samples && (uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
         return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
     if (!d_accum && n_rays != (size_t)ctx->width * ctx->height)
         return fail(ctx, RT_EINVAL, "%zu rays into the accumulator of a %d x %d frame", n_rays, ctx->width, ctx->height);
     if (d_accum && (uintptr_t)d_accum % sizeof(float4)) return fail(ctx, RT_EINVAL, "d_accum is not 16-byte aligned");
-    const void *rays = ray_source(ctx, d_rays, n_rays);
+    const void *rays = ray_source(ctx, d_rays, records);
     if (!rays) return RT_EINVAL;
     if (n_samples == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float4 *accum = d_accum ? static_cast<float4 *>(d_accum) : ctx->accum.p;
-    // (launches of RT_SPP_PER_LAUNCH samples, as rt_render_spp cuts its calls: the target holds the sum of their sums)
+    // (launches of RT_SPP_PER_LAUNCH samples, as rt_render_spp cuts its calls: the target holds the sum of their sums; a set
+    // is indexed by the absolute sample, so a later launch needs no offset into it)
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        rc = ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum,
-                                  d_accum ? nullptr : ctx->moments.target());
+        float *m2 = d_accum ? nullptr : ctx->moments.target();
+        rc = sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first_sample + done, c, group_log2_for(c), accum, m2)
+                  : ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum, m2);
         if (rc != RT_OK) return rc;
         done += c;
         if (!d_accum) ctx->accum_count += c;
     }
     return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_render_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t first_sample, uint32_t n_samples, void *d_accum) {
+    return render_rays_or_sets(ctx, d_rays, n_rays, 0u, false, first_sample, n_samples, d_accum);
+}
+
+int rt_render_ray_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, uint32_t first_sample,
+                       uint32_t n_samples, void *d_accum) {
+    return render_rays_or_sets(ctx, d_rays, n_rays, set_size, true, first_sample, n_samples, d_accum);
 }
 
 int rt_render_again_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras) {

@@ -41,6 +41,7 @@ SYMBOLS = (
     "rt_render_adaptive_cameras", "rt_render_again_cameras",
     "rt_render_adaptive_variance", "rt_render_adaptive_variance_cameras", "rt_read_pixel_error", "rt_device_pixel_error",
     "rt_upload_rays", "rt_device_rays", "rt_render_rays", "rt_render_features_rays", "rt_debug_last_ray_plan",
+    "rt_render_ray_sets",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -476,6 +477,35 @@ class RayTracer:
             target = C.c_void_p(out.data_ptr())
         self._check(self._lib.rt_render_rays(self._ctx, ptr, n, int(first_sample), int(n_samples), target))
 
+    def renderRaySets(self, rays, set_size, first_sample, n_samples, out=None):
+        """Samples first..first+n-1 of every ray through its SET of set_size records (rt_render_ray_sets, asynchronous):
+        sample s of ray i starts at record s mod set_size of ray i's set — anti-aliasing and depth of field for any
+        projection (rays.ray_sets, rays.thin_lens make the sets).  `rays`: a torch device tensor (n_rays * set_size, 8) or
+        (n_rays, set_size, 8) float32 holding rt_ray bits ray-major, read in place; None: the uploaded records; a numpy
+        batch ((n_rays, set_size) _abi.RAY, or float32 of the shapes above) is uploaded first.  `out` as renderRays: an
+        (n_rays, 4) device tensor the sums and counts are ADDED to, None: the accumulator (n_rays == w * h)."""
+        k = int(set_size)
+        if not 1 <= k <= _abi.RAY_SET_MAX:
+            raise ValueError("a ray set holds 1 .. %d records, not %d" % (_abi.RAY_SET_MAX, k))
+        if rays is None or isinstance(rays, np.ndarray):
+            if rays is None:
+                records = self.deviceRays()[1]
+            else:
+                if rays.dtype != _abi.RAY:
+                    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+                records = self.uploadRays(rays)
+            if records == 0 or records % k:
+                raise ValueError("%d uploaded records are not whole sets of %d" % (records, k))
+            ptr, n, _keep = None, records // k, None
+        else:
+            n = _abi.check_ray_sets(rays, k)
+            ptr, _keep = C.c_void_p(rays.data_ptr()), rays
+        target = None
+        if out is not None:
+            _abi.check_ray_target(out, n)
+            target = C.c_void_p(out.data_ptr())
+        self._check(self._lib.rt_render_ray_sets(self._ctx, ptr, n, k, int(first_sample), int(n_samples), target))
+
     def renderFeaturesRays(self, rays, follow=0, max_chain=0):
         """Feature records for a w * h batch of rays, ray i = pixel i (rt_render_features_rays, asynchronous): what
         renderFeaturesChain writes for a camera with these primary rays (follow 0: first hits).  `rays` as renderRays.
@@ -485,7 +515,7 @@ class RayTracer:
         self._check(self._lib.rt_render_features_rays(self._ctx, ptr, n, C.byref(p)))
 
     def lastRayPlan(self):
-        """(facts, plan) dicts of the last renderRays launch (rt_debug_last_ray_plan): the camera planner's, with
+        """(facts, plan) dicts of the last renderRays / renderRaySets launch (rt_debug_last_ray_plan): the camera planner's, with
         n = the rays of the launch's last range."""
         f, p = _abi.CameraFacts(), _abi.CameraPlan()
         self._check(self._lib.rt_debug_last_ray_plan(self._ctx, C.byref(f), C.byref(p)))

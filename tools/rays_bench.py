@@ -11,7 +11,19 @@ configurations alternating inside every round; median and (min .. max) per confi
 --pano SCENE: an equirectangular --pano-size frame of SCENE at --spp through rt_render_rays — the new capability's own figure.
 On a checkout without rt_render_rays only `cameras` and `fused` are measured (the parent's side of the comparison).
 
+--sets K: ray sets (rt_render_ray_sets; DESIGN.md §5 "Ray sets") instead — the pinhole's own rays through --spp jittered
+camera blocks (Camera.sampleBlocks, pixel jitter only; directions formed on the device in float32, their last bits do not
+matter to a timing), everything into the accumulator:
+    loop     (A) what a caller writes without ray sets: --spp single-sample rt_render_rays calls over --spp sample-major
+             batches, batch j = every pixel's ray through block j
+    sets     (B) one rt_render_ray_sets call, set_size K (block j mod K at sample j)
+    sets16   (B') the same call with set_size 16 (only if K > 16)
+    rays     (C) rt_render_rays with the unjittered rays: what anti-aliasing costs
+    cameras  (D) rt_render_spp_cameras with the jittered blocks
+On a checkout without rt_render_ray_sets `loop`, `rays` and `cameras` are measured (the parent's side).
+
     python tools/rays_bench.py [--scenes c2,c5] [--size 1920x1080] [--spp 64] [--rounds 5] [--policy 2] [--pano c2] [--pano-size 2048x1024] [--json out.json]
+    python tools/rays_bench.py --sets 64 [--scenes c2,c5] [--size 1920x1080] [--spp 64] [--rounds 5] [--policy 2] [--json out.json]
 """
 import argparse
 import json
@@ -47,6 +59,67 @@ def stats(ms):
     return {k: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v))) for k, v in ms.items()}
 
 
+def device_rays(block, w, h):
+    """the pinhole block's primary rays as an (w * h, 8) float32 device tensor of rt_ray bits, ids = pixel coordinates"""
+    import torch
+    cam = torch.as_tensor(np.asarray(block, np.float32), device="cuda")
+    ys, xs = torch.meshgrid(torch.arange(h, device="cuda"), torch.arange(w, device="cuda"), indexing="ij")
+    s, t = (xs.reshape(-1).float() / w)[:, None], (ys.reshape(-1).float() / h)[:, None]
+    d = cam[3:6][None, :] + s * cam[6:9][None, :] + t * cam[9:12][None, :]
+    d = d / d.norm(dim=1, keepdim=True)
+    out = torch.empty((w * h, 8), dtype=torch.float32, device="cuda")
+    out[:, 0:3], out[:, 4:7] = cam[0:3][None, :], d
+    out[:, 3] = xs.reshape(-1).int().view(torch.float32)
+    out[:, 7] = ys.reshape(-1).int().view(torch.float32)
+    return out
+
+
+def bench_sets(a, result):
+    import torch
+    T = rt.RayTracer
+    have_sets = hasattr(T, "renderRaySets")
+    w, h = (int(v) for v in a.size.split("x"))
+    n, k = a.spp, a.sets
+    result.update(have_sets=have_sets, set_size=k)
+    for name in [s for s in a.scenes.split(",") if s]:
+        wl = rt.workloads.get(name, width=w, height=h)
+        t = T(w, h, scene=wl.scene, seed=rt.workloads.SEED)
+        t.setArith(a.policy)
+        stream = torch.cuda.Stream()
+        t.setStream(stream.cuda_stream)
+        pos, yaw, pitch = a.camera[name]
+        cam = rt.Camera(60, np.float32(w) / np.float32(h), pos, yaw, pitch)
+        assert np.array_equal(cam.transferData(), wl.camera), "the workload's camera"
+        blocks = cam.sampleBlocks(n, width=w, height=h)
+        batches = [device_rays(blocks[j % k], w, h) for j in range(n)]          # sample-major: batch j for sample j
+        central = device_rays(wl.camera, w, h)
+        torch.cuda.synchronize()
+
+        def loop():
+            for j in range(n):
+                t.renderRays(batches[j], j, 1)
+        configs = [("loop", loop), ("rays", lambda: t.renderRays(central, 0, n)), ("cameras", lambda: t.renderSamplesCameras(blocks, 0))]
+        if have_sets:
+            sets = torch.stack(batches[:k], dim=1).contiguous()                  # (w * h, k, 8): ray-major
+            configs.insert(1, ("sets", lambda: t.renderRaySets(sets, k, 0, n)))
+            if k > 16:
+                sets16 = sets[:, :16].contiguous()
+                configs.insert(2, ("sets16", lambda: t.renderRaySets(sets16, 16, 0, n)))
+            torch.cuda.synchronize()
+        row = stats(timed(t, stream, configs, a.rounds))
+        if have_sets:
+            row["plan"] = t.lastRayPlan()[1]
+        result["scenes"][name] = row
+        print("%s %dx%d, %d samples, sets of %d, policy %d, %d rounds (ms: median, min .. max)" % (name, w, h, n, k, a.policy, a.rounds))
+        for c, _ in configs:
+            print("  %-8s %8.3f  (%.3f .. %.3f)" % (c, row[c]["median"], row[c]["min"], row[c]["max"]))
+        if have_sets:
+            print("  sets / loop %.4f, sets / rays %.4f, sets / cameras %.4f" % tuple(row["sets"]["median"] / row[c]["median"]
+                                                                                   for c in ("loop", "rays", "cameras")), flush=True)
+        t.close()
+        del batches, central
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="c2,c5")
@@ -57,7 +130,19 @@ def main():
     ap.add_argument("--pano", default="c2")
     ap.add_argument("--pano-size", default="2048x1024")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--sets", type=int, default=0)
     a = ap.parse_args()
+    if a.sets:
+        # the workloads' cameras (workloads.py): a Camera object makes the jittered blocks
+        a.camera = {"c1": ((0, 0, 0), 0.0, 0.0), "c2": ((-8, -1, -8), 45.0, 0.0), "c3": ((-6, -2, -7), 40.0, 8.0),
+                    "c4": ((-8, -1, -8), 45.0, 0.0), "c5": ((-7, 0, -7), 45.0, 8.0), "all_kinds": ((-8, -1, -8), 45.0, 0.0)}
+        w, h = (int(v) for v in a.size.split("x"))
+        result = {"size": [w, h], "spp": a.spp, "policy": a.policy, "rounds": a.rounds, "scenes": {}}
+        bench_sets(a, result)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(result, f, indent=1)
+        return
     import torch
     T = rt.RayTracer
     have_rays = hasattr(T, "renderRays")
