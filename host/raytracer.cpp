@@ -148,6 +148,20 @@ rt_adaptive_stats RayTracer::renderAdaptiveVarianceCameras(const std::vector<flo
     return st;
 }
 
+rt_adaptive_stats RayTracer::renderAdaptiveRays(uint32_t set_size, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive_rays(ctx, nullptr, (size_t)width * height, set_size, &params, &st));
+    transferImage();
+    return st;
+}
+
+rt_adaptive_stats RayTracer::renderAdaptiveVarianceRays(uint32_t set_size, const rt_adaptive_params &params) {
+    rt_adaptive_stats st{};
+    check(rt_render_adaptive_variance_rays(ctx, nullptr, (size_t)width * height, set_size, &params, &st));
+    transferImage();
+    return st;
+}
+
 std::vector<float> RayTracer::pixelError() {
     std::vector<float> e((size_t)width * height);
     check(rt_read_pixel_error(ctx, e.data(), e.size() * sizeof(float)));

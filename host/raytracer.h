@@ -88,6 +88,11 @@ public:
     // first; pixelError() reads the W x H standard errors the rule decided on
     rt_adaptive_stats renderAdaptiveVariance(const Camera *camera, const rt_adaptive_params &params);
     rt_adaptive_stats renderAdaptiveVarianceCameras(const std::vector<float> &blocks, const rt_adaptive_params &params);
+    // adaptive frames of caller-supplied rays (rt_render_adaptive_rays, rt_render_adaptive_variance_rays): the uploaded
+    // records are w x h rays (set_size 0) or w x h ray-major sets of set_size records, sample s along record s mod set_size;
+    // rounds, stopping rules and stats are those of renderAdaptive / renderAdaptiveVariance (setMoments(true) first)
+    rt_adaptive_stats renderAdaptiveRays(uint32_t set_size, const rt_adaptive_params &params);
+    rt_adaptive_stats renderAdaptiveVarianceRays(uint32_t set_size, const rt_adaptive_params &params);
     std::vector<float> pixelError();
     std::vector<uint32_t> sampleCounts();  // per-pixel sample counts, row-major
     const float *lastImage() const { return pixels.data(); }  // what the last read-back returned

@@ -10,13 +10,18 @@
 //          [--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N]
 //          [--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]]
 //          [--progressive-cameras [--lookahead N]]
-//          [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K]]
+//          [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K] [--adaptive THRESHOLD ...]]
 // --projection renders --spp samples through caller-supplied rays instead of the pinhole camera (host/rays.h →
 // rt_upload_rays + rt_render_rays into the accumulator): an equirectangular panorama about --camera's position and yaw, an
 // equidistant fisheye of --fov-deg degrees (default 180) or an orthographic view --extent world units wide (default 10)
 // along --camera's direction.  It goes with --spp, --denoise (plain or --variance-guided, with or without --follow), --aov
 // and the image outputs — the guides then come from rt_render_features_rays — and is refused with every other way to spend
-// the samples (--progressive, --adaptive, --aa, --aperture, ...) and with --measured.
+// the samples (--progressive, --aa, --aperture, --adaptive-cameras, ...).
+// --projection P [--ray-sets K] --adaptive THRESHOLD renders such a frame adaptively (rt_render_adaptive_rays; with
+// --adaptive-rule variance rt_render_adaptive_variance_rays): --adaptive's rounds, --batch, --min-spp, --spp (the maximum,
+// default 1024) and --counts over the frame's rays, with --ray-sets K sample s through record s mod K; --aov writes
+// PREFIX_error.pfm under the variance rule as for the pinhole, and --denoise --variance-guided --measured filters on the
+// moments the rule measured.
 // --ray-sets K (1 .. RT_RAY_SET_MAX, only with --projection) anti-aliases such a frame: K records per pixel, jittered inside
 // the pixel by the Halton points of Camera::sampleOffsets(K) (rays::ray_sets), sample s through record s mod K
 // (rt_render_ray_sets); the guides of --denoise / --aov still come from the central rays.
@@ -94,7 +99,8 @@ static void usage() {
                  "[--follow mirror,glass,dielectric [--max-chain N] [--split-chains]]] "
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
-                 "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K]]\n";
+                 "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K] "
+                 "[--adaptive THRESHOLD ...]]\n";
     std::exit(2);
 }
 
@@ -306,7 +312,7 @@ int main(int argc, char **argv) {
     if (cameras && spp > (long)RT_MAX_SAMPLE + 1) usage();
     if (aa_guides && (!cameras || (!denoise && aov_prefix.empty()))) usage();   // guides of a per-sample-camera frame, for --denoise / --aov
     const bool rays_frame = !projection.empty();
-    if (rays_frame && (cameras || progressive || progressive_cameras || adaptive || adaptive_cameras || measured)) usage();   // one way to spend the samples
+    if (rays_frame && (cameras || progressive || progressive_cameras || adaptive_cameras)) usage();   // one way to spend the samples
     if (fov_deg_given && projection != "fisheye") usage();
     if (ray_set && !rays_frame) usage();   // ray sets belong to a projection (--aa is the pinhole camera's)
     if (extent_given && projection != "ortho") usage();
@@ -356,7 +362,7 @@ int main(int argc, char **argv) {
     auto t0 = std::chrono::steady_clock::now();
     const float *img;
     rt_adaptive_stats st{};
-    if (adaptive) {
+    if (adaptive && !rays_frame) {
         rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
         st = rule_variance ? tracer.renderAdaptiveVariance(&camera, p) : tracer.renderAdaptive(&camera, p);
         img = tracer.lastImage();
@@ -383,7 +389,13 @@ int main(int argc, char **argv) {
                    : projection == "fisheye" ? rays::fisheye(pos, w, h, fov_deg, cam[3], cam[4], off)
                                              : rays::orthographic(pos, w, h, extent, cam[3], cam[4], off);
         };
-        if (ray_set) {
+        if (adaptive) {   // the frame's rays (or its sets of --ray-sets records) under --adaptive's rounds
+            rt_adaptive_params p{(uint32_t)batch, (uint32_t)min_spp, (uint32_t)spp, threshold, 8, 8};
+            tracer.uploadRays(ray_set ? rays::ray_sets(generate, Camera::sampleOffsets((uint32_t)ray_set)) : generate(rays::Offset{}));
+            st = rule_variance ? tracer.renderAdaptiveVarianceRays((uint32_t)ray_set, p) : tracer.renderAdaptiveRays((uint32_t)ray_set, p);
+            img = tracer.lastImage();
+            if (ray_set && (denoise || !aov_prefix.empty())) tracer.uploadRays(generate(rays::Offset{}));   // the guides' central rays
+        } else if (ray_set) {
             img = tracer.renderFrameRaySets(rays::ray_sets(generate, Camera::sampleOffsets((uint32_t)ray_set)), (uint32_t)ray_set, (uint32_t)spp);
             if (denoise || !aov_prefix.empty()) tracer.uploadRays(generate(rays::Offset{}));   // the guides' central rays
         } else {
@@ -396,7 +408,7 @@ int main(int argc, char **argv) {
     }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (adaptive || adaptive_cameras) {
-        std::cout << w << "x" << h << (adaptive_cameras ? " adaptive per-sample cameras threshold " : " adaptive threshold ") << threshold << (rule_variance ? " (variance rule)" : "") << " batch " << batch << " spp " << min_spp
+        std::cout << w << "x" << h << (adaptive_cameras ? " adaptive per-sample cameras threshold " : rays_frame ? (ray_set ? " adaptive caller-supplied ray sets threshold " : " adaptive caller-supplied rays threshold ") : " adaptive threshold ") << threshold << (rule_variance ? " (variance rule)" : "") << " batch " << batch << " spp " << min_spp
                   << ".." << spp << ": " << st.rounds << " rounds, mean " << (double)st.pixel_samples / ((double)w * h)
                   << " spp, " << st.blocks_at_max << " of " << st.blocks << " blocks at max, " << sec * 1e3
                   << " ms incl. read-back" << std::endl;

@@ -505,6 +505,38 @@ int rt_read_pixel_error(rt_context *ctx, float *err, size_t bytes);      /* W*H 
 int rt_device_pixel_error(rt_context *ctx, void **d_err);
 
 /*
+ * Adaptive sampling for caller-supplied rays (new): rt_render_adaptive and rt_render_adaptive_variance for frames made of
+ * rays — a panorama, a fisheye or orthographic view, a cube-map face, a bake.  d_rays has the meaning it has in
+ * rt_render_rays / rt_render_ray_sets: device memory, 16-byte aligned, or NULL for the uploaded records.  n_rays must equal
+ * W*H: ray i is pixel (i mod W, i div W), the target is the context's accumulator, and the decision blocks are the frame's
+ * block_w x block_h blocks exactly as for the camera calls.
+ *   set_size 0                    one record per ray: the rounds run rt_render_rays' kernels.
+ *   set_size 1 .. RT_RAY_SET_MAX  ray-major sets under rt_render_ray_sets' cyclic rule — sample s starts at record
+ *                                 s mod set_size, so set_size and max_spp need no relation: rt_render_ray_sets' kernels.
+ *   - Round k traces samples k*batch .. k*batch+c-1 of every pixel of a still-active block, and adds to it, bit for bit,
+ *     what rt_render_rays(d_rays, n_rays, k*batch, c, NULL) / rt_render_ray_sets(d_rays, n_rays, set_size, k*batch, c, NULL)
+ *     would add.  So a batch of a camera's own primary rays gives rt_render_adaptive's accumulator, counts, block errors,
+ *     image and stats bit for bit, and sets built from camera blocks 0 .. max_spp-1 with set_size == max_spp give
+ *     rt_render_adaptive_cameras'; the variance form equals its twins likewise, pixel errors included.
+ *   - Parameters, estimators, stopping rules, rt_adaptive_stats, rt_read_sample_counts, rt_read_block_error and — for the
+ *     variance form — rt_read_pixel_error / rt_device_pixel_error are those of the existing calls of the same rule.
+ *   - A self-contained clear + rounds + resolve: synchronous, unsharded contexts only; it starts the sample moments when
+ *     RT_OPT_MOMENTS is 1 and drops pending look-ahead frames.  The sample counter, the feature records, a kept prefix and
+ *     the uploaded rays stay as they are.
+ *   - Counters, RT_OPT_SAMPLE_QUEUE, RT_OPT_ACCEL, RT_OPT_WAVE_FILL and RT_OPT_MAX_THREADS_PER_LAUNCH are honoured as by
+ *     rt_render_rays, none changes a bit; with RT_OPT_MOMENTS 1 (always, for the variance form) the launches run the
+ *     fixed-lane ray kernels.  Only an owned ray of an active block is staged, traced, summed and counted.
+ *     rt_debug_last_ray_plan reports the last round; plan and grid are those of the unmasked launch.
+ * RT_EINVAL: what rt_render_adaptive refuses (a sharded context included) and what rt_render_rays / rt_render_ray_sets
+ * refuse — n_rays != W*H, a misaligned d_rays, NULL d_rays with fewer than n_rays (x set_size) records uploaded, set_size
+ * above RT_RAY_SET_MAX.  RT_ESTATE: no scene set; the variance form with RT_OPT_MOMENTS 0.  A failed call changes nothing.
+ */
+int rt_render_adaptive_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, const rt_adaptive_params *p,
+                            rt_adaptive_stats *out);
+int rt_render_adaptive_variance_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size,
+                                     const rt_adaptive_params *p, rt_adaptive_stats *out);
+
+/*
  * First-hit feature buffers (new; the reference has no such entry point).  One record per pixel of the frame,
  * row-major W x H in the layout of rt_read_image: the pixel's primary ray (no jitter, raytracer.cl:500-505, so one
  * first hit per pixel) through the same nearest-hit search and winner rebuild as the trace kernels, under the
@@ -1048,8 +1080,9 @@ int rt_debug_plan_camera_samples(const rt_camera_facts *facts, rt_camera_plan *p
 int rt_debug_last_camera_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 
 /* Test instrumentation: the facts (n = the rays of the range) and the plan of the context's last ray launch (rt_render_rays or
- * rt_render_ray_sets, its last slot range) — rt_render_spp_cameras' planner, the one rt_debug_plan_camera_samples calls.  RT_EINVAL before the
- * first one. */
+ * rt_render_ray_sets, its last slot range; after rt_render_adaptive_rays / ..._variance_rays the last round's — a masked launch
+ * has the plan and the grid of the unmasked one) — rt_render_spp_cameras' planner, the one rt_debug_plan_camera_samples calls.
+ * RT_EINVAL before the first one. */
 int rt_debug_last_ray_plan(rt_context *ctx, rt_camera_facts *facts_out, rt_camera_plan *plan_out);
 
 /* Test instrumentation: resident workgroups per compute unit the runtime reports for the headline sample-queue kernel

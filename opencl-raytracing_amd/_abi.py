@@ -348,6 +348,25 @@ def check_ray_sets(t, set_size):
     return n
 
 
+def check_adaptive_set_size(set_size):
+    """The set size of renderAdaptiveRays: 0 (one record per ray) or 1 .. RAY_SET_MAX.  ValueError otherwise.  → int."""
+    k = int(set_size)
+    if not 0 <= k <= RAY_SET_MAX:
+        raise ValueError("set_size is 0 (one record per ray) or 1 .. %d, not %d" % (RAY_SET_MAX, k))
+    return k
+
+
+def check_adaptive_rays(t, set_size, width, height):
+    """A device batch as renderAdaptiveRays takes it: check_rays' tensor (set_size 0) or check_ray_sets' (set_size 1 ..
+    RAY_SET_MAX) holding exactly one ray per pixel of the width x height frame.  Raises ValueError otherwise, before any
+    library call; needs no device.  → n_rays."""
+    k = check_adaptive_set_size(set_size)
+    n = check_ray_sets(t, k) if k else check_rays(t)
+    if n != int(width) * int(height):
+        raise ValueError("an adaptive frame takes one ray per pixel: %d rays for %d x %d" % (n, width, height))
+    return n
+
+
 def check_ray_target(t, n):
     """The external target of renderRays: a torch (n, 4) float32 contiguous device tensor.  ValueError otherwise."""
     try:
@@ -371,6 +390,8 @@ def ray_prototypes(lib):
     lib.rt_render_ray_sets.argtypes = [vp, vp, sz, u32, u32, u32, vp]
     lib.rt_render_features_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams)]
     lib.rt_debug_last_ray_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
+    lib.rt_render_adaptive_rays.argtypes = [vp, vp, sz, u32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_render_adaptive_variance_rays.argtypes = [vp, vp, sz, u32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
 
 
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)

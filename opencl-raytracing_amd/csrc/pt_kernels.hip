@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParam
     const uint32_t g = 1u << fp.group_log2;
     const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
     const uint32_t lane = tid & (g - 1u);
-    const bool valid = index < fp.slot_end;
+    const bool valid = index < fp.slot_end && ray_active(fp, index);   // (an adaptive round: the rays of active blocks only)
 
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     const bool mom = fp.m2 != nullptr;   // (uniform)
@@ -986,7 +986,7 @@ PT_DEV CameraEntry queue_fetch_cam(const WaveQueue &q, const FrameParams &fp, ui
 
 // ---- the queue's entry FROM A RAY BUFFER (pt_samples_q_rays; rt_render_rays) -----------------------------------------------
 // The camera entry with the primary ray given instead of formed: slot i of the launch's range IS ray i of fp.rays (no tiles,
-// no shard, no mask), a wave owns the slots below slot_end among its `pixels_per_wave` consecutive ones, and a ray's `count`
+// no shard; an adaptive round's mask is tested by ray_active at the kernel's entry), a wave owns the slots below slot_end among its `pixels_per_wave` consecutive ones, and a ray's `count`
 // samples are the queue entries of one "pixel".  The LDS layout is queue_stage's once more, so the sizing rules stay shared:
 //   coordinates   (x: the ray index, y: 0, rnd_base_v(0, ray.x, ray.y), rnd_base_u(0, ray.x, ray.y)) — queue_sums forms
 //                 y · fp.w + x = the ray index with its code unchanged, and the random stream is the one the ray names;
@@ -1143,7 +1143,7 @@ __global__ __launch_bounds__(256) void pt_render_raysets(DeviceScene sc, FramePa
     const uint32_t g = 1u << fp.group_log2;
     const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
     const uint32_t lane = tid & (g - 1u);
-    const bool valid = index < fp.slot_end;
+    const bool valid = index < fp.slot_end && ray_active(fp, index);   // (an adaptive round: the rays of active blocks only)
 
     V3 sum = mk(0.0f, 0.0f, 0.0f);
     const bool mom = fp.m2 != nullptr;   // (uniform)
@@ -2342,8 +2342,11 @@ static RayRenderKernel ray_render_kernel(bool count, bool accel, bool sets) {   
 // set_size 0: one record per ray (rt_render_rays).  1 .. RT_RAY_SET_MAX: d_rays holds n sets of that many records, ray-major
 // (rt_render_ray_sets), and the launch runs the sets form of the same rows; the set size and its reciprocal travel in the
 // camera block's first two words (queue_stage_raysets).
+// mask != NULL (rt_render_adaptive_rays): the launch has one ray per pixel of the frame, ray i being pixel (i mod W, i div W),
+// and only the rays of active decision blocks are staged and traced — the four ray families test ray_active where they take
+// ownership of a slot; the plan and the grid are those of the unmasked launch, as launch_cameras has it.
 static int launch_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count,
-                               uint32_t glog2, float4 *accum, float *m2) {
+                               uint32_t glog2, float4 *accum, const BlockMask *mask, float *m2) {
     if (!d_rays || !accum || n < 1u || n > (1u << 28) || count < 1u || count > RT_SPP_PER_LAUNCH)
         return fail(ctx, RT_EINVAL, "a ray launch takes 1 .. 2^28 rays and 1 .. %u samples", RT_SPP_PER_LAUNCH);
     if (set_size > RT_RAY_SET_MAX || (uint64_t)n * set_size > (1ull << 31))
@@ -2354,7 +2357,10 @@ static int launch_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n, ui
         memcpy(&cam0[0], &set_size, sizeof(uint32_t));
         cam0[1] = 1.0f / (float)set_size;
     }
+    if (mask && n != (size_t)ctx->width * ctx->height)   // (ray_active reads the block of pixel i: i must be one)
+        return fail(ctx, RT_EINVAL, "a masked ray launch takes one ray per pixel of the %d x %d frame", ctx->width, ctx->height);
     FrameParams fp = frame_params(ctx, cam0, first, count, glog2, 0, 1);   // (unsharded: slot = ray index)
+    apply_mask(fp, mask);
     fp.m2 = m2;
     fp.rays = reinterpret_cast<const float4 *>(d_rays);
     const DeviceScene sc = device_scene(ctx);
@@ -2389,13 +2395,13 @@ static int launch_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n, ui
     return RT_OK;
 }
 int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                float *m2) {
-    return launch_rays_or_sets(ctx, d_rays, n, 0u, first, count, glog2, accum, m2);
+                const BlockMask *mask, float *m2) {
+    return launch_rays_or_sets(ctx, d_rays, n, 0u, first, count, glog2, accum, mask, m2);
 }
 int launch_ray_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
-                    float4 *accum, float *m2) {
+                    float4 *accum, const BlockMask *mask, float *m2) {
     if (set_size < 1u) return fail(ctx, RT_EINVAL, "a ray set holds at least one record");
-    return launch_rays_or_sets(ctx, d_rays, n, set_size, first, count, glog2, accum, m2);
+    return launch_rays_or_sets(ctx, d_rays, n, set_size, first, count, glog2, accum, mask, m2);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------

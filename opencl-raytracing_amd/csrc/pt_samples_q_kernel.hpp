@@ -66,9 +66,9 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     uint32_t cam_x = 0, cam_y = 0;   // CAM: the pixel of this lane's slot, if the wave owns it
     bool cam_owns = false;
     unsigned long long cam_owners = 0;
-    if (RAYS) {   // (slot = ray index: no tiles, no mask; cam_x carries it)
+    if (RAYS) {   // (slot = ray index: no tiles; cam_x carries it.  An adaptive round's mask is tested here: ray_active)
         cam_x = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
-        cam_owns = threadIdx.x < pixels_per_wave && cam_x < fp.slot_end;
+        cam_owns = threadIdx.x < pixels_per_wave && cam_x < fp.slot_end && ray_active(fp, cam_x);
         cam_owners = __ballot(cam_owns);
         npix = (uint32_t)__popcll(cam_owners);
     } else if (CAM) {

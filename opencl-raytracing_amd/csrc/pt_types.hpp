@@ -240,6 +240,15 @@ PT_DEV bool pixel_active(const FrameParams &fp, uint32_t x, uint32_t y) {
     return !fp.block_active || fp.block_active[(y >> fp.blk_h_log2) * fp.blocks_x + (x >> fp.blk_w_log2)] != 0u;
 }
 
+// The same test for ray i of a masked ray launch (rt_render_adaptive_rays: the launch has W x H rays, ray i is pixel
+// (i mod W, i div W)).  Behind the wave-uniform test of the pointer, so an unmasked launch pays one scalar branch; a masked
+// one takes a plain 32-bit division once per lane at the kernel's entry — exact for every index, no reciprocal to pin.
+PT_DEV bool ray_active(const FrameParams &fp, uint32_t index) {
+    if (!fp.block_active) return true;
+    const uint32_t y = index / (uint32_t)fp.w, x = index - y * (uint32_t)fp.w;
+    return fp.block_active[(y >> fp.blk_h_log2) * fp.blocks_x + (x >> fp.blk_w_log2)] != 0u;
+}
+
 #define PT_MESH_BVH_NONE 0xFFFFFFFFu   // mesh_bvh_root[m]: mesh m has no BVH (face scan)
 
 // Sticky "a walk ran out of its loop bound" bits (DeviceScene::walk_overflow; rt_walk_overflow()): a walk that ends

@@ -965,11 +965,11 @@ const void *ray_source(rt_context *ctx, const void *d_rays, size_t n_rays) {
 
 extern "C++" {
 namespace {
-// rt_render_rays (set_size 0) and rt_render_ray_sets (set_size 1 .. RT_RAY_SET_MAX): one set of checks, one launch loop
-int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, bool sets, uint32_t first_sample,
-                        uint32_t n_samples, void *d_accum) {
-    int rc = check_ready(ctx, k_no_camera);
-    if (rc) return rc;
+// The argument rules of a ray call (after check_ready): rt_render_rays (sets false), rt_render_ray_sets (set_size 1 ..
+// RT_RAY_SET_MAX) and the adaptive ray calls, which pass their whole sample range and a NULL d_accum.  RT_OK and the ray
+// buffer in *rays_out, or an RT_* code recorded on the context.
+int check_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, bool sets, uint32_t first_sample,
+                       uint32_t n_samples, void *d_accum, const void **rays_out) {
     if (ctx->world > 1) return fail(ctx, RT_EINVAL, "rays on a sharded context (rank %d of %d): shard the batch instead", ctx->rank, ctx->world);
     if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "%s takes 1 .. %u rays", sets ? "rt_render_ray_sets" : "rt_render_rays", RT_MAX_RAYS);
     if (sets && (set_size == 0 || set_size > RT_RAY_SET_MAX)) return fail(ctx, RT_EINVAL, "a ray set holds 1 .. %u records, not %u", RT_RAY_SET_MAX, set_size);
@@ -980,8 +980,17 @@ int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint
     if (!d_accum && n_rays != (size_t)ctx->width * ctx->height)
         return fail(ctx, RT_EINVAL, "%zu rays into the accumulator of a %d x %d frame", n_rays, ctx->width, ctx->height);
     if (d_accum && (uintptr_t)d_accum % sizeof(float4)) return fail(ctx, RT_EINVAL, "d_accum is not 16-byte aligned");
-    const void *rays = ray_source(ctx, d_rays, records);
-    if (!rays) return RT_EINVAL;
+    *rays_out = ray_source(ctx, d_rays, records);
+    return *rays_out ? RT_OK : RT_EINVAL;
+}
+
+// rt_render_rays (set_size 0) and rt_render_ray_sets (set_size 1 .. RT_RAY_SET_MAX): one set of checks, one launch loop
+int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, bool sets, uint32_t first_sample,
+                        uint32_t n_samples, void *d_accum) {
+    int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    const void *rays = nullptr;
+    if ((rc = check_rays_or_sets(ctx, d_rays, n_rays, set_size, sets, first_sample, n_samples, d_accum, &rays)) != RT_OK) return rc;
     if (n_samples == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float4 *accum = d_accum ? static_cast<float4 *>(d_accum) : ctx->accum.p;
@@ -990,8 +999,8 @@ int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint
     for (uint32_t done = 0; done < n_samples;) {
         const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
         float *m2 = d_accum ? nullptr : ctx->moments.target();
-        rc = sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first_sample + done, c, group_log2_for(c), accum, m2)
-                  : ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum, m2);
+        rc = sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first_sample + done, c, group_log2_for(c), accum, nullptr, m2)
+                  : ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum, nullptr, m2);
         if (rc != RT_OK) return rc;
         done += c;
         if (!d_accum) ctx->accum_count += c;
@@ -1263,6 +1272,24 @@ int render_adaptive_cameras(rt_context *ctx, AdaptiveRule rule, const float *cam
     });
 }
 
+// rt_render_adaptive_rays / rt_render_adaptive_variance_rays: sample s of pixel i along ray i (set_size 0), or along record
+// s mod set_size of ray i's set — the rounds run rt_render_rays' / rt_render_ray_sets' launches under the block mask
+int render_adaptive_rays(rt_context *ctx, AdaptiveRule rule, const void *d_rays, size_t n_rays, uint32_t set_size,
+                         const rt_adaptive_params *p, rt_adaptive_stats *out) {
+    int rc = check_ready(ctx, k_no_camera), bwl = 0, bhl = 0;
+    if (rc) return rc;
+    if ((rc = check_adaptive(ctx, rule, p, out, &bwl, &bhl)) != RT_OK) return rc;
+    // (the call's whole sample range 0 .. max_spp-1 into the context's accumulator: n_rays == W*H)
+    const bool sets = set_size != 0u;
+    const void *rays = nullptr;
+    if ((rc = check_rays_or_sets(ctx, d_rays, n_rays, set_size, sets, 0u, p->max_spp, nullptr, &rays)) != RT_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return adaptive_rounds(ctx, rule, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
+        return sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first, c, group_log2_for(c), scratch, mask, m2_scratch)
+                    : ctx->ks->launch_rays(ctx, rays, n_rays, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+    });
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1282,6 +1309,16 @@ int rt_render_adaptive_variance(rt_context *ctx, const float camera[12], const r
 int rt_render_adaptive_variance_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_adaptive_params *p,
                                         rt_adaptive_stats *out) {
     return render_adaptive_cameras(ctx, RULE_VARIANCE, cameras, n_cameras, p, out);
+}
+
+int rt_render_adaptive_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, const rt_adaptive_params *p,
+                            rt_adaptive_stats *out) {
+    return render_adaptive_rays(ctx, RULE_DAMMERTZ, d_rays, n_rays, set_size, p, out);
+}
+
+int rt_render_adaptive_variance_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, const rt_adaptive_params *p,
+                                     rt_adaptive_stats *out) {
+    return render_adaptive_rays(ctx, RULE_VARIANCE, d_rays, n_rays, set_size, p, out);
 }
 
 int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {

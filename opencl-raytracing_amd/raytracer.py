@@ -42,6 +42,7 @@ SYMBOLS = (
     "rt_render_adaptive_variance", "rt_render_adaptive_variance_cameras", "rt_read_pixel_error", "rt_device_pixel_error",
     "rt_upload_rays", "rt_device_rays", "rt_render_rays", "rt_render_features_rays", "rt_debug_last_ray_plan",
     "rt_render_ray_sets",
+    "rt_render_adaptive_rays", "rt_render_adaptive_variance_rays",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -587,8 +588,46 @@ class RayTracer:
         self._adaptive_block = (int(block[0]), int(block[1]))
         return st.as_dict()
 
+    def _adaptive_rays(self, fn, rays, threshold, set_size, batch, min_spp, max_spp, block):
+        k = _abi.check_adaptive_set_size(set_size)
+        if rays is None or isinstance(rays, np.ndarray):
+            if rays is None:
+                records = self.deviceRays()[1]
+            else:
+                if rays.dtype != _abi.RAY:
+                    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+                records = self.uploadRays(rays)
+            if records == 0 or records % max(k, 1):
+                raise ValueError("%d uploaded records are not whole sets of %d" % (records, k))
+            ptr, n, _keep = None, records // max(k, 1), None
+            if n != self.width * self.height:
+                raise ValueError("an adaptive frame takes one ray per pixel: %d rays for %d x %d" % (n, self.width, self.height))
+        else:
+            n = _abi.check_adaptive_rays(rays, k, self.width, self.height)
+            ptr, _keep = C.c_void_p(rays.data_ptr()), rays
+        p = _abi.AdaptiveParams(int(batch), int(min_spp), int(max_spp), float(threshold), int(block[0]), int(block[1]))
+        st = _abi.AdaptiveStats()
+        self._check(fn(self._ctx, ptr, n, k, C.byref(p), C.byref(st)))
+        self._adaptive_block = (int(block[0]), int(block[1]))
+        return st.as_dict()
+
+    def renderAdaptiveRays(self, rays, threshold, set_size=0, batch=64, min_spp=128, max_spp=1024, block=(8, 8)):
+        """Adaptive frame of caller-supplied rays (rt_render_adaptive_rays): renderAdaptive's rounds, stopping rule and
+        stats for a w * h batch, ray i = pixel i — a panorama, a fisheye or orthographic view.  `rays` as renderRays
+        (set_size 0: one record per ray) or as renderRaySets (set_size 1 .. 4096: ray-major sets, sample s along record
+        s mod set_size): a torch device tensor read in place, None for the uploaded records, a numpy batch is uploaded
+        first.  Each round adds what renderRays / renderRaySets(first, c) adds to the pixels of the still-active blocks.
+        → the stats dict renderAdaptive returns."""
+        return self._adaptive_rays(self._lib.rt_render_adaptive_rays, rays, threshold, set_size, batch, min_spp, max_spp, block)
+
+    def renderAdaptiveVarianceRays(self, rays, threshold, set_size=0, batch=16, min_spp=32, max_spp=1024, block=(8, 8)):
+        """renderAdaptiveRays under the variance-driven stopping rule (rt_render_adaptive_variance_rays): the rule, the
+        parameters and the defaults of renderAdaptiveVariance.  Needs OPT_MOMENTS 1; pixelError() and blockError() read the
+        estimates, and denoiseMoments can follow directly.  → the stats dict renderAdaptive returns."""
+        return self._adaptive_rays(self._lib.rt_render_adaptive_variance_rays, rays, threshold, set_size, batch, min_spp, max_spp, block)
+
     def pixelError(self):
-        """Pixel errors of the last renderAdaptiveVariance(Cameras) call (rt_read_pixel_error): each pixel's value after
+        """Pixel errors of the last renderAdaptiveVariance(Cameras / Rays) call (rt_read_pixel_error): each pixel's value after
         the last round its block was traced in → (h, w) float32."""
         out = np.empty((self.height, self.width), dtype=np.float32)
         self._check(self._lib.rt_read_pixel_error(self._ctx, out.ctypes.data, out.nbytes))

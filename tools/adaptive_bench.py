@@ -21,6 +21,12 @@ bisection so that renderAdaptiveVariance spends the same pixel samples within 2 
 the sample moments are on for both, batch / min_spp / max_spp are shared.  It ends with the cameras form at threshold 0
 (every block in every round, --cameras-spp jittered samples): renderAdaptiveCameras without and with moments and
 renderAdaptiveVarianceCameras — what the fixed-lane camera kernel the moments ask for costs.
+--rays [--sets K] runs the experiment on a frame of CALLER-SUPPLIED rays (DESIGN.md "Adaptive sampling for caller-supplied
+rays"): an equirectangular panorama about the workload's camera position (rays.equirect_rays), with --sets K anti-aliased by K
+jittered records per pixel (rays.ray_sets over Camera.sampleOffsets(K); 1080p x 16 records are 1.06 GB).  The ground truth is
+a fixed --truth-spp renderRays / renderRaySets frame, the fixed runs are such frames of 256 and 1024 samples, and the adaptive
+runs are renderAdaptiveRays and — with the sample moments on, whose ray launches run the fixed-lane kernels —
+renderAdaptiveVarianceRays frames at the --thresholds; the configurations alternate inside each of --rounds rounds.
 The merge kernels' own time per round comes from a kernel trace:
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/adaptive_bench.py --rule variance --merge-rounds 20
 renders 20 two-round threshold-0 frames per rule and scene (every block active in round 0 and in round 1), and
@@ -173,6 +179,85 @@ def rule_main(a):
             json.dump(dict(rules=rows, cameras=cam_rows), f, indent=1)
 
 
+def rays_main(a):
+    """--rays [--sets K]: the experiment on an equirectangular frame of caller-supplied rays, both stopping rules."""
+    import torch
+    w, h = (int(v) for v in a.size.split("x"))
+    thresholds = [float(v) for v in a.thresholds.split(",")]
+    rows = []
+    for name in a.scenes.split(","):
+        wl = rt.workloads.get(name, width=w, height=h)
+        t = rt.RayTracer(w, h, scene=wl.scene, seed=rt.workloads.SEED)
+        t.setArith(2 if a.policy is None else a.policy)
+        stream = torch.cuda.Stream()
+        t.setStream(stream.cuda_stream)
+        kw = dict(pos=np.asarray(wl.camera, np.float32)[:3], w=w, h=h, yaw=a.yaw)
+        host = rt.rays.ray_sets(rt.rays.equirect_rays, rt.Camera.sampleOffsets(a.sets), **kw) if a.sets else rt.rays.equirect_rays(**kw)
+        d = torch.from_numpy(rt.rays.as_floats(host).copy()).cuda()
+        del host
+        torch.cuda.synchronize()
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            r = fn()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1), r
+
+        def fixed(spp):
+            t.clear()
+            if a.sets:
+                t.renderRaySets(d, a.sets, 0, spp)
+            else:
+                t.renderRays(d, 0, spp)
+            t.resolve()
+
+        akw = dict(set_size=a.sets, batch=a.batch, min_spp=a.min_spp, max_spp=a.max_spp)
+        calls = {"dammertz": lambda thr: t.renderAdaptiveRays(d, thr, **akw), "variance": lambda thr: t.renderAdaptiveVarianceRays(d, thr, **akw)}
+        fixed(64)                                           # warm-up (code objects, buffers)
+        calls["dammertz"](thresholds[0])
+        t.setOption(t.OPT_MOMENTS, 1)
+        calls["variance"](thresholds[0])
+        t.setOption(t.OPT_MOMENTS, 0)
+        fixed(a.truth_spp)
+        truth = t.transferImage()[..., :3].astype(np.float64)
+
+        def rmse():
+            return float(np.sqrt(((t.transferImage()[..., :3].astype(np.float64) - truth) ** 2).mean()))
+
+        configs = [("fixed", spp) for spp in (256, 1024)] + [(rule, thr) for rule in ("dammertz", "variance") for thr in thresholds]
+        recs = {c: dict(scene=name, mode=c[0], ms=[]) for c in configs}
+        for rnd in range(a.rounds):
+            for c in configs:
+                r = recs[c]
+                t.setOption(t.OPT_MOMENTS, 1 if c[0] == "variance" else 0)
+                if c[0] == "fixed":
+                    ms, _ = timed(lambda: fixed(c[1]))
+                    r["ms"].append(ms)
+                    if rnd == 0:
+                        r.update(spp=c[1], mean_spp=float(c[1]), rounds=1, rmse=rmse(), family=t.lastRayPlan()[1]["family"])
+                    continue
+                ms, st = timed(lambda: calls[c[0]](c[1]))
+                r["ms"].append(ms)
+                if rnd == 0:
+                    r.update(threshold=c[1], mean_spp=st["pixel_samples"] / float(w * h), rounds=st["rounds"],
+                             blocks_at_max=st["blocks_at_max"], blocks=st["blocks"], rmse=rmse(), family=t.lastRayPlan()[1]["family"])
+        rows += [recs[c] for c in configs]
+        t.setStream(None)
+        t.close()
+    print("equirect %s, %s, truth %d spp" % (a.size, "sets of %d" % a.sets if a.sets else "one record per ray", a.truth_spp))
+    print("| scene | run | kernel family | ms: median (min .. max) of %d | mean spp | rounds | RMSE (gamma) |" % a.rounds)
+    print("|---|---|---:|---:|---:|---:|---:|")
+    for r in rows:
+        run = "fixed %d" % r["spp"] if r["mode"] == "fixed" else "%s thr %g" % (r["mode"], r["threshold"])
+        print("| %s | %s | %s | %s | %.1f | %d | %.5f |" % (r["scene"], run, "queue" if r["family"] else "fixed lanes", spread(r["ms"]),
+                                                         r["mean_spp"], r["rounds"], r["rmse"]))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 def cameras_main(a):
     """--cameras: the experiment on anti-aliased frames."""
     import torch
@@ -269,7 +354,10 @@ def main():
     ap.add_argument("--max-spp", type=int, default=1024)
     ap.add_argument("--json", default=None)
     ap.add_argument("--cameras", action="store_true", help="anti-aliased frames: per-sample cameras (see the module text)")
-    ap.add_argument("--rounds", type=int, default=5, help="--cameras: repeats, the configurations alternating inside each")
+    ap.add_argument("--rays", action="store_true", help="a frame of caller-supplied rays: an equirectangular panorama (see the module text)")
+    ap.add_argument("--sets", type=int, default=0, help="--rays: K jittered records per pixel (ray sets); 0: one record per ray")
+    ap.add_argument("--yaw", type=float, default=45.0, help="--rays: the panorama's yaw in degrees")
+    ap.add_argument("--rounds", type=int, default=5, help="--cameras, --rays: repeats, the configurations alternating inside each")
     ap.add_argument("--policy", type=int, default=None, help="--cameras: arithmetic policy (default: the tracer's)")
     ap.add_argument("--rule", choices=("dammertz", "variance"), default="dammertz",
                     help="variance: compare the two stopping rules at equal pixel-sample budgets (see the module text)")
@@ -281,6 +369,8 @@ def main():
     a = ap.parse_args()
     if a.merge_trace:
         return merge_trace_main(a.merge_trace)
+    if a.rays:
+        return rays_main(a)
     if a.rule == "variance":
         return rule_main(a)
     if a.cameras:
