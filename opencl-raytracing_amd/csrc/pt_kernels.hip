@@ -1923,27 +1923,25 @@ static RenderKernel render_kernel(int mode, bool count, bool accel) {   // [MODE
         {{pt_render<MODE_RETRACE, false, false>, pt_render<MODE_RETRACE, false, true>}, {pt_render<MODE_RETRACE, true, false>, pt_render<MODE_RETRACE, true, true>}}};
     return k[mode][count][accel];
 }
-// Direct path (every sample from the camera): trace / retrace compat modes, and the fused mode when prefix sharing is switched off.
-int launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                  const BlockMask *mask, float *m2) {
-    if (mode < MODE_ACCUM || mode > MODE_RETRACE) return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
-    FrameParams fp = frame_params(ctx, cam, first, count, glog2);
-    apply_mask(fp, mask);
-    fp.m2 = mode == MODE_ACCUM ? m2 : nullptr;
-    DeviceScene sc = device_scene(ctx);
-    uint32_t slots = fp.slot_end;
-    if (slots == 0) return RT_OK;
-    // split very long launches into slot ranges (keeps single kernels short on huge scenes)
-    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
-    const RenderKernel kernel = render_kernel(mode, ctx->count_enabled, scene_has_accel(sc));
+
+// Very long launches are split into slot ranges (RT_OPT_MAX_THREADS_PER_LAUNCH; keeps single kernels short on huge scenes):
+// the slots of a range, and where the range that begins at b ends (never b + per, which may pass 2^32).
+static uint32_t slots_per_launch(const rt_context *ctx, uint32_t glog2) { return std::max(ctx->max_threads_per_launch >> glog2, 1u); }
+static uint32_t range_end(uint32_t b, uint32_t slots, uint32_t per) { return slots - b > per ? b + per : slots; }
+
+// The launch of a call without a first stage: the call's entry in the event history around body(), once per slot range with
+// fp.slot_begin / fp.slot_end set.  A failure inside the loop returns its code and leaves the entry unused.
+template <class Body>
+static int launch_ranges(rt_context *ctx, FrameParams &fp, uint32_t slots, Body body) {
+    const uint32_t per = slots_per_launch(ctx, fp.group_log2);
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // no first stage on the direct path
-    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
+    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
+    for (uint32_t b = 0; b < slots; b = fp.slot_end) {
         fp.slot_begin = b;
-        fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
-        uint64_t threads = (uint64_t)(fp.slot_end - fp.slot_begin) << glog2;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p);
+        fp.slot_end = range_end(b, slots, per);
+        const int rc = body();
+        if (rc != RT_OK) return rc;
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
@@ -1951,21 +1949,46 @@ int launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first
     return RT_OK;
 }
 
-// ---- the fused path's sample stage: facts (sample_facts, rt_context.hpp) → plan → launch --------------------------------
-// plan_samples is THE place that decides which sample kernel a slot range of a fused call runs, with how many pixels per
-// wave, how much LDS and how many workgroups: a pure function of the facts (no HIP call, no context), so the table can be
-// pinned without a device (rt_debug_plan_samples, tests/test_sample_plan_host.py).
+// Direct path (every sample from the camera): trace / retrace compat modes, and the fused mode when prefix sharing is switched off.
+int launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                  const BlockMask *mask, float *m2) {
+    if (mode < MODE_ACCUM || mode > MODE_RETRACE) return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
+    FrameParams fp = frame_params(ctx, cam, first, count, glog2);
+    apply_mask(fp, mask);
+    fp.m2 = mode == MODE_ACCUM ? m2 : nullptr;
+    const DeviceScene sc = device_scene(ctx);
+    const uint32_t slots = fp.slot_end;
+    if (slots == 0) return RT_OK;
+    const RenderKernel kernel = render_kernel(mode, ctx->count_enabled, scene_has_accel(sc));
+    return launch_ranges(ctx, fp, slots, [&]() -> int {
+        const uint64_t threads = (uint64_t)(fp.slot_end - fp.slot_begin) << glog2;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p);
+        return RT_OK;
+    });
+}
+
+// ---- the sample stage: facts (sample_facts, camera_facts: rt_context.hpp) → plan → launch -------------------------------
 using SampleFacts = rt_sample_facts;
 using SamplePlan = rt_sample_plan;
-static SamplePlan plan_samples(const SampleFacts &f) {
-    SamplePlan p = {};
-    const bool queue = f.sample_queue && f.count <= QUEUE_SLOTS;
-    const bool accel = f.sphere_bvh || f.mesh_bvh;
+using CameraFacts = rt_camera_facts;
+using CameraPlan = rt_camera_plan;
+
+// THE sizing rule of the sample queue, for every way of feeding it (plan_samples, plan_camera_samples): the geometry row
+// (accel, geom, waves) by the scene's BVHs and primitive kinds, the pixels a wave owns, and its LDS — the static prefix
+// (static_f4: tables, then lds_face_f4 of faces), then the queue.  ppw_cap is what the wave-fill rule allows at most.
+struct QueueSize {
+    uint32_t accel, geom, waves, pixels_per_wave, ppw_cap, lds_face_f4, static_f4, lds_bytes;
+};
+template <class Facts>   // (the scene part of either facts, count, n, cu_count, wave_fill; stage_faces: the launch may keep faces in LDS)
+static QueueSize queue_size(const Facts &f, bool stage_faces) {
+    QueueSize q = {};
     const bool simple_geom = f.lens_count == 0 && f.model_count == 0;   // spheres and planes only
     const bool sphere_bvh_only = f.sphere_bvh && !f.mesh_bvh;
-    const uint32_t q_waves = !accel ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
-    // sample queue: a wave owns ppw live pixels (<= QUEUE_SLOTS samples); its LDS is the static prefix (tables, then faces), then the queue
-    uint32_t static_f4 = lds_static_used(f.material_count, f.sphere_count, f.plane_count);
+    q.accel = f.sphere_bvh || f.mesh_bvh;
+    q.geom = !q.accel || sphere_bvh_only ? (simple_geom ? 0u : 1u) : 2u;
+    q.waves = !q.accel ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
+    // a wave owns pixels_per_wave live pixels (<= QUEUE_SLOTS samples)
+    q.static_f4 = lds_static_used(f.material_count, f.sphere_count, f.plane_count);
     // Small launches (small frames, a rank's share of a sharded frame): fewer pixels per wave, so that there are about
     // PT_UNITS_PER_WAVE_SLOT waves per wave slot of the chip — a wave works through its pixels' samples one batch of
     // 64 after the other, and 4 200 waves of 384 samples leave a third of the slots empty for the whole launch.
@@ -1973,31 +1996,47 @@ static SamplePlan plan_samples(const SampleFacts &f) {
     // 0.344 → 0.268, 640 x 360 0.419 → 0.369, 960 x 540 0.619 → 0.59; 1080p and up unchanged (6).
     const uint32_t want_units = (f.cu_count ? f.cu_count : 256u) * 4u * 6u * PT_UNITS_PER_WAVE_SLOT;
     const uint32_t ppw_full = (64u + f.count - 1u) / f.count;   // (never fewer than the 64 samples that fill a wave's lanes once)
-    const uint32_t ppw_par = !f.wave_fill ? QUEUE_MAX_PIXELS : std::max(f.n / want_units, ppw_full);
-    uint32_t ppw = std::min(queue_pixels_per_wave(f.count, q_waves, static_f4), ppw_par);
+    q.ppw_cap = !f.wave_fill ? QUEUE_MAX_PIXELS : std::max(f.n / want_units, ppw_full);
+    q.pixels_per_wave = std::min(queue_pixels_per_wave(f.count, q.waves, q.static_f4), q.ppw_cap);
     // Face records in LDS for hit_models' candidate loop: scenes whose meshes are all face-scanned (no mesh BVH) and
     // hold at most PT_LDS_FACE_CAP faces together, and only when the copy fits into what the 1 KiB allocation granule
     // leaves over anyway (C3: 576 bytes of a cube into 609 spare ones) — never at the price of a pixel per wave.
-    if (PT_FACE_MASK && !simple_geom && !f.mesh_bvh && !f.count_enabled && f.faces > 0 && f.faces <= PT_LDS_FACE_CAP &&
-        queue_pixels_per_wave(f.count, q_waves, static_f4 + 3u * f.faces) >= ppw) {
-        p.lds_face_f4 = 3u * f.faces;
-        static_f4 += p.lds_face_f4;
+    if (PT_FACE_MASK && stage_faces && !simple_geom && !f.mesh_bvh && f.faces > 0 && f.faces <= PT_LDS_FACE_CAP &&
+        queue_pixels_per_wave(f.count, q.waves, q.static_f4 + 3u * f.faces) >= q.pixels_per_wave) {
+        q.lds_face_f4 = 3u * f.faces;
+        q.static_f4 += q.lds_face_f4;
     }
+    q.lds_bytes = q.static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(q.pixels_per_wave, f.count);
+    return q;
+}
+
+// plan_samples is THE place that decides which sample kernel a slot range of a fused call runs, with how many pixels per
+// wave, how much LDS and how many workgroups: a pure function of the facts (no HIP call, no context), so the table can be
+// pinned without a device (rt_debug_plan_samples, tests/test_sample_plan_host.py).  Its own, beside queue_size: the walk
+// family's waves and pixels per wave, count_log2, the units of the live list and the exact grid.
+static SamplePlan plan_samples(const SampleFacts &f) {
+    SamplePlan p = {};
+    const QueueSize q = queue_size(f, !f.count_enabled);
+    const bool queue = f.sample_queue && f.count <= QUEUE_SLOTS;
+    uint32_t ppw = q.pixels_per_wave;
     p.count = f.count_enabled;
-    p.accel = accel;
+    p.accel = q.accel;
     p.moments = f.moments;
+    p.lds_face_f4 = q.lds_face_f4;   // (whatever the family: the facts decide it)
     p.block_size = 64u;
     if (queue && f.mesh_bvh && f.walk_jobs && f.walk_slices && !f.count_enabled) {   // every mesh has a BVH: walk slices, sized for their own occupancy
         p.family = RT_PLAN_WALK;
         p.multi = f.walk_jobs != 1u;
         p.waves = p.multi ? PT_W_WAVES_MULTI : PT_W_WAVES;
-        ppw = std::min(queue_pixels_per_wave(f.count, p.waves, static_f4), ppw_par);
+        ppw = std::min(queue_pixels_per_wave(f.count, p.waves, q.static_f4), q.ppw_cap);
+        p.lds_bytes = q.static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(ppw, f.count);
     } else if (queue) {
         p.family = RT_PLAN_QUEUE;
-        p.geom = !accel || sphere_bvh_only ? (simple_geom ? 0u : 1u) : 2u;
-        p.waves = q_waves;
+        p.geom = q.geom;
+        p.waves = q.waves;
+        p.lds_bytes = q.lds_bytes;
         // (the count-specialised instantiation: exactly 64 samples on 64 lanes per pixel, no counters, no BVH, no moments)
-        const bool count64 = PT_Q_COUNT64 && !accel && !p.count && !p.moments && f.count == 64u && f.glog2 == 6u;
+        const bool count64 = PT_Q_COUNT64 && !p.accel && !p.count && !p.moments && f.count == 64u && f.glog2 == 6u;
         p.count_log2 = count64 ? 6u : RT_PLAN_GENERIC_COUNT;
     } else {
         p.family = RT_PLAN_FIXED;
@@ -2010,7 +2049,38 @@ static SamplePlan plan_samples(const SampleFacts &f) {
     uint32_t units = (f.seg_cap + ppw - 1u) / ppw + 1u;
     if (f.exact) (void)rt_sample_units(f.seg_cap, ppw, f.count_light, f.count_heavy, &units);
     p.grid_units = p.family == RT_PLAN_FIXED ? (uint32_t)((((uint64_t)units << f.glog2) + 255u) / 256u) : units;
-    if (p.family != RT_PLAN_FIXED) p.lds_bytes = static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(ppw, f.count);
+    return p;
+}
+
+// plan_camera_samples is THE place that decides what a slot range of a camera or ray launch runs (launch_source) — like
+// plan_samples a pure function of its facts (rt_debug_plan_camera_samples, tests/test_cameras_host.py), sized by queue_size.
+//  * RT_CAMERA_PLAN_QUEUE: the row's camera, ray or ray-set kernel, one wave per pixels_per_wave SLOTS — the grid is exact,
+//    ceil(n / pixels_per_wave).  A scene plan_samples would give the walk-slice kernel runs the (1, 2) row, its walks in place.
+//  * RT_CAMERA_PLAN_FIXED: pt_render<MODE_ACCUM, COUNT, ACCEL, true> (pt_render_rays, pt_render_raysets) — counting builds,
+//    RT_OPT_SAMPLE_QUEUE 0, and launches that keep sample moments (a MOMENTS row of the camera queue would be five more
+//    kernels for an option that is off by default; the fixed-lane kernel's moments are the ones rt_render_spp keeps with
+//    prefix sharing off).
+static CameraPlan plan_camera_samples(const CameraFacts &f) {
+    CameraPlan p = {};
+    p.count = f.count_enabled;
+    p.accel = f.sphere_bvh || f.mesh_bvh;
+    p.moments = f.moments;
+    if (!f.sample_queue || f.count > QUEUE_SLOTS || f.count_enabled || f.moments) {   // no queue with counters or moments
+        p.family = RT_CAMERA_PLAN_FIXED;
+        p.pixels_per_wave = 1u;
+        p.block_size = 256u;
+        p.grid_units = (uint32_t)((((uint64_t)f.n << f.glog2) + 255u) / 256u);
+        return p;
+    }
+    const QueueSize q = queue_size(f, true);
+    p.family = RT_CAMERA_PLAN_QUEUE;
+    p.geom = q.geom;
+    p.waves = q.waves;
+    p.pixels_per_wave = q.pixels_per_wave;
+    p.lds_face_f4 = q.lds_face_f4;
+    p.lds_bytes = q.lds_bytes;
+    p.block_size = 64u;
+    p.grid_units = (f.n + q.pixels_per_wave - 1u) / q.pixels_per_wave;
     return p;
 }
 
@@ -2020,27 +2090,45 @@ static FixedKernel fixed_kernel(const SamplePlan &p) {   // [COUNT][ACCEL]
     return k[p.count != 0u][p.accel != 0u];
 }
 using QueueKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *, uint32_t);
-static QueueKernel queue_kernel(const SamplePlan &p) {   // NULL: no such instantiation (plan_samples never asks for one)
-    struct Row { uint32_t accel, geom, waves; QueueKernel k[2][2]; };   // [COUNT][MOMENTS]
-    static const Row rows[] = {
-        {0u, 0u, PT_Q_WAVES, {{pt_samples_q<false, false, 0, PT_Q_WAVES, false>, pt_samples_q<false, false, 0, PT_Q_WAVES, true>},
-          {pt_samples_q<true, false, 0, PT_Q_WAVES, false>, pt_samples_q<true, false, 0, PT_Q_WAVES, true>}}},
-        {0u, 1u, PT_Q_WAVES, {{pt_samples_q<false, false, 1, PT_Q_WAVES, false>, pt_samples_q<false, false, 1, PT_Q_WAVES, true>},
-          {pt_samples_q<true, false, 1, PT_Q_WAVES, false>, pt_samples_q<true, false, 1, PT_Q_WAVES, true>}}},
-        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, {{pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false>, pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, true>},
-          {pt_samples_q<true, true, 0, PT_Q_WAVES_SPHERE_BVH, false>, pt_samples_q<true, true, 0, PT_Q_WAVES_SPHERE_BVH, true>}}},
-        {1u, 1u, PT_Q_WAVES_ACCEL, {{pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false>, pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, true>},
-          {pt_samples_q<true, true, 1, PT_Q_WAVES_ACCEL, false>, pt_samples_q<true, true, 1, PT_Q_WAVES_ACCEL, true>}}},
-        {1u, 2u, PT_Q_WAVES_ACCEL, {{pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false>, pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, true>},
-          {pt_samples_q<true, true, 2, PT_Q_WAVES_ACCEL, false>, pt_samples_q<true, true, 2, PT_Q_WAVES_ACCEL, true>}}}};
+// The sample queue's five geometry rows: the key (accel, geom, waves) that queue_size yields, once, with every kernel of the
+// row — fed from pt_prefix's records, from camera blocks (its look-ahead form: the rows without a BVH walk branch on
+// fp.la_ring themselves, the ACCEL rows have pt_samples_q_la), from rays and from ray sets.
+struct QueueRow {
+    uint32_t accel, geom, waves;
+    QueueKernel recs[2][2];   // [COUNT][MOMENTS]
+    QueueKernel cams[2];      // [look-ahead]
+    QueueKernel rays, ray_sets;
+};
+template <bool ACCEL, int GEOM, int WAVES>
+static QueueRow queue_row() {
+    const QueueKernel cam = pt_samples_q<false, ACCEL, GEOM, WAVES, false, -1, true>;
+    QueueKernel cam_la = cam;
+    if constexpr (ACCEL) cam_la = pt_samples_q_la<GEOM, WAVES>;   // (constexpr: naming it for the other rows would instantiate it)
+    return {ACCEL, GEOM, WAVES,
+            {{pt_samples_q<false, ACCEL, GEOM, WAVES, false>, pt_samples_q<false, ACCEL, GEOM, WAVES, true>},
+             {pt_samples_q<true, ACCEL, GEOM, WAVES, false>, pt_samples_q<true, ACCEL, GEOM, WAVES, true>}},
+            {cam, cam_la}, pt_samples_q_rays<ACCEL, GEOM, WAVES>, pt_samples_q_raysets<ACCEL, GEOM, WAVES>};
+}
+// The row of a plan — its kernels take any count, so a plan with another count_log2 has none — or NULL with RT_ESTATE recorded
+// for the `family` that asked (neither planner asks for a row that is not there).
+static const QueueRow *find_queue_row(rt_context *ctx, const char *family, uint32_t accel, uint32_t geom, uint32_t waves,
+                                      uint32_t count_log2 = RT_PLAN_GENERIC_COUNT) {
+    static const QueueRow rows[] = {queue_row<false, 0, PT_Q_WAVES>(), queue_row<false, 1, PT_Q_WAVES>(), queue_row<true, 0, PT_Q_WAVES_SPHERE_BVH>(),
+                                    queue_row<true, 1, PT_Q_WAVES_ACCEL>(), queue_row<true, 2, PT_Q_WAVES_ACCEL>()};
+    if (count_log2 == RT_PLAN_GENERIC_COUNT)
+        for (const QueueRow &r : rows)
+            if (r.accel == accel && r.geom == geom && r.waves == waves) return &r;
+    (void)fail(ctx, RT_ESTATE, "no %s instantiation of pt_samples_q for the plan (accel %u, geom %u, %u waves)", family, accel, geom, waves);
+    return nullptr;
+}
+// the record-fed kernel of a queue plan; the two COUNT_LOG2 = 6 kernels stand beside the table
+static QueueKernel queue_kernel(rt_context *ctx, const SamplePlan &p) {
 #if PT_Q_COUNT64
     static const QueueKernel k64[2] = {pt_samples_q<false, false, 0, PT_Q_WAVES, false, 6>, pt_samples_q<false, false, 1, PT_Q_WAVES, false, 6>};   // [GEOM]
-    if (p.count_log2 == 6u) return !p.count && !p.accel && !p.moments && p.geom < 2u && p.waves == PT_Q_WAVES ? k64[p.geom] : nullptr;
+    if (p.count_log2 == 6u && !p.count && !p.accel && !p.moments && p.geom < 2u && p.waves == PT_Q_WAVES) return k64[p.geom];
 #endif
-    if (p.count_log2 != RT_PLAN_GENERIC_COUNT) return nullptr;
-    for (const Row &r : rows)
-        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k[p.count != 0u][p.moments != 0u];
-    return nullptr;
+    const QueueRow *r = find_queue_row(ctx, "record", p.accel, p.geom, p.waves, p.count_log2);
+    return r ? r->recs[p.count != 0u][p.moments != 0u] : nullptr;
 }
 #ifdef PT_WSTAT   // (the diagnostic build's kernels take their statistics block as one argument more)
 using WalkKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, uint32_t, const uint2 *, uint32_t, unsigned long long *);
@@ -2066,8 +2154,8 @@ static int launch_plan(rt_context *ctx, const SamplePlan &p, const DeviceScene &
                            p.pixels_per_wave, ctx->walk_jobs.p, (uint32_t)ctx->walk_jobs.n);
 #endif
     } else if (p.family == RT_PLAN_QUEUE) {
-        const QueueKernel kernel = queue_kernel(p);
-        if (!kernel) return fail(ctx, RT_ESTATE, "no pt_samples_q instantiation for the plan");
+        const QueueKernel kernel = queue_kernel(ctx, p);
+        if (!kernel) return RT_ESTATE;
         hipLaunchKernelGGL(kernel, grid, block, p.lds_bytes, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum,
                            ctx->counters.p, p.pixels_per_wave);
     } else hipLaunchKernelGGL(fixed_kernel(p), grid, block, 0, ctx->stream, sc, fp, ss.recs.p, ss.live.p, live_count, accum, ctx->counters.p);
@@ -2134,10 +2222,10 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
     refresh_stage_block(ctx, sc);
     const rt_context::Slots &ss = ctx->slots;
     uint32_t *live_count = ss.live.p + ss.capacity + 256u;
-    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
+    const uint32_t per = slots_per_launch(ctx, glog2);
     // may this launch's pt_prefix be kept, and is the last one's still good?
     const bool tree_on = ctx->prefix_tree == 2 || (ctx->prefix_tree == 1 && count >= PT_TREE_MIN_SAMPLES);
-    const bool keepable = !mask && !ctx->count_enabled && slots_per_launch >= slots;
+    const bool keepable = !mask && !ctx->count_enabled && per >= slots;
     uint32_t cam_bits[12];
     memcpy(cam_bits, cam, sizeof cam_bits);
     const bool hit = prefix_lookup(ctx->prefix_cache, keepable, tree_on, cam_bits);   // (a hit is one slot range)
@@ -2146,9 +2234,9 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
     rt_context::SampleGrid &sg = ctx->sample_grid;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
-    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
+    for (uint32_t b = 0; b < slots; b = fp.slot_end) {
         fp.slot_begin = b;
-        fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
+        fp.slot_end = range_end(b, slots, per);
         if (!hit) HIP_TRY(ctx, hipMemsetAsync(live_count, 0, LIVE_COUNT_STRIDE * sizeof(uint32_t), ctx->stream));
         // shared decision trees (RT_OPT_PREFIX_TREE): not in counting builds — the counters price per-sample work
         fp.trees = ss.trees.p;
@@ -2189,142 +2277,13 @@ int launch_lookahead(rt_context *ctx, const float cam[12], uint32_t first, uint3
     return launch_fused_any(ctx, cam, first, count, group_log2_for(count), nullptr, nullptr, ring, nullptr);
 }
 
-// ---- per-sample camera blocks (rt_render_spp_cameras): facts (camera_facts, rt_context.hpp) → plan → launch ---------------
-// plan_camera_samples is THE place that decides what a slot range of a camera call runs — like plan_samples a pure function
-// of its facts (rt_debug_plan_camera_samples, tests/test_cameras_host.py).  The queue's sizing rules are plan_samples':
-// waves per SIMD by the scene's BVHs, pixels per wave by the LDS share and the wave-fill rule, a small scene's faces in LDS.
-//  * RT_CAMERA_PLAN_QUEUE: pt_samples_q<false, ACCEL, GEOM, WAVES, false, -1, true>, one wave per pixels_per_wave SLOTS — the
-//    grid is exact, ceil(n / pixels_per_wave).  A scene plan_samples would give the walk-slice kernel runs the (1, 2) row,
-//    its walks in place.
-//  * RT_CAMERA_PLAN_FIXED: pt_render<MODE_ACCUM, COUNT, ACCEL, true> — counting builds, RT_OPT_SAMPLE_QUEUE 0, and launches
-//    that keep sample moments (a MOMENTS row of the camera queue would be five more kernels for an option that is off
-//    by default; the fixed-lane kernel's moments are the ones rt_render_spp keeps with prefix sharing off).
-using CameraFacts = rt_camera_facts;
-using CameraPlan = rt_camera_plan;
-static CameraPlan plan_camera_samples(const CameraFacts &f) {
-    CameraPlan p = {};
-    const bool queue = f.sample_queue && f.count <= QUEUE_SLOTS && !f.count_enabled && !f.moments;
-    const bool accel = f.sphere_bvh || f.mesh_bvh;
-    const bool simple_geom = f.lens_count == 0 && f.model_count == 0;
-    const bool sphere_bvh_only = f.sphere_bvh && !f.mesh_bvh;
-    p.count = f.count_enabled;
-    p.accel = accel;
-    p.moments = f.moments;
-    if (!queue) {
-        p.family = RT_CAMERA_PLAN_FIXED;
-        p.pixels_per_wave = 1u;
-        p.block_size = 256u;
-        p.grid_units = (uint32_t)((((uint64_t)f.n << f.glog2) + 255u) / 256u);
-        return p;
-    }
-    p.family = RT_CAMERA_PLAN_QUEUE;
-    p.geom = !accel || sphere_bvh_only ? (simple_geom ? 0u : 1u) : 2u;
-    p.waves = !accel ? PT_Q_WAVES : ((sphere_bvh_only && simple_geom) ? PT_Q_WAVES_SPHERE_BVH : PT_Q_WAVES_ACCEL);
-    uint32_t static_f4 = lds_static_used(f.material_count, f.sphere_count, f.plane_count);
-    const uint32_t want_units = (f.cu_count ? f.cu_count : 256u) * 4u * 6u * PT_UNITS_PER_WAVE_SLOT;
-    const uint32_t ppw_full = (64u + f.count - 1u) / f.count;
-    const uint32_t ppw_par = !f.wave_fill ? QUEUE_MAX_PIXELS : std::max(f.n / want_units, ppw_full);
-    const uint32_t ppw = std::min(queue_pixels_per_wave(f.count, p.waves, static_f4), ppw_par);
-    if (PT_FACE_MASK && !simple_geom && !f.mesh_bvh && f.faces > 0 && f.faces <= PT_LDS_FACE_CAP &&
-        queue_pixels_per_wave(f.count, p.waves, static_f4 + 3u * f.faces) >= ppw) {
-        p.lds_face_f4 = 3u * f.faces;
-        static_f4 += p.lds_face_f4;
-    }
-    p.pixels_per_wave = ppw;
-    p.block_size = 64u;
-    p.grid_units = (f.n + ppw - 1u) / ppw;
-    p.lds_bytes = static_f4 * (uint32_t)sizeof(float4) + queue_wave_lds_bytes(ppw, f.count);
-    return p;
-}
-
-// the five geometry rows of queue_kernel; lookahead: the rows without a BVH walk branch on fp.la_ring themselves, the ACCEL
-// rows have pt_samples_q_la; NULL: no such row
-static QueueKernel camera_queue_kernel(const CameraPlan &p, bool lookahead) {
-    struct Row { uint32_t accel, geom, waves; QueueKernel k[2]; };
-    static const Row rows[] = {
-        {0u, 0u, PT_Q_WAVES, {pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>, pt_samples_q<false, false, 0, PT_Q_WAVES, false, -1, true>}},
-        {0u, 1u, PT_Q_WAVES, {pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>, pt_samples_q<false, false, 1, PT_Q_WAVES, false, -1, true>}},
-        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, {pt_samples_q<false, true, 0, PT_Q_WAVES_SPHERE_BVH, false, -1, true>, pt_samples_q_la<0, PT_Q_WAVES_SPHERE_BVH>}},
-        {1u, 1u, PT_Q_WAVES_ACCEL, {pt_samples_q<false, true, 1, PT_Q_WAVES_ACCEL, false, -1, true>, pt_samples_q_la<1, PT_Q_WAVES_ACCEL>}},
-        {1u, 2u, PT_Q_WAVES_ACCEL, {pt_samples_q<false, true, 2, PT_Q_WAVES_ACCEL, false, -1, true>, pt_samples_q_la<2, PT_Q_WAVES_ACCEL>}}};
-    for (const Row &r : rows)
-        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return r.k[lookahead];
-    return nullptr;
-}
+// ---- samples from a source of their own: per-sample camera blocks, caller-supplied rays, ray sets ---------------------------
+// facts (camera_facts, rt_context.hpp: n = the slots of the range) → plan_camera_samples → the row's kernel for the source,
+// or the source's fixed-lane kernel.
 static RenderKernel camera_render_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
     static const RenderKernel k[2][2] = {{pt_render<MODE_ACCUM, false, false, true>, pt_render<MODE_ACCUM, false, true, true>},
                                          {pt_render<MODE_ACCUM, true, false, true>, pt_render<MODE_ACCUM, true, true, true>}};
     return k[count][accel];
-}
-
-// One launch of a camera call: `count` blocks at d_cams.  cam0 (the first block) fills FrameParams::cam, which no camera
-// kernel reads.  Slot ranges as launch_render and launch_fused cut them (RT_OPT_MAX_THREADS_PER_LAUNCH).  Nothing here
-// reads or writes the slot buffers or the prefix cache; the staged scene block is the context's, refreshed as launch_fused
-// refreshes it.  mask != NULL (rt_render_adaptive_cameras): only the pixels of active decision blocks are traced — the camera
-// kernels test pixel_active where they take ownership of a slot; the plan and the grid are those of the unmasked launch.
-// ring != NULL: a LOOK-AHEAD launch (rt_render_again_cameras, RT_OPT_LOOKAHEAD) — the queue family only, accum, mask and m2
-// NULL: the `count` samples become `count` frames of the ring (queue_replay<true>), whose frame 0 holds the image as it lies
-// (the caller copied it there on the stream), and the accumulator is not touched.  The facts carry moments = 0.
-int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
-                   float4 *accum, const BlockMask *mask, float *m2, float4 *ring) {
-    if (!d_cams || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
-    FrameParams fp = frame_params(ctx, cam0, first, count, glog2);
-    apply_mask(fp, mask);
-    fp.m2 = m2;
-    fp.cams = d_cams;
-    if (ring) {
-        if (!lookahead_ok(ctx, fp, accum, mask, m2) || plan_camera_samples(camera_facts(ctx, device_scene(ctx), fp)).family != RT_CAMERA_PLAN_QUEUE)
-            return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
-        fp.la_ring = ring;   // (la_image's bytes hold `cams`: the start image is the ring's frame 0)
-    }
-    const DeviceScene sc = device_scene(ctx);
-    const uint32_t slots = fp.slot_end;
-    if (slots == 0) return RT_OK;
-    refresh_stage_block(ctx, sc);
-    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
-    hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
-    HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
-    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
-        fp.slot_begin = b;
-        fp.slot_end = b + slots_per_launch < slots ? b + slots_per_launch : slots;
-        const CameraFacts facts = camera_facts(ctx, sc, fp);
-        const CameraPlan plan = plan_camera_samples(facts);
-        fp.lds_face_f4 = plan.lds_face_f4;
-        if (plan.family == RT_CAMERA_PLAN_QUEUE) {
-            const QueueKernel kernel = camera_queue_kernel(plan, ring != nullptr);
-            if (!kernel) return fail(ctx, RT_ESTATE, "no camera instantiation of pt_samples_q for the plan");
-            hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
-                               (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,
-                               plan.pixels_per_wave);
-        } else {
-            hipLaunchKernelGGL(camera_render_kernel(plan.count != 0u, plan.accel != 0u), dim3(plan.grid_units), dim3(plan.block_size), 0,
-                               ctx->stream, sc, fp, accum, ctx->image.p, ctx->counters.p);
-        }
-        ctx->cameras.last_facts = facts;
-        ctx->cameras.last_plan = plan;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
-    ctx->ev_count++;
-    return RT_OK;
-}
-
-// ---- caller-supplied rays (rt_render_rays): the camera launch with a ray buffer in place of the camera blocks ---------------
-// The facts are camera_facts with n = the slots (= rays) of the range and the plan is plan_camera_samples' — one planner, the
-// same sizing rules; the rows are camera_queue_kernel's five, in the ray form of the kernel text.
-// (sets: the rows of pt_samples_q_raysets, rt_render_ray_sets)
-static QueueKernel ray_queue_kernel(const CameraPlan &p, bool sets) {
-    struct Row { uint32_t accel, geom, waves; QueueKernel k, k_sets; };
-    static const Row rows[] = {
-        {0u, 0u, PT_Q_WAVES, pt_samples_q_rays<false, 0, PT_Q_WAVES>, pt_samples_q_raysets<false, 0, PT_Q_WAVES>},
-        {0u, 1u, PT_Q_WAVES, pt_samples_q_rays<false, 1, PT_Q_WAVES>, pt_samples_q_raysets<false, 1, PT_Q_WAVES>},
-        {1u, 0u, PT_Q_WAVES_SPHERE_BVH, pt_samples_q_rays<true, 0, PT_Q_WAVES_SPHERE_BVH>, pt_samples_q_raysets<true, 0, PT_Q_WAVES_SPHERE_BVH>},
-        {1u, 1u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 1, PT_Q_WAVES_ACCEL>, pt_samples_q_raysets<true, 1, PT_Q_WAVES_ACCEL>},
-        {1u, 2u, PT_Q_WAVES_ACCEL, pt_samples_q_rays<true, 2, PT_Q_WAVES_ACCEL>, pt_samples_q_raysets<true, 2, PT_Q_WAVES_ACCEL>}};
-    for (const Row &r : rows)
-        if (r.accel == p.accel && r.geom == p.geom && r.waves == p.waves) return sets ? r.k_sets : r.k;
-    return nullptr;
 }
 typedef void (*RayRenderKernel)(DeviceScene, FrameParams, float4 *, unsigned long long *);
 static RayRenderKernel ray_render_kernel(bool count, bool accel, bool sets) {   // [COUNT][ACCEL]
@@ -2335,73 +2294,94 @@ static RayRenderKernel ray_render_kernel(bool count, bool accel, bool sets) {   
     return sets ? k_sets[count][accel] : k[count][accel];
 }
 
-// One launch of a ray call: samples first .. first+count-1 of rays 0 .. n-1 at d_rays, the sums added to accum[i] (and
-// m2[i]).  The event pair, the slot ranges (RT_OPT_MAX_THREADS_PER_LAUNCH) and the staged scene block as launch_cameras has
-// them; the frame parameters carry the context's frame, of which the ray kernels read nothing but what queue_sums
-// multiplies by the row 0.  Nothing here reads or writes the slot buffers or the prefix cache.
-// set_size 0: one record per ray (rt_render_rays).  1 .. RT_RAY_SET_MAX: d_rays holds n sets of that many records, ray-major
-// (rt_render_ray_sets), and the launch runs the sets form of the same rows; the set size and its reciprocal travel in the
-// camera block's first two words (queue_stage_raysets).
-// mask != NULL (rt_render_adaptive_rays): the launch has one ray per pixel of the frame, ray i being pixel (i mod W, i div W),
-// and only the rays of active decision blocks are staged and traced — the four ray families test ray_active where they take
-// ownership of a slot; the plan and the grid are those of the unmasked launch, as launch_cameras has it.
-static int launch_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count,
-                               uint32_t glog2, float4 *accum, const BlockMask *mask, float *m2) {
-    if (!d_rays || !accum || n < 1u || n > (1u << 28) || count < 1u || count > RT_SPP_PER_LAUNCH)
-        return fail(ctx, RT_EINVAL, "a ray launch takes 1 .. 2^28 rays and 1 .. %u samples", RT_SPP_PER_LAUNCH);
-    if (set_size > RT_RAY_SET_MAX || (uint64_t)n * set_size > (1ull << 31))
-        return fail(ctx, RT_EINVAL, "a ray-set launch takes sets of 1 .. %u records, 2^31 records in all", RT_RAY_SET_MAX);
-    const bool sets = set_size != 0u;
+// What feeds a launch of launch_source, on the device.  Cameras: `count` blocks of 12 floats at p, sample first + j through
+// block j, over the owned pixels of the (sharded) frame; cam0 is the first block.  Rays: n rt_ray records at p (set_size 0) or
+// n sets of set_size records, ray-major, slot = ray index; cam0 is zero but for the set size and its reciprocal in its first
+// two words (queue_stage_raysets).  cam0 fills FrameParams::cam, which no camera kernel reads.
+struct SampleSource {
+    bool rays;
+    const void *p;
+    size_t n;
+    uint32_t set_size;
+    const float *cam0;
+};
+
+// One launch of a camera or ray call: samples first .. first+count-1 of every slot, the sums added to `accum` (and `m2`) at
+// the pixel (cameras) or at the ray's index.  Nothing here reads or writes the slot buffers or the prefix cache; the staged
+// scene block is the context's, refreshed as launch_fused refreshes it.  The facts and the plan of the last slot range go to
+// rt_context::Cameras / Rays.
+// mask != NULL (the adaptive calls): only the slots of active decision blocks are staged and traced — the kernels test
+// pixel_active / ray_active where they take ownership of a slot, a ray launch then has one ray per pixel of the frame, ray i
+// being pixel (i mod W, i div W); the plan and the grid are those of the unmasked launch.
+// ring != NULL, cameras only: a LOOK-AHEAD launch (rt_render_again_cameras, RT_OPT_LOOKAHEAD) — the queue family only, accum,
+// mask and m2 NULL: the `count` samples become `count` frames of the ring (queue_replay<true>), whose frame 0 holds the image as
+// it lies (the caller copied it there on the stream), and the accumulator is not touched.  The facts carry moments = 0.
+static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
+                         const BlockMask *mask, float *m2, float4 *ring) {
+    const bool sets = src.set_size != 0u;
+    if (!src.rays) {
+        if (!src.p || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
+    } else {
+        if (!src.p || !accum || src.n < 1u || src.n > (1u << 28) || count < 1u || count > RT_SPP_PER_LAUNCH)
+            return fail(ctx, RT_EINVAL, "a ray launch takes 1 .. 2^28 rays and 1 .. %u samples", RT_SPP_PER_LAUNCH);
+        if (src.set_size > RT_RAY_SET_MAX || (uint64_t)src.n * src.set_size > (1ull << 31))
+            return fail(ctx, RT_EINVAL, "a ray-set launch takes sets of 1 .. %u records, 2^31 records in all", RT_RAY_SET_MAX);
+        if (mask && src.n != (size_t)ctx->width * ctx->height)   // (ray_active reads the block of pixel i: i must be one)
+            return fail(ctx, RT_EINVAL, "a masked ray launch takes one ray per pixel of the %d x %d frame", ctx->width, ctx->height);
+    }
+    FrameParams fp = src.rays ? frame_params(ctx, src.cam0, first, count, glog2, 0, 1)   // (unsharded: slot = ray index)
+                              : frame_params(ctx, src.cam0, first, count, glog2);
+    apply_mask(fp, mask);
+    fp.m2 = m2;
+    if (src.rays) fp.rays = reinterpret_cast<const float4 *>(src.p);
+    else fp.cams = reinterpret_cast<const float *>(src.p);
+    const DeviceScene sc = device_scene(ctx);
+    if (ring) {
+        if (src.rays || !lookahead_ok(ctx, fp, accum, mask, m2) || plan_camera_samples(camera_facts(ctx, sc, fp)).family != RT_CAMERA_PLAN_QUEUE)
+            return fail(ctx, RT_EINVAL, "a look-ahead launch needs the sample queue, an unsharded frame in one slot range and no counters");
+        fp.la_ring = ring;   // (la_image's bytes hold `cams`: the start image is the ring's frame 0)
+    }
+    const uint32_t slots = src.rays ? (uint32_t)src.n : fp.slot_end;
+    if (slots == 0) return RT_OK;
+    refresh_stage_block(ctx, sc);
+    return launch_ranges(ctx, fp, slots, [&]() -> int {
+        const CameraFacts facts = camera_facts(ctx, sc, fp);
+        const CameraPlan plan = plan_camera_samples(facts);
+        const dim3 grid(plan.grid_units), block(plan.block_size);
+        fp.lds_face_f4 = plan.lds_face_f4;
+        if (plan.family == RT_CAMERA_PLAN_QUEUE) {
+            const QueueRow *r = find_queue_row(ctx, src.rays ? "ray" : "camera", plan.accel, plan.geom, plan.waves);
+            if (!r) return RT_ESTATE;
+            hipLaunchKernelGGL(!src.rays ? r->cams[ring != nullptr] : sets ? r->ray_sets : r->rays, grid, block, plan.lds_bytes, ctx->stream,
+                               sc, fp, (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum,
+                               ctx->counters.p, plan.pixels_per_wave);
+        } else if (src.rays) {
+            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u, sets), grid, block, 0, ctx->stream, sc, fp, accum,
+                               ctx->counters.p);
+        } else {
+            hipLaunchKernelGGL(camera_render_kernel(plan.count != 0u, plan.accel != 0u), grid, block, 0, ctx->stream, sc, fp, accum,
+                               ctx->image.p, ctx->counters.p);
+        }
+        if (src.rays) ctx->rays.last_facts = facts, ctx->rays.last_plan = plan;
+        else ctx->cameras.last_facts = facts, ctx->cameras.last_plan = plan;
+        return RT_OK;
+    });
+}
+
+// rt_render_spp_cameras, rt_render_adaptive_cameras, rt_render_again_cameras: `count` blocks at d_cams, cam0 the first of them
+int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
+                   float4 *accum, const BlockMask *mask, float *m2, float4 *ring) {
+    return launch_source(ctx, {false, d_cams, 0u, 0u, cam0}, first, count, glog2, accum, mask, m2, ring);
+}
+// rt_render_rays (set_size 0: one record per ray), rt_render_ray_sets (1 .. RT_RAY_SET_MAX) and their adaptive forms
+int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
+                float4 *accum, const BlockMask *mask, float *m2) {
     float cam0[12] = {};
-    if (sets) {
+    if (set_size) {
         memcpy(&cam0[0], &set_size, sizeof(uint32_t));
         cam0[1] = 1.0f / (float)set_size;
     }
-    if (mask && n != (size_t)ctx->width * ctx->height)   // (ray_active reads the block of pixel i: i must be one)
-        return fail(ctx, RT_EINVAL, "a masked ray launch takes one ray per pixel of the %d x %d frame", ctx->width, ctx->height);
-    FrameParams fp = frame_params(ctx, cam0, first, count, glog2, 0, 1);   // (unsharded: slot = ray index)
-    apply_mask(fp, mask);
-    fp.m2 = m2;
-    fp.rays = reinterpret_cast<const float4 *>(d_rays);
-    const DeviceScene sc = device_scene(ctx);
-    const uint32_t slots = (uint32_t)n;
-    refresh_stage_block(ctx, sc);
-    const uint32_t slots_per_launch = std::max(ctx->max_threads_per_launch >> glog2, 1u);
-    hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
-    HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));   // no first stage
-    for (uint32_t b = 0; b < slots; b += slots_per_launch) {
-        fp.slot_begin = b;
-        fp.slot_end = slots - b > slots_per_launch ? b + slots_per_launch : slots;
-        const CameraFacts facts = camera_facts(ctx, sc, fp);
-        const CameraPlan plan = plan_camera_samples(facts);
-        fp.lds_face_f4 = plan.lds_face_f4;
-        if (plan.family == RT_CAMERA_PLAN_QUEUE) {
-            const QueueKernel kernel = ray_queue_kernel(plan, sets);
-            if (!kernel) return fail(ctx, RT_ESTATE, "no ray instantiation of pt_samples_q for the plan");
-            hipLaunchKernelGGL(kernel, dim3(plan.grid_units), dim3(plan.block_size), plan.lds_bytes, ctx->stream, sc, fp,
-                               (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum, ctx->counters.p,
-                               plan.pixels_per_wave);
-        } else {
-            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u, sets), dim3(plan.grid_units), dim3(plan.block_size), 0,
-                               ctx->stream, sc, fp, accum, ctx->counters.p);
-        }
-        ctx->rays.last_facts = facts;
-        ctx->rays.last_plan = plan;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(evp[1], ctx->stream));
-    ctx->ev_count++;
-    return RT_OK;
-}
-int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                const BlockMask *mask, float *m2) {
-    return launch_rays_or_sets(ctx, d_rays, n, 0u, first, count, glog2, accum, mask, m2);
-}
-int launch_ray_sets(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
-                    float4 *accum, const BlockMask *mask, float *m2) {
-    if (set_size < 1u) return fail(ctx, RT_EINVAL, "a ray set holds at least one record");
-    return launch_rays_or_sets(ctx, d_rays, n, set_size, first, count, glog2, accum, mask, m2);
+    return launch_source(ctx, {true, d_rays, n, set_size, cam0}, first, count, glog2, accum, mask, m2, nullptr);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
@@ -2575,7 +2555,7 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, launch_ray_sets};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays};
 
 }  // namespace
 

@@ -72,21 +72,19 @@ struct KernelSet {
                                    uint32_t follow, uint32_t max_chain, rt_feature *d_out, uint2 *d_cov);
     // rt_debug_plan_feature_cameras: that launcher's geometry for a frame of `pixels` pixels — a pure function, no device
     FeatureCamerasPlan (*plan_feature_cameras)(uint32_t pixels, uint32_t n);
-    // rt_render_rays: samples first .. first+count-1 (count <= RT_SPP_PER_LAUNCH) of the n <= 2^28 rays at d_rays (rt_ray
-    // records on the device), ray i's sum added to accum[i] (updating m2[i]; NULL = no moments): the sample queue's ray
-    // entry, or pt_render_rays where plan_camera_samples says fixed lanes; facts and plan go to rt_context::Rays;
+    // rt_render_rays, rt_render_ray_sets: samples first .. first+count-1 (count <= RT_SPP_PER_LAUNCH) of the n <= 2^28 rays at
+    // d_rays (rt_ray records on the device), ray i's sum added to accum[i] (updating m2[i]; NULL = no moments).  set_size 0:
+    // one record per ray — the sample queue's ray entry, or pt_render_rays where plan_camera_samples says fixed lanes.
+    // set_size 1 .. RT_RAY_SET_MAX: n sets of that many records, ray-major; sample s of ray i starts at record
+    // i * set_size + s % set_size — pt_samples_q_raysets, or pt_render_raysets for fixed lanes.  Facts and plan go to
+    // rt_context::Rays;
     // mask != NULL (rt_render_adaptive_rays; n == W x H, ray i is pixel (i mod W, i div W)): the rays of active decision
     // blocks only, as launch_cameras — the plan and the grid are those of the unmasked launch
-    int (*launch_rays)(rt_context *ctx, const void *d_rays, size_t n, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
-                       const BlockMask *mask, float *m2);
+    int (*launch_rays)(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
+                       float4 *accum, const BlockMask *mask, float *m2);
     // rt_render_features_rays: pt_features_rays, pt_features_chain's record for each of the n rays at d_rays into d_out
     int (*launch_features_rays)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow,
                                 uint32_t max_chain, rt_feature *d_out);
-    // rt_render_ray_sets: launch_rays with n sets of set_size (1 .. RT_RAY_SET_MAX) records at d_rays, ray-major; sample s of
-    // ray i starts at record i * set_size + s % set_size: pt_samples_q_raysets, or pt_render_raysets for fixed lanes;
-    // mask as launch_rays takes it
-    int (*launch_ray_sets)(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count,
-                           uint32_t glog2, float4 *accum, const BlockMask *mask, float *m2);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

@@ -818,6 +818,28 @@ int moments_begin(rt_context *ctx) {
     mo.valid = true;
     return RT_OK;
 }
+
+// Samples first .. first+c-1 of one camera into `target` (and `m2`): the fused launch, or every sample from the camera where
+// prefix sharing is switched off.
+int launch_camera_samples(rt_context *ctx, const float camera[12], uint32_t first, uint32_t c, float4 *target, const BlockMask *mask, float *m2) {
+    return ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), target, mask, m2)
+                               : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), target, mask, m2);
+}
+
+// A call of more than RT_SPP_PER_LAUNCH samples per pixel runs as consecutive launches of that many (the capacity of a
+// wave's sample queue: beyond it a frame would fall back to the fixed-lane kernel, 1.8 x slower — 520 samples took
+// 18.4 ms where 512 take 10.2); the target then holds the sum of those launches' sums, on every path alike.
+// launch(done, c): samples done .. done+c-1 of the call; the first failure ends it.
+template <class Launch>
+int for_each_launch(uint32_t n_samples, Launch launch) {
+    for (uint32_t done = 0; done < n_samples;) {
+        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
+        const int rc = launch(done, c);
+        if (rc != RT_OK) return rc;
+        done += c;
+    }
+    return RT_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -836,20 +858,11 @@ int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample
     if ((uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
         return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // A call of more than RT_SPP_PER_LAUNCH samples per pixel runs as consecutive launches of that many (the capacity of a
-    // wave's sample queue: beyond it a frame would fall back to the fixed-lane kernel, 1.8 x slower — 520 samples took
-    // 18.4 ms where 512 take 10.2); the accumulator then is the sum of those launches' sums, on every path alike.
-    for (uint32_t done = 0; done < n_samples;) {
-        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
-        float *m2 = ctx->moments.target();
-        rc = ctx->prefix_sharing ? ctx->ks->launch_fused(ctx, camera, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr, m2)
-                                 : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first_sample + done, c, group_log2_for(c),
-                                                          ctx->accum.p, nullptr, m2);
-        if (rc != RT_OK) return rc;
-        done += c;
-        ctx->accum_count += c;
-    }
-    return RT_OK;
+    return for_each_launch(n_samples, [&](uint32_t done, uint32_t c) {
+        const int r = launch_camera_samples(ctx, camera, first_sample + done, c, ctx->accum.p, nullptr, ctx->moments.target());
+        if (r == RT_OK) ctx->accum_count += c;
+        return r;
+    });
 }
 
 extern "C++" {
@@ -900,20 +913,16 @@ int rt_render_spp_cameras(rt_context *ctx, const float *cameras, uint32_t first_
         return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_cameras(ctx)) != RT_OK) return rc;
-    // (launches of RT_SPP_PER_LAUNCH blocks, as rt_render_spp cuts its calls: the accumulator is the sum of their sums)
-    for (uint32_t done = 0; done < n_samples;) {
-        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
+    return for_each_launch(n_samples, [&](uint32_t done, uint32_t c) {
         CameraTable tb;
-        if ((rc = camera_table_send(ctx, cameras + (size_t)done * 12u, c, &tb)) != RT_OK) return rc;
-        rc = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr,
-                                     ctx->moments.target(), nullptr);
+        int r = camera_table_send(ctx, cameras + (size_t)done * 12u, c, &tb);
+        if (r != RT_OK) return r;
+        r = ctx->ks->launch_cameras(ctx, tb.d, tb.h, first_sample + done, c, group_log2_for(c), ctx->accum.p, nullptr,
+                                    ctx->moments.target(), nullptr);
         const int rd = camera_table_read(ctx, tb);
-        if (rd != RT_OK) return rd;
-        if (rc != RT_OK) return rc;
-        done += c;
-        ctx->accum_count += c;
-    }
-    return RT_OK;
+        if (rd == RT_OK && r == RT_OK) ctx->accum_count += c;
+        return rd != RT_OK ? rd : r;
+    });
 }
 
 // ---- caller-supplied rays ------------------------------------------------------------------------------------------------
@@ -994,18 +1003,13 @@ int render_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint
     if (n_samples == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float4 *accum = d_accum ? static_cast<float4 *>(d_accum) : ctx->accum.p;
-    // (launches of RT_SPP_PER_LAUNCH samples, as rt_render_spp cuts its calls: the target holds the sum of their sums; a set
-    // is indexed by the absolute sample, so a later launch needs no offset into it)
-    for (uint32_t done = 0; done < n_samples;) {
-        const uint32_t c = n_samples - done < RT_SPP_PER_LAUNCH ? n_samples - done : RT_SPP_PER_LAUNCH;
+    // (a set is indexed by the absolute sample, so a later launch needs no offset into it)
+    return for_each_launch(n_samples, [&](uint32_t done, uint32_t c) {
         float *m2 = d_accum ? nullptr : ctx->moments.target();
-        rc = sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first_sample + done, c, group_log2_for(c), accum, nullptr, m2)
-                  : ctx->ks->launch_rays(ctx, rays, n_rays, first_sample + done, c, group_log2_for(c), accum, nullptr, m2);
-        if (rc != RT_OK) return rc;
-        done += c;
-        if (!d_accum) ctx->accum_count += c;
-    }
-    return RT_OK;
+        const int r = ctx->ks->launch_rays(ctx, rays, n_rays, set_size, first_sample + done, c, group_log2_for(c), accum, nullptr, m2);
+        if (r == RT_OK && !d_accum) ctx->accum_count += c;
+        return r;
+    });
 }
 }  // namespace
 }  // extern "C++"
@@ -1244,9 +1248,7 @@ int render_adaptive(rt_context *ctx, AdaptiveRule rule, const float camera[12], 
     if ((rc = check_adaptive(ctx, rule, p, out, &bwl, &bhl)) != RT_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return adaptive_rounds(ctx, rule, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
-        return ctx->prefix_sharing
-                   ? ctx->ks->launch_fused(ctx, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch)
-                   : ctx->ks->launch_render(ctx, MODE_ACCUM, camera, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+        return launch_camera_samples(ctx, camera, first, c, scratch, mask, m2_scratch);
     });
 }
 
@@ -1285,8 +1287,7 @@ int render_adaptive_rays(rt_context *ctx, AdaptiveRule rule, const void *d_rays,
     if ((rc = check_rays_or_sets(ctx, d_rays, n_rays, set_size, sets, 0u, p->max_spp, nullptr, &rays)) != RT_OK) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return adaptive_rounds(ctx, rule, p, bwl, bhl, out, [&](uint32_t first, uint32_t c, float4 *scratch, const BlockMask *mask, float *m2_scratch) {
-        return sets ? ctx->ks->launch_ray_sets(ctx, rays, n_rays, set_size, first, c, group_log2_for(c), scratch, mask, m2_scratch)
-                    : ctx->ks->launch_rays(ctx, rays, n_rays, first, c, group_log2_for(c), scratch, mask, m2_scratch);
+        return ctx->ks->launch_rays(ctx, rays, n_rays, set_size, first, c, group_log2_for(c), scratch, mask, m2_scratch);
     });
 }
 

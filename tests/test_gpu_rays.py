@@ -131,6 +131,29 @@ def test_520_samples_are_two_launches_and_a_first_sample_of_7(policy):
         t.close()
 
 
+@pytest.mark.parametrize("queue", [1, 0])
+def test_three_slot_ranges_change_no_bit(queue):
+    """A plain ray call cut into slot ranges (RT_OPT_MAX_THREADS_PER_LAUNCH): 24 samples are 32 lanes per ray, so W * H * 32 // 3
+    + 64 threads are 434 rays per range — three ranges, the last one of 428 rays — in the queue and in the fixed-lane family."""
+    wl, _ = workload("c2")
+    n = 24
+    threads = W * H * 32 // 3 + 64
+    t = tracer(wl, 2, OPT_SAMPLE_QUEUE=queue)
+    try:
+        batch = primary_batch(t, wl.camera)
+        want = render_batch(t, batch, 0, n)
+        facts, plan = t.lastRayPlan()
+        assert facts["n"] == W * H and plan["family"] == (QUEUE if queue else FIXED) and want[:, :3].any()
+        t.setOption(T.OPT_MAX_THREADS_PER_LAUNCH, threads)
+        got = render_batch(t, batch, 0, n)
+        facts, plan = t.lastRayPlan()
+        assert facts["n"] < W * H and facts["n"] == W * H - 2 * (threads >> 5), "the last of three slot ranges"
+        assert plan["family"] == (QUEUE if queue else FIXED)
+        assert same_bits(got, want)
+    finally:
+        t.close()
+
+
 # ---- 2. mixed batch and slot independence --------------------------------------------------------------------------------
 @pytest.mark.parametrize("policy", POLICIES)
 def test_mixed_batch_and_slot_independence(policy):
