@@ -141,4 +141,48 @@ std::vector<rt_ray> ray_sets(G generator, const std::vector<float> &offsets, siz
     return out;
 }
 
+// Philox-4x32-10 on the counter (i, stream, 0, 0) with the key (seed lo, seed hi): workloads.uniforms' generator; the first
+// two words as 24-bit uniforms in [0, 1)
+inline void uniforms2(uint32_t i, uint32_t stream, uint64_t seed, double &u, double &v) {
+    uint32_t c0 = i, c1 = stream, c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int round = 0; round < 10; round++) {
+        const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    u = (double)(c0 >> 8) / 16777216.0, v = (double)(c1 >> 8) / 16777216.0;
+}
+
+// Hemisphere sets for RayTracer::occludedRays (rt_occluded_rays; ambient occlusion, visibility bakes): n x k records,
+// ray-major — record i * k + t starts at points[i] + offset * n_i and leaves along a cosine-weighted direction about
+// n_i = normals[i] / |normals[i]| (Malley's method on the uniforms of counter i * k + t, stream 0: the disk point
+// sqrt(u) (cos 2 pi v, sin 2 pi v) lifted to height sqrt(1 - u) > 0).  points, normals: n x 3 floats.  Deterministic;
+// double, rounded once: unit length to 1e-6, dot(n_i, d) > 0.  The ids are (i, 0).  Empty for bad arguments.
+inline std::vector<rt_ray> hemisphere_sets(const std::vector<float> &points, const std::vector<float> &normals, uint32_t k,
+                                           uint64_t seed, double offset = 0.0) {
+    std::vector<rt_ray> out;
+    if (points.size() != normals.size() || points.size() % 3 || k < 1 || k > RT_RAY_SET_MAX) return out;
+    const size_t n = points.size() / 3;
+    out.reserve(n * k);
+    for (size_t i = 0; i < n; i++) {
+        D3 nr = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+        if (!(nr.x * nr.x + nr.y * nr.y + nr.z * nr.z > 0.0)) return {};
+        nr = unit(nr);
+        // a tangent frame: the world axis the normal leans on least, made perpendicular to it
+        const double ax = std::fabs(nr.x), ay = std::fabs(nr.y), az = std::fabs(nr.z);
+        const D3 axis = ax <= ay && ax <= az ? D3{1, 0, 0} : (ay <= az ? D3{0, 1, 0} : D3{0, 0, 1});
+        const D3 tan = unit(cross(nr, axis)), bit = cross(nr, tan);
+        const D3 o = D3{points[3 * i], points[3 * i + 1], points[3 * i + 2]} + offset * nr;
+        for (uint32_t t = 0; t < k; t++) {
+            double u, v;
+            uniforms2((uint32_t)(i * k + t), 0u, seed, u, v);
+            const double rad = std::sqrt(u), phi = 2.0 * 3.14159265358979323846 * v;
+            const D3 d = unit((rad * std::cos(phi)) * tan + (rad * std::sin(phi)) * bit + std::sqrt(1.0 - u) * nr);
+            out.push_back(pack(o, d, (uint32_t)i, 0u));
+        }
+    }
+    return out;
+}
+
 }  // namespace rays

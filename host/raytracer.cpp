@@ -89,6 +89,52 @@ void RayTracer::renderFeaturesRays(uint32_t follow, uint32_t max_chain) {
     check(rt_render_features_rays(ctx, nullptr, (size_t)width * height, &p));
 }
 
+namespace {
+// a block of device memory for the results of a ray query, from the library (the façade has no HIP runtime of its own)
+struct DeviceBlock {
+    rt_context *ctx;
+    void *p = nullptr;
+    DeviceBlock(rt_context *c, size_t bytes, int *rc) : ctx(c) { *rc = rt_device_alloc(c, bytes, &p); }
+    ~DeviceBlock() { (void)rt_device_free(ctx, p); }
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+};
+}  // namespace
+
+std::vector<rt_feature> RayTracer::intersectRays(const std::vector<rt_ray> &batch, uint32_t follow, uint32_t max_chain) {
+    uploadRays(batch);
+    std::vector<rt_feature> out(batch.size());
+    int rc = RT_OK;
+    DeviceBlock d(ctx, out.size() * sizeof(rt_feature), &rc);
+    check(rc);
+    const rt_feature_chain_params p{follow, max_chain};
+    check(rt_intersect_rays(ctx, nullptr, batch.size(), &p, d.p));
+    check(rt_device_copy(ctx, out.data(), d.p, out.size() * sizeof(rt_feature), 0));   // (behind the query on the stream)
+    return out;
+}
+
+std::vector<uint32_t> RayTracer::occludedRays(const std::vector<rt_ray> &records, uint32_t set_size, float t_max,
+                                              const std::vector<float> *bounds) {
+    if (set_size == 0 || records.empty() || records.size() % set_size || (bounds && bounds->size() != records.size()))
+        throw RayTracerError(RT_EINVAL, "occludedRays takes whole sets of set_size records and one bound per record");
+    uploadRays(records);
+    std::vector<uint32_t> out(records.size() / set_size);
+    int rc = RT_OK;
+    DeviceBlock d(ctx, out.size() * sizeof(uint32_t), &rc);
+    check(rc);
+    if (!bounds) {
+        check(rt_occluded_rays(ctx, nullptr, out.size(), set_size, nullptr, t_max, d.p));
+    } else {
+        DeviceBlock b(ctx, bounds->size() * sizeof(float), &rc);
+        check(rc);
+        check(rt_device_copy(ctx, b.p, bounds->data(), bounds->size() * sizeof(float), 1));
+        check(rt_occluded_rays(ctx, nullptr, out.size(), set_size, static_cast<const float *>(b.p), t_max, d.p));
+        check(rt_sync(ctx));   // (the bounds are read until the query has run)
+    }
+    check(rt_device_copy(ctx, out.data(), d.p, out.size() * sizeof(uint32_t), 0));
+    return out;
+}
+
 const float *RayTracer::renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp) {
     uploadRays(batch);
     check(rt_clear(ctx));

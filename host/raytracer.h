@@ -5,6 +5,7 @@
 // reference does (src/kernelgl.cpp:47-56), unless exceptions are enabled with
 // RayTracer::throwOnError(true).
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -75,6 +76,17 @@ public:
     void renderRays(uint32_t first_sample, uint32_t n_samples);
     void renderFeaturesRays(uint32_t follow = 0, uint32_t max_chain = 0);
     const float *renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp);  // upload + clear + renderRays + resolve + read back
+    // ray queries (rt_intersect_rays, rt_occluded_rays): the geometric questions beside renderRays, for ANY batch.  The
+    // image, the accumulator and the feature records stay as they are — but BOTH CALLS REPLACE THE UPLOADED RAYS: the batch
+    // goes through uploadRays into the context's ray buffer, so a caller who uploaded a frame's rays before (renderRays,
+    // renderFeaturesRays, the adaptive ray calls) uploads them again afterwards.  The device buffers the query writes come
+    // from the library (rt_device_alloc); the calls wait for the query and return its results.  intersectRays: ray i's
+    // rt_feature record as renderFeaturesRays / renderFeaturesChain writes it.  occludedRays: `records` holds sets of set_size
+    // records, ray-major (rays::hemisphere_sets makes them); → per set the number of records whose first hit lies below its
+    // bound, (*bounds)[k] or, with bounds null, t_max for every record (+inf: any hit)
+    std::vector<rt_feature> intersectRays(const std::vector<rt_ray> &batch, uint32_t follow = 0, uint32_t max_chain = 0);
+    std::vector<uint32_t> occludedRays(const std::vector<rt_ray> &records, uint32_t set_size = 1, float t_max = INFINITY,
+                                       const std::vector<float> *bounds = nullptr);
     // ray sets (rt_render_ray_sets; rays::ray_sets makes them): the uploaded records are w x h sets of set_size records,
     // ray-major, and sample s of pixel i starts at record s mod set_size of its set — anti-aliasing for any projection
     void renderRaySets(uint32_t set_size, uint32_t first_sample, uint32_t n_samples);

@@ -69,6 +69,11 @@
 // --split-chains adds RT_DENOISE_SPLIT_CHAINS, so that pixels whose chains differ in length or objects never mix.
 // --aov then writes the chain's records and also PREFIX_chain.pfm: per pixel (followed vertices, the signature's upper
 // half as a number 0 .. 65535, 1 where the chain was cut at --max-chain).
+// --ao K [--ao-distance D] (with --aov, first-hit guides: not with --follow or --aa-guides) adds ambient occlusion by the ray
+// queries: K cosine-weighted hemisphere rays from every pixel's first hit (rays::hemisphere_sets, origin on the surface),
+// one rt_occluded_rays call with set_size K and the bound D (default +inf: any hit), PREFIX_ao.pfm = 1 - count / K and 1
+// where the pixel's primary ray missed.  The rays take 32 B x W x H x K of host and of device memory, and take the place of
+// the uploaded rays of a --projection frame (nothing after this step reads those).
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -100,7 +105,9 @@ static void usage() {
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K] "
-                 "[--adaptive THRESHOLD ...]]\n";
+                 "[--adaptive THRESHOLD ...]] [--ao K [--ao-distance D]]\n"
+                 "  --ao K (1 .. 4096, with --aov): PREFIX_ao.pfm from K hemisphere rays per first hit, bound D (default inf);"
+                 " its rays take 32 B x W x H x K of host and of device memory\n";
     std::exit(2);
 }
 
@@ -199,6 +206,9 @@ int main(int argc, char **argv) {
     float fov_deg = 180.0f, extent = 10.0f;
     bool fov_deg_given = false, extent_given = false;
     long ray_set = 0;   // (0: one record per pixel)
+    long ao = 0;        // (0: no ambient occlusion)
+    float ao_distance = INFINITY;
+    bool ao_distance_given = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -251,6 +261,13 @@ int main(int argc, char **argv) {
         else if ((v = val("--sigma"))) { parse_sigmas(v, sigmas); sigmas_given = true; }
         else if ((v = val("--follow"))) follow = parse_follow(v);
         else if ((v = val("--max-chain"))) max_chain = parse_int(v, 0, RT_FEATURE_CHAIN_MAX);
+        else if ((v = val("--ao"))) ao = parse_int(v, 1, (long)RT_RAY_SET_MAX);
+        else if ((v = val("--ao-distance"))) {
+            char *end = nullptr;
+            ao_distance = std::strtof(v, &end);
+            ao_distance_given = true;
+            if (!*v || *end || !(ao_distance > 0.0f)) usage();
+        }
         else if ((v = val("--aov"))) { aov_prefix = v; if (aov_prefix.empty()) usage(); }
         else if ((v = val("--aperture"))) {
             char *end = nullptr;
@@ -298,6 +315,8 @@ int main(int argc, char **argv) {
     if (follow && !denoise && aov_prefix.empty()) usage();                 // --follow guides --denoise and / or fills --aov
     if ((max_chain >= 0 || split_chains) && !follow) usage();
     if (split_chains && !denoise) usage();
+    if (ao && (aov_prefix.empty() || follow || aa_guides)) usage();        // --ao fills --aov from first-hit records
+    if (ao_distance_given && !ao) usage();
     if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
     if (progressive_cameras && (progressive || adaptive || adaptive_cameras || denoise)) usage();   // one way to spend the samples; the running mean lives in the image
     if (!progressive && !progressive_cameras && lookahead >= 0) usage();   // progressive-only flag
@@ -467,6 +486,28 @@ int main(int argc, char **argv) {
                 c3[3 * i + 1] = cv[2 * i + 1];
             }
             write_pfm(aov_prefix + "_coverage.pfm", c3.data(), 3, 0, 3, w, h);
+        }
+        if (ao) {   // ambient occlusion: K hemisphere rays per first hit, counted by one occlusion query
+            std::vector<float> points, normals;
+            std::vector<size_t> pixel;
+            for (size_t i = 0; i < f.size(); i++)
+                if (f[i].flags & RT_FEATURE_HIT) {
+                    pixel.push_back(i);
+                    points.insert(points.end(), f[i].pos, f[i].pos + 3);
+                    // (the record's normal is the hit routine's: turned to the side the ray came from)
+                    const float *nr = f[i].normal, *dr = f[i].dir;
+                    const float side = nr[0] * dr[0] + nr[1] * dr[1] + nr[2] * dr[2] > 0.0f ? -1.0f : 1.0f;
+                    for (int c = 0; c < 3; c++) normals.push_back(side * nr[c]);
+                }
+            std::vector<float> open((size_t)w * h, 1.0f);
+            if (!pixel.empty()) {
+                auto a0 = std::chrono::steady_clock::now();
+                const std::vector<uint32_t> count = tracer.occludedRays(rays::hemisphere_sets(points, normals, (uint32_t)ao, seed), (uint32_t)ao, ao_distance);
+                for (size_t j = 0; j < pixel.size(); j++) open[pixel[j]] = 1.0f - (float)count[j] / (float)ao;
+                std::cout << "ambient occlusion: " << ao << " rays from each of " << pixel.size() << " hits, bound " << ao_distance << ": "
+                          << std::chrono::duration<double>(std::chrono::steady_clock::now() - a0).count() * 1e3 << " ms incl. ray generation and read-back" << std::endl;
+            }
+            write_pfm(aov_prefix + "_ao.pfm", open.data(), 1, 0, 1, w, h);
         }
         if (rule_variance) write_pfm(aov_prefix + "_error.pfm", tracer.pixelError().data(), 1, 0, 1, w, h);
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);

@@ -615,6 +615,55 @@ int rt_render_features_rays(rt_context *ctx, const void *d_rays, size_t n_rays, 
 int rt_feature_chain_signature(const uint32_t *objects, uint32_t n, uint32_t *sig_out);   /* host-only, no context */
 
 /*
+ * Ray queries (new): the two geometric questions beside the radiance query rt_render_rays — for bakes, pickers, visibility
+ * passes.  Both are asynchronous on the context's stream and leave the context as it is: its feature records with their
+ * ready and coverage state (on a fresh context rt_read_features is still RT_ESTATE afterwards), the image, the accumulator,
+ * the sample counter, the moments, a kept prefix, pending look-ahead frames and the counters.  RT_ESTATE: no scene set.  A
+ * failed call writes nothing.
+ *
+ * rt_intersect_rays: nearest hits for ANY batch.  Record i of d_out (n_rays rt_feature records on the device, 16-byte
+ * aligned) is, bit for bit, the record rt_render_features_rays / rt_render_features_chain would write for ray i (p NULL =
+ * first hits): the 80-byte layout, the miss values, the chain flags and `dir` as given.  n_rays: 1 .. RT_MAX_RAYS; d_rays
+ * NULL = the uploaded rays, at least n_rays of them.  Record i depends on ray i only — not on its slot, its neighbours or
+ * the length of the batch.  RT_EINVAL: a NULL ctx or d_out, a misaligned pointer, n_rays 0 or above RT_MAX_RAYS, NULL
+ * d_rays with too few rays uploaded, unknown follow bits, max_chain above RT_FEATURE_CHAIN_MAX, a sharded context.
+ */
+int rt_intersect_rays(rt_context *ctx, const void *d_rays, size_t n_rays, const rt_feature_chain_params *p, void *d_out);
+
+/*
+ * rt_occluded_rays: occlusion (any hit).  d_rays: n_rays * set_size rt_ray records, ray-major as in rt_render_ray_sets — the
+ * set of entry i is records i*set_size .. i*set_size + set_size-1; NULL = the uploaded records; set_size 1 ..
+ * RT_RAY_SET_MAX, 1 being the plain per-ray query; the fields x, y of a record are not read.  With F(r) the first-hit record
+ * rt_render_features_rays writes for r under the selected arithmetic policy (p NULL; F(r).t = +inf on a miss), record k
+ * with bound b_k — d_tmax[k] (n_rays * set_size floats on the device), or t_max for every record where d_tmax is NULL —
+ *   is occluded  iff  F(record k).t < b_k   in binary32.
+ * A NaN bound, a bound <= RT_MIN_DISTANCE or a negative one never occludes; +inf asks for any hit; a hit at exactly b_k does
+ * not occlude.  Directions are used as given, so t is in units of |d|; the guard against self-intersection is the hit
+ * routines' own RT_MIN_DISTANCE.  The query is geometric: glass and lights occlude like anything else.
+ * d_out[i] (n_rays uint32 on the device) = the number of occluded records of set i — 0 or 1 for set_size 1; OVERWRITTEN, not
+ * added to.  The search stops at the first primitive that reports a t below min(b_k, RT_MAX_DISTANCE), which is exact: the
+ * nearest hit is below the bound iff some sphere, plane, lens or mesh reports a t below it (a mesh reports its first
+ * front-facing face in face order, as ever).  RT_OPT_ACCEL is honoured and changes no bit; rt_walk_overflow reports these
+ * walks too.
+ * RT_EINVAL: everything rt_render_ray_sets refuses for its ray arguments (n_rays 0 or above RT_MAX_RAYS, set_size 0 or above
+ * RT_RAY_SET_MAX, n_rays * set_size above 2^31, a misaligned d_rays, too few uploaded records, a sharded context), a NULL
+ * d_out, a d_out or d_tmax that is not 4-byte aligned.
+ */
+int rt_occluded_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, const float *d_tmax, float t_max,
+                     void *d_out);
+
+/*
+ * Device memory for a host that has no HIP runtime of its own (new) — the buffers the ray queries write into, as the C++
+ * façade of host/ makes them.  rt_device_alloc: `bytes` > 0 of memory on the context's device (hipMalloc's alignment), owned by the
+ * caller until rt_device_free (NULL is fine; waits for the work that uses the block).  rt_device_copy: `bytes` from `src` to
+ * `dst`, to_device != 0: host to device, 0: device to host — ordered on the context's stream behind the calls before it, and
+ * complete on return.  RT_EINVAL: a NULL ctx, a NULL pointer to fill or copy, bytes 0 for an allocation.  RT_EHIP: no memory.
+ */
+int rt_device_alloc(rt_context *ctx, size_t bytes, void **d_out);
+int rt_device_free(rt_context *ctx, void *d_ptr);
+int rt_device_copy(rt_context *ctx, void *dst, const void *src, size_t bytes, int to_device);
+
+/*
  * Feature records through per-sample cameras (new): the guides that belong to an rt_render_spp_cameras frame.  One call
  * renders the feature records of n_cameras camera blocks per pixel (cameras[12*j .. 12*j+11], host pointer, copied at the
  * call) and reduces them on the device to ONE record per pixel, in rt_feature's layout, plus a two-channel coverage buffer.

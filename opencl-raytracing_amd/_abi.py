@@ -381,6 +381,60 @@ def check_ray_target(t, n):
         raise ValueError("out must be a contiguous device tensor")
 
 
+def check_ray_bounds(t, records):
+    """The per-record bounds of occludedRays: a torch float32 contiguous device tensor of `records` elements — (records,),
+    or (n_rays, set_size) with n_rays * set_size == records.  ValueError otherwise, before any library call."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("bounds must be a torch tensor on the device")
+    if t.dtype != torch.float32:
+        raise ValueError("bounds must be float32, not %s" % t.dtype)
+    if t.dim() not in (1, 2) or t.numel() != int(records):
+        raise ValueError("bounds must hold one float per record (%d), not shape %s" % (records, tuple(t.shape)))
+    if not t.is_contiguous() or t.device.type != "cuda":
+        raise ValueError("bounds must be a contiguous device tensor")
+
+
+FEATURE_FLOATS = 20   # an rt_feature record as float32 words (FEATURE.itemsize / 4)
+
+
+def check_feature_target(t, n):
+    """The output of intersectRays: a torch (n, 20) float32 contiguous device tensor (n rt_feature records).  ValueError
+    otherwise."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("out must be a torch tensor on the device")
+    if t.dtype != torch.float32 or tuple(t.shape) != (int(n), FEATURE_FLOATS):
+        raise ValueError("out must be float32 of shape (%d, %d), not %s %s" % (n, FEATURE_FLOATS, t.dtype, tuple(t.shape)))
+    if not t.is_contiguous() or t.device.type != "cuda":
+        raise ValueError("out must be a contiguous device tensor")
+
+
+def check_count_target(t, n):
+    """The output of occludedRays: a torch (n,) int32 contiguous device tensor.  ValueError otherwise."""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError("out must be a torch tensor on the device")
+    if t.dtype != torch.int32 or tuple(t.shape) != (int(n),):
+        raise ValueError("out must be int32 of shape (%d,), not %s %s" % (n, t.dtype, tuple(t.shape)))
+    if not t.is_contiguous() or t.device.type != "cuda":
+        raise ValueError("out must be a contiguous device tensor")
+
+
+def feature_records(t):
+    """intersectRays' (n, 20) float32 tensor → (n,) FEATURE records on the host (a copy; the caller has synchronised)."""
+    return np.ascontiguousarray(t.detach().cpu().numpy()).view(FEATURE).reshape(-1)
+
+
 def ray_prototypes(lib):
     """ctypes prototypes of the caller-supplied-ray entry points (rt_render_rays & co.)."""
     vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
@@ -392,6 +446,11 @@ def ray_prototypes(lib):
     lib.rt_debug_last_ray_plan.argtypes = [vp, C.POINTER(CameraFacts), C.POINTER(CameraPlan)]
     lib.rt_render_adaptive_rays.argtypes = [vp, vp, sz, u32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
     lib.rt_render_adaptive_variance_rays.argtypes = [vp, vp, sz, u32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
+    lib.rt_intersect_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams), vp]
+    lib.rt_occluded_rays.argtypes = [vp, vp, sz, u32, vp, C.c_float, vp]
+    lib.rt_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
+    lib.rt_device_free.argtypes = [vp, vp]
+    lib.rt_device_copy.argtypes = [vp, vp, vp, sz, C.c_int]
 
 
 # the caps of the sample kernels' LDS tables (csrc/pt_types.hpp PT_LDS_MATERIALS, PT_LDS_WINNERS, PT_LDS_PLANES)

@@ -821,6 +821,153 @@ PT_DEV bool hit_scene(const Ctx &c, const Ray &r, Hit &hit) {
     return hit_finish<COUNT>(c, r, nb, hit);
 }
 
+// ---- occlusion (any hit) ----------------------------------------------------------
+// rt_occluded_rays asks whether hit_scene's t is below a bound b, and for nothing else.  With B = min(b, MAX_DISTANCE)
+// that is: SOME sphere, plane, lens or mesh reports a t < B — the nearest search only ever takes a t that is below
+// MAX_DISTANCE (strict '<' from there), and the minimum of the reports is below B iff one of them is.  So the reports
+// may be asked in any order and the search may stop at the first one below B; each report is the hit routine's own
+// (sphere_t, plane_t, lens_t, and a mesh's first front-facing face in face order — which neither B nor "any face" may
+// cut short).  Every report is >= MIN_DISTANCE (in_range, lens_t), so a bound at or below it, or a NaN, never occludes.
+
+// hit_spheres_bvh's threaded walk, its margins unchanged, asked "is a sphere below B?": the pruning bound is B from the
+// start, and a lane leaves the tree at its first leaf sphere with t < B — no winner, no tie-break, no index.
+PT_DEV bool occluded_spheres_bvh(const DeviceScene &sc, const Ray &r, const float B) {
+    float dd = dot(r.d, r.d);
+    float c_ray = 2.0e-6f + 2.0f * fabsf(dd - 1.0f) * (__builtin_amdgcn_rcpf(fminf(dd, 1.0f)) * 1.000002f);
+    float k_ray = __builtin_amdgcn_sqrtf(2.0f * c_ray) * 1.02f;
+    float o_max = fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z));
+    V3 inv = cull_inverse(r.d);
+    const uint32_t oct = (r.d.x < 0.0f ? 1u : 0u) | (r.d.y < 0.0f ? 2u : 0u) | (r.d.z < 0.0f ? 4u : 0u);
+    const float beyond = __builtin_fmaf(B, 1.00001f, 1.0e-2f);   // a box that starts past this holds no sphere below B
+    uint32_t cur = 1u;
+    bool occ = false, at_leaf = false;
+    uint32_t leaf_b = 0, leaf_skip = 0;
+    for (uint32_t guard = 0; guard < (PT_SPHERE_LEAF_EVERY + 1u) * sc.bvh_node_count + 8u; guard++) {
+        if (cur != PT_BVH_END && !at_leaf) {
+            float4 a = *at32(sc.bvh_nodes, cur << 4);
+            float4 b = *at32(sc.bvh_links, (cur << 7) + (oct << 4));
+            uint32_t A = __float_as_uint(b.x) & 0x30000000u, Bw = __float_as_uint(a.w), skip = __float_as_uint(b.x) & PT_BVH_END;
+            asm("" : "+v"(A), "+v"(Bw), "+v"(skip));   // (both header words with the box: hit_spheres_bvh)
+            const V3 dc = mk(a.x - r.o.x, a.y - r.o.y, a.z - r.o.z);
+            const V3 h = mk(b.y, b.z, b.w);
+            float fx = fabsf(dc.x) + h.x, fy = fabsf(dc.y) + h.y, fz = fabsf(dc.z) + h.z;
+            float dfar = __builtin_amdgcn_sqrtf(__builtin_fmaf(fz, fz, __builtin_fmaf(fy, fy, fx * fx))) * 1.001f;
+            float m = __builtin_fmaf(k_ray, dfar, __builtin_fmaf(1.0e-5f, dfar + o_max, 1.0e-6f));
+            float tcx = dc.x * inv.x, tcy = dc.y * inv.y, tcz = dc.z * inv.z;
+            float tex = (h.x + m) * fabsf(inv.x), tey = (h.y + m) * fabsf(inv.y), tez = (h.z + m) * fabsf(inv.z);
+            float tmin = fmaxf(fmaxf(tcx - tex, tcy - tey), tcz - tez), tmax = fminf(fminf(tcx + tex, tcy + tey), tcz + tez);
+            bool miss = tmin > __builtin_fmaf(fabsf(tmax), 1.0e-5f, tmax) + 1.0e-4f || tmax < -1.0e-2f || tmin > beyond;
+            if (miss) {
+                cur = skip;
+            } else if (Bw & 0x80000000u) {
+                at_leaf = true;
+                leaf_b = Bw;
+                leaf_skip = skip;
+            } else {
+                cur = Bw + ((oct >> ((A >> 28) & 3u)) & 1u);
+            }
+        }
+        // ---- leaf phase (wave-uniform decision)
+        bool flush = (guard & (PT_SPHERE_LEAF_EVERY - 1u)) == PT_SPHERE_LEAF_EVERY - 1u || __all(at_leaf || cur == PT_BVH_END);
+        if (flush && __any(at_leaf)) {
+            if (at_leaf) {
+                uint32_t first = leaf_b & 0x0FFFFFFFu, cnt = (leaf_b >> 28) & 7u;
+                for (uint32_t k = 0; k < cnt; k++) occ |= sphere_t(r, *at32(sc.bvh_sph, (first + k) << 4)) < B;
+                at_leaf = false;
+                cur = occ ? PT_BVH_END : leaf_skip;   // the answer is known: out of the tree
+            }
+        }
+        if (__all(cur == PT_BVH_END)) break;
+    }
+    if (cur != PT_BVH_END || at_leaf) atomicOr(sc.walk_overflow, PT_OVF_SPHERE_WALK);   // (cold: hit_spheres_bvh)
+    return occ;
+}
+
+// Is a mesh's report — its first front-facing face in face order, hit_models' very search — below B in some model?
+template <bool ACCEL>
+PT_DEV bool occluded_models(const DeviceScene &sc, const Ray &r, const float B) {
+    bool occ = false;
+    for (uint32_t mo = 0; mo < (PT_NO_MODELS ? 0u : sc.model_count); mo++) {
+        const rt_model &model = sc.models[mo];
+        for (uint32_t k = 0; k < model.mesh_count; k++) {
+            const uint32_t mi = model.mesh_anchor + k;
+            const rt_mesh &mesh = sc.meshes[mi];
+            bool found = false;
+            float ft = 0.0f, fu = 0.0f, fv = 0.0f;
+            const uint32_t root = (ACCEL && sc.mesh_bvh_root) ? sc.mesh_bvh_root[mi] : PT_MESH_BVH_NONE;
+            if (!occ) {   // (a lane that has its answer idles)
+                if (ACCEL && root != PT_MESH_BVH_NONE) {
+                    uint32_t best = mesh.face_count;
+                    (void)mesh_bvh_walk<0>(sc, r, root, best, ft, fu, fv, nullptr);
+                    found = best < mesh.face_count;
+                } else {
+                    const float4 *fr = sc.faces + 3u * (size_t)sc.mesh_face_base[mi];
+                    float4 q0 = fr[0], q1 = fr[1], q2 = fr[2];
+                    for (uint32_t f = 0; f < mesh.face_count; f++) {
+                        fr += 3;  // the array ends with a dummy record, so this prefetch stays in bounds
+                        float4 p0 = fr[0], p1 = fr[1], p2 = fr[2];
+                        if (!found) {
+                            float u, v;
+                            float t = triangle_t(r, mk(q0.x, q0.y, q0.z), mk(q0.w, q1.x, q1.y), mk(q1.z, q1.w, q2.x), &u, &v);
+                            if (t < PT_MISS && dot(mk(q2.y, q2.z, q2.w), r.d) < 0.0f) {
+                                found = true;
+                                ft = t;
+                            }
+                        }
+                        q0 = p0; q1 = p1; q2 = p2;
+                        if (__all(found)) break;
+                    }
+                }
+                occ = found && ft < B;
+            }
+            if (__all(occ)) return true;
+        }
+    }
+    return occ;
+}
+
+// One record of rt_occluded_rays: planes, spheres, lenses, models — cheapest first, leaving where the whole wave is done.
+// `done` on entry: the lanes without a record, or whose bound no report can be below.
+template <bool ACCEL>
+PT_DEV bool occluded_scene(const DeviceScene &sc, const Ray &r, const float B, const bool skip) {
+    bool occ = false;
+    if (__all(skip)) return false;
+    for (uint32_t i = 0; i < sc.plane_count; i++) {
+        const rt_plane &p = sc.planes[i];
+        occ |= plane_t(r, ld3(p.pos), ld3(p.normal)) < B;
+    }
+    if (__all(occ || skip)) return occ && !skip;
+    // spheres: through the BVH when one was built, for lanes whose direction is (nearly) unit length (hit_primitives)
+    bool brute = true;
+    if (ACCEL && sc.bvh_node_count) {
+        float dd = dot(r.d, r.d);
+        brute = !(fabsf(dd - 1.0f) < 0.25f);
+        if (!brute && !occ && !skip) occ = occluded_spheres_bvh(sc, r, B);
+    }
+    if (brute && !occ && !skip && sc.sphere_batches) {
+        const float4 *sp = sc.sph4;
+        float4 a0 = sp[0], a1 = sp[1], a2 = sp[2], a3 = sp[3];
+        for (uint32_t b = 0; b < sc.sphere_batches; b++) {
+            sp += PT_SPHERE_BATCH;  // the array ends with one dummy batch, so this prefetch is always in bounds
+            float4 n0_ = sp[0], n1_ = sp[1], n2_ = sp[2], n3_ = sp[3];
+            occ |= sphere_t(r, a0) < B;
+            occ |= sphere_t(r, a1) < B;
+            occ |= sphere_t(r, a2) < B;
+            occ |= sphere_t(r, a3) < B;
+            a0 = n0_; a1 = n1_; a2 = n2_; a3 = n3_;
+            if (__all(occ)) break;
+        }
+    }
+    if (__all(occ || skip)) return occ && !skip;
+    for (uint32_t i = 0; i < sc.lens_count; i++) {
+        int which;
+        occ |= lens_t(r, sc.lenses[i], &which) < B;
+    }
+    if (__all(occ || skip)) return occ && !skip;
+    if (!occ && !skip) occ = occluded_models<ACCEL>(sc, r, B);
+    return occ && !skip;
+}
+
 // ---- materials -------------------------------------------------------------------
 // :401-405
 PT_DEV float schlick(float cosine, float r0) { return mad(1.0f - r0, pow5(1.0f - cosine), r0); }   // r0 + (1 - r0) * pow(1 - cai, 5)

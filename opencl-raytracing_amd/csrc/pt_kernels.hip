@@ -1653,6 +1653,47 @@ __global__ __launch_bounds__(256) void pt_features_rays(DeviceScene sc, const fl
     o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
 }
 
+// Occlusion queries (rt_occluded_rays): one lane per record k of n sets x set_size records, ray-major.  The record is
+// occluded iff pt_features_rays' first-hit t for it is below its bound — tmax[k], or t_max where tmax is NULL —
+// (occluded_scene, pt_device.hpp: the search stops at the first report below the bound; no materials, no record).
+// set_size 1: out[k] = 0 | 1, a plain store.  Otherwise out (zeroed on the stream before the launch) receives one integer
+// atomicAdd per run of lanes of a wave that share a set — records are consecutive, so a set's lanes are — with the
+// run's count from the ballot: integer sums, the same whatever the order.  No lane leaves before the ballot.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_occluded(DeviceScene sc, const float4 *__restrict__ rays, const float *__restrict__ tmax,
+                                                   float t_max, uint32_t records, uint32_t set_size, uint32_t *__restrict__ out) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;   // (records <= 2^31: the grid covers them in 32 bits)
+    const bool live = k < records;
+    Ray r;
+    r.o = r.d = mk(0.0f, 0.0f, 0.0f);
+    float b = 0.0f;
+    if (live) {
+        const float4 ro = rays[2u * (size_t)k], rd = rays[2u * (size_t)k + 1u];
+        r.o = mk(ro.x, ro.y, ro.z);
+        r.d = mk(rd.x, rd.y, rd.z);
+        b = tmax ? tmax[(size_t)k] : t_max;
+    }
+    // B = min(b, MAX_DISTANCE); a NaN bound or one at or below MIN_DISTANCE is below no report
+    const float B = b < RT_MAX_DISTANCE ? b : RT_MAX_DISTANCE;
+    const bool skip = !live || !(b > RT_MIN_DISTANCE);
+    const bool occ = occluded_scene<ACCEL>(sc, r, B, skip);
+    if (set_size == 1u) {
+        if (live) out[(size_t)k] = occ ? 1u : 0u;
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u, set = k / set_size;
+    const uint32_t before = (uint32_t)__shfl_up((int)set, 1);
+    const bool head = live && (lane == 0u || before != set);
+    const unsigned long long occ_m = __ballot(occ), heads = __ballot(head);
+    if (head) {   // this lane's run ends before the next head (lanes past the last record are not occluded)
+        const unsigned long long above = lane == 63u ? 0ull : heads >> (lane + 1u);
+        const uint32_t len = above ? (uint32_t)__builtin_ctzll(above) + 1u : 64u - lane;
+        const unsigned long long run = (len == 64u ? ~0ull : (1ull << len) - 1ull) << lane;
+        const uint32_t count = (uint32_t)__popcll(occ_m & run);
+        if (count) atomicAdd(out + (size_t)set, count);
+    }
+}
+
 // Feature records through per-sample cameras (rt_render_features_cameras): lane j < n of a pixel's g = 2^glog2 lanes (one
 // wave holds whole pixels) looks through block j of fp.cams and runs pt_features_chain's loop — the same search, scatter
 // and flags, duplicated here so that the single-camera kernel keeps its code — into five registers instead of memory.
@@ -2489,6 +2530,20 @@ int ks_launch_features_rays(rt_context *ctx, const DeviceScene &sc, const void *
     return RT_OK;
 }
 
+// rt_occluded_rays: pt_occluded over n sets of set_size records; the counts of sets of more than one record are summed
+// into d_out by atomics, so it is zeroed on the stream first
+int ks_launch_occluded(rt_context *ctx, const DeviceScene &sc, const void *d_rays, size_t n, uint32_t set_size, const float *d_tmax,
+                       float t_max, uint32_t *d_out) {
+    const size_t records = n * set_size;
+    if (!d_rays || !d_out || n < 1u || set_size < 1u || records > ((size_t)1 << 31))
+        return fail(ctx, RT_EINVAL, "an occlusion launch needs rays, an output and at most 2^31 records");
+    if (set_size > 1u) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, n * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_occluded<true> : pt_occluded<false>, dim3((uint32_t)((records + 255u) / 256u)), dim3(256),
+                       0, ctx->stream, sc, reinterpret_cast<const float4 *>(d_rays), d_tmax, t_max, (uint32_t)records, set_size, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -2555,7 +2610,7 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, ks_launch_occluded};
 
 }  // namespace
 

@@ -85,6 +85,11 @@ struct KernelSet {
     // rt_render_features_rays: pt_features_rays, pt_features_chain's record for each of the n rays at d_rays into d_out
     int (*launch_features_rays)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow,
                                 uint32_t max_chain, rt_feature *d_out);
+    // rt_occluded_rays: pt_occluded, for each of the n sets of set_size >= 1 rt_ray records at d_rays (ray-major, at most
+    // 2^31 records) the number of records whose first hit lies below the record's bound — d_tmax[k], or t_max where
+    // d_tmax is NULL — into d_out[set] (n uint32, overwritten)
+    int (*launch_occluded)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, size_t n, uint32_t set_size,
+                           const float *d_tmax, float t_max, uint32_t *d_out);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

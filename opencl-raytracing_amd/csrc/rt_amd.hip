@@ -974,16 +974,25 @@ const void *ray_source(rt_context *ctx, const void *d_rays, size_t n_rays) {
 
 extern "C++" {
 namespace {
+// The rules of the ray arguments alone, which the ray queries share: RT_OK and the number of records in *records_out
+int check_ray_records(rt_context *ctx, const char *call, size_t n_rays, uint32_t set_size, bool sets, size_t *records_out) {
+    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "rays on a sharded context (rank %d of %d): shard the batch instead", ctx->rank, ctx->world);
+    if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "%s takes 1 .. %u rays", call, RT_MAX_RAYS);
+    if (sets && (set_size == 0 || set_size > RT_RAY_SET_MAX)) return fail(ctx, RT_EINVAL, "a ray set holds 1 .. %u records, not %u", RT_RAY_SET_MAX, set_size);
+    const size_t records = sets ? n_rays * set_size : n_rays;   // (<= 2^28 * 2^12: no overflow)
+    if (records > ((size_t)1 << 31)) return fail(ctx, RT_EINVAL, "%zu rays x %u records exceed 2^31 records", n_rays, set_size);
+    *records_out = records;
+    return RT_OK;
+}
+
 // The argument rules of a ray call (after check_ready): rt_render_rays (sets false), rt_render_ray_sets (set_size 1 ..
 // RT_RAY_SET_MAX) and the adaptive ray calls, which pass their whole sample range and a NULL d_accum.  RT_OK and the ray
 // buffer in *rays_out, or an RT_* code recorded on the context.
 int check_rays_or_sets(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, bool sets, uint32_t first_sample,
                        uint32_t n_samples, void *d_accum, const void **rays_out) {
-    if (ctx->world > 1) return fail(ctx, RT_EINVAL, "rays on a sharded context (rank %d of %d): shard the batch instead", ctx->rank, ctx->world);
-    if (n_rays == 0 || n_rays > RT_MAX_RAYS) return fail(ctx, RT_EINVAL, "%s takes 1 .. %u rays", sets ? "rt_render_ray_sets" : "rt_render_rays", RT_MAX_RAYS);
-    if (sets && (set_size == 0 || set_size > RT_RAY_SET_MAX)) return fail(ctx, RT_EINVAL, "a ray set holds 1 .. %u records, not %u", RT_RAY_SET_MAX, set_size);
-    const size_t records = sets ? n_rays * set_size : n_rays;   // (<= 2^28 * 2^12: no overflow)
-    if (records > ((size_t)1 << 31)) return fail(ctx, RT_EINVAL, "%zu rays x %u records exceed 2^31 records", n_rays, set_size);
+    size_t records = 0;
+    const int rc = check_ray_records(ctx, sets ? "rt_render_ray_sets" : "rt_render_rays", n_rays, set_size, sets, &records);
+    if (rc != RT_OK) return rc;
     if (n_samples && (uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
         return fail(ctx, RT_EINVAL, "samples %u..+%u exceed the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
     if (!d_accum && n_rays != (size_t)ctx->width * ctx->height)
@@ -1424,6 +1433,73 @@ int rt_render_features_rays(rt_context *ctx, const void *d_rays, size_t n_rays, 
     return render_features_with(ctx, k_no_camera, ok, [&](const FrameParams &, const DeviceScene &sc, rt_feature *out) {
         return ctx->ks->launch_features_rays(ctx, sc, rays, (uint32_t)n_rays, p->follow, p->max_chain, out);
     });
+}
+
+// ---- ray queries: nearest hit and occlusion for any batch; nothing of the context's state moves ---------------------------
+int rt_intersect_rays(rt_context *ctx, const void *d_rays, size_t n_rays, const rt_feature_chain_params *p, void *d_out) {
+    const int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    const rt_feature_chain_params first_hits = {0u, 0u};
+    if (!p) p = &first_hits;
+    size_t records = 0;
+    const int bad = check_ray_records(ctx, "rt_intersect_rays", n_rays, 0u, false, &records);
+    if (bad != RT_OK) return bad;
+    if (!d_out || (uintptr_t)d_out % 16u) return fail(ctx, RT_EINVAL, "d_out must be a 16-byte aligned device buffer of rt_feature records");
+    if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
+        return fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
+    if (p->max_chain > RT_FEATURE_CHAIN_MAX) return fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    const void *rays = ray_source(ctx, d_rays, n_rays);
+    if (!rays) return RT_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ctx->ks->launch_features_rays(ctx, device_scene(ctx), rays, (uint32_t)n_rays, p->follow, p->max_chain,
+                                         static_cast<rt_feature *>(d_out));
+}
+
+int rt_occluded_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_t set_size, const float *d_tmax, float t_max,
+                     void *d_out) {
+    const int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    size_t records = 0;
+    const int bad = check_ray_records(ctx, "rt_occluded_rays", n_rays, set_size, true, &records);
+    if (bad != RT_OK) return bad;
+    if (!d_out || (uintptr_t)d_out % sizeof(uint32_t)) return fail(ctx, RT_EINVAL, "d_out must be a 4-byte aligned device buffer of n_rays uint32");
+    if ((uintptr_t)d_tmax % sizeof(float)) return fail(ctx, RT_EINVAL, "d_tmax is not 4-byte aligned");
+    const void *rays = ray_source(ctx, d_rays, records);
+    if (!rays) return RT_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ctx->ks->launch_occluded(ctx, device_scene(ctx), rays, n_rays, set_size, d_tmax, t_max, static_cast<uint32_t *>(d_out));
+}
+
+// ---- device memory for a host without a HIP runtime of its own (the buffers the ray queries write into) ----------------------
+int rt_device_alloc(rt_context *ctx, size_t bytes, void **d_out) {
+    if (!ctx) return RT_EINVAL;
+    if (!d_out || bytes == 0) return fail(ctx, RT_EINVAL, "rt_device_alloc takes a size above 0 and a place for the pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    *d_out = nullptr;
+    if (hipMalloc(d_out, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *d_out = nullptr;
+        return fail(ctx, RT_EHIP, "no device memory for %zu bytes", bytes);
+    }
+    return RT_OK;
+}
+
+int rt_device_free(rt_context *ctx, void *d_ptr) {
+    if (!ctx) return RT_EINVAL;
+    if (!d_ptr) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipFree(d_ptr));   // (waits for the work that uses it)
+    return RT_OK;
+}
+
+int rt_device_copy(rt_context *ctx, void *dst, const void *src, size_t bytes, int to_device) {
+    if (!ctx) return RT_EINVAL;
+    if (!dst || !src) return fail(ctx, RT_EINVAL, "rt_device_copy: a NULL pointer");
+    if (bytes == 0) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n_cameras, const rt_feature_chain_params *p) {

@@ -199,3 +199,38 @@ def thin_lens(sets, U, V, aperture, focus, lens_points):
     d2 /= np.linalg.norm(d2, axis=-1, keepdims=True)
     out["o"], out["d"] = o2.astype(f32), d2.astype(f32)
     return out
+
+
+# ---- hemisphere sets (RayTracer.occludedRays, rt_occluded_rays): k directions about a surface normal, ray-major --------------
+def hemisphere_sets(points, normals, k, seed, offset=0.0):
+    """An (n, k) array of _abi.RAY records for occludedRays (ambient occlusion, visibility bakes): record (i, t) starts at
+    points[i] + offset * n_i and leaves along a cosine-weighted direction about n_i = normals[i] / |normals[i]| — Malley's
+    method on the uniforms (u, v) = workloads.uniforms(n * k, 0, seed)[i * k + t, :2]: the disk point sqrt(u) (cos 2 pi v,
+    sin 2 pi v) lifted to height sqrt(1 - u) > 0 over the tangent plane.  Deterministic in (points, normals, k, seed);
+    float64, rounded once: directions are unit length to 1e-6 and dot(n_i, d) > 0.  The ids are (i, 0)."""
+    from . import workloads
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    nrm = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+    k = int(k)
+    if len(p) != len(nrm) or not 1 <= k <= MAX_SET:
+        raise ValueError("hemisphere_sets takes n points, n normals and 1 <= k <= %d" % MAX_SET)
+    n = len(p)
+    length = np.linalg.norm(nrm, axis=1, keepdims=True)
+    if n and not (length > 0).all():
+        raise ValueError("a normal of length 0 has no hemisphere")
+    nrm = nrm / length
+    # a tangent frame: the world axis the normal leans on least, made perpendicular to it
+    axis = np.eye(3)[np.argmin(np.abs(nrm), axis=1)]
+    tan = np.cross(nrm, axis)
+    tan /= np.linalg.norm(tan, axis=1, keepdims=True)
+    bit = np.cross(nrm, tan)
+    u = workloads.uniforms(n * k, 0, int(seed))[:, :2].astype(np.float64).reshape(n, k, 2)
+    rad, phi = np.sqrt(u[..., 0]), 2.0 * np.pi * u[..., 1]
+    d = ((rad * np.cos(phi))[..., None] * tan[:, None, :] + (rad * np.sin(phi))[..., None] * bit[:, None, :] +
+         np.sqrt(1.0 - u[..., 0])[..., None] * nrm[:, None, :])
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    out = np.zeros((n, k), dtype=_abi.RAY)
+    out["o"] = (p + float(offset) * nrm).astype(f32)[:, None, :]
+    out["d"] = d.astype(f32)
+    out["x"] = (np.arange(n, dtype=np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)[:, None]
+    return out

@@ -43,6 +43,7 @@ SYMBOLS = (
     "rt_upload_rays", "rt_device_rays", "rt_render_rays", "rt_render_features_rays", "rt_debug_last_ray_plan",
     "rt_render_ray_sets",
     "rt_render_adaptive_rays", "rt_render_adaptive_variance_rays",
+    "rt_intersect_rays", "rt_occluded_rays", "rt_device_alloc", "rt_device_free", "rt_device_copy",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -305,6 +306,7 @@ class RayTracer:
             self._ctx = C.c_void_p()
             raise RtError(rc, self._lib.rt_last_error(None).decode())
         self.width, self.height = w, h
+        self._device = int(device)   # (where intersectRays / occludedRays make their outputs)
         if seed != 0xC0FFEE:
             self.setSeed(seed)
         if scene is None:
@@ -478,13 +480,10 @@ class RayTracer:
             target = C.c_void_p(out.data_ptr())
         self._check(self._lib.rt_render_rays(self._ctx, ptr, n, int(first_sample), int(n_samples), target))
 
-    def renderRaySets(self, rays, set_size, first_sample, n_samples, out=None):
-        """Samples first..first+n-1 of every ray through its SET of set_size records (rt_render_ray_sets, asynchronous):
-        sample s of ray i starts at record s mod set_size of ray i's set — anti-aliasing and depth of field for any
-        projection (rays.ray_sets, rays.thin_lens make the sets).  `rays`: a torch device tensor (n_rays * set_size, 8) or
-        (n_rays, set_size, 8) float32 holding rt_ray bits ray-major, read in place; None: the uploaded records; a numpy
-        batch ((n_rays, set_size) _abi.RAY, or float32 of the shapes above) is uploaded first.  `out` as renderRays: an
-        (n_rays, 4) device tensor the sums and counts are ADDED to, None: the accumulator (n_rays == w * h)."""
+    def _ray_set_args(self, rays, set_size):
+        """→ (device pointer or None, n_rays, set_size, what must stay alive until the call has been enqueued) of a call
+        that takes ray sets: a device tensor as check_ray_sets has it, None for the uploaded records, or a numpy batch,
+        which is uploaded first."""
         k = int(set_size)
         if not 1 <= k <= _abi.RAY_SET_MAX:
             raise ValueError("a ray set holds 1 .. %d records, not %d" % (_abi.RAY_SET_MAX, k))
@@ -501,6 +500,16 @@ class RayTracer:
         else:
             n = _abi.check_ray_sets(rays, k)
             ptr, _keep = C.c_void_p(rays.data_ptr()), rays
+        return ptr, n, k, _keep
+
+    def renderRaySets(self, rays, set_size, first_sample, n_samples, out=None):
+        """Samples first..first+n-1 of every ray through its SET of set_size records (rt_render_ray_sets, asynchronous):
+        sample s of ray i starts at record s mod set_size of ray i's set — anti-aliasing and depth of field for any
+        projection (rays.ray_sets, rays.thin_lens make the sets).  `rays`: a torch device tensor (n_rays * set_size, 8) or
+        (n_rays, set_size, 8) float32 holding rt_ray bits ray-major, read in place; None: the uploaded records; a numpy
+        batch ((n_rays, set_size) _abi.RAY, or float32 of the shapes above) is uploaded first.  `out` as renderRays: an
+        (n_rays, 4) device tensor the sums and counts are ADDED to, None: the accumulator (n_rays == w * h)."""
+        ptr, n, k, _keep = self._ray_set_args(rays, set_size)
         target = None
         if out is not None:
             _abi.check_ray_target(out, n)
@@ -514,6 +523,42 @@ class RayTracer:
         ptr, n, _keep = self._ray_args(rays)
         p = _abi.FeatureChainParams(int(follow), int(max_chain))
         self._check(self._lib.rt_render_features_rays(self._ctx, ptr, n, C.byref(p)))
+
+    # -- ray queries: nearest hit and occlusion for any batch; the context's state stays as it is ---------------------------
+    def intersectRays(self, rays, follow=0, max_chain=0, out=None):
+        """Nearest-hit records for ANY batch of rays (rt_intersect_rays, asynchronous): record i is what renderFeaturesRays
+        / renderFeaturesChain would write for ray i (follow 0: first hits), into the caller's buffer — the context's own
+        feature records do not move.  `rays` as renderRays.  `out`: an (n, 20) float32 device tensor (n rt_feature
+        records), made here if None.  → that tensor; _abi.feature_records(t) gives the (n,) FEATURE records after a sync."""
+        import torch
+        ptr, n, _keep = self._ray_args(rays)
+        if out is None:
+            out = torch.empty((n, _abi.FEATURE_FLOATS), dtype=torch.float32, device="cuda:%d" % self._device)
+            torch.cuda.synchronize(out.device)
+        _abi.check_feature_target(out, n)
+        p = _abi.FeatureChainParams(int(follow), int(max_chain))
+        self._check(self._lib.rt_intersect_rays(self._ctx, ptr, n, C.byref(p), C.c_void_p(out.data_ptr())))
+        return out
+
+    def occludedRays(self, rays, set_size=1, t_max=float("inf"), bounds=None, out=None):
+        """Occlusion (any hit) for n sets of set_size records (rt_occluded_rays, asynchronous): a record is occluded iff
+        its first hit's t is below its bound — bounds[k] (a float32 device tensor with one float per record, read in place:
+        the caller keeps it alive and unchanged until the call has run), or t_max for every record.  `rays` as renderRaySets
+        (set_size 1: as renderRays).
+        `out`: an (n,) int32 device tensor, made here if None; OVERWRITTEN with the number of occluded records per set.
+        → that tensor."""
+        import torch
+        ptr, n, k, _keep = self._ray_set_args(rays, set_size)
+        dev = "cuda:%d" % self._device
+        if bounds is not None:
+            _abi.check_ray_bounds(bounds, n * k)
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(out.device)
+        _abi.check_count_target(out, n)
+        self._check(self._lib.rt_occluded_rays(self._ctx, ptr, n, k, C.c_void_p(bounds.data_ptr()) if bounds is not None else None,
+                                               float(t_max), C.c_void_p(out.data_ptr())))
+        return out
 
     def lastRayPlan(self):
         """(facts, plan) dicts of the last renderRays / renderRaySets launch (rt_debug_last_ray_plan): the camera planner's, with
