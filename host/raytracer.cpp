@@ -135,6 +135,26 @@ std::vector<uint32_t> RayTracer::occludedRays(const std::vector<rt_ray> &records
     return out;
 }
 
+std::vector<uint32_t> RayTracer::occludedHemispheres(const rt_hemisphere_params &p, const void *d_features, size_t n) {
+    if (!d_features) n = (size_t)width * height;
+    if (n == 0) throw RayTracerError(RT_EINVAL, "occludedHemispheres takes at least one feature record");
+    std::vector<uint32_t> out(n);
+    int rc = RT_OK;
+    DeviceBlock d(ctx, out.size() * sizeof(uint32_t), &rc);
+    check(rc);
+    check(rt_occluded_hemispheres(ctx, d_features, n, &p, d.p, nullptr));
+    check(rt_device_copy(ctx, out.data(), d.p, out.size() * sizeof(uint32_t), 0));   // (behind the query on the stream)
+    return out;
+}
+
+std::vector<float> RayTracer::ambientOcclusion(uint32_t k, float distance, uint64_t seed, float offset) {
+    const rt_hemisphere_params p{k, RT_HEMI_FACE_FORWARD, seed, offset, distance};
+    const std::vector<uint32_t> counts = occludedHemispheres(p);
+    std::vector<float> out(counts.size());
+    for (size_t i = 0; i < counts.size(); i++) out[i] = 1.0f - (float)counts[i] / (float)k;
+    return out;
+}
+
 const float *RayTracer::renderFrameRays(const std::vector<rt_ray> &batch, uint32_t spp) {
     uploadRays(batch);
     check(rt_clear(ctx));

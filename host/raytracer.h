@@ -87,6 +87,13 @@ public:
     std::vector<rt_feature> intersectRays(const std::vector<rt_ray> &batch, uint32_t follow = 0, uint32_t max_chain = 0);
     std::vector<uint32_t> occludedRays(const std::vector<rt_ray> &records, uint32_t set_size = 1, float t_max = INFINITY,
                                        const std::vector<float> *bounds = nullptr);
+    // hemisphere queries (rt_occluded_hemispheres): per feature record the number of occluded rays among p.k cosine-weighted
+    // rays about its normal, the rays being made on the device — no host rays, no upload, and the uploaded rays stay.
+    // d_features: n rt_feature records in device memory (rt_device_alloc + rt_intersect_rays), or null: the context's own
+    // w x h records (renderFeatures & co. first).  The call waits for the query.  ambientOcclusion: 1 - count / k per pixel
+    // of the context's records (1 on a miss), about the normal turned to face the viewer, rays bounded by `distance`
+    std::vector<uint32_t> occludedHemispheres(const rt_hemisphere_params &p, const void *d_features = nullptr, size_t n = 0);
+    std::vector<float> ambientOcclusion(uint32_t k = 16, float distance = INFINITY, uint64_t seed = 0, float offset = 0.0f);
     // ray sets (rt_render_ray_sets; rays::ray_sets makes them): the uploaded records are w x h sets of set_size records,
     // ray-major, and sample s of pixel i starts at record s mod set_size of its set — anti-aliasing for any projection
     void renderRaySets(uint32_t set_size, uint32_t first_sample, uint32_t n_samples);

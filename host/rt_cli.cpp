@@ -74,6 +74,10 @@
 // one rt_occluded_rays call with set_size K and the bound D (default +inf: any hit), PREFIX_ao.pfm = 1 - count / K and 1
 // where the pixel's primary ray missed.  The rays take 32 B x W x H x K of host and of device memory, and take the place of
 // the uploaded rays of a --projection frame (nothing after this step reads those).
+// --ao K --ao-device asks the device for the same picture instead (rt_occluded_hemispheres over the context's feature
+// records, face-forward, seed --seed): the K rays of every pixel are made in the kernel's registers, so there are no host
+// rays, no upload, and the uploaded rays stay.  The rays are those of the float64 generator to 1e-6, numbered by pixel
+// (the host path numbers them by hit), so the two pictures agree as two estimates do, not bit for bit.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -105,9 +109,10 @@ static void usage() {
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K] "
-                 "[--adaptive THRESHOLD ...]] [--ao K [--ao-distance D]]\n"
+                 "[--adaptive THRESHOLD ...]] [--ao K [--ao-distance D] [--ao-device]]\n"
                  "  --ao K (1 .. 4096, with --aov): PREFIX_ao.pfm from K hemisphere rays per first hit, bound D (default inf);"
-                 " its rays take 32 B x W x H x K of host and of device memory\n";
+                 " its rays take 32 B x W x H x K of host and of device memory, unless --ao-device has the device make them"
+                 " in registers (rt_occluded_hemispheres)\n";
     std::exit(2);
 }
 
@@ -209,6 +214,7 @@ int main(int argc, char **argv) {
     long ao = 0;        // (0: no ambient occlusion)
     float ao_distance = INFINITY;
     bool ao_distance_given = false;
+    bool ao_device = false;   // (the rays of --ao made on the device)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -299,6 +305,7 @@ int main(int argc, char **argv) {
         else if ((v = val("--ray-sets"))) ray_set = parse_int(v, 1, RT_RAY_SET_MAX);
         else if ((v = val("--aa-guides"))) aa_guides = parse_int(v, 1, RT_FEATURE_CAMERAS_MAX);
         else if (a == "--aa") aa = true;
+        else if (a == "--ao-device") ao_device = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--variance-guided") variance_guided = true;
         else if (a == "--measured") measured = true;
@@ -316,7 +323,7 @@ int main(int argc, char **argv) {
     if ((max_chain >= 0 || split_chains) && !follow) usage();
     if (split_chains && !denoise) usage();
     if (ao && (aov_prefix.empty() || follow || aa_guides)) usage();        // --ao fills --aov from first-hit records
-    if (ao_distance_given && !ao) usage();
+    if ((ao_distance_given || ao_device) && !ao) usage();
     if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
     if (progressive_cameras && (progressive || adaptive || adaptive_cameras || denoise)) usage();   // one way to spend the samples; the running mean lives in the image
     if (!progressive && !progressive_cameras && lookahead >= 0) usage();   // progressive-only flag
@@ -487,7 +494,13 @@ int main(int argc, char **argv) {
             }
             write_pfm(aov_prefix + "_coverage.pfm", c3.data(), 3, 0, 3, w, h);
         }
-        if (ao) {   // ambient occlusion: K hemisphere rays per first hit, counted by one occlusion query
+        if (ao && ao_device) {   // ambient occlusion with the rays made on the device: no host rays, no upload
+            auto a0 = std::chrono::steady_clock::now();
+            const std::vector<float> open = tracer.ambientOcclusion((uint32_t)ao, ao_distance, seed);
+            std::cout << "ambient occlusion: " << ao << " device-made rays per pixel, bound " << ao_distance << ": "
+                      << std::chrono::duration<double>(std::chrono::steady_clock::now() - a0).count() * 1e3 << " ms incl. read-back" << std::endl;
+            write_pfm(aov_prefix + "_ao.pfm", open.data(), 1, 0, 1, w, h);
+        } else if (ao) {   // ambient occlusion: K hemisphere rays per first hit, counted by one occlusion query
             std::vector<float> points, normals;
             std::vector<size_t> pixel;
             for (size_t i = 0; i < f.size(); i++)

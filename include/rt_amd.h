@@ -653,6 +653,45 @@ int rt_occluded_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_
                      void *d_out);
 
 /*
+ * Hemisphere queries (new): ambient occlusion and visibility or irradiance bakes from hit points, with the rays made on the
+ * device.  For each of the n rt_feature records at d_features (device, 16-byte aligned — typically rt_intersect_rays' output;
+ * NULL: the context's own W*H records, RT_ESTATE while rt_read_features would be) the kernel makes p->k cosine-weighted
+ * rays about the record's normal in registers and
+ *   d_counts   (n uint32, OVERWRITTEN) receives the number of occluded rays among record i's k — or is NULL: no search runs
+ *              (the spawn form);
+ *   d_rays_out (n * k rt_ray records, ray-major, 16-byte aligned, OVERWRITTEN) receives the rays — ready for
+ *              rt_render_ray_sets, rt_occluded_rays or any later query — or is NULL: no ray reaches memory (the fused form).
+ * One of the two at least.  Record i is VALID when it has RT_FEATURE_HIT and the squared length of its normal is, in
+ * binary32, a finite number above 0.  Ray t of a valid record:
+ *   n^ = normal / |normal|, of -normal under RT_HEMI_FACE_FORWARD where dot(normal, record.dir) > 0;
+ *   the tangent frame of rays::hemisphere_sets: axis = the world axis of the smallest |component| of the normal, ties to
+ *     the lower index; tan = unit(n^ x axis), bit = n^ x tan;
+ *   (u, v) = the first two 24-bit uniforms of Philox-4x32-10 on the counter (i*k + t, 0, 0, 0) with the key (seed lo, seed hi)
+ *     (workloads.uniforms(n*k, 0, seed)[i*k + t, :2]);
+ *   d = unit(sqrt(u) cos(2 pi v) tan + sqrt(u) sin(2 pi v) bit + sqrt(1 - u) n^),  o = pos + offset * n^,  x = i, y = 0
+ * — Malley's method as host/rays.h states it, evaluated in binary32: a direction lies within 1e-6 per component of the
+ * float64 generators' (measured: 1.8e-7, DESIGN.md "Hemisphere queries"), an origin within two roundings of pos + offset *
+ * n^, and the rays are deterministic: the same call gives the same bytes.  An invalid record counts 0 and its k records of
+ * d_rays_out are all-zero bytes: not rays.
+ * For every valid record d_counts[i] equals, bit for bit, what rt_occluded_rays(d_rays_out, n, k, NULL, p->t_max, .) writes
+ * for set i, under every arithmetic policy and RT_OPT_ACCEL setting, whether d_rays_out was given or not.
+ * Asynchronous on the context's stream; the context stays as it is, as under the ray queries; rt_walk_overflow reports these
+ * walks too.  RT_EINVAL: a NULL ctx or p, both outputs NULL, n 0 or above RT_MAX_RAYS, k 0 or above RT_RAY_SET_MAX, n * k above
+ * 2^31, a misaligned pointer (16 bytes; d_counts 4), unknown flag bits, a non-finite offset, NULL d_features with n != W*H, a
+ * sharded context.  RT_ESTATE: no scene set; NULL d_features without ready records.  A failed call writes nothing.
+ */
+#define RT_HEMI_FACE_FORWARD 1u   /* use -normal where dot(normal, record.dir) > 0 */
+typedef struct rt_hemisphere_params {
+    uint32_t k;        /* rays per record, 1 .. RT_RAY_SET_MAX                       */
+    uint32_t flags;    /* RT_HEMI_FACE_FORWARD; any other bit: RT_EINVAL            */
+    uint64_t seed;
+    float offset;      /* origin = pos + offset * unit normal; finite               */
+    float t_max;       /* the bound of every ray, with rt_occluded_rays' meaning    */
+} rt_hemisphere_params;
+int rt_occluded_hemispheres(rt_context *ctx, const void *d_features, size_t n, const rt_hemisphere_params *p,
+                            void *d_counts, void *d_rays_out);
+
+/*
  * Device memory for a host that has no HIP runtime of its own (new) — the buffers the ray queries write into, as the C++
  * façade of host/ makes them.  rt_device_alloc: `bytes` > 0 of memory on the context's device (hipMalloc's alignment), owned by the
  * caller until rt_device_free (NULL is fine; waits for the work that uses the block).  rt_device_copy: `bytes` from `src` to

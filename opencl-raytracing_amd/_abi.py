@@ -430,6 +430,52 @@ def check_count_target(t, n):
         raise ValueError("out must be a contiguous device tensor")
 
 
+HEMI_FACE_FORWARD = 1       # RT_HEMI_FACE_FORWARD: use -normal where dot(normal, record.dir) > 0
+
+
+class HemisphereParams(C.Structure):
+    """rt_hemisphere_params (include/rt_amd.h)."""
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("offset", C.c_float), ("t_max", C.c_float)]
+
+
+def check_hemispheres(features, n, k, flags, offset, counts, rays_out, width, height, world=1):
+    """What rt_occluded_hemispheres refuses with RT_EINVAL, restated without a device: `features` an (n, 20) float32
+    contiguous device tensor of rt_feature records or None (the context's own width x height records: n must be their
+    number), 1 <= n <= MAX_RAYS, 1 <= k <= RAY_SET_MAX, n * k <= 2^31, flags within HEMI_FACE_FORWARD, a finite offset,
+    `counts` an (n,) int32 and `rays_out` an (n * k, 8) or (n, k, 8) float32 contiguous device tensor — each may be None,
+    not both — 16-byte aligned records, an unsharded context.  ValueError otherwise; → HemisphereParams' k and flags."""
+    n, k, flags = int(n), int(k), int(flags)
+    if int(world) > 1:
+        raise ValueError("hemisphere queries on a sharded context: shard the records instead")
+    if not 1 <= n <= MAX_RAYS:
+        raise ValueError("a hemisphere query takes 1 .. %d records, not %d" % (MAX_RAYS, n))
+    if not 1 <= k <= RAY_SET_MAX:
+        raise ValueError("a hemisphere holds 1 .. %d rays, not %d" % (RAY_SET_MAX, k))
+    if n * k > MAX_RAY_RECORDS:
+        raise ValueError("%d records x %d rays exceed 2^31 rays" % (n, k))
+    if flags & ~HEMI_FACE_FORWARD:
+        raise ValueError("unknown hemisphere flags 0x%x" % flags)
+    if not np.isfinite(offset) or abs(float(offset)) > float(np.finfo(np.float32).max):   # (finite as a float)
+        raise ValueError("the hemisphere offset must be finite, not %r" % (offset,))
+    if counts is None and rays_out is None:
+        raise ValueError("a hemisphere query needs counts, rays_out or both")
+    if features is None:
+        if n != int(width) * int(height):
+            raise ValueError("the context's feature records are %d x %d, not %d" % (width, height, n))
+    else:
+        check_feature_target(features, n)
+        if features.data_ptr() % 16:
+            raise ValueError("features must be 16-byte aligned")
+    if counts is not None:
+        check_count_target(counts, n)
+    if rays_out is not None:
+        if check_ray_sets(rays_out, k) != n:
+            raise ValueError("rays_out must hold %d x %d records, not shape %s" % (n, k, tuple(rays_out.shape)))
+        if rays_out.data_ptr() % 16:
+            raise ValueError("rays_out must be 16-byte aligned")
+    return k, flags
+
+
 def feature_records(t):
     """intersectRays' (n, 20) float32 tensor → (n,) FEATURE records on the host (a copy; the caller has synchronised)."""
     return np.ascontiguousarray(t.detach().cpu().numpy()).view(FEATURE).reshape(-1)
@@ -448,6 +494,7 @@ def ray_prototypes(lib):
     lib.rt_render_adaptive_variance_rays.argtypes = [vp, vp, sz, u32, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveStats)]
     lib.rt_intersect_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams), vp]
     lib.rt_occluded_rays.argtypes = [vp, vp, sz, u32, vp, C.c_float, vp]
+    lib.rt_occluded_hemispheres.argtypes = [vp, vp, sz, C.POINTER(HemisphereParams), vp, vp]
     lib.rt_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     lib.rt_device_free.argtypes = [vp, vp]
     lib.rt_device_copy.argtypes = [vp, vp, vp, sz, C.c_int]

@@ -968,6 +968,71 @@ PT_DEV bool occluded_scene(const DeviceScene &sc, const Ray &r, const float B, c
     return occ && !skip;
 }
 
+// ---- hemisphere rays (rt_occluded_hemispheres): the ray source of pt_occluded_hemi ----------------------------------------
+// Philox-4x32-10 on the counter (c0, 0, 0, 0) with the key (k0, k1) — workloads.uniforms' generator, host/rays.h uniforms2
+// — in integer registers; the first two words
+PT_DEV void philox_words2(uint32_t c0, uint32_t k0, uint32_t k1, uint32_t &w0, uint32_t &w1) {
+    uint32_t c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int round = 0; round < 10; round++) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0, c1 = l1, c2 = h0 ^ c3 ^ k1, c3 = l0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    w0 = c0, w1 = c1;
+}
+
+// sin and cos of m / 2^24 of a turn, m < 2^24: the nearest quarter turn is taken off in integers, so the remainder
+// |x| <= pi/4 carries one rounding (the product with 2 pi / 2^24), then the two minimax polynomials of Cephes' sinf / cosf
+// with written-out fma — the same bits under every arithmetic policy, and on a host that has fmaf.
+PT_DEV void sincos_turn24(uint32_t m, float &sn, float &cs) {
+    const uint32_t q = (m + (1u << 21)) >> 22;
+    const float x = (float)((int)m - (int)(q << 22)) * (0x1.921fb6p+2f * 0x1p-24f);
+    const float z = x * x;
+    const float s = __builtin_fmaf(x * z, __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), x);
+    const float c = __builtin_fmaf(z * z, __builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
+                                   __builtin_fmaf(-0.5f, z, 1.0f));
+    sn = (q & 1u) ? c : s;
+    cs = (q & 1u) ? s : c;
+    if (q & 2u) sn = -sn;
+    if ((q + 1u) & 2u) cs = -cs;
+}
+
+// Ray t of record `rec` (80 bytes at f) under rt_hemisphere_params, `index` = rec * k + t: Malley's method as host/rays.h
+// hemisphere_sets states it, in binary32.  False (and a zero ray) for a record that has no hemisphere: no RT_FEATURE_HIT,
+// or a normal whose squared length is not a finite number above 0.  The world axis of the frame is chosen on the normal
+// as given: scaling by a positive length keeps the order of the components, and the float64 generators choose the same.
+PT_DEV bool hemisphere_ray(const float4 *__restrict__ f, uint32_t index, uint32_t k0, uint32_t k1, bool face_forward, float offset, Ray &r) {
+    const float4 fp = f[0], fn = f[1];
+    const uint32_t flags = __float_as_uint(f[4].w);
+    V3 n = mk(fn.x, fn.y, fn.z);
+    const float len2 = dot(n, n);
+    const bool valid = (flags & RT_FEATURE_HIT) && len2 > 0.0f && len2 < INFINITY;
+    r.o = r.d = mk(0.0f, 0.0f, 0.0f);
+    if (!__any(valid)) return false;   // a wave over a region of misses makes no ray: no generator, no frame
+    if (face_forward) {
+        const float4 fd = f[3];
+        if (dot(n, mk(fd.x, fd.y, fd.z)) > 0.0f) n = neg(n);
+    }
+    if (!valid) n = mk(0.0f, 0.0f, 1.0f);   // (keeps the arithmetic below on ordinary numbers)
+    const float ax = fabsf(n.x), ay = fabsf(n.y), az = fabsf(n.z);
+    n = normalize(n);
+    // unit(n x axis) for the axis of the smallest |component|, ties to the lower index; bit = n x tan
+    const V3 tan = normalize(ax <= ay && ax <= az ? mk(0.0f, n.z, -n.y) : (ay <= az ? mk(-n.z, 0.0f, n.x) : mk(n.y, -n.x, 0.0f)));
+    const V3 bit = cross(n, tan);
+    uint32_t w0, w1;
+    philox_words2(index, k0, k1, w0, w1);
+    const float u = (float)(w0 >> 8) * 0x1p-24f;   // (exact, and so is 1 - u)
+    float sn, cs;
+    sincos_turn24(w1 >> 8, sn, cs);
+    const float rad = sqrt1(u), up = sqrt1(1.0f - u);
+    const V3 d = normalize((tan * (rad * cs) + bit * (rad * sn)) + n * up);
+    r.o = valid ? mk(fp.x, fp.y, fp.z) + n * offset : mk(0.0f, 0.0f, 0.0f);
+    r.d = valid ? d : mk(0.0f, 0.0f, 0.0f);
+    return valid;
+}
+
 // ---- materials -------------------------------------------------------------------
 // :401-405
 PT_DEV float schlick(float cosine, float r0) { return mad(1.0f - r0, pow5(1.0f - cosine), r0); }   // r0 + (1 - r0) * pow(1 - cai, 5)

@@ -1694,6 +1694,49 @@ __global__ __launch_bounds__(256) void pt_occluded(DeviceScene sc, const float4 
     }
 }
 
+// Hemisphere queries (rt_occluded_hemispheres): pt_occluded with its rays made in registers.  Lane k = i * set_size + t
+// makes ray t of feature record i (hemisphere_ray, pt_device.hpp: the lanes of a set read the same 80 bytes) and asks
+// occluded_scene with the bound t_max, pt_occluded's rule; a record without a hemisphere is skipped and counts 0.  DUMP
+// stores the ray (zero bytes for such a record) at rays_out[k].  out NULL: the spawn form, every lane skips the search.
+// The counts leave as in pt_occluded (duplicated here so that pt_occluded keeps its code).
+template <bool ACCEL, bool DUMP>
+__global__ __launch_bounds__(256) void pt_occluded_hemi(DeviceScene sc, const float4 *__restrict__ feats, uint32_t k0, uint32_t k1,
+                                                        uint32_t flags, float offset, float t_max, uint32_t records, uint32_t set_size,
+                                                        uint32_t *__restrict__ out, float4 *__restrict__ rays_out) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;   // (records <= 2^31: the grid covers them in 32 bits)
+    const bool live = k < records;
+    const uint32_t set = k / set_size;
+    Ray r;
+    r.o = r.d = mk(0.0f, 0.0f, 0.0f);
+    bool valid = false;
+    if (live) {
+        valid = hemisphere_ray(feats + 5u * (size_t)set, k, k0, k1, (flags & RT_HEMI_FACE_FORWARD) != 0u, offset, r);
+        if (DUMP) {
+            rays_out[2u * (size_t)k] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(valid ? set : 0u));
+            rays_out[2u * (size_t)k + 1u] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+        }
+    }
+    if (!out) return;
+    const float B = t_max < RT_MAX_DISTANCE ? t_max : RT_MAX_DISTANCE;
+    const bool skip = !valid || !(t_max > RT_MIN_DISTANCE);
+    const bool occ = occluded_scene<ACCEL>(sc, r, B, skip);
+    if (set_size == 1u) {
+        if (live) out[(size_t)k] = occ ? 1u : 0u;
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t before = (uint32_t)__shfl_up((int)set, 1);
+    const bool head = live && (lane == 0u || before != set);
+    const unsigned long long occ_m = __ballot(occ), heads = __ballot(head);
+    if (head) {
+        const unsigned long long above = lane == 63u ? 0ull : heads >> (lane + 1u);
+        const uint32_t len = above ? (uint32_t)__builtin_ctzll(above) + 1u : 64u - lane;
+        const unsigned long long run = (len == 64u ? ~0ull : (1ull << len) - 1ull) << lane;
+        const uint32_t count = (uint32_t)__popcll(occ_m & run);
+        if (count) atomicAdd(out + (size_t)set, count);
+    }
+}
+
 // Feature records through per-sample cameras (rt_render_features_cameras): lane j < n of a pixel's g = 2^glog2 lanes (one
 // wave holds whole pixels) looks through block j of fp.cams and runs pt_features_chain's loop — the same search, scatter
 // and flags, duplicated here so that the single-camera kernel keeps its code — into five registers instead of memory.
@@ -2544,6 +2587,24 @@ int ks_launch_occluded(rt_context *ctx, const DeviceScene &sc, const void *d_ray
     return RT_OK;
 }
 
+// rt_occluded_hemispheres: pt_occluded_hemi over n feature records x p.k rays.  d_counts (zeroed on the stream first where
+// atomics sum into it) and d_rays_out may each be NULL, not both; without d_counts no search runs
+int ks_launch_occluded_hemi(rt_context *ctx, const DeviceScene &sc, const rt_feature *d_features, size_t n, const rt_hemisphere_params &p,
+                            uint32_t *d_counts, void *d_rays_out) {
+    const size_t records = n * p.k;
+    if (!d_features || (!d_counts && !d_rays_out) || n < 1u || p.k < 1u || records > ((size_t)1 << 31))
+        return fail(ctx, RT_EINVAL, "a hemisphere launch needs records, an output and at most 2^31 rays");
+    if (d_counts && p.k > 1u) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, n * sizeof(uint32_t), ctx->stream));
+    const bool accel = d_counts && scene_has_accel(sc);
+    auto kernel = d_rays_out ? (accel ? pt_occluded_hemi<true, true> : pt_occluded_hemi<false, true>)
+                             : (accel ? pt_occluded_hemi<true, false> : pt_occluded_hemi<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((records + 255u) / 256u)), dim3(256), 0, ctx->stream, sc,
+                       reinterpret_cast<const float4 *>(d_features), (uint32_t)p.seed, (uint32_t)(p.seed >> 32), p.flags, p.offset, p.t_max,
+                       (uint32_t)records, p.k, d_counts, static_cast<float4 *>(d_rays_out));
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
     dim3 grid((n + 255u) / 256u), block(256);
@@ -2610,7 +2671,7 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, ks_launch_occluded};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, ks_launch_occluded, ks_launch_occluded_hemi};
 
 }  // namespace
 

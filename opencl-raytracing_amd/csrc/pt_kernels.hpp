@@ -90,6 +90,11 @@ struct KernelSet {
     // d_tmax is NULL — into d_out[set] (n uint32, overwritten)
     int (*launch_occluded)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, size_t n, uint32_t set_size,
                            const float *d_tmax, float t_max, uint32_t *d_out);
+    // rt_occluded_hemispheres: pt_occluded_hemi, the p.k hemisphere rays of each of the n feature records at d_features made
+    // in registers: their occluded count into d_counts[record] (n uint32, overwritten; NULL: no search runs) and the rays
+    // themselves into d_rays_out (n * p.k rt_ray records, ray-major; NULL: not stored) — one of the two at least
+    int (*launch_occluded_hemi)(rt_context *ctx, const DeviceScene &sc, const rt_feature *d_features, size_t n,
+                                const rt_hemisphere_params &p, uint32_t *d_counts, void *d_rays_out);
 };
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2

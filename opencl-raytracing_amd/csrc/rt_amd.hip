@@ -1470,6 +1470,32 @@ int rt_occluded_rays(rt_context *ctx, const void *d_rays, size_t n_rays, uint32_
     return ctx->ks->launch_occluded(ctx, device_scene(ctx), rays, n_rays, set_size, d_tmax, t_max, static_cast<uint32_t *>(d_out));
 }
 
+// rt_occluded_hemispheres: the rays of n feature records made in registers (pt_occluded_hemi); counts, rays or both
+int rt_occluded_hemispheres(rt_context *ctx, const void *d_features, size_t n, const rt_hemisphere_params *p, void *d_counts,
+                            void *d_rays_out) {
+    const int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    if (!p) return fail(ctx, RT_EINVAL, "rt_occluded_hemispheres: the parameters are NULL");
+    size_t records = 0;
+    const int bad = check_ray_records(ctx, "rt_occluded_hemispheres", n, p->k, true, &records);
+    if (bad != RT_OK) return bad;
+    if (!d_counts && !d_rays_out) return fail(ctx, RT_EINVAL, "rt_occluded_hemispheres needs d_counts, d_rays_out or both");
+    if ((uintptr_t)d_counts % sizeof(uint32_t)) return fail(ctx, RT_EINVAL, "d_counts is not 4-byte aligned");
+    if ((uintptr_t)d_rays_out % alignof(rt_ray)) return fail(ctx, RT_EINVAL, "d_rays_out is not 16-byte aligned");
+    if ((uintptr_t)d_features % 16u) return fail(ctx, RT_EINVAL, "d_features is not 16-byte aligned");
+    if (p->flags & ~RT_HEMI_FACE_FORWARD) return fail(ctx, RT_EINVAL, "unknown hemisphere flags 0x%x", p->flags);
+    if (!std::isfinite(p->offset)) return fail(ctx, RT_EINVAL, "the hemisphere offset must be finite");
+    if (!d_features) {
+        if (n != (size_t)ctx->width * ctx->height)
+            return fail(ctx, RT_EINVAL, "the context's feature records are %d x %d, not %zu", ctx->width, ctx->height, n);
+        if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+        d_features = ctx->features.records.p;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return ctx->ks->launch_occluded_hemi(ctx, device_scene(ctx), static_cast<const rt_feature *>(d_features), n, *p,
+                                         static_cast<uint32_t *>(d_counts), d_rays_out);
+}
+
 // ---- device memory for a host without a HIP runtime of its own (the buffers the ray queries write into) ----------------------
 int rt_device_alloc(rt_context *ctx, size_t bytes, void **d_out) {
     if (!ctx) return RT_EINVAL;

@@ -44,6 +44,7 @@ SYMBOLS = (
     "rt_render_ray_sets",
     "rt_render_adaptive_rays", "rt_render_adaptive_variance_rays",
     "rt_intersect_rays", "rt_occluded_rays", "rt_device_alloc", "rt_device_free", "rt_device_copy",
+    "rt_occluded_hemispheres",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -356,6 +357,7 @@ class RayTracer:
 
     def setShard(self, rank, world, tile_w=8, tile_h=8):
         self._check(self._lib.rt_set_shard(self._ctx, rank, world, tile_w, tile_h))
+        self._world = int(world)   # (check_hemispheres restates the library's refusal of sharded contexts)
 
     OPT_PREFIX_SHARING, OPT_MAX_THREADS_PER_LAUNCH, OPT_SAMPLE_QUEUE, OPT_ACCEL, OPT_WALK_SLICES, OPT_ARITH, OPT_PREFIX_TREE, OPT_WAVE_FILL = 1, 2, 3, 4, 5, 6, 7, 8
     OPT_PREFIX_CACHE = 9
@@ -559,6 +561,55 @@ class RayTracer:
         self._check(self._lib.rt_occluded_rays(self._ctx, ptr, n, k, C.c_void_p(bounds.data_ptr()) if bounds is not None else None,
                                                float(t_max), C.c_void_p(out.data_ptr())))
         return out
+
+    # -- hemisphere queries: the rays of ambient occlusion and of bakes from hit points, made on the device --------------------
+    def _hemispheres(self, features, k, seed, offset, t_max, face_forward, counts, rays_out, want_counts, want_rays):
+        import torch
+        n = self.width * self.height if features is None else (int(features.shape[0]) if hasattr(features, "shape") and len(features.shape) else 0)
+        flags = _abi.HEMI_FACE_FORWARD if face_forward else 0
+        dev = "cuda:%d" % self._device
+        made = False
+        if want_counts and counts is None:
+            counts, made = torch.empty((max(n, 0),), dtype=torch.int32, device=dev), True
+        if want_rays and rays_out is None and 1 <= int(k) <= _abi.RAY_SET_MAX and 1 <= n * int(k) <= _abi.MAX_RAY_RECORDS:
+            rays_out, made = torch.empty((n * int(k), 8), dtype=torch.float32, device=dev), True
+        if made:
+            torch.cuda.synchronize(torch.device(dev))
+        k, flags = _abi.check_hemispheres(features, n, k, flags, offset, counts, rays_out, self.width, self.height,
+                                          getattr(self, "_world", 1))
+        p = _abi.HemisphereParams(k, flags, int(seed) & 0xFFFFFFFFFFFFFFFF, float(offset), float(t_max))
+        self._check(self._lib.rt_occluded_hemispheres(
+            self._ctx, C.c_void_p(features.data_ptr()) if features is not None else None, n, C.byref(p),
+            C.c_void_p(counts.data_ptr()) if counts is not None else None,
+            C.c_void_p(rays_out.data_ptr()) if rays_out is not None else None))
+        return counts, rays_out
+
+    def occludedHemispheres(self, features=None, k=16, seed=0, offset=0.0, t_max=float("inf"), face_forward=False, out=None,
+                            rays_out=None):
+        """How many of k cosine-weighted rays about each record's normal are occluded (rt_occluded_hemispheres,
+        asynchronous): the rays are made on the device in registers — rays.hemisphere_sets' rays, in float32 — from
+        `features`, an (n, 20) float32 device tensor of rt_feature records (intersectRays' output), or None: the context's
+        own width x height records.  A ray is occluded iff its first hit's t is below t_max (occludedRays' rule); a record
+        without a hit or with a zero or non-finite normal counts 0.  face_forward: about -normal where the normal looks
+        along the record's direction.  `out`: an (n,) int32 device tensor, made here if None, OVERWRITTEN.  `rays_out`: an
+        (n * k, 8) or (n, k, 8) float32 device tensor that receives the rays as well (zero bytes for a record without a
+        hemisphere).  → out."""
+        return self._hemispheres(features, k, seed, offset, t_max, face_forward, out, rays_out, True, False)[0]
+
+    def spawnHemispheres(self, features=None, k=16, seed=0, offset=0.0, face_forward=False, out=None):
+        """The rays occludedHemispheres would ask about, without the search (rt_occluded_hemispheres with no counts,
+        asynchronous) → an (n * k, 8) float32 device tensor of rt_ray bits, ray-major (`out`, made here if None): it goes
+        straight into renderRaySets / occludedRays with set_size k.  The records of a feature record without a hemisphere
+        are zero bytes, not rays."""
+        return self._hemispheres(features, k, seed, offset, float("inf"), face_forward, None, out, False, True)[1]
+
+    def ambientOcclusion(self, k=16, distance=float("inf"), seed=0, offset=0.0):
+        """Ambient occlusion of the context's feature records (renderFeatures & co. made them) → an (h, w) float32 device
+        tensor 1 - count / k, 1 where the pixel missed: k rays per pixel about the normal turned to face the viewer,
+        occluded by anything nearer than `distance` (occludedHemispheres(None, k, seed, offset, distance, True))."""
+        counts = self.occludedHemispheres(None, k, seed, offset, distance, True)
+        self.sync()   # (the division runs on torch's stream)
+        return (1.0 - counts.float() / float(int(k))).reshape(self.height, self.width)
 
     def lastRayPlan(self):
         """(facts, plan) dicts of the last renderRays / renderRaySets launch (rt_debug_last_ray_plan): the camera planner's, with

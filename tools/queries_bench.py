@@ -16,6 +16,16 @@ then `ao16`: one rt_occluded_rays call with set_size 16 — 16 hemisphere rays p
 The hemisphere rays are made on the device with torch's generator (a timing needs no particular bits).  On a checkout
 without the ray queries only `features` is measured (the parent's side of the comparison).
 
+With the hemisphere queries (rt_occluded_hemispheres, DESIGN.md §5 "Hemisphere queries") --ao K adds, over the same W x H
+first-hit records and alternating inside every round:
+    fused        occludedHemispheres: the K rays of every record made in registers, counts only
+    spawn        spawnHemispheres alone: the same rays written to memory, no search
+    occ_dumped   rt_occluded_rays with set_size K over the very rays `spawn` wrote — pt_occluded on identical work
+    spawn_occ    spawn, then that query: what a caller pays who wants the rays as well
+and, by the host's clock over --host-rounds rounds (default --rounds; seconds each at 1080p x 16, so no warm-up round), `host_path`: the first-hit
+records as they lie on the host -> rays.hemisphere_sets -> upload -> rt_occluded_rays -> sync, which is what rt_cli --ao K and
+every user of hemisphere_sets ran before.  The fused counts are checked against occ_dumped's on the way.
+
     python tools/queries_bench.py [--scenes c2,c4,c5] [--size 1920x1080] [--rounds 5] [--policy 2] [--ao 16] [--json out.json]
 """
 import argparse
@@ -72,6 +82,52 @@ def hemisphere_on_device(pos, normal, incoming, k, gen):
     return out
 
 
+def hemisphere_rows(t, stream, rec, k, rounds, host_rounds):
+    """The rows of rt_occluded_hemispheres over the (n,) FEATURE records `rec` → {configuration: statistics}"""
+    import time
+    import torch
+    n = len(rec)
+    feats = torch.from_numpy(np.ascontiguousarray(rec).view(np.float32).reshape(n, 20).copy()).cuda()
+    counts = torch.empty((n,), dtype=torch.int32, device="cuda")
+    counts2 = torch.empty((n,), dtype=torch.int32, device="cuda")
+    dumped = torch.empty((n * k, 8), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    kw = dict(k=k, seed=7, offset=0.0, face_forward=True)
+    t.spawnHemispheres(feats, out=dumped, **kw)
+    t.sync()
+
+    def spawn_occ():
+        t.spawnHemispheres(feats, out=dumped, **kw)
+        t.occludedRays(dumped, k, out=counts2)
+
+    configs = [("fused", lambda: t.occludedHemispheres(feats, out=counts, **kw)),
+               ("occ_dumped", lambda: t.occludedRays(dumped, k, out=counts2)),
+               ("spawn", lambda: t.spawnHemispheres(feats, out=dumped, **kw)),
+               ("spawn_occ", spawn_occ)]
+    row = stats(timed(stream, configs, rounds))
+    t.sync()
+    valid = torch.from_numpy((rec["flags"] & 1) != 0).cuda()
+    row["counts_equal"] = bool((counts[valid] == counts2[valid]).all()) and not bool(counts[~valid].any())
+    row["mean_open"] = float(1.0 - counts.float().mean() / k)
+    del dumped
+    if host_rounds > 0:
+        hit = (rec["flags"] & 1) != 0
+        ms = []
+        for r in range(host_rounds):
+            t.sync()
+            t0 = time.perf_counter()
+            normal = rec["normal"][hit]
+            facing = (normal * rec["dir"][hit]).sum(1) > 0
+            sets = rt.rays.hemisphere_sets(rec["pos"][hit], np.where(facing[:, None], -normal, normal), k, 7)
+            d = torch.from_numpy(rt.rays.as_floats(sets).reshape(-1, 8)).cuda()
+            out = t.occludedRays(d, k)
+            t.sync()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            del sets, d, out
+        row.update(stats({"host_path": ms}))
+    return row
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -80,6 +136,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--policy", type=int, default=2)
     ap.add_argument("--ao", type=int, default=16)
+    ap.add_argument("--host-rounds", type=int, default=None)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     T = rt.RayTracer
@@ -126,6 +183,8 @@ def main():
             t.sync()
             row["ao"]["mean_open"] = float(1.0 - out_n.float().mean() / a.ao)
             del sets
+        if hasattr(T, "occludedHemispheres") and a.ao:
+            row["hemi_ao"] = hemisphere_rows(t, stream, rec, a.ao, a.rounds, a.rounds if a.host_rounds is None else a.host_rounds)
         row["walk_overflow"] = t.walkOverflow()
         result["scenes"][name] = row
         print("%s %dx%d, policy %d, %d rounds (ms: median, min .. max); %.1f %% of the primary rays hit" %
@@ -142,6 +201,15 @@ def main():
             v = row["ao"]["ao%d" % a.ao]
             print("  ao%-6d %8.3f  (%.3f .. %.3f): %.0f Mrays/s, mean openness %.3f" %
                   (a.ao, v["median"], v["min"], v["max"], w * h * a.ao / v["median"] / 1e3, row["ao"]["mean_open"]), flush=True)
+        if "hemi_ao" in row:
+            r = row["hemi_ao"]
+            for c in ("fused", "spawn", "occ_dumped", "spawn_occ", "host_path"):
+                if c in r:
+                    print("  ao%-3d %-10s %9.3f  (%.3f .. %.3f)" % (a.ao, c, r[c]["median"], r[c]["min"], r[c]["max"]))
+            print("  fused / occ_dumped %.3f, spawn_occ / fused %.2f%s; counts equal: %s" %
+                  (r["fused"]["median"] / r["occ_dumped"]["median"], r["spawn_occ"]["median"] / r["fused"]["median"],
+                   ", host_path / fused %.0f" % (r["host_path"]["median"] / r["fused"]["median"]) if "host_path" in r else "",
+                   r["counts_equal"]), flush=True)
         t.close()
     if a.json:
         with open(a.json, "w") as f:
