@@ -1034,7 +1034,8 @@ int rt_debug_div3(rt_context *ctx, const float *in4, size_t n, float *out6);
  * 3 {a0/a1, 1/a0, (a.yz)/a6}, 4 sqrt, 5 mix(a, b, a6), 6 min, 7 sign, 8 pow(a0, 5), 9 the table hash of a.xyz (uint
  * bits); 10 sqrt and 11 normalize in the tagged forms the sample queue runs (csrc/pt_arith.hpp: the WAVE — 64
  * consecutive records — chooses between the bare instruction and the untagged form; same bits as ops 4 and 2,
- * tests/test_gpu_fast_builtins.py).  in8: n × 8 floats {a.xyz, b.xyz, t, -}; out4: n × 4 floats.
+ * tests/test_gpu_fast_builtins.py); 12 min in the tagged form (no canonicalising of the operands: same bits as op 6
+ * for operands that hold no signalling NaN, tests/test_gpu_mixcol.py).  in8: n × 8 floats {a.xyz, b.xyz, t, -}; out4: n × 4 floats.
  * tests/test_gpu_ref950.py compares policies 1 / 2 with probe kernels that call ROCm's OpenCL builtins themselves. */
 int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float *out4);
 /* rt_debug_queue_sums: the sample-queue kernels' per-pixel summation on its own.  ONE wave owns npix pixels of `count`

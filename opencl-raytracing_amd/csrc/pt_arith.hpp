@@ -243,6 +243,36 @@ PT_DEV V3 normalize(V3 v) {
 #endif
     return normalize(v);
 }
+// min (mixCol): __ocml_min_f32 is llvm.minnum, and under the IEEE mode kernels run in the backend puts a
+// canonicalising v_max_f32 x, x in front of each operand it cannot prove quiet — a colour read from LDS, the path
+// colour carried round the loop — so that a signalling NaN comes out quiet: nine half-rate instructions for three
+// minima, at both sites of the sample loop.  They change no bit unless an operand IS a signalling NaN: v_min_f32
+// itself returns the other operand for a quiet NaN, keeps −0 below +0 and keeps denormals.  The tagged form is the
+// instruction alone.  (A minnum whose call carries the no-NaN flag would make the backend leave the operands alone
+// too, but nothing puts that flag on one call here: the tool chain ignores #pragma float_control for this target,
+// and the translation unit is compiled without fast math.)  The asm is not volatile and touches no memory: it may
+// be moved, merged and dropped like the call it stands for.  tools/isa_stats.py is the proof, tests/test_mixcol_host.py
+// keeps it.  Contract: identical to __ocml_min_f32 for every pair of operands that holds no signalling NaN; a
+// signalling NaN in a colour is outside it, as a NaN radiance already is (pt_kernels.hip, queue_sums_tree).
+// -DPT_MIXCOL_FAST=0: the sample queue asks for the untagged min (the switch is read where the tag is set,
+// pt_samples_q_kernel.hpp, so that rt_debug_builtin's probe of the tagged form is the same code in both builds).
+#ifndef PT_MIXCOL_FAST
+#define PT_MIXCOL_FAST 1
+#endif
+#if PT_OCL
+PT_DEV float min_bare(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#endif
+template <bool FAST>
+PT_DEV V3 vmin(V3 a, V3 b) {
+#if PT_OCL
+    if (FAST) return V3{min_bare(a.x, b.x), min_bare(a.y, b.y), min_bare(a.z, b.z)};
+#endif
+    return vmin(a, b);
+}
 // :127 — false for NaN
 PT_DEV bool in_range(float x) { return (x - RT_MAX_DISTANCE) * (x - RT_MIN_DISTANCE) <= 0.0f; }
 

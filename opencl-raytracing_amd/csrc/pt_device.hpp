@@ -1124,8 +1124,16 @@ PT_DEV GlassTerms glass_terms(const Ctx &c, V3 d, V3 hn, uint32_t mat, float ext
 }
 PT_DEV float glass_disc(const GlassTerms &g) { return nmad(g.ratio * g.ratio, nmad(g.cai, g.cai, 1.0f), 1.0f); }   // 1 - ratio * ratio * (1 - cai * cai)   (:381,:424)
 
-// FAST: the glass refraction's square root and the shared tail's normalize in their tagged forms (pt_arith.hpp)
-template <bool COUNT, bool FAST = false, bool BY_COUNT = false>
+// FAST: the glass refraction's square root and the shared tail's normalize in their tagged forms (pt_arith.hpp);
+// MIN_FAST: mixCol's min in its tagged form
+// IN_PLACE (PT_STATE_IN_PLACE bit 0, the sample queue): the glass arm is the chain's last and takes every type the first
+// two do not.  rt_set_scene accepts no type beyond the six, and a light never comes here, so the arm that returned with
+// the ray as it was is never taken — but it made the new direction a value of its own, copied from the old one before
+// the arms and back after them.
+#ifndef PT_STATE_IN_PLACE
+#define PT_STATE_IN_PLACE 3   // bit 0: scatter's arms; bit 1: the hit section of pt_samples_q (pt_samples_q_kernel.hpp)
+#endif
+template <bool COUNT, bool FAST = false, bool BY_COUNT = false, bool MIN_FAST = false, bool IN_PLACE = false>
 PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float extra, V3 col, const Rnd &rnd,
                     bool set_origin = true) {
     V3 v;
@@ -1138,7 +1146,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
         float k = 2.0f * dot(r.d, h.n);
         v = nmad(h.n, k, r.d);   // dir - 2 dot(dir, n) * n
         out = out * extra;  // :366 — only for t_reflective
-    } else if (type == RT_REFRACTIVE || type == RT_DIELECTRIC) {
+    } else if (IN_PLACE || type == RT_REFRACTIVE || type == RT_DIELECTRIC) {
         const GlassTerms g = glass_terms<BY_COUNT>(c, r.d, h.n, h.mat, extra);
         const V3 n = g.n;
         const float ratio = g.ratio, cai = g.cai;
@@ -1164,7 +1172,7 @@ PT_DEV void scatter(const Ctx &c, Ray &r, V3 &out, const Hit &h, int type, float
     if (set_origin) r.o = h.p;
     if (renorm) v = normalize<FAST>(v);
     r.d = v;
-    out = vmin(out, col);  // mixCol is min(), :437
+    out = vmin<MIN_FAST>(out, col);  // mixCol is min(), :437
 }
 
 // :444-486 getCol from bounce i0 on — the sky is black, a path that survives

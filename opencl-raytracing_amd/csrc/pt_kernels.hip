@@ -2504,6 +2504,7 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
     // the tagged forms of pt_arith.hpp as the sample queue runs them (the wave decides: 64 consecutive records)
     else if (op == 10) o.x = sqrt1<true>(a[0]);
     else if (op == 11) { V3 c = normalize<true>(x); o = make_float4(c.x, c.y, c.z, 0.0f); }
+    else if (op == 12) { V3 c = vmin<true>(x, y); o = make_float4(c.x, c.y, c.z, 0.0f); }   // mixCol's min, tagged (op 6: untagged)
     reinterpret_cast<float4 *>(out)[i] = o;
 }
 

@@ -48,6 +48,12 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     // (pt_device.hpp sphere_take): this kernel without counters and without a BVH walk only — every other kernel, and
     // every other instantiation of this one, keeps the untagged code.
     constexpr bool FAST = PT_OCL && !COUNT && !ACCEL && GEOM != 2;
+    // mixCol's min in its tagged form (pt_arith.hpp vmin<FAST>): the same family, without the ray forms, which keep their code
+    constexpr bool MIN_FAST = PT_MIXCOL_FAST && FAST && !RAYS;
+    // The carried state written where it is computed (PT_STATE_IN_PLACE, pt_device.hpp), the same family: scatter's arms
+    // without the arm that leaves the direction alone (SIP_ARMS), and below the hit section under ONE test of "no hit",
+    // with the colour a retiring lane returns in `out` (SIP_HIT: that lane's path colour is dead).
+    constexpr bool SIP_ARMS = FAST && !RAYS && (PT_STATE_IN_PLACE & 1), SIP_HIT = FAST && !RAYS && (PT_STATE_IN_PLACE & 2);
     // The presence of the staged tables by count (pt_device.hpp has_materials): the instantiations that copy the staged block, in every policy.
     // (the ray form was written after that A/B was settled: it takes the settled form whatever the switch says, so the
     // switch keeps changing exactly the instantiations it changed — tests/test_loop_terms_host.py)
@@ -201,7 +207,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             if (BY_USE) fetch_rnd_by_use(rnd, sc.table, r.d, (int)htype, depth, bv, bu);
             load_material<BY_COUNT>(c, hmat, type, extra, mcol);   // extra_data is not carried, nor the type without BY_USE: one LDS read each
             if (BY_USE) type = (int)htype;   // (the same value, and the type's LDS read goes)
-            scatter<COUNT, FAST, BY_COUNT>(c, r, out, at, type, extra, col, rnd, false);
+            scatter<COUNT, FAST, BY_COUNT, MIN_FAST, SIP_ARMS>(c, r, out, at, type, extra, col, rnd, false);
             depth++;
             if (depth >= RT_DEPTH) {  // survived DEPTH bounces: returns what it has (:447,485)
                 queue_put(q, idx, out);
@@ -214,14 +220,17 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         // interaction are issued first (they depend on the ray direction only)
         if (active) {
             if (PT_RNG_PREFETCH == 1) rnd = fetch_rnd_b(sc.table, r.d, depth, bv, bu);
-            V3 res;
+            V3 res;   // what a retiring lane returns (SIP_HIT: in `out`, that lane's path colour being dead)
             bool done = false;
             Hit h;   // (every field is written by hit_finish on a hit, and read only then)
             Nearest nb;
             hit_primitives<COUNT, ACCEL, GEOM != 0, FAST>(c, r, nb);
             if (GEOM != 0) hit_models<COUNT, GEOM == 2>(c, r, nb);
-            if (!hit_finish<COUNT, GEOM == 0, BY_COUNT>(c, r, nb, h)) {
-                res = mk(0.0f, 0.0f, 0.0f);
+            // (SIP_HIT: the test hit_finish makes, made here first — the hit's state is then computed and stored under one
+            // condition, not under two equal ones with the miss between them, across which it lived in registers of its own)
+            if ((SIP_HIT && nb.id == PT_NO_HIT) || !hit_finish<COUNT, GEOM == 0, BY_COUNT>(c, r, nb, h)) {
+                if (SIP_HIT) out = mk(0.0f, 0.0f, 0.0f);
+                else res = mk(0.0f, 0.0f, 0.0f);
                 done = true;
             } else {
                 if (COUNT) cn.c[CN_H_BOUNCE]++;
@@ -235,7 +244,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 load_material<BY_COUNT>(c, h.mat, type, extra, col);
                 if (BY_USE) htype = (uint32_t)type;
                 if (type == RT_LIGHT) {
-                    res = vmin(out, col);
+                    if (SIP_HIT) out = vmin<MIN_FAST>(out, col);
+                    else res = vmin<MIN_FAST>(out, col);
                     done = true;
                 } else if (type == RT_TEXTURED) {
                     if (COUNT) cn.c[CN_N_TEXFETCH]++;
@@ -251,7 +261,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                 }
             }
             if (done) {
-                queue_put(q, idx, res);
+                queue_put(q, idx, SIP_HIT ? out : res);
                 active = false;
             } else if (PT_RNG_PREFETCH == 2) {
                 // this lane WILL interact next iteration: its table reads fly during the refill step

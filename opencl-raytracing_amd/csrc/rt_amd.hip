@@ -2072,7 +2072,7 @@ int rt_walk_overflow(rt_context *ctx, uint32_t *flags_out) {
 }
 
 int rt_debug_builtin(rt_context *ctx, int op, const float *in8, size_t n, float *out4) {
-    if (!ctx || !in8 || !out4 || op < 0 || op > 11 || n > (1u << 26)) return RT_EINVAL;
+    if (!ctx || !in8 || !out4 || op < 0 || op > 12 || n > (1u << 26)) return RT_EINVAL;
     if (n == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return debug_roundtrip(ctx, in8, 8 * n * sizeof(float), out4, 4 * n * sizeof(float), [&](void *d_in, void *d_out) {

@@ -1092,7 +1092,8 @@ class RayTracer:
 
     def debugBuiltin(self, op, vec):
         """One builtin of the selected arithmetic policy per record (rt_debug_builtin): n × 8 floats → n × 4 floats.
-        Ops 10 and 11 are sqrt and normalize in the tagged forms of the sample queue: a wave is 64 consecutive records."""
+        Ops 10 and 11 are sqrt and normalize in the tagged forms of the sample queue: a wave is 64 consecutive records.
+        Op 12 is min in its tagged form (op 6: the untagged one)."""
         vec = np.ascontiguousarray(vec, dtype=np.float32).reshape(-1, 8)
         out = np.zeros((len(vec), 4), dtype=np.float32)
         self._check(self._lib.rt_debug_builtin(self._ctx, op, vec.ctypes.data, len(vec), out.ctypes.data))
