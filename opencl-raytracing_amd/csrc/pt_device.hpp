@@ -315,15 +315,25 @@ PT_DEV float sphere_root(float b, float cc, float dis) {
 #ifndef PT_ROOT_UPDATE
 #define PT_ROOT_UPDATE 1
 #endif
+// The wave is asked first (PT_SPHERE_ANY_FIRST): `dis > 0` is one term of sphere_needs_roots, and in a good half of a
+// C2 wave's tests no active lane has it — a wave-uniform fact, one v_cmp and one s_cbranch_vccz.  Only behind that
+// branch are the three compares of the behind-the-origin skip, their mask logic and the root block issued; the
+// boolean guarding the root block is sphere_needs_roots' own for every lane, so no lane enters that the untagged
+// scan would not have entered (profiles/r30_experiments.md).
+#ifndef PT_SPHERE_ANY_FIRST
+#define PT_SPHERE_ANY_FIRST 1
+#endif
 template <bool FAST>
 PT_DEV void sphere_take(const Ray &r, float4 s, uint32_t id, float &best_t, uint32_t &best_id) {
     float b, cc, dis;
     sphere_disc(r, s, b, cc, dis);
-    if (sphere_needs_roots(b, cc, dis)) {
-        const float t = sphere_roots<FAST>(b, dis);
-        if (t < best_t) {
-            best_t = t;
-            best_id = id;
+    if (!PT_SPHERE_ANY_FIRST || __any(dis > 0)) {
+        if (sphere_needs_roots(b, cc, dis)) {
+            const float t = sphere_roots<FAST>(b, dis);
+            if (t < best_t) {
+                best_t = t;
+                best_id = id;
+            }
         }
     }
 }

@@ -7,8 +7,10 @@ kernel: VGPRs / SGPRs / scratch bytes / spilled VGPRs from the code-object metad
 histogram grouped into the issue-cost classes measured by tools/valu_microbench.hip
 (profiles/r02_valu_microbench.md).  --unit rt_denoise / --unit rt_amd read the policy-free kernels of csrc/rt_denoise.hip
 (pt_atrous, pt_dn_variance, pt_atrous_vg) / csrc/rt_amd.hip (pt_adaptive_merge, ...) instead: compiled once, with the
-IEEE divide.  --json dumps everything for bench.py / profile summaries."""
+IEEE divide.  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
+instructions); --listing prints the labels and instructions of the named kernels."""
 import collections
+import hashlib
 import json
 import os
 import re
@@ -128,11 +130,15 @@ def kernels(path):
         if name not in meta:
             continue
         ops = collections.Counter()
+        code = []   # the listing without directives and comments: labels and instructions with their operands
         for line in body.split("\n"):
             t = line.strip().split()
             if t and re.match(r"^[vs]_|^ds_|^global_|^scratch_|^buffer_|^flat_", t[0]):
                 ops[t[0]] += 1
-        out[name] = dict(meta[name], ops=ops)
+                code.append(re.sub(r"\s*;.*", "", line.strip()))
+            elif t and re.match(r"^\.LBB\d+_\d+:", t[0]):
+                code.append(line.strip())   # a label keeps the compiler's loop comment ("Loop Header", "in Loop")
+        out[name] = dict(meta[name], ops=ops, code=code)
     names = list(out)
     for n, d in zip(names, demangle(names)):
         out[n]["demangled"] = d
@@ -161,8 +167,16 @@ if __name__ == "__main__":
     args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--arith", "--unit")]
     ks = kernels(device_asm("--force" in sys.argv))
     if "--json" in sys.argv:
+        # --digest adds a hash of each kernel's instructions (operands included): two builds whose totals agree can still differ
+        more = (lambda k: dict(code_sha1=hashlib.sha1("\n".join(re.sub(r"\s*;.*", "", c) for c in k["code"]).encode()).hexdigest())) \
+            if "--digest" in sys.argv else (lambda k: {})
         print(json.dumps({k["demangled"]: dict(summarize(k), vgpr=k["vgpr"], sgpr=k["sgpr"], scratch=k["scratch"],
-                                               spilled_vgprs=k["spilled_vgprs"], lds_static=k["lds_static"]) for k in ks.values()}, indent=1))
+                                               spilled_vgprs=k["spilled_vgprs"], lds_static=k["lds_static"], **more(k)) for k in ks.values()}, indent=1))
+        sys.exit(0)
+    if "--listing" in sys.argv:   # the body of every kernel whose name contains one of the substrings
+        for k in ks.values():
+            if any(a in k["demangled"] for a in args):
+                print("; %s\n%s" % (k["demangled"], "\n".join(k["code"])))
         sys.exit(0)
     for k in ks.values():
         if args and not any(a in k["demangled"] for a in args):
