@@ -214,13 +214,26 @@ __global__ __launch_bounds__(256) void pt_render(DeviceScene sc, FrameParams fp,
     flush_counters<COUNT>(cn, counters, 1);
 }
 
-// Caller-supplied rays, fixed lanes (rt_render_rays with counters on, RT_OPT_SAMPLE_QUEUE 0 or sample moments — as
-// plan_camera_samples decides): pt_render<MODE_ACCUM>'s shape with slot i of the launch's range = ray i of fp.rays.  Lane l of
-// the ray's g lanes traces samples first+l, first+l+g, … of the given ray — used as given, not normalised — under the
-// random stream (ray.x, ray.y); the g partial sums meet in the same butterfly and lane 0 adds to accum[i] (and m2[i]).
-template <bool COUNT, bool ACCEL>
-__global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
-                                                      unsigned long long *counters) {
+// s mod set_size for s <= RT_MAX_SAMPLE and set_size <= RT_RAY_SET_MAX without an integer division: the quotient is
+// floor((s + 0.5) · (1 / set_size)) in float — s + 0.5 is exact, the true quotient (s + 0.5) / set_size stands at least
+// 0.5 / set_size from every integer, and the two roundings move the product by less than 2^-22 · 2^16 / set_size =
+// 0.016 / set_size.  (tests/test_ray_sets_host.py walks the whole domain.)
+PT_DEV uint32_t ray_set_member(const FrameParams &fp, uint32_t sample) {
+    const uint32_t set_size = __float_as_uint(fp.cam[0]);
+    return sample - (uint32_t)(((float)sample + 0.5f) * fp.cam[1]) * set_size;
+}
+// the two float4 of record `member` of ray `index`'s set; the record index stays below 2^31 and is formed in 64 bits
+PT_DEV const float4 *ray_set_record(const FrameParams &fp, uint32_t index, uint32_t member) {
+    return fp.rays + 2u * ((size_t)index * __float_as_uint(fp.cam[0]) + member);
+}
+// Caller-supplied rays, fixed lanes (rt_render_rays / rt_render_ray_sets with counters on, RT_OPT_SAMPLE_QUEUE 0 or sample
+// moments — as plan_camera_samples decides): pt_render<MODE_ACCUM>'s shape with slot i of the launch's range = ray i of
+// fp.rays.  Lane l of the ray's g lanes traces samples first+l, first+l+g, … of the given ray — used as given, not
+// normalised — under the random stream (ray.x, ray.y); the g partial sums meet in the same butterfly and lane 0 adds to
+// accum[i] (and m2[i]).  SETS: sample s starts at record s mod set_size of the ray's set, loaded INSIDE the sample loop;
+// otherwise the ray's one record is loaded ahead of it.
+template <bool COUNT, bool ACCEL, bool SETS>
+PT_DEV void render_rays_fixed(const DeviceScene &sc, const FrameParams &fp, float4 *__restrict__ accum, unsigned long long *counters) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
     LaneCounters cn;
     if (COUNT) zero_counters(cn);
@@ -238,14 +251,18 @@ __global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParam
     const bool mom = fp.m2 != nullptr;   // (uniform)
     LaneMoments lm{0.0f, 0.0f};
     if (valid) {
-        const float4 ro = fp.rays[2u * (size_t)index], rd = fp.rays[2u * (size_t)index + 1u];
-        Ray r0;
-        r0.o = mk(ro.x, ro.y, ro.z);
-        r0.d = mk(rd.x, rd.y, rd.z);
-        const uint32_t rx = __float_as_uint(ro.w), ry = __float_as_uint(rd.w);
+        float4 ro, rd;
+        if (!SETS) ro = fp.rays[2u * (size_t)index], rd = fp.rays[2u * (size_t)index + 1u];
         for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
             if (COUNT) cn.c[CN_SAMPLES]++;
-            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, rx, ry);
+            if (SETS) {
+                const float4 *rec = ray_set_record(fp, index, ray_set_member(fp, s));
+                ro = rec[0], rd = rec[1];
+            }
+            Ray r0;
+            r0.o = mk(ro.x, ro.y, ro.z);
+            r0.d = mk(rd.x, rd.y, rd.z);
+            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, __float_as_uint(ro.w), __float_as_uint(rd.w));
             if (mom) moments_fold(lm, sum, rad);
             sum = sum + rad;
         }
@@ -256,6 +273,16 @@ __global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParam
         accumulate(accum, (size_t)index, sum, fp.count);
     }
     flush_counters<COUNT>(cn, counters, 1);
+}
+template <bool COUNT, bool ACCEL>
+__global__ __launch_bounds__(256) void pt_render_rays(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
+                                                      unsigned long long *counters) {
+    render_rays_fixed<COUNT, ACCEL, false>(sc, fp, accum, counters);
+}
+template <bool COUNT, bool ACCEL>
+__global__ __launch_bounds__(256) void pt_render_raysets(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
+                                                         unsigned long long *counters) {
+    render_rays_fixed<COUNT, ACCEL, true>(sc, fp, accum, counters);
 }
 
 // Fused path, stage 1: one work-item per owned PIXEL traces the sample-invariant
@@ -1063,18 +1090,6 @@ PT_DEV WaveQueue queue_stage_raysets(const DeviceScene &sc, const FrameParams &f
     q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
     return q;
 }
-// s mod set_size for s <= RT_MAX_SAMPLE and set_size <= RT_RAY_SET_MAX without an integer division: the quotient is
-// floor((s + 0.5) · (1 / set_size)) in float — s + 0.5 is exact, the true quotient (s + 0.5) / set_size stands at least
-// 0.5 / set_size from every integer, and the two roundings move the product by less than 2^-22 · 2^16 / set_size =
-// 0.016 / set_size.  (tests/test_ray_sets_host.py walks the whole domain.)
-PT_DEV uint32_t ray_set_member(const FrameParams &fp, uint32_t sample) {
-    const uint32_t set_size = __float_as_uint(fp.cam[0]);
-    return sample - (uint32_t)(((float)sample + 0.5f) * fp.cam[1]) * set_size;
-}
-// the two float4 of record `member` of ray `index`'s set; the record index stays below 2^31 and is formed in 64 bits
-PT_DEV const float4 *ray_set_record(const FrameParams &fp, uint32_t index, uint32_t member) {
-    return fp.rays + 2u * ((size_t)index * __float_as_uint(fp.cam[0]) + member);
-}
 // Queue entry idx → (ray p, sample first + j): the sample's own record, and both index sums in full from the record's ids.
 PT_DEV CameraEntry queue_fetch_raysets(const WaveQueue &q, const FrameParams &fp, uint32_t idx) {
     // (p = idx / count as queue_fetch forms it)
@@ -1125,49 +1140,6 @@ PT_DEV CameraEntry queue_fetch_raysets(const WaveQueue &q, const FrameParams &fp
 #define PT_Q_LOOKAHEAD_FORM 3
 #include "pt_samples_q_kernel.hpp"
 #undef PT_Q_LOOKAHEAD_FORM
-
-// Ray sets, fixed lanes (rt_render_ray_sets with counters on, RT_OPT_SAMPLE_QUEUE 0 or sample moments): pt_render_rays with
-// the record loaded INSIDE the sample loop — sample s of ray i starts at record s mod set_size of the ray's set.  A sibling
-// kernel, so that pt_render_rays keeps its name and its code.
-template <bool COUNT, bool ACCEL>
-__global__ __launch_bounds__(256) void pt_render_raysets(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
-                                                         unsigned long long *counters) {
-    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
-    LaneCounters cn;
-    if (COUNT) zero_counters(cn);
-    Ctx c{sc, stage_materials(sc, s_mat), &cn};
-    c.lwin = staged_winners(sc, s_mat);
-    c.lpln = staged_planes(sc, s_mat);
-
-    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t g = 1u << fp.group_log2;
-    const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
-    const uint32_t lane = tid & (g - 1u);
-    const bool valid = index < fp.slot_end && ray_active(fp, index);   // (an adaptive round: the rays of active blocks only)
-
-    V3 sum = mk(0.0f, 0.0f, 0.0f);
-    const bool mom = fp.m2 != nullptr;   // (uniform)
-    LaneMoments lm{0.0f, 0.0f};
-    if (valid) {
-        for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
-            if (COUNT) cn.c[CN_SAMPLES]++;
-            const float4 *rec = ray_set_record(fp, index, ray_set_member(fp, s));
-            const float4 ro = rec[0], rd = rec[1];
-            Ray r0;
-            r0.o = mk(ro.x, ro.y, ro.z);
-            r0.d = mk(rd.x, rd.y, rd.z);
-            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, __float_as_uint(ro.w), __float_as_uint(rd.w));
-            if (mom) moments_fold(lm, sum, rad);
-            sum = sum + rad;
-        }
-    }
-    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
-    if (valid && lane == 0) {
-        if (mom) moments_update(accum, fp.m2, (size_t)index, sum, fp.count, lm.m2);
-        accumulate(accum, (size_t)index, sum, fp.count);
-    }
-    flush_counters<COUNT>(cn, counters, 1);
-}
 
 // The context's staged scene block (rt_context::StageBlock): stage_materials' tables by stage_materials' loops, compiled
 // in this translation unit — the divisions are the policy's.  One workgroup.
@@ -1485,69 +1457,29 @@ __global__ __launch_bounds__(256) void pt_probe(DeviceScene sc, FrameParams fp, 
     out[3 * i + 2] = col.z;
 }
 
-// First-hit feature buffers (rt_render_features): one work-item per pixel of the whole frame.  The primary ray through
-// the nearest-hit search of the trace kernels (hit_primitives + hit_models + hit_finish, the parts of hit_scene, kept
-// apart for the winner's id and face), the material colour or the path's texel, into the public rt_feature record
-// (include/rt_amd.h) as five 16-byte stores.
-template <bool ACCEL>
-__global__ __launch_bounds__(256) void pt_features(DeviceScene sc, FrameParams fp, float4 *__restrict__ out) {
-    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
-    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
-    c.lwin = staged_winners(sc, s_mat);
-    c.lpln = staged_planes(sc, s_mat);
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
-    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
-    const Ray r = primary_ray(fp.cam, x, y, fp.w, fp.h);
-    Nearest nb;
-    hit_primitives<false, ACCEL>(c, r, nb);
-    hit_models<false, ACCEL>(c, r, nb);
-    Hit h;
-    float4 *o = out + 5 * (size_t)i;
-    if (hit_finish<false>(c, r, nb, h)) {
-        int type;
-        float extra;
-        V3 col;
-        load_material(c, h.mat, type, extra, col);
-        if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
-        const bool mesh = (nb.id & K_MASK) == K_MESH;
-        o[0] = make_float4(h.p.x, h.p.y, h.p.z, nb.t);
-        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
-        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
-        o[3] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
-        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(RT_FEATURE_HIT));
-    } else {
-        const float none = __uint_as_float(0xFFFFFFFFu);
-        o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
-        o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
-        o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
-        o[3] = make_float4(r.d.x, r.d.y, r.d.z, none);
-        o[4] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-}
-
-// Feature buffers at the end of the pixel's mirror / glass chain (rt_render_features_chain): pt_features' search and
-// record, in a loop of at most max_chain + 1 hits.  A hit whose material type is selected in `follow` (RT_FOLLOW_*) is
-// followed through scatter() — a dielectric as RT_REFRACTIVE, rayRefract's rule, so no lane draws a random number and
-// nothing reads the table — while fewer than max_chain vertices have been followed; the first hit that is not is the
-// terminal.  t sums the segments in path order; the flags carry RT_FEATURE_CUT, the chain length (bits 8..12) and the
-// upper half of the signature (pt_chain.hpp).  follow == 0 or max_chain == 0: pt_features' record, bit for bit.
-template <bool ACCEL>
-__global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FrameParams fp, uint32_t follow, uint32_t max_chain,
-                                                         float4 *__restrict__ out) {
-    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
-    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
-    c.lwin = staged_winners(sc, s_mat);
-    c.lpln = staged_planes(sc, s_mat);
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
-    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
-    Ray r = primary_ray(fp.cam, x, y, fp.w, fp.h);
+// The feature record of one ray, the body of every pt_features* kernel: the nearest-hit search of the trace kernels
+// (hit_primitives + hit_models + hit_finish, the parts of hit_scene, kept apart for the winner's id and face) in a loop of
+// at most max_chain + 1 hits (max_chain <= RT_FEATURE_CHAIN_MAX: at most RT_DEPTH).  A hit whose material type is selected
+// in `follow` (RT_FOLLOW_*) is followed through scatter() — a dielectric as RT_REFRACTIVE, rayRefract's rule, so no lane
+// draws a random number and nothing reads the table — while fewer than max_chain vertices have been followed; the first
+// hit that is not is the terminal: position, normal, the material colour or the path's texel, the primary direction as
+// given.  t sums the segments in path order; the flags carry RT_FEATURE_CUT, the chain length (bits 8..12) and the upper
+// half of the signature (pt_chain.hpp).  follow == 0 or max_chain == 0: the first hit's record with flags RT_FEATURE_HIT.
+// The five float4 of the public rt_feature (include/rt_amd.h) go to `sink`, called exactly once: inside the terminal branch
+// or at the miss exit, so that the record is never live across the loop (returned by value it cost 18 to 22 VGPRs,
+// profiles/r31_experiments.md).
+struct FeatureRec { float4 o0, o1, o2, o3, o4; };
+struct FeatureStore {   // the sink of the kernels that write memory: five 16-byte stores
+    float4 *o;
+    PT_DEV void operator()(const FeatureRec &f) const { o[0] = f.o0; o[1] = f.o1; o[2] = f.o2; o[3] = f.o3; o[4] = f.o4; }
+};
+template <bool ACCEL, class Sink>
+PT_DEV void feature_chain(const Ctx &c, Ray r, uint32_t follow, uint32_t max_chain, Sink sink) {
     const V3 d0 = r.d;
-    float4 *o = out + 5 * (size_t)i;
     float t_sum = 0.0f;
     uint32_t len = 0u, sig = 0u;
-    for (uint32_t k = 0u; k <= max_chain; k++) {   // (max_chain <= RT_FEATURE_CHAIN_MAX: at most RT_DEPTH hits)
+    FeatureRec f;
+    for (uint32_t k = 0u; k <= max_chain; k++) {
         Nearest nb;
         hit_primitives<false, ACCEL>(c, r, nb);
         hit_models<false, ACCEL>(c, r, nb);
@@ -1574,25 +1506,56 @@ __global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FramePa
         if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
         const bool mesh = (nb.id & K_MASK) == K_MESH;
         const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
-        o[0] = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
-        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
-        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
-        o[3] = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
-        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
+        f.o0 = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
+        f.o1 = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
+        f.o2 = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
+        f.o3 = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
+        f.o4 = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
+        sink(f);
         return;
     }
     // the chain left the scene (a terminal exists whenever the loop runs out: its last pass cannot follow)
     const float none = __uint_as_float(0xFFFFFFFFu);
-    o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
-    o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
-    o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
-    o[3] = make_float4(d0.x, d0.y, d0.z, none);
-    o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
+    f.o0 = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
+    f.o1 = make_float4(0.0f, 0.0f, 0.0f, none);
+    f.o2 = make_float4(0.0f, 0.0f, 0.0f, none);
+    f.o3 = make_float4(d0.x, d0.y, d0.z, none);
+    f.o4 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
+    sink(f);
 }
 
-// Feature records for caller-supplied rays (rt_render_features_rays): pt_features_chain's loop — the same search, scatter
-// and flags, duplicated here so that the camera kernel keeps its code — with record i's primary ray read from ray i of the
-// buffer (n rays = the frame's pixels, row-major).  `dir` is the direction as given.
+// First-hit feature buffers (rt_render_features): one work-item per pixel of the whole frame, feature_chain of the
+// pixel's primary ray with literal (follow, max_chain) = (0, 0) — one search, no follow test.  A kernel of its own: it is
+// the lean one (47 VGPRs without the BVH walk) that the denoisers run every frame.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features(DeviceScene sc, FrameParams fp, float4 *__restrict__ out) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
+    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
+    feature_chain<ACCEL>(c, primary_ray(fp.cam, x, y, fp.w, fp.h), 0u, 0u, FeatureStore{out + 5 * (size_t)i});
+}
+
+// Feature buffers at the end of the pixel's mirror / glass chain (rt_render_features_chain): feature_chain of the pixel's
+// primary ray.  follow == 0 or max_chain == 0: pt_features' record, bit for bit.
+template <bool ACCEL>
+__global__ __launch_bounds__(256) void pt_features_chain(DeviceScene sc, FrameParams fp, uint32_t follow, uint32_t max_chain,
+                                                         float4 *__restrict__ out) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    Ctx c{sc, stage_materials(sc, s_mat), nullptr};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)fp.w * (uint32_t)fp.h) return;
+    const uint32_t x = i % (uint32_t)fp.w, y = i / (uint32_t)fp.w;
+    feature_chain<ACCEL>(c, primary_ray(fp.cam, x, y, fp.w, fp.h), follow, max_chain, FeatureStore{out + 5 * (size_t)i});
+}
+
+// Feature records for caller-supplied rays (rt_render_features_rays): feature_chain with record i's primary ray read from
+// ray i of the buffer (n rays = the frame's pixels, row-major).  `dir` is the direction as given.
 template <bool ACCEL>
 __global__ __launch_bounds__(256) void pt_features_rays(DeviceScene sc, const float4 *__restrict__ rays, uint32_t n, uint32_t follow,
                                                         uint32_t max_chain, float4 *__restrict__ out) {
@@ -1606,59 +1569,43 @@ __global__ __launch_bounds__(256) void pt_features_rays(DeviceScene sc, const fl
     Ray r;
     r.o = mk(ro.x, ro.y, ro.z);
     r.d = mk(rd.x, rd.y, rd.z);
-    const V3 d0 = r.d;
-    float4 *o = out + 5 * (size_t)i;
-    float t_sum = 0.0f;
-    uint32_t len = 0u, sig = 0u;
-    for (uint32_t k = 0u; k <= max_chain; k++) {   // (pt_features_chain's loop)
-        Nearest nb;
-        hit_primitives<false, ACCEL>(c, r, nb);
-        hit_models<false, ACCEL>(c, r, nb);
-        Hit h;
-        if (!hit_finish<false>(c, r, nb, h)) break;
-        int type;
-        float extra;
-        V3 col;
-        load_material(c, h.mat, type, extra, col);
-        t_sum = k == 0u ? nb.t : t_sum + nb.t;
-        const bool followed = (type == RT_REFLECTIVE && (follow & RT_FOLLOW_REFLECTIVE)) ||
-                              (type == RT_REFRACTIVE && (follow & RT_FOLLOW_REFRACTIVE)) ||
-                              (type == RT_DIELECTRIC && (follow & RT_FOLLOW_DIELECTRIC));
-        if (followed && len < max_chain) {
-            sig = pt::chain_signature_step(sig, nb.id);
-            len++;
-            Rnd none;  // mirror / glass by rayRefract's rule: no random numbers
-            none.v = mk(0.0f, 0.0f, 0.0f);
-            none.u = 0.0f;
-            V3 path = mk(1.0f, 1.0f, 1.0f);   // (the path colour is not needed)
-            scatter<false>(c, r, path, h, type == RT_DIELECTRIC ? RT_REFRACTIVE : type, extra, col, none);
-            continue;
-        }
-        if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
-        const bool mesh = (nb.id & K_MASK) == K_MESH;
-        const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
-        o[0] = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
-        o[1] = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
-        o[2] = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
-        o[3] = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
-        o[4] = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
-        return;
-    }
-    // the chain left the scene
-    const float none = __uint_as_float(0xFFFFFFFFu);
-    o[0] = make_float4(0.0f, 0.0f, 0.0f, INFINITY);
-    o[1] = make_float4(0.0f, 0.0f, 0.0f, none);
-    o[2] = make_float4(0.0f, 0.0f, 0.0f, none);
-    o[3] = make_float4(d0.x, d0.y, d0.z, none);
-    o[4] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((len << 8) | (sig & 0xFFFF0000u)));
+    feature_chain<ACCEL>(c, r, follow, max_chain, FeatureStore{out + 5 * (size_t)i});
 }
+
+// The counts of an occlusion kernel leave here (pt_occluded, pt_occluded_hemi): lane = record k of set `set`, occ = its
+// answer (false for a lane that is not live).  set_size 1: out[k] = 0 | 1, a plain store.  Otherwise out (zeroed on the
+// stream before the launch) receives one integer atomicAdd per run of lanes of a wave that share a set — records are
+// consecutive, so a set's lanes are — with the run's count from the ballot: integer sums, the same whatever the order.
+// Every lane of the wave arrives here: none leaves before the ballots.  (A run ends before the next head; lanes past the
+// last record are not occluded.)
+// One text as a statement macro, not a function: with it both kernels keep, instruction for instruction, the code they had
+// with the tail written out.  As a force-inlined function (five forms were tried) the compiler lays pt_occluded's search out
+// under other registers with 4 – 5 more scalar instructions, and pt_occluded<true> took 1.3 % longer over C5's sets of 16
+// in two sessions (profiles/r31_experiments.md).  Each argument is evaluated once on the path that uses it.
+#define PT_OCCLUDED_COUNTS(live, occ, k, set, set_size, out)                                                          \
+    do {                                                                                                              \
+        if ((set_size) == 1u) { /* (uniform) */                                                                       \
+            if (live) (out)[(size_t)(k)] = (occ) ? 1u : 0u;                                                           \
+        } else {                                                                                                      \
+            const uint32_t lane_ = threadIdx.x & 63u, set_ = (set);                                                   \
+            const uint32_t before_ = (uint32_t)__shfl_up((int)set_, 1);                                               \
+            const bool head_ = (live) && (lane_ == 0u || before_ != set_);                                            \
+            const unsigned long long occ_m_ = __ballot(occ), heads_ = __ballot(head_);                                \
+            if (head_) {                                                                                              \
+                const unsigned long long above_ = lane_ == 63u ? 0ull : heads_ >> (lane_ + 1u);                       \
+                const uint32_t len_ = above_ ? (uint32_t)__builtin_ctzll(above_) + 1u : 64u - lane_;                  \
+                const unsigned long long run_ = (len_ == 64u ? ~0ull : (1ull << len_) - 1ull) << lane_;               \
+                const uint32_t count_ = (uint32_t)__popcll(occ_m_ & run_);                                            \
+                if (count_) atomicAdd((out) + (size_t)set_, count_);                                                  \
+            }                                                                                                         \
+        }                                                                                                             \
+    } while (0)
 
 // Occlusion queries (rt_occluded_rays): one lane per record k of n sets x set_size records, ray-major.  The record is
 // occluded iff pt_features_rays' first-hit t for it is below its bound — tmax[k], or t_max where tmax is NULL —
 // (occluded_scene, pt_device.hpp: the search stops at the first report below the bound; no materials, no record).
-// set_size 1: out[k] = 0 | 1, a plain store.  Otherwise out (zeroed on the stream before the launch) receives one integer
-// atomicAdd per run of lanes of a wave that share a set — records are consecutive, so a set's lanes are — with the
-// run's count from the ballot: integer sums, the same whatever the order.  No lane leaves before the ballot.
+// The answers leave through PT_OCCLUDED_COUNTS: out[k] = 0 | 1 for set_size 1, otherwise a count per set.  No lane leaves
+// before it.
 template <bool ACCEL>
 __global__ __launch_bounds__(256) void pt_occluded(DeviceScene sc, const float4 *__restrict__ rays, const float *__restrict__ tmax,
                                                    float t_max, uint32_t records, uint32_t set_size, uint32_t *__restrict__ out) {
@@ -1677,28 +1624,14 @@ __global__ __launch_bounds__(256) void pt_occluded(DeviceScene sc, const float4 
     const float B = b < RT_MAX_DISTANCE ? b : RT_MAX_DISTANCE;
     const bool skip = !live || !(b > RT_MIN_DISTANCE);
     const bool occ = occluded_scene<ACCEL>(sc, r, B, skip);
-    if (set_size == 1u) {
-        if (live) out[(size_t)k] = occ ? 1u : 0u;
-        return;
-    }
-    const uint32_t lane = threadIdx.x & 63u, set = k / set_size;
-    const uint32_t before = (uint32_t)__shfl_up((int)set, 1);
-    const bool head = live && (lane == 0u || before != set);
-    const unsigned long long occ_m = __ballot(occ), heads = __ballot(head);
-    if (head) {   // this lane's run ends before the next head (lanes past the last record are not occluded)
-        const unsigned long long above = lane == 63u ? 0ull : heads >> (lane + 1u);
-        const uint32_t len = above ? (uint32_t)__builtin_ctzll(above) + 1u : 64u - lane;
-        const unsigned long long run = (len == 64u ? ~0ull : (1ull << len) - 1ull) << lane;
-        const uint32_t count = (uint32_t)__popcll(occ_m & run);
-        if (count) atomicAdd(out + (size_t)set, count);
-    }
+    PT_OCCLUDED_COUNTS(live, occ, k, k / set_size, set_size, out);
 }
 
 // Hemisphere queries (rt_occluded_hemispheres): pt_occluded with its rays made in registers.  Lane k = i * set_size + t
 // makes ray t of feature record i (hemisphere_ray, pt_device.hpp: the lanes of a set read the same 80 bytes) and asks
 // occluded_scene with the bound t_max, pt_occluded's rule; a record without a hemisphere is skipped and counts 0.  DUMP
 // stores the ray (zero bytes for such a record) at rays_out[k].  out NULL: the spawn form, every lane skips the search.
-// The counts leave as in pt_occluded (duplicated here so that pt_occluded keeps its code).
+// The counts leave through PT_OCCLUDED_COUNTS, as pt_occluded's do.
 template <bool ACCEL, bool DUMP>
 __global__ __launch_bounds__(256) void pt_occluded_hemi(DeviceScene sc, const float4 *__restrict__ feats, uint32_t k0, uint32_t k1,
                                                         uint32_t flags, float offset, float t_max, uint32_t records, uint32_t set_size,
@@ -1720,27 +1653,12 @@ __global__ __launch_bounds__(256) void pt_occluded_hemi(DeviceScene sc, const fl
     const float B = t_max < RT_MAX_DISTANCE ? t_max : RT_MAX_DISTANCE;
     const bool skip = !valid || !(t_max > RT_MIN_DISTANCE);
     const bool occ = occluded_scene<ACCEL>(sc, r, B, skip);
-    if (set_size == 1u) {
-        if (live) out[(size_t)k] = occ ? 1u : 0u;
-        return;
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t before = (uint32_t)__shfl_up((int)set, 1);
-    const bool head = live && (lane == 0u || before != set);
-    const unsigned long long occ_m = __ballot(occ), heads = __ballot(head);
-    if (head) {
-        const unsigned long long above = lane == 63u ? 0ull : heads >> (lane + 1u);
-        const uint32_t len = above ? (uint32_t)__builtin_ctzll(above) + 1u : 64u - lane;
-        const unsigned long long run = (len == 64u ? ~0ull : (1ull << len) - 1ull) << lane;
-        const uint32_t count = (uint32_t)__popcll(occ_m & run);
-        if (count) atomicAdd(out + (size_t)set, count);
-    }
+    PT_OCCLUDED_COUNTS(live, occ, k, set, set_size, out);
 }
 
 // Feature records through per-sample cameras (rt_render_features_cameras): lane j < n of a pixel's g = 2^glog2 lanes (one
-// wave holds whole pixels) looks through block j of fp.cams and runs pt_features_chain's loop — the same search, scatter
-// and flags, duplicated here so that the single-camera kernel keeps its code — into five registers instead of memory.
-// No lane leaves before the cross-lane steps: a lane without a sample (j >= n, or a pixel past the frame) skips the
+// wave holds whole pixels) looks through block j of fp.cams and takes feature_chain's record into five registers instead of
+// memory.  No lane leaves before the cross-lane steps: a lane without a sample (j >= n, or a pixel past the frame) skips the
 // search under a branch and carries neutral values.  Then, per pixel:
 //   vote   every lane counts the samples that share its key (object, flags >> 8), reading lanes 0 .. n-1 of its group
 //          only; the maximum of (count << 6) | (63 - j) by the butterfly is (m, j*): the largest group, the smallest j
@@ -1768,50 +1686,8 @@ __global__ __launch_bounds__(256) void pt_features_cameras(DeviceScene sc, Frame
     float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (in_frame && j < n) {
         const uint32_t x = pix % (uint32_t)fp.w, y = pix / (uint32_t)fp.w;
-        Ray r = primary_ray(fp.cams + 12u * j, x, y, fp.w, fp.h);
-        const V3 d0 = r.d;
-        float t_sum = 0.0f;
-        uint32_t len = 0u, sig = 0u;
-        bool terminal = false;
-        for (uint32_t k = 0u; k <= max_chain; k++) {   // (pt_features_chain's loop)
-            Nearest nb;
-            hit_primitives<false, ACCEL>(c, r, nb);
-            hit_models<false, ACCEL>(c, r, nb);
-            Hit h;
-            if (!hit_finish<false>(c, r, nb, h)) break;
-            int type;
-            float extra;
-            V3 col;
-            load_material(c, h.mat, type, extra, col);
-            t_sum = k == 0u ? nb.t : t_sum + nb.t;
-            const bool followed = (type == RT_REFLECTIVE && (follow & RT_FOLLOW_REFLECTIVE)) ||
-                                  (type == RT_REFRACTIVE && (follow & RT_FOLLOW_REFRACTIVE)) ||
-                                  (type == RT_DIELECTRIC && (follow & RT_FOLLOW_DIELECTRIC));
-            if (followed && len < max_chain) {
-                sig = pt::chain_signature_step(sig, nb.id);
-                len++;
-                Rnd rnd;  // mirror / glass by rayRefract's rule: no random numbers
-                rnd.v = mk(0.0f, 0.0f, 0.0f);
-                rnd.u = 0.0f;
-                V3 path = mk(1.0f, 1.0f, 1.0f);
-                scatter<false>(c, r, path, h, type == RT_DIELECTRIC ? RT_REFRACTIVE : type, extra, col, rnd);
-                continue;
-            }
-            if (type == RT_TEXTURED) col = texture_rgb(c.sc, h.u, h.v, h.tex);
-            const bool mesh = (nb.id & K_MASK) == K_MESH;
-            const uint32_t flags = RT_FEATURE_HIT | (followed && max_chain ? RT_FEATURE_CUT : 0u) | (len << 8) | (sig & 0xFFFF0000u);
-            o0 = make_float4(h.p.x, h.p.y, h.p.z, t_sum);
-            o1 = make_float4(h.n.x, h.n.y, h.n.z, __uint_as_float(nb.id));
-            o2 = make_float4(col.x, col.y, col.z, __uint_as_float(h.mat));
-            o3 = make_float4(d0.x, d0.y, d0.z, __uint_as_float(mesh ? nb.face : 0xFFFFFFFFu));
-            o4 = make_float4(h.u, h.v, __uint_as_float(h.tex), __uint_as_float(flags));
-            terminal = true;
-            break;
-        }
-        if (!terminal) {   // the chain left the scene
-            o3 = make_float4(d0.x, d0.y, d0.z, none);
-            o4.w = __uint_as_float((len << 8) | (sig & 0xFFFF0000u));
-        }
+        feature_chain<ACCEL>(c, primary_ray(fp.cams + 12u * j, x, y, fp.w, fp.h), follow, max_chain,
+                             [&](const FeatureRec &f) { o0 = f.o0; o1 = f.o1; o2 = f.o2; o3 = f.o3; o4 = f.o4; });
     }
     // ---- the vote: lanes 0 .. n-1 of the group all hold a sample (or none does, past the frame: nothing is written then)
     const uint32_t flags = __float_as_uint(o4.w), key_o = __float_as_uint(o1.w), key_c = flags >> 8;
@@ -2510,33 +2386,30 @@ __global__ __launch_bounds__(256) void pt_debug_builtin(int op, const float *__r
 
 namespace {
 
-int ks_launch_probe(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out) {
-    dim3 grid((n + 255u) / 256u), block(256);
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_probe<true> : pt_probe<false>, grid, block, 0, ctx->stream, sc, fp, d_in, d_in + n,
-                       d_in + 2 * (size_t)n, n, d_out);
+// The launch of every kernel that takes one lane per item: a flat grid of 256-thread workgroups on the context's stream.
+template <class Kernel, class... Args>
+int launch_flat(rt_context *ctx, Kernel kernel, size_t items, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((items + 255u) / 256u)), dim3(256), 0, ctx->stream, args...);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
 
+int ks_launch_probe(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out) {
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_probe<true> : pt_probe<false>, n, sc, fp, d_in, d_in + n, d_in + 2 * (size_t)n, n, d_out);
+}
+
+// rt_render_features: pt_features, one record per pixel
 // (the ACCEL choice of launch_fused: the BVH walks are compiled in when the scene has a BVH)
 int ks_launch_features(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, rt_feature *d_out) {
-    const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
-    dim3 grid((n + 255u) / 256u), block(256);
-    float4 *o = reinterpret_cast<float4 *>(d_out);
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features<true> : pt_features<false>, grid, block, 0, ctx->stream, sc, fp, o);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_features<true> : pt_features<false>, (size_t)fp.w * (size_t)fp.h, sc, fp,
+                       reinterpret_cast<float4 *>(d_out));
 }
 
+// rt_render_features_chain: pt_features_chain, one record per pixel
 int ks_launch_features_chain(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, uint32_t follow, uint32_t max_chain,
                              rt_feature *d_out) {
-    const uint32_t n = (uint32_t)fp.w * (uint32_t)fp.h;
-    dim3 grid((n + 255u) / 256u), block(256);
-    float4 *o = reinterpret_cast<float4 *>(d_out);
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features_chain<true> : pt_features_chain<false>, grid, block, 0, ctx->stream, sc, fp,
-                       follow, max_chain, o);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_features_chain<true> : pt_features_chain<false>, (size_t)fp.w * (size_t)fp.h, sc, fp,
+                       follow, max_chain, reinterpret_cast<float4 *>(d_out));
 }
 
 // rt_debug_plan_feature_cameras: one lane per sample, g = 2^ceil(log2 n) lanes per pixel, whole pixels per 256-thread
@@ -2551,6 +2424,7 @@ FeatureCamerasPlan ks_plan_feature_cameras(uint32_t pixels, uint32_t n) {
     return p;
 }
 
+// rt_render_features_cameras: pt_features_cameras on ks_plan_feature_cameras' grid
 int ks_launch_features_cameras(rt_context *ctx, FrameParams fp, const DeviceScene &sc, const float *d_cams, uint32_t n,
                                uint32_t follow, uint32_t max_chain, rt_feature *d_out, uint2 *d_cov) {
     if (!d_cams || n < 1u || n > RT_FEATURE_CAMERAS_MAX) return fail(ctx, RT_EINVAL, "a feature launch takes 1 .. %u camera blocks", RT_FEATURE_CAMERAS_MAX);
@@ -2563,15 +2437,12 @@ int ks_launch_features_cameras(rt_context *ctx, FrameParams fp, const DeviceScen
     return RT_OK;
 }
 
-// rt_render_features_rays: pt_features_rays, one record per ray (n = the frame's pixels) into d_out
+// rt_render_features_rays, rt_intersect_rays: pt_features_rays, one record per ray into d_out
 int ks_launch_features_rays(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow, uint32_t max_chain,
                             rt_feature *d_out) {
     if (!d_rays || n < 1u) return fail(ctx, RT_EINVAL, "a feature launch over rays needs a ray buffer");
-    float4 *o = reinterpret_cast<float4 *>(d_out);
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_features_rays<true> : pt_features_rays<false>, dim3((n + 255u) / 256u), dim3(256), 0,
-                       ctx->stream, sc, reinterpret_cast<const float4 *>(d_rays), n, follow, max_chain, o);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_features_rays<true> : pt_features_rays<false>, n, sc,
+                       reinterpret_cast<const float4 *>(d_rays), n, follow, max_chain, reinterpret_cast<float4 *>(d_out));
 }
 
 // rt_occluded_rays: pt_occluded over n sets of set_size records; the counts of sets of more than one record are summed
@@ -2582,10 +2453,8 @@ int ks_launch_occluded(rt_context *ctx, const DeviceScene &sc, const void *d_ray
     if (!d_rays || !d_out || n < 1u || set_size < 1u || records > ((size_t)1 << 31))
         return fail(ctx, RT_EINVAL, "an occlusion launch needs rays, an output and at most 2^31 records");
     if (set_size > 1u) HIP_TRY(ctx, hipMemsetAsync(d_out, 0, n * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_occluded<true> : pt_occluded<false>, dim3((uint32_t)((records + 255u) / 256u)), dim3(256),
-                       0, ctx->stream, sc, reinterpret_cast<const float4 *>(d_rays), d_tmax, t_max, (uint32_t)records, set_size, d_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_occluded<true> : pt_occluded<false>, records, sc,
+                       reinterpret_cast<const float4 *>(d_rays), d_tmax, t_max, (uint32_t)records, set_size, d_out);
 }
 
 // rt_occluded_hemispheres: pt_occluded_hemi over n feature records x p.k rays.  d_counts (zeroed on the stream first where
@@ -2599,32 +2468,21 @@ int ks_launch_occluded_hemi(rt_context *ctx, const DeviceScene &sc, const rt_fea
     const bool accel = d_counts && scene_has_accel(sc);
     auto kernel = d_rays_out ? (accel ? pt_occluded_hemi<true, true> : pt_occluded_hemi<false, true>)
                              : (accel ? pt_occluded_hemi<true, false> : pt_occluded_hemi<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)((records + 255u) / 256u)), dim3(256), 0, ctx->stream, sc,
-                       reinterpret_cast<const float4 *>(d_features), (uint32_t)p.seed, (uint32_t)(p.seed >> 32), p.flags, p.offset, p.t_max,
-                       (uint32_t)records, p.k, d_counts, static_cast<float4 *>(d_rays_out));
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, kernel, records, sc, reinterpret_cast<const float4 *>(d_features), (uint32_t)p.seed, (uint32_t)(p.seed >> 32),
+                       p.flags, p.offset, p.t_max, (uint32_t)records, p.k, d_counts, static_cast<float4 *>(d_rays_out));
 }
 
 int ks_launch_debug_hit(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
                         const uint32_t *d_face, uint32_t n, float *d_out) {
-    dim3 grid((n + 255u) / 256u), block(256);
-    hipLaunchKernelGGL(scene_has_accel(sc) ? pt_debug_hit<true> : pt_debug_hit<false>, grid, block, 0, ctx->stream, sc, kind, d_rays,
-                       d_prim, d_face, n, d_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, scene_has_accel(sc) ? pt_debug_hit<true> : pt_debug_hit<false>, n, sc, kind, d_rays, d_prim, d_face, n, d_out);
 }
 
 int ks_launch_debug_material(rt_context *ctx, const DeviceScene &sc, int routine, const float *d_in, uint32_t n, float *d_out) {
-    hipLaunchKernelGGL(pt_debug_material, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, sc, routine, d_in, n, d_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, pt_debug_material, n, sc, routine, d_in, n, d_out);
 }
 
 int ks_launch_debug_div3(rt_context *ctx, const float *d_in, uint32_t n, float *d_out) {
-    hipLaunchKernelGGL(pt_debug_div3, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_in, n, d_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, pt_debug_div3, n, d_in, n, d_out);
 }
 
 int ks_launch_debug_queue_sums(rt_context *ctx, const float *d_in, uint32_t npix, uint32_t count, uint32_t glog2, float *d_out) {
@@ -2638,15 +2496,11 @@ int ks_launch_debug_queue_sums(rt_context *ctx, const float *d_in, uint32_t npix
 
 int ks_launch_face_normals(rt_context *ctx, float4 *d_records, uint32_t n_records) {
     if (n_records == 0) return RT_OK;
-    hipLaunchKernelGGL(pt_face_normals, dim3((n_records + 255u) / 256u), dim3(256), 0, ctx->stream, d_records, n_records);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, pt_face_normals, n_records, d_records, n_records);
 }
 
 int ks_launch_debug_builtin(rt_context *ctx, int op, const float *d_in, uint32_t n, float *d_out) {
-    hipLaunchKernelGGL(pt_debug_builtin, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, op, d_in, n, d_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return launch_flat(ctx, pt_debug_builtin, n, op, d_in, n, d_out);
 }
 
 // rt_debug_queue_pixels: queue_pixels_per_wave as the launcher calls it, under a granule of the caller's choice (0: PT_LDS_GRANULE)

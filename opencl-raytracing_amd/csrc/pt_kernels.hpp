@@ -29,7 +29,8 @@ struct KernelSet {
     int (*launch_lookahead)(rt_context *ctx, const float cam[12], uint32_t first, uint32_t count, float4 *ring);
     // rt_trace_samples: d_in = n x, n y, n sample (uint32), d_out = 3 n floats
     int (*launch_probe)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, const uint32_t *d_in, uint32_t n, float *d_out);
-    // rt_render_features: pt_features, one rt_feature per pixel of the fp.w x fp.h frame into d_out
+    // rt_render_features: pt_features (feature_chain with no follow bits), one rt_feature per pixel of the fp.w x fp.h frame
+    // into d_out
     int (*launch_features)(rt_context *ctx, const FrameParams &fp, const DeviceScene &sc, rt_feature *d_out);
     // unit probes (rt_debug_hit / rt_debug_material / rt_debug_div3)
     int (*launch_debug_hit)(rt_context *ctx, const DeviceScene &sc, int kind, const float *d_rays, const uint32_t *d_prim,
@@ -40,7 +41,8 @@ struct KernelSet {
     // (A, e1, e2, n) records: n_records records of 3 float4 each
     int (*launch_face_normals)(rt_context *ctx, float4 *d_records, uint32_t n_records);
     // one builtin per record, for tests against oracle/_ref/gfx950's probe kernels: op 0 dot, 1 cross, 2 normalize,
-    // 3 a/b, 4 sqrt, 5 mix, 6 min, 7 sign, 8 pow(x,5), 9 the table hash, 10 / 11 sqrt / normalize in their tagged forms;
+    // 3 a/b, 4 sqrt, 5 mix, 6 min, 7 sign, 8 pow(x,5), 9 the table hash, 10 / 11 / 12 sqrt / normalize / min in their tagged
+    // forms;
     // in: n × 8 floats, out: n × 4 floats
     int (*launch_debug_builtin)(rt_context *ctx, int op, const float *d_in, uint32_t n, float *d_out);
     // rt_debug_queue_sums: one wave's queue_sums over npix × count × 3 slot floats into npix float4 (zeroed here)
@@ -82,17 +84,19 @@ struct KernelSet {
     // blocks only, as launch_cameras — the plan and the grid are those of the unmasked launch
     int (*launch_rays)(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
                        float4 *accum, const BlockMask *mask, float *m2);
-    // rt_render_features_rays: pt_features_rays, pt_features_chain's record for each of the n rays at d_rays into d_out
+    // rt_render_features_rays, rt_intersect_rays: pt_features_rays, pt_features_chain's record (the same feature_chain) for
+    // each of the n rays at d_rays into d_out
     int (*launch_features_rays)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, uint32_t n, uint32_t follow,
                                 uint32_t max_chain, rt_feature *d_out);
     // rt_occluded_rays: pt_occluded, for each of the n sets of set_size >= 1 rt_ray records at d_rays (ray-major, at most
     // 2^31 records) the number of records whose first hit lies below the record's bound — d_tmax[k], or t_max where
-    // d_tmax is NULL — into d_out[set] (n uint32, overwritten)
+    // d_tmax is NULL — into d_out[set] (n uint32, overwritten; PT_OCCLUDED_COUNTS)
     int (*launch_occluded)(rt_context *ctx, const DeviceScene &sc, const void *d_rays, size_t n, uint32_t set_size,
                            const float *d_tmax, float t_max, uint32_t *d_out);
     // rt_occluded_hemispheres: pt_occluded_hemi, the p.k hemisphere rays of each of the n feature records at d_features made
-    // in registers: their occluded count into d_counts[record] (n uint32, overwritten; NULL: no search runs) and the rays
-    // themselves into d_rays_out (n * p.k rt_ray records, ray-major; NULL: not stored) — one of the two at least
+    // in registers: their occluded count into d_counts[record] (n uint32, overwritten, through launch_occluded's
+    // PT_OCCLUDED_COUNTS; NULL: no search runs) and the rays themselves into d_rays_out (n * p.k rt_ray records, ray-major;
+    // NULL: not stored) — one of the two at least
     int (*launch_occluded_hemi)(rt_context *ctx, const DeviceScene &sc, const rt_feature *d_features, size_t n,
                                 const rt_hemisphere_params &p, uint32_t *d_counts, void *d_rays_out);
 };

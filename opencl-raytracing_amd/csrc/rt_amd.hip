@@ -1374,6 +1374,14 @@ int rt_device_pixel_error(rt_context *ctx, void **d_err) {
 }  // extern "C"
 
 namespace {
+// the follow bits and the chain length of every call that takes rt_feature_chain_params
+int check_chain_params(rt_context *ctx, const rt_feature_chain_params *p) {
+    if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
+        return fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
+    if (p->max_chain > RT_FEATURE_CHAIN_MAX) return fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    return RT_OK;
+}
+
 // What rt_render_features and rt_render_features_chain share — the state rules, the records' allocation, the frame and
 // scene blocks, `ready` — round the one launch in which they differ (`params_ok`: the caller's own argument checks,
 // made after check_ready and before the shard check, 0 or an RT_* code already recorded on the context).
@@ -1407,11 +1415,7 @@ int rt_render_features(rt_context *ctx, const float camera[12]) {
 int rt_render_features_chain(rt_context *ctx, const float camera[12], const rt_feature_chain_params *p) {
     const int rc = check_ready(ctx, camera);
     if (rc) return rc;
-    int ok = RT_OK;
-    if (!p) ok = fail(ctx, RT_EINVAL, "feature chain parameters are NULL");
-    else if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
-        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
-    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    const int ok = p ? check_chain_params(ctx, p) : fail(ctx, RT_EINVAL, "feature chain parameters are NULL");
     return render_features_with(ctx, camera, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
         return ctx->ks->launch_features_chain(ctx, fp, sc, p->follow, p->max_chain, out);
     });
@@ -1422,14 +1426,11 @@ int rt_render_features_rays(rt_context *ctx, const void *d_rays, size_t n_rays, 
     if (rc) return rc;
     const rt_feature_chain_params first_hits = {0u, 0u};
     if (!p) p = &first_hits;
-    int ok = RT_OK;
+    int ok = check_chain_params(ctx, p);
     const void *rays = nullptr;
-    if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
-        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
-    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
-    else if (n_rays != (size_t)ctx->width * ctx->height)
+    if (ok == RT_OK && n_rays != (size_t)ctx->width * ctx->height)
         ok = fail(ctx, RT_EINVAL, "%zu rays for the feature records of a %d x %d frame", n_rays, ctx->width, ctx->height);
-    else if (!(rays = ray_source(ctx, d_rays, n_rays))) ok = RT_EINVAL;
+    if (ok == RT_OK && !(rays = ray_source(ctx, d_rays, n_rays))) ok = RT_EINVAL;
     return render_features_with(ctx, k_no_camera, ok, [&](const FrameParams &, const DeviceScene &sc, rt_feature *out) {
         return ctx->ks->launch_features_rays(ctx, sc, rays, (uint32_t)n_rays, p->follow, p->max_chain, out);
     });
@@ -1445,9 +1446,8 @@ int rt_intersect_rays(rt_context *ctx, const void *d_rays, size_t n_rays, const 
     const int bad = check_ray_records(ctx, "rt_intersect_rays", n_rays, 0u, false, &records);
     if (bad != RT_OK) return bad;
     if (!d_out || (uintptr_t)d_out % 16u) return fail(ctx, RT_EINVAL, "d_out must be a 16-byte aligned device buffer of rt_feature records");
-    if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
-        return fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
-    if (p->max_chain > RT_FEATURE_CHAIN_MAX) return fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    const int chain = check_chain_params(ctx, p);
+    if (chain != RT_OK) return chain;
     const void *rays = ray_source(ctx, d_rays, n_rays);
     if (!rays) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1533,12 +1533,9 @@ int rt_render_features_cameras(rt_context *ctx, const float *cameras, uint32_t n
     if (rc) return rc;
     const rt_feature_chain_params first_hits = {0u, 0u};
     if (!p) p = &first_hits;
-    int ok = RT_OK;
-    if (n_cameras < 1u || n_cameras > RT_FEATURE_CAMERAS_MAX)
-        ok = fail(ctx, RT_EINVAL, "%u camera blocks outside 1..%u", n_cameras, RT_FEATURE_CAMERAS_MAX);
-    else if (p->follow & ~(RT_FOLLOW_REFLECTIVE | RT_FOLLOW_REFRACTIVE | RT_FOLLOW_DIELECTRIC))
-        ok = fail(ctx, RT_EINVAL, "unknown follow bits 0x%x", p->follow);
-    else if (p->max_chain > RT_FEATURE_CHAIN_MAX) ok = fail(ctx, RT_EINVAL, "max_chain %u above %u", p->max_chain, RT_FEATURE_CHAIN_MAX);
+    const int ok = n_cameras < 1u || n_cameras > RT_FEATURE_CAMERAS_MAX
+                       ? fail(ctx, RT_EINVAL, "%u camera blocks outside 1..%u", n_cameras, RT_FEATURE_CAMERAS_MAX)
+                       : check_chain_params(ctx, p);
     // (cameras: the first block fills FrameParams::cam, which pt_features_cameras does not read)
     const int done = render_features_with(ctx, cameras, ok, [&](const FrameParams &fp, const DeviceScene &sc, rt_feature *out) {
         rt_context::Features &f = ctx->features;

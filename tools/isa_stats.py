@@ -8,7 +8,10 @@ histogram grouped into the issue-cost classes measured by tools/valu_microbench.
 (profiles/r02_valu_microbench.md).  --unit rt_denoise / --unit rt_amd read the policy-free kernels of csrc/rt_denoise.hip
 (pt_atrous, pt_dn_variance, pt_atrous_vg) / csrc/rt_amd.hip (pt_adaptive_merge, ...) instead: compiled once, with the
 IEEE divide.  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
-instructions); --listing prints the labels and instructions of the named kernels."""
+instructions); --listing prints the labels and instructions of the named kernels.  --diff A.json B.json [kernel-substring
+...] compiles nothing: it compares two --json --digest dumps, prints the kernels present in one only and, for every kernel
+whose hash differs, VGPRs, waves per SIMD, scratch, spilled VGPRs and the VALU / SALU / VMEM / LDS instruction counts before
+-> after, and exits non-zero if a kernel that none of the substrings names differs."""
 import collections
 import hashlib
 import json
@@ -163,8 +166,42 @@ def summarize(k):
                 lds=sum(n for o, n in ops.items() if o.startswith("ds_")))
 
 
+def waves_per_simd(vgpr):
+    """Waves per SIMD the VGPR count allows on gfx950: 512 VGPRs per lane, allocated in granules of 8, at most 8 waves."""
+    return min(8, 512 // max(8, -(-vgpr // 8) * 8))
+
+
+def diff(path_a, path_b, allowed):
+    """Compares two --json --digest dumps: kernels in one only, then every kernel whose instruction hash differs, before → after.
+    Returns the number of such kernels whose name contains none of the substrings in `allowed`."""
+    a, b = json.load(open(path_a)), json.load(open(path_b))
+    if not all("code_sha1" in k for d in (a, b) for k in d.values()):
+        sys.exit("--diff needs two dumps made with --json --digest")
+    stray = 0
+    for side, names in (("A", sorted(set(a) - set(b))), ("B", sorted(set(b) - set(a)))):
+        for n in names:
+            ok = any(s in n for s in allowed)
+            stray += not ok
+            print("only in %s: %s%s" % (side, n, "" if ok else "   <-- not named"))
+    changed = [n for n in a if n in b and a[n]["code_sha1"] != b[n]["code_sha1"]]
+    fields = (("vgpr", "VGPR"), ("waves", "waves"), ("scratch", "scratch"), ("spilled_vgprs", "spilled"), ("valu", "VALU"),
+              ("salu", "SALU"), ("vmem", "VMEM"), ("lds", "LDS"))
+    for n in changed:
+        ka, kb = dict(a[n], waves=waves_per_simd(a[n]["vgpr"])), dict(b[n], waves=waves_per_simd(b[n]["vgpr"]))
+        ok = any(s in n for s in allowed)
+        stray += not ok
+        print("%-40s %s%s" % (n, "  ".join("%s %d -> %d" % (t, ka[f], kb[f]) for f, t in fields), "" if ok else "   <-- not named"))
+    print("%d of %d kernels differ, %d of them not named" % (len(changed) + len(set(a) ^ set(b)), len(set(a) | set(b)), stray))
+    return stray
+
+
 if __name__ == "__main__":
-    args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--arith", "--unit")]
+    if "--diff" in sys.argv:   # --diff A.json B.json [kernel-substring ...]: the kernels that are expected to differ
+        rest = sys.argv[sys.argv.index("--diff") + 1:]
+        if len(rest) < 2:
+            sys.exit("--diff A.json B.json [kernel-substring ...]")
+        sys.exit(1 if diff(rest[0], rest[1], rest[2:]) else 0)
+    args =[a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] not in ("--arith", "--unit")]
     ks = kernels(device_asm("--force" in sys.argv))
     if "--json" in sys.argv:
         # --digest adds a hash of each kernel's instructions (operands included): two builds whose totals agree can still differ
