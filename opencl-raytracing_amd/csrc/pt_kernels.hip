@@ -1764,7 +1764,8 @@ __global__ __launch_bounds__(256) void pt_debug_hit(DeviceScene sc, int kind, co
         // a single primitive through the SAME (t, id) search + winner rebuild the trace kernels use
         uint32_t p = prim[i];
         float t = PT_MISS;
-        if (kind == 0) { const rt_sphere &sp = sc.spheres[p]; t = sphere_t(r, make_float4(sp.pos.x, sp.pos.y, sp.pos.z, sp.r * sp.r)); nb.id = K_SPHERE | p; }
+        // (the sphere's test record as apply_arith makes it: w = r under policy 2, whose sphere_disc contracts the product, else r²)
+        if (kind == 0) { const rt_sphere &sp = sc.spheres[p]; t = sphere_t(r, make_float4(sp.pos.x, sp.pos.y, sp.pos.z, PT_SPHERE_W_IS_RADIUS ? sp.r : sp.r * sp.r)); nb.id = K_SPHERE | p; }
         else if (kind == 1) { const rt_plane &pl = sc.planes[p]; t = plane_t(r, ld3(pl.pos), ld3(pl.normal)); nb.id = K_PLANE | p; }
         else if (kind == 2) { int which; t = lens_t(r, sc.lenses[p], &which); nb.id = K_LENS | p; }
         else if (kind == 4) {             // hitTriangle :257-289 on face face[i] of mesh p

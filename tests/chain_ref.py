@@ -137,27 +137,10 @@ def _surface_residuals(scene, rays, out):
     return np.concatenate(res, axis=1), np.concatenate(ids)
 
 
-def identify(probe, scene, rays, out, want_face):
-    """The object id (kind << 30 | index) of every scene hit `out` (n x 12 records of the kind-3 probe for `rays`) and,
-    where `want_face`, the face of a mesh hit.  The hit records carry no object id, so it is found from the geometry, in
-    float64 and independent of the arithmetic policy: the sphere, plane or lens of the hit's material on whose surface the
-    hit point lies (residual <= RESIDUAL_BOUND, every other candidate at least ten bounds away); a hit on none of them
-    belongs to a mesh — the one of the hit's material and texture id (where several share both, the one with a face that
-    returns the hit) — and its face is the first whose triangle probe returns the hit's t, u and v bit for bit."""
-    n = len(rays)
-    obj = np.full(n, A.NO_ID, np.uint32)
-    face = np.full(n, A.NO_ID, np.uint32)
+def _identify_meshes(probe, scene, rays, out, want_face, obj, face):
+    """The mesh and face search of `identify`, for the hits whose obj is still NO_ID: fills obj and face in place."""
     t_bits = bits(out[:, 1])
     mat = bits(out[:, 11])
-    res, ids = _surface_residuals(scene, rays, out)
-    if res.shape[1]:
-        order = np.argsort(res, axis=1, kind="stable")
-        best = np.take_along_axis(res, order[:, :1], 1)[:, 0]
-        on = best <= RESIDUAL_BOUND
-        if res.shape[1] > 1:
-            second = np.take_along_axis(res, order[:, 1:2], 1)[:, 0]
-            assert (second[on] > 10 * RESIDUAL_BOUND).all(), "a hit point on two primitives of one material"
-        obj[on] = ids[order[on, 0]]
     sel = np.nonzero(obj == A.NO_ID)[0]
     if len(sel):
         tex = bits(out[:, 10])
@@ -184,11 +167,60 @@ def identify(probe, scene, rays, out, want_face):
     return obj, face
 
 
-def replay(probe, scene, origin, dirs, follow, max_chain):
+def identify(probe, scene, rays, out, want_face):
+    """The object id (kind << 30 | index) of every scene hit `out` (n x 12 records of the kind-3 probe for `rays`) and,
+    where `want_face`, the face of a mesh hit.  The hit records carry no object id, so it is found from the geometry, in
+    float64 and independent of the arithmetic policy: the sphere, plane or lens of the hit's material on whose surface the
+    hit point lies (residual <= RESIDUAL_BOUND, every other candidate at least ten bounds away); a hit on none of them
+    belongs to a mesh — the one of the hit's material and texture id (where several share both, the one with a face that
+    returns the hit) — and its face is the first whose triangle probe returns the hit's t, u and v bit for bit."""
+    n = len(rays)
+    obj = np.full(n, A.NO_ID, np.uint32)
+    face = np.full(n, A.NO_ID, np.uint32)
+    res, ids = _surface_residuals(scene, rays, out)
+    if res.shape[1]:
+        order = np.argsort(res, axis=1, kind="stable")
+        best = np.take_along_axis(res, order[:, :1], 1)[:, 0]
+        on = best <= RESIDUAL_BOUND
+        if res.shape[1] > 1:
+            second = np.take_along_axis(res, order[:, 1:2], 1)[:, 0]
+            assert (second[on] > 10 * RESIDUAL_BOUND).all(), "a hit point on two primitives of one material"
+        obj[on] = ids[order[on, 0]]
+    return _identify_meshes(probe, scene, rays, out, want_face, obj, face)
+
+
+def identify_by_probe(probe, scene, rays, out, want_face):
+    """`identify` by the search's own rule instead of by geometry, for scenes whose primitives overlap or coincide (tests/
+    edge_scenes.py): the scene search keeps the first primitive, in its order spheres, planes, lenses, that reports the
+    smallest t, so a hit belongs to the first sphere, plane or lens whose own probe (kind 0, 1, 2) for the ray returns the
+    scene hit's t and material bit for bit; a hit that none of them returns belongs to a mesh, found as `identify` finds
+    it.  The probes are those of the arithmetic policy under test, so the rule holds under every policy."""
+    n = len(rays)
+    obj = np.full(n, A.NO_ID, np.uint32)
+    face = np.full(n, A.NO_ID, np.uint32)
+    t_bits = bits(out[:, 1])
+    mat = bits(out[:, 11])
+    for kind, count in ((0, len(scene.spheres)), (1, len(scene.planes)), (2, len(scene.lenses))):
+        todo = np.nonzero(obj == A.NO_ID)[0]
+        if not count or not len(todo):
+            continue
+        step = max(1, MAX_PROBES // count)
+        for a in range(0, len(todo), step):
+            sel = todo[a:a + step]
+            idx = np.tile(np.arange(count, dtype=np.uint32), len(sel))
+            o = probe.hit(kind, np.repeat(rays[sel], count, axis=0), idx).reshape(len(sel), count, 12)
+            cand = (o[..., 0] > 0) & (bits(o[..., 1]) == t_bits[sel, None]) & (bits(o[..., 11]) == mat[sel, None])
+            found = cand.any(1)
+            obj[sel[found]] = (np.uint32(kind) << np.uint32(KIND_SHIFT)) | cand.argmax(1).astype(np.uint32)[found]
+    return _identify_meshes(probe, scene, rays, out, want_face, obj, face)
+
+
+def replay(probe, scene, origin, dirs, follow, max_chain, identify=identify):
     """rt_render_features_chain for the primary rays (origin, dirs[i]) → (records, chain objects): len(dirs) records of
     _abi.FEATURE and, per pixel, the list of followed object ids.  One batched scene probe and one batched call per
     material routine per bounce: routine 0 (rayReflect) for reflective vertices, routine 1 (rayRefract) for refractive
-    and followed dielectric ones."""
+    and followed dielectric ones.  `identify`: the rule that names a hit's object and face — `identify` (the default) or
+    `identify_by_probe`."""
     dirs = np.ascontiguousarray(dirs, dtype=F32).reshape(-1, 3)
     n = len(dirs)
     rec = np.zeros(n, A.FEATURE)

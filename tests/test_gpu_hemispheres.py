@@ -273,7 +273,7 @@ def test_the_calls_move_no_state():
             t.sync()
             accum = torch.as_tensor(t.deviceAccum(), device="cuda").cpu().numpy().copy()
             return (accum.tobytes(), t.transferImage().tobytes(), t.sample_counter, t.moments().tobytes(), t.featureRecords().tobytes(),
-                    repr(t.counters()))
+                    t.counters().as_dict())        # (the values: a Counters object's repr is its address)
 
         before = state()
         hemispheres(t, feats, 64, True, True, seed=2, offset=1e-3, t_max=2.0, face_forward=True)
