@@ -1,6 +1,8 @@
 // raytracer.cpp — see raytracer.h.
 #include "raytracer.h"
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <iostream>
 
@@ -152,6 +154,30 @@ std::vector<float> RayTracer::ambientOcclusion(uint32_t k, float distance, uint6
     const std::vector<uint32_t> counts = occludedHemispheres(p);
     std::vector<float> out(counts.size());
     for (size_t i = 0; i < counts.size(); i++) out[i] = 1.0f - (float)counts[i] / (float)k;
+    return out;
+}
+
+void RayTracer::renderHemispheres(const rt_hemisphere_params &p, uint32_t first_sample, uint32_t n_samples, void *d_accum,
+                                  const void *d_features, size_t n) {
+    if (!d_features) n = (size_t)width * height;
+    check(rt_render_hemispheres(ctx, d_features, n, &p, first_sample, n_samples, d_accum));
+}
+
+std::vector<float> RayTracer::irradiance(uint32_t k, uint32_t spp_per_direction, uint64_t seed, float offset) {
+    const size_t n = (size_t)width * height;
+    if (n == 0 || spp_per_direction == 0) throw RayTracerError(RT_EINVAL, "irradiance takes a frame and at least one sample per direction");
+    std::vector<float> acc(4 * n, 0.0f), out(3 * n, 0.0f);
+    int rc = RT_OK;
+    DeviceBlock d(ctx, acc.size() * sizeof(float), &rc);
+    check(rc);
+    check(rt_device_copy(ctx, d.p, acc.data(), acc.size() * sizeof(float), 1));   // the gather adds: it starts from zero
+    const rt_hemisphere_params p{k, RT_HEMI_FACE_FORWARD, seed, offset, INFINITY};
+    renderHemispheres(p, 0, (uint32_t)std::min<uint64_t>((uint64_t)k * spp_per_direction, UINT32_MAX), d.p);
+    check(rt_device_copy(ctx, acc.data(), d.p, acc.size() * sizeof(float), 0));   // (behind the gather on the stream)
+    const float pi = 3.14159265358979323846f;
+    for (size_t i = 0; i < n; i++)
+        if (acc[4 * i + 3] > 0.0f)
+            for (int c = 0; c < 3; c++) out[3 * i + c] = (pi * acc[4 * i + c]) / acc[4 * i + 3];
     return out;
 }
 

@@ -94,6 +94,14 @@ public:
     // of the context's records (1 on a miss), about the normal turned to face the viewer, rays bounded by `distance`
     std::vector<uint32_t> occludedHemispheres(const rt_hemisphere_params &p, const void *d_features = nullptr, size_t n = 0);
     std::vector<float> ambientOcclusion(uint32_t k = 16, float distance = INFINITY, uint64_t seed = 0, float offset = 0.0f);
+    // hemisphere gather (rt_render_hemispheres, asynchronous): radiance along the same rays, sample s of record i along
+    // hemisphere ray s mod p.k, ADDED to d_accum — n x 4 floats of sums and counts in device memory (rt_device_alloc) — or,
+    // with d_accum null, to the accumulator (the context's own records then).  No ray reaches memory.  irradiance: pi * rgb /
+    // count per pixel of the context's records, three floats each (0 on a miss), k directions about the normal turned to
+    // face the viewer, each followed spp_per_direction times; it waits for the gather
+    void renderHemispheres(const rt_hemisphere_params &p, uint32_t first_sample, uint32_t n_samples, void *d_accum = nullptr,
+                           const void *d_features = nullptr, size_t n = 0);
+    std::vector<float> irradiance(uint32_t k = 16, uint32_t spp_per_direction = 1, uint64_t seed = 0, float offset = 1e-3f);
     // ray sets (rt_render_ray_sets; rays::ray_sets makes them): the uploaded records are w x h sets of set_size records,
     // ray-major, and sample s of pixel i starts at record s mod set_size of its set — anti-aliasing for any projection
     void renderRaySets(uint32_t set_size, uint32_t first_sample, uint32_t n_samples);

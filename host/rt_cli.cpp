@@ -78,6 +78,10 @@
 // records, face-forward, seed --seed): the K rays of every pixel are made in the kernel's registers, so there are no host
 // rays, no upload, and the uploaded rays stay.  The rays are those of the float64 generator to 1e-6, numbered by pixel
 // (the host path numbers them by hit), so the two pictures agree as two estimates do, not bit for bit.
+// --gather K [--gather-spp N] (with --aov, first-hit guides as --ao) adds an irradiance bake: radiance gathered along K
+// device-made cosine-weighted directions from every pixel's first hit, each followed N times (default 1), in one
+// rt_render_hemispheres call over the context's feature records (face-forward, seed --seed, origins lifted by 1e-3);
+// PREFIX_irradiance.pfm = pi * rgb / count, three channels, 0 where the pixel's primary ray missed.  No ray is stored.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -109,10 +113,12 @@ static void usage() {
                  "[--aov PREFIX] [--aa] [--aperture R --focus D] [--aa-guides N] "
                  "[--adaptive-cameras THRESHOLD [--batch N] [--min-spp N] [--counts F.pgm|F.u32]] "
                  "[--adaptive-rule dammertz|variance] [--projection equirect|fisheye|ortho [--fov-deg F] [--extent E] [--ray-sets K] "
-                 "[--adaptive THRESHOLD ...]] [--ao K [--ao-distance D] [--ao-device]]\n"
+                 "[--adaptive THRESHOLD ...]] [--ao K [--ao-distance D] [--ao-device]] [--gather K [--gather-spp N]]\n"
                  "  --ao K (1 .. 4096, with --aov): PREFIX_ao.pfm from K hemisphere rays per first hit, bound D (default inf);"
                  " its rays take 32 B x W x H x K of host and of device memory, unless --ao-device has the device make them"
-                 " in registers (rt_occluded_hemispheres)\n";
+                 " in registers (rt_occluded_hemispheres)\n"
+                 "  --gather K (1 .. 4096, with --aov): PREFIX_irradiance.pfm from K device-made directions per first hit, N samples"
+                 " each (rt_render_hemispheres)\n";
     std::exit(2);
 }
 
@@ -215,6 +221,8 @@ int main(int argc, char **argv) {
     float ao_distance = INFINITY;
     bool ao_distance_given = false;
     bool ao_device = false;   // (the rays of --ao made on the device)
+    long gather = 0;          // (0: no irradiance bake)
+    long gather_spp = 0;      // (0: not given, 1)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&](const char *name) -> const char * {
@@ -268,6 +276,8 @@ int main(int argc, char **argv) {
         else if ((v = val("--follow"))) follow = parse_follow(v);
         else if ((v = val("--max-chain"))) max_chain = parse_int(v, 0, RT_FEATURE_CHAIN_MAX);
         else if ((v = val("--ao"))) ao = parse_int(v, 1, (long)RT_RAY_SET_MAX);
+        else if ((v = val("--gather"))) gather = parse_int(v, 1, (long)RT_RAY_SET_MAX);
+        else if ((v = val("--gather-spp"))) gather_spp = parse_int(v, 1, (long)RT_MAX_SAMPLE + 1);
         else if ((v = val("--ao-distance"))) {
             char *end = nullptr;
             ao_distance = std::strtof(v, &end);
@@ -324,6 +334,9 @@ int main(int argc, char **argv) {
     if (split_chains && !denoise) usage();
     if (ao && (aov_prefix.empty() || follow || aa_guides)) usage();        // --ao fills --aov from first-hit records
     if ((ao_distance_given || ao_device) && !ao) usage();
+    if (gather && (aov_prefix.empty() || follow || aa_guides)) usage();    // --gather fills --aov from first-hit records
+    if (gather_spp && !gather) usage();
+    if (gather && (uint64_t)gather * (uint64_t)std::max(gather_spp, 1L) > (uint64_t)RT_MAX_SAMPLE + 1u) usage();
     if (max_chain < 0) max_chain = RT_FEATURE_CHAIN_MAX;
     if (progressive_cameras && (progressive || adaptive || adaptive_cameras || denoise)) usage();   // one way to spend the samples; the running mean lives in the image
     if (!progressive && !progressive_cameras && lookahead >= 0) usage();   // progressive-only flag
@@ -521,6 +534,14 @@ int main(int argc, char **argv) {
                           << std::chrono::duration<double>(std::chrono::steady_clock::now() - a0).count() * 1e3 << " ms incl. ray generation and read-back" << std::endl;
             }
             write_pfm(aov_prefix + "_ao.pfm", open.data(), 1, 0, 1, w, h);
+        }
+        if (gather) {   // irradiance: radiance gathered along device-made hemisphere rays, in one call
+            const long each = std::max(gather_spp, 1L);
+            auto g0 = std::chrono::steady_clock::now();
+            const std::vector<float> e = tracer.irradiance((uint32_t)gather, (uint32_t)each, seed);
+            std::cout << "irradiance: " << gather << " device-made directions per pixel, " << each << " samples each: "
+                      << std::chrono::duration<double>(std::chrono::steady_clock::now() - g0).count() * 1e3 << " ms incl. read-back" << std::endl;
+            write_pfm(aov_prefix + "_irradiance.pfm", e.data(), 3, 0, 3, w, h);
         }
         if (rule_variance) write_pfm(aov_prefix + "_error.pfm", tracer.pixelError().data(), 1, 0, 1, w, h);
         if (denoise && variance_guided) write_pfm(aov_prefix + "_variance.pfm", tracer.variance(0).data(), 1, 0, 1, w, h);

@@ -692,6 +692,31 @@ int rt_occluded_hemispheres(rt_context *ctx, const void *d_features, size_t n, c
                             void *d_counts, void *d_rays_out);
 
 /*
+ * Hemisphere gather (new): radiance along the same rays — a final gather from hit points, for irradiance bakes, light maps
+ * and probes, in one call and without a ray buffer.  d_features and p as in rt_occluded_hemispheres (p->t_max is not read);
+ * d_accum: n x 4 floats on the device, 16-byte aligned, or NULL for the context's accumulator (n must be W*H then, record i
+ * is pixel i, and rt_resolve, the denoisers and RT_OPT_MOMENTS work as after rt_render_ray_sets).
+ * With R the n * k records rt_occluded_hemispheres' spawn form writes for the same d_features, n and p, the call ADDS to
+ * d_accum[i], for every VALID record i, what rt_render_ray_sets(ctx, R, n, p->k, first_sample, n_samples, d_accum) adds for
+ * set i — bit for bit in all four channels, under every arithmetic policy, RT_OPT_ACCEL, RT_OPT_SAMPLE_QUEUE,
+ * RT_OPT_WAVE_FILL and RT_OPT_MAX_THREADS_PER_LAUNCH, with counters on or off: absolute sample s starts at hemisphere ray
+ * s mod k (Philox counter i*k + s mod k), under the random stream (i, 0), with the sample index s; the samples are summed in
+ * rt_render_spp's fixed order, more than RT_SPP_PER_LAUNCH of them as launches of that many.  An INVALID record adds nothing:
+ * d_accum[i] (count included) and its moment keep their bytes, nothing is traced for it and the counters do not see it —
+ * enabled counters receive what rt_render_ray_sets would add over the valid sets alone.  No ray reaches memory.  With d_accum
+ * NULL the sample moments are updated as rt_render_ray_sets updates them; an external d_accum keeps none.
+ * accum.rgb / accum.w is the mean incoming radiance under the cosine-weighted density: irradiance is pi times it, and the
+ * mean times the record's albedo is the diffuse one-bounce radiance.
+ * Asynchronous on the context's stream; the image, the sample counter, the feature records, a kept prefix and pending
+ * look-ahead frames stay as they are, as under rt_render_rays; rt_debug_last_ray_plan reports these launches.
+ * RT_EINVAL: a NULL ctx or p, n 0 or above RT_MAX_RAYS, k 0 or above RT_RAY_SET_MAX, n * k above 2^31, a misaligned pointer,
+ * unknown flag bits, a non-finite offset, n_samples 0 or samples beyond RT_MAX_SAMPLE, NULL d_features or NULL d_accum with
+ * n != W*H, a sharded context.  RT_ESTATE: no scene set; NULL d_features without ready records.  A failed call changes nothing.
+ */
+int rt_render_hemispheres(rt_context *ctx, const void *d_features, size_t n, const rt_hemisphere_params *p,
+                          uint32_t first_sample, uint32_t n_samples, void *d_accum);
+
+/*
  * Device memory for a host that has no HIP runtime of its own (new) — the buffers the ray queries write into, as the C++
  * façade of host/ makes them.  rt_device_alloc: `bytes` > 0 of memory on the context's device (hipMalloc's alignment), owned by the
  * caller until rt_device_free (NULL is fine; waits for the work that uses the block).  rt_device_copy: `bytes` from `src` to

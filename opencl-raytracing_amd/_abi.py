@@ -444,6 +444,22 @@ def check_hemispheres(features, n, k, flags, offset, counts, rays_out, width, he
     number), 1 <= n <= MAX_RAYS, 1 <= k <= RAY_SET_MAX, n * k <= 2^31, flags within HEMI_FACE_FORWARD, a finite offset,
     `counts` an (n,) int32 and `rays_out` an (n * k, 8) or (n, k, 8) float32 contiguous device tensor — each may be None,
     not both — 16-byte aligned records, an unsharded context.  ValueError otherwise; → HemisphereParams' k and flags."""
+    n, k, flags = check_hemisphere_source(features, n, k, flags, offset, width, height, world)
+    if counts is None and rays_out is None:
+        raise ValueError("a hemisphere query needs counts, rays_out or both")
+    if counts is not None:
+        check_count_target(counts, n)
+    if rays_out is not None:
+        if check_ray_sets(rays_out, k) != n:
+            raise ValueError("rays_out must hold %d x %d records, not shape %s" % (n, k, tuple(rays_out.shape)))
+        if rays_out.data_ptr() % 16:
+            raise ValueError("rays_out must be 16-byte aligned")
+    return k, flags
+
+
+def check_hemisphere_source(features, n, k, flags, offset, width, height, world=1):
+    """The rules rt_occluded_hemispheres and rt_render_hemispheres share, for the records and the parameters (see
+    check_hemispheres).  ValueError otherwise; → (n, k, flags) as ints."""
     n, k, flags = int(n), int(k), int(flags)
     if int(world) > 1:
         raise ValueError("hemisphere queries on a sharded context: shard the records instead")
@@ -457,8 +473,6 @@ def check_hemispheres(features, n, k, flags, offset, counts, rays_out, width, he
         raise ValueError("unknown hemisphere flags 0x%x" % flags)
     if not np.isfinite(offset) or abs(float(offset)) > float(np.finfo(np.float32).max):   # (finite as a float)
         raise ValueError("the hemisphere offset must be finite, not %r" % (offset,))
-    if counts is None and rays_out is None:
-        raise ValueError("a hemisphere query needs counts, rays_out or both")
     if features is None:
         if n != int(width) * int(height):
             raise ValueError("the context's feature records are %d x %d, not %d" % (width, height, n))
@@ -466,14 +480,32 @@ def check_hemispheres(features, n, k, flags, offset, counts, rays_out, width, he
         check_feature_target(features, n)
         if features.data_ptr() % 16:
             raise ValueError("features must be 16-byte aligned")
-    if counts is not None:
-        check_count_target(counts, n)
-    if rays_out is not None:
-        if check_ray_sets(rays_out, k) != n:
-            raise ValueError("rays_out must hold %d x %d records, not shape %s" % (n, k, tuple(rays_out.shape)))
-        if rays_out.data_ptr() % 16:
-            raise ValueError("rays_out must be 16-byte aligned")
-    return k, flags
+    return n, k, flags
+
+
+def check_hemisphere_target(t, n):
+    """The external target of renderHemispheres: renderRays' (check_ray_target) — a torch (n, 4) float32 contiguous device
+    tensor — 16-byte aligned.  ValueError otherwise."""
+    check_ray_target(t, int(n))
+    if t.data_ptr() % 16:
+        raise ValueError("out must be 16-byte aligned")
+
+
+def check_gather(features, n, k, flags, offset, first_sample, n_samples, out, width, height, world=1):
+    """What rt_render_hemispheres refuses with RT_EINVAL, restated without a device: check_hemisphere_source's rules for the
+    records and the parameters, then n_samples (None: k) at least 1 with first_sample + n_samples - 1 <= MAX_SAMPLE, and
+    `out` a check_hemisphere_target or None (the accumulator: n must be width x height).  ValueError otherwise; → (k, flags,
+    first_sample, n_samples) as ints."""
+    n, k, flags = check_hemisphere_source(features, n, k, flags, offset, width, height, world)
+    first_sample, n_samples = int(first_sample), k if n_samples is None else int(n_samples)
+    if n_samples < 1 or first_sample < 0 or first_sample + n_samples - 1 > MAX_SAMPLE:
+        raise ValueError("samples %d..+%d: 1 or more, up to the limit %d" % (first_sample, n_samples, MAX_SAMPLE))
+    if out is None:
+        if n != int(width) * int(height):
+            raise ValueError("%d records into the accumulator of a %d x %d frame" % (n, width, height))
+    else:
+        check_hemisphere_target(out, n)
+    return k, flags, first_sample, n_samples
 
 
 def feature_records(t):
@@ -495,6 +527,7 @@ def ray_prototypes(lib):
     lib.rt_intersect_rays.argtypes = [vp, vp, sz, C.POINTER(FeatureChainParams), vp]
     lib.rt_occluded_rays.argtypes = [vp, vp, sz, u32, vp, C.c_float, vp]
     lib.rt_occluded_hemispheres.argtypes = [vp, vp, sz, C.POINTER(HemisphereParams), vp, vp]
+    lib.rt_render_hemispheres.argtypes = [vp, vp, sz, C.POINTER(HemisphereParams), u32, u32, vp]
     lib.rt_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     lib.rt_device_free.argtypes = [vp, vp]
     lib.rt_device_copy.argtypes = [vp, vp, vp, sz, C.c_int]

@@ -1043,6 +1043,50 @@ PT_DEV bool hemisphere_ray(const float4 *__restrict__ f, uint32_t index, uint32_
     return valid;
 }
 
+// The same ray in two parts, for the kernels that make the k rays of a record one after another (rt_render_hemispheres:
+// pt_samples_q_hemi, pt_render_hemi): what the rays of a record share — hemisphere_valid, hemisphere_frame — once per
+// record, and what ray t adds — hemisphere_point, hemisphere_dir — once per sample.  Operation for operation
+// hemisphere_ray's text above, which pt_occluded_hemi keeps (as one function its code stays what it was): nothing here is
+// contracted and every fma is written out, so frame-then-direction gives hemisphere_ray's bits (tests/test_gpu_gather.py
+// compares them per record).
+PT_DEV bool hemisphere_valid(const float4 *__restrict__ f) {
+    const float4 fn = f[1];
+    const V3 n = mk(fn.x, fn.y, fn.z);
+    const float len2 = dot(n, n);
+    return (__float_as_uint(f[4].w) & RT_FEATURE_HIT) && len2 > 0.0f && len2 < INFINITY;
+}
+struct HemiFrame {
+    V3 o, n, tan, bit;   // the origin pos + offset * n, the unit normal, unit(n x axis) and n x tan
+};
+// (of a record that has a hemisphere)
+PT_DEV void hemisphere_frame(const float4 *__restrict__ f, bool face_forward, float offset, HemiFrame &fr) {
+    const float4 fp = f[0], fn = f[1];
+    V3 n = mk(fn.x, fn.y, fn.z);
+    if (face_forward) {
+        const float4 fd = f[3];
+        if (dot(n, mk(fd.x, fd.y, fd.z)) > 0.0f) n = neg(n);
+    }
+    const float ax = fabsf(n.x), ay = fabsf(n.y), az = fabsf(n.z);
+    n = normalize(n);
+    fr.tan = normalize(ax <= ay && ax <= az ? mk(0.0f, n.z, -n.y) : (ay <= az ? mk(-n.z, 0.0f, n.x) : mk(n.y, -n.x, 0.0f)));
+    fr.bit = cross(n, fr.tan);
+    fr.n = n;
+    fr.o = mk(fp.x, fp.y, fp.z) + n * offset;
+}
+// The ray with Philox counter `index` = rec * k + t in the coordinates of any frame, (along tan, along bit, along n):
+// Malley's point on the unit disk and its height.  It needs nothing of the record.
+PT_DEV V3 hemisphere_point(uint32_t index, uint32_t k0, uint32_t k1) {
+    uint32_t w0, w1;
+    philox_words2(index, k0, k1, w0, w1);
+    const float u = (float)(w0 >> 8) * 0x1p-24f;
+    float sn, cs;
+    sincos_turn24(w1 >> 8, sn, cs);
+    const float rad = sqrt1(u), up = sqrt1(1.0f - u);
+    return mk(rad * cs, rad * sn, up);
+}
+// … and its direction about the record's frame
+PT_DEV V3 hemisphere_dir(const HemiFrame &fr, const V3 &pt) { return normalize((fr.tan * pt.x + fr.bit * pt.y) + fr.n * pt.z); }
+
 // ---- materials -------------------------------------------------------------------
 // :401-405
 PT_DEV float schlick(float cosine, float r0) { return mad(1.0f - r0, pow5(1.0f - cosine), r0); }   // r0 + (1 - r0) * pow(1 - cai, 5)

@@ -17,6 +17,15 @@
 #include "rt_context.hpp"
 #include "pt_kernels.hpp"
 
+// This text is compiled twice per arithmetic policy.  As it stands it is the policy's translation unit: every kernel but
+// those of rt_render_hemispheres.  Included by pt_gather.hip, which defines PT_GATHER_UNIT, it is the unit of those kernels
+// (pt_samples_q_hemi, pt_render_hemi): the device code they share with the rest is the text below, the kernels that are no
+// templates and the launchers are left out, and nothing else is instantiated.  A policy's code object of this unit keeps
+// the kernels it had; the launchers here reach the others through pt::GatherKernels (pt_kernels.hpp).
+#ifndef PT_GATHER_UNIT
+#define PT_GATHER_UNIT 0
+#endif
+
 namespace PT_NS {
 using namespace rtamd;
 
@@ -285,6 +294,69 @@ __global__ __launch_bounds__(256) void pt_render_raysets(DeviceScene sc, FramePa
     render_rays_fixed<COUNT, ACCEL, true>(sc, fp, accum, counters);
 }
 
+// Hemisphere gathers (rt_render_hemispheres): a ray-set launch whose sets are MADE — slot i is feature record i of fp.feats,
+// sample s starts at hemisphere ray s mod k of the record (Philox counter i · k + s mod k, random stream (i, 0)): the rays
+// rt_occluded_hemispheres' spawn form writes, never written.  What the spawn kernel takes as arguments travels in fp.cam
+// beside the set size and its reciprocal (ray_set_member reads those two as it does for a ray-set launch):
+#define HEMI_CAM_KEY0 2     // the Philox key: the seed's low and high word
+#define HEMI_CAM_KEY1 3
+#define HEMI_CAM_OFFSET 4   // rt_hemisphere_params::offset
+#define HEMI_CAM_FLAGS 5    // rt_hemisphere_params::flags
+PT_DEV void hemi_frame_of(const FrameParams &fp, uint32_t index, HemiFrame &fr) {   // (of a record that has a hemisphere)
+    hemisphere_frame(fp.feats + 5u * (size_t)index, (__float_as_uint(fp.cam[HEMI_CAM_FLAGS]) & RT_HEMI_FACE_FORWARD) != 0u,
+                     fp.cam[HEMI_CAM_OFFSET], fr);
+}
+// (The key is opaque to the optimiser and waits for the counter: the generator's twenty round keys are launch constants, and
+// lifted out of the sample loop they took twenty scalar registers of kernels that have none to spare — they went to VGPR
+// lanes, and the (ACCEL, GEOM 2) row spilled one vector register more than its ray-set twin.  DESIGN.md §5 "Hemisphere gather")
+PT_DEV V3 hemi_point_of(const FrameParams &fp, uint32_t index, uint32_t sample) {
+    uint32_t counter = index * __float_as_uint(fp.cam[0]) + ray_set_member(fp, sample);   // (< 2^31)
+    uint32_t k0 = __float_as_uint(fp.cam[HEMI_CAM_KEY0]), k1 = __float_as_uint(fp.cam[HEMI_CAM_KEY1]);
+    asm("" : "+s"(k0), "+s"(k1), "+v"(counter));
+    return hemisphere_point(counter, k0, k1);
+}
+// Fixed lanes (counters on, RT_OPT_SAMPLE_QUEUE 0 or sample moments): render_rays_fixed with the ray made inside the sample
+// loop from a frame formed ahead of it.  A record without a hemisphere is an unowned slot: no sample, no sum, no counter.
+template <bool COUNT, bool ACCEL>
+__global__ __launch_bounds__(256) void pt_render_hemi(DeviceScene sc, FrameParams fp, float4 *__restrict__ accum,
+                                                      unsigned long long *counters) {
+    __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
+    LaneCounters cn;
+    if (COUNT) zero_counters(cn);
+    Ctx c{sc, stage_materials(sc, s_mat), &cn};
+    c.lwin = staged_winners(sc, s_mat);
+    c.lpln = staged_planes(sc, s_mat);
+
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t g = 1u << fp.group_log2;
+    const uint32_t index = fp.slot_begin + (tid >> fp.group_log2);
+    const uint32_t lane = tid & (g - 1u);
+    const bool valid = index < fp.slot_end && hemisphere_valid(fp.feats + 5u * (size_t)index);
+
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    const bool mom = fp.m2 != nullptr;   // (uniform)
+    LaneMoments lm{0.0f, 0.0f};
+    if (valid) {
+        HemiFrame fr;
+        hemi_frame_of(fp, index, fr);
+        for (uint32_t s = fp.first + lane; s < fp.first + fp.count; s += g) {
+            if (COUNT) cn.c[CN_SAMPLES]++;
+            Ray r0;
+            r0.o = fr.o;
+            r0.d = hemisphere_dir(fr, hemi_point_of(fp, index, s));
+            const V3 rad = radiance<COUNT, ACCEL>(c, r0, s, index, 0u);
+            if (mom) moments_fold(lm, sum, rad);
+            sum = sum + rad;
+        }
+    }
+    sum = mom ? group_sum_moments(sum, lm, g) : group_sum(sum, g);
+    if (valid && lane == 0) {
+        if (mom) moments_update(accum, fp.m2, (size_t)index, sum, fp.count, lm.m2);
+        accumulate(accum, (size_t)index, sum, fp.count);
+    }
+    flush_counters<COUNT>(cn, counters, 1);
+}
+
 // Fused path, stage 1: one work-item per owned PIXEL traces the sample-invariant
 // prefix of the pixel's paths (pt_device.hpp "shared deterministic prefix").
 // A pixel whose paths never meet a random event (sky, direct light, mirror /
@@ -442,6 +514,7 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
     }
 }
 
+#if !PT_GATHER_UNIT   // (no template: a kernel of the policy's own unit)
 // Fused path, stage 1 while the prefix is still valid (launch_fused, rt_context::PrefixCache): records, live list,
 // counters and trees lie in the slot buffers as the last pt_prefix left them, and all that remains of the first stage is
 // the finished pixels' share of THIS call's samples.  One workgroup per pt_prefix workgroup over its run of the
@@ -456,6 +529,7 @@ __global__ __launch_bounds__(256) void pt_final_replay(FrameParams fp, const Fin
     if (fp.m2) moments_update(accum, fp.m2, (size_t)y * fp.w + x, fsum, fp.count, 0.0f);   // (as pt_prefix)
     accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
 }
+#endif
 
 // Where frame j of pixel pix lies in the look-ahead ring (in float4).  Shipped: FRAME-MAJOR, frame after frame, so that a frame
 // is handed out as one contiguous device copy.  -DPT_RING_PIXEL_MAJOR=1 builds the A/B variant that keeps a pixel's `count`
@@ -464,6 +538,7 @@ PT_DEV size_t ring_at(const FrameParams &fp, size_t pix, uint32_t j) {
     return PT_RING_PIXEL_MAJOR ? pix * fp.count + j : j * ((size_t)fp.w * fp.h) + pix;
 }
 
+#if !PT_GATHER_UNIT
 // Look-ahead launches (FrameParams::la_ring): the finished pixels' part of the fp.count frames.  Every sample of such a pixel
 // is the listed colour, so its chain is `count` retrace steps with that colour from the image as it lies, the result of
 // step j going to frame j of the ring.  pt_final_replay's grid; runs after pt_prefix and on a prefix-cache hit alike.
@@ -482,6 +557,7 @@ __global__ __launch_bounds__(256) void pt_final_retrace(FrameParams fp, const Fi
         fp.la_ring[ring_at(fp, pix, j)] = make_float4(prev.x, prev.y, prev.z, 1.0f);
     }
 }
+#endif
 
 // Fused path, stage 2: one group of g lanes per LIVE pixel; each lane continues
 // its samples from the pixel's record.  Same summation order as pt_render.
@@ -1105,6 +1181,64 @@ PT_DEV CameraEntry queue_fetch_raysets(const WaveQueue &q, const FrameParams &fp
     return e;
 }
 
+// ---- the queue's entry FROM FEATURE RECORDS (pt_samples_q_hemi; rt_render_hemispheres) ------------------------------------
+// The ray-set entry with the set made at the refill instead of loaded: slot i of the launch's range is feature record i of
+// fp.feats, and the kernel gives a slot to a lane only where the record has a hemisphere (hemisphere_valid, where the ray
+// forms test ray_active) — an invalid record is in no wave's queue.  What a record's k rays share is staged once, in the
+// LDS layout of the ray entry:
+//   coordinates   (x: the record index, y: 0, rnd_base_v(0, i, 0), rnd_base_u(0, i, 0)): the spawn form's rays name the
+//                 random stream (i, 0);
+//   record        of the 80 bytes the first four float4 hold the frame — o, n̂, tan, bit, three floats each.
+// A refill reads the frame back (four 12-byte LDS reads) and makes ray s mod k in registers: nothing comes from global memory.
+PT_DEV WaveQueue queue_stage_hemi(const DeviceScene &sc, const FrameParams &fp, bool owns, uint32_t index,
+                                  unsigned long long owners, uint32_t pixels_per_wave, float4 *lds, uint32_t face_f4) {
+    float4 *wave_lds = lds + queue_static_f4(sc, face_f4);
+    WaveQueue q;
+    q.rec = (LdsQueueF4)wave_lds;
+    q.xy = (LdsQueueXY)(wave_lds + queue_xy_f4(pixels_per_wave));
+    q.slot = (LdsF32)(wave_lds + queue_slot_f4(pixels_per_wave));
+    q.npix = (uint32_t)__popcll(owners);
+    q.count = fp.count;
+    q.total = q.npix * q.count;
+    if (owns) {
+        const uint32_t k = lanes_below(owners);   // (< npix <= pixels_per_wave)
+        HemiFrame fr;
+        hemi_frame_of(fp, index, fr);
+        q.xy[k].x = index;
+        q.xy[k].y = 0u;
+        q.xy[k].bv = rnd_base_v(0u, index, 0u);
+        q.xy[k].bu = rnd_base_u(0u, index, 0u);
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k) = v4f{fr.o.x, fr.o.y, fr.o.z, 0.0f};
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k + 1u) = v4f{fr.n.x, fr.n.y, fr.n.z, 0.0f};
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k + 2u) = v4f{fr.tan.x, fr.tan.y, fr.tan.z, 0.0f};
+        *(LdsV4Rw)(q.rec + QUEUE_REC_F4 * k + 3u) = v4f{fr.bit.x, fr.bit.y, fr.bit.z, 0.0f};
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    q.inv_count = fp.inv_count;
+    q.count_log2 = (q.count & (q.count - 1u)) == 0u ? (uint32_t)__builtin_ctz(q.count) : 0xFFu;
+    return q;
+}
+// Queue entry idx → (record p, sample first + j): hemisphere ray s mod k about the staged frame, and the sample's part of the
+// two index sums.
+PT_DEV CameraEntry queue_fetch_hemi(const WaveQueue &q, const FrameParams &fp, uint32_t idx) {
+    // (p = idx / count as queue_fetch forms it)
+    const uint32_t p = q.count_log2 != 0xFFu ? idx >> q.count_log2 : (uint32_t)(((float)idx + 0.5f) * q.inv_count);
+    const uint32_t sample = fp.first + (idx - p * q.count);
+    const LdsQueueF4 st = q.rec + QUEUE_REC_F4 * p;
+    HemiFrame fr;
+    fr.o = mk(st[0].x, st[0].y, st[0].z);
+    fr.n = mk(st[1].x, st[1].y, st[1].z);
+    fr.tan = mk(st[2].x, st[2].y, st[2].z);
+    fr.bit = mk(st[3].x, st[3].y, st[3].z);
+    CameraEntry e;
+    e.r.o = fr.o;
+    e.r.d = hemisphere_dir(fr, hemi_point_of(fp, q.xy[p].x, sample));
+    e.bv = sample * 8049u + q.xy[p].bv;   // = rnd_base_v(sample, i, 0)
+    e.bu = sample * 2683u + q.xy[p].bu;   // = rnd_base_u(sample, i, 0)
+    return e;
+}
+
 // ACCEL: the sphere BVH walk is compiled in.  GEOM: 0 = the scene holds spheres and planes only (C1, C2, C4: no
 // lens, model or mesh code at all), 1 = everything by brute force or through the sphere BVH, 2 = the mesh BVH
 // walk too.  A scene whose only BVH is the sphere BVH (C4) runs <true, 0>: without the mesh walk's registers the
@@ -1140,12 +1274,19 @@ PT_DEV CameraEntry queue_fetch_raysets(const WaveQueue &q, const FrameParams &fp
 #define PT_Q_LOOKAHEAD_FORM 3
 #include "pt_samples_q_kernel.hpp"
 #undef PT_Q_LOOKAHEAD_FORM
+// … and a fifth time as pt_samples_q_hemi<ACCEL, GEOM, WAVES>, the ray-set form with the sets made from feature records
+// (rt_render_hemispheres; queue_stage_hemi above).
+#define PT_Q_LOOKAHEAD_FORM 4
+#include "pt_samples_q_kernel.hpp"
+#undef PT_Q_LOOKAHEAD_FORM
 
+#if !PT_GATHER_UNIT
 // The context's staged scene block (rt_context::StageBlock): stage_materials' tables by stage_materials' loops, compiled
 // in this translation unit — the divisions are the policy's.  One workgroup.
 __global__ __launch_bounds__(64) void pt_stage_block(DeviceScene sc, float4 *__restrict__ block) {
     stage_tables(sc, block, lds_mat_n(sc.material_count), lds_win_n(sc.sphere_count), lds_pln_n(sc.plane_count));
 }
+#endif
 
 // pt_samples_w — the sample queue for scenes in which every mesh of every model has a BVH (C5: one mesh of
 // 50 000 faces).  The mesh walk
@@ -1785,6 +1926,32 @@ __global__ __launch_bounds__(256) void pt_debug_hit(DeviceScene sc, int kind, co
     put_hit(out + 12 * (size_t)i, hit, nb.t, h);
 }
 
+// The sample queue's five geometry rows, the key (accel, geom, waves) that queue_size yields: X(ACCEL, GEOM, WAVES) per row,
+// for the launchers' table below and for the gather unit's
+#define PT_QUEUE_ROWS(X) \
+    X(false, 0, PT_Q_WAVES) X(false, 1, PT_Q_WAVES) X(true, 0, PT_Q_WAVES_SPHERE_BVH) X(true, 1, PT_Q_WAVES_ACCEL) X(true, 2, PT_Q_WAVES_ACCEL)
+
+#if PT_GATHER_UNIT
+// ---- the gather unit: the kernels of rt_render_hemispheres and nothing else ------------------------------------------------
+namespace {
+pt::GatherKernels::Queue gather_queue_kernel(uint32_t accel, uint32_t geom, uint32_t waves) {
+    struct Row { uint32_t accel, geom, waves; pt::GatherKernels::Queue kernel; };
+#define PT_GATHER_ROW(ACCEL, GEOM, WAVES) {ACCEL, GEOM, WAVES, pt_samples_q_hemi<ACCEL, GEOM, WAVES>},
+    static const Row rows[] = {PT_QUEUE_ROWS(PT_GATHER_ROW)};
+#undef PT_GATHER_ROW
+    for (const Row &r : rows)
+        if (r.accel == accel && r.geom == geom && r.waves == waves) return r.kernel;
+    return nullptr;
+}
+pt::GatherKernels::Fixed gather_fixed_kernel(bool count, bool accel) {   // [COUNT][ACCEL]
+    static const pt::GatherKernels::Fixed k[2][2] = {{pt_render_hemi<false, false>, pt_render_hemi<false, true>},
+                                                 {pt_render_hemi<true, false>, pt_render_hemi<true, true>}};
+    return k[count][accel];
+}
+const pt::GatherKernels g_gather_kernels = {gather_queue_kernel, gather_fixed_kernel};
+}  // namespace
+#else   // the policy's own unit, to the end of the text
+
 __global__ __launch_bounds__(256) void pt_debug_material(DeviceScene sc, int routine, const float *__restrict__ in,
                                                          uint32_t n, float *__restrict__ out) {
     __shared__ float4 s_mat[PT_LDS_STATIC_FLOAT4];
@@ -2053,7 +2220,8 @@ static FixedKernel fixed_kernel(const SamplePlan &p) {   // [COUNT][ACCEL]
 using QueueKernel = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *, uint32_t);
 // The sample queue's five geometry rows: the key (accel, geom, waves) that queue_size yields, once, with every kernel of the
 // row — fed from pt_prefix's records, from camera blocks (its look-ahead form: the rows without a BVH walk branch on
-// fp.la_ring themselves, the ACCEL rows have pt_samples_q_la), from rays and from ray sets.
+// fp.la_ring themselves, the ACCEL rows have pt_samples_q_la), from rays and from ray sets.  (Fed from feature records:
+// pt_samples_q_hemi, the gather unit's — gather_kernels below.)
 struct QueueRow {
     uint32_t accel, geom, waves;
     QueueKernel recs[2][2];   // [COUNT][MOMENTS]
@@ -2074,8 +2242,9 @@ static QueueRow queue_row() {
 // for the `family` that asked (neither planner asks for a row that is not there).
 static const QueueRow *find_queue_row(rt_context *ctx, const char *family, uint32_t accel, uint32_t geom, uint32_t waves,
                                       uint32_t count_log2 = RT_PLAN_GENERIC_COUNT) {
-    static const QueueRow rows[] = {queue_row<false, 0, PT_Q_WAVES>(), queue_row<false, 1, PT_Q_WAVES>(), queue_row<true, 0, PT_Q_WAVES_SPHERE_BVH>(),
-                                    queue_row<true, 1, PT_Q_WAVES_ACCEL>(), queue_row<true, 2, PT_Q_WAVES_ACCEL>()};
+#define PT_QUEUE_ROW(ACCEL, GEOM, WAVES) queue_row<ACCEL, GEOM, WAVES>(),
+    static const QueueRow rows[] = {PT_QUEUE_ROWS(PT_QUEUE_ROW)};
+#undef PT_QUEUE_ROW
     if (count_log2 == RT_PLAN_GENERIC_COUNT)
         for (const QueueRow &r : rows)
             if (r.accel == accel && r.geom == geom && r.waves == waves) return &r;
@@ -2254,13 +2423,24 @@ static RayRenderKernel ray_render_kernel(bool count, bool accel, bool sets) {   
                                                  {pt_render_raysets<true, false>, pt_render_raysets<true, true>}};
     return sets ? k_sets[count][accel] : k[count][accel];
 }
+// the kernels of rt_render_hemispheres: this policy's gather unit has them (pt_gather.hip)
+static const pt::GatherKernels &gather_kernels() {
+#if PT_ARITH == 0
+    return *pt::gather_kernels_a0();
+#elif PT_ARITH == 1
+    return *pt::gather_kernels_a1();
+#else
+    return *pt::gather_kernels_a2();
+#endif
+}
 
 // What feeds a launch of launch_source, on the device.  Cameras: `count` blocks of 12 floats at p, sample first + j through
 // block j, over the owned pixels of the (sharded) frame; cam0 is the first block.  Rays: n rt_ray records at p (set_size 0) or
 // n sets of set_size records, ray-major, slot = ray index; cam0 is zero but for the set size and its reciprocal in its first
-// two words (queue_stage_raysets).  cam0 fills FrameParams::cam, which no camera kernel reads.
+// two words (queue_stage_raysets).  Hemispheres (`hemi`, a ray source): n rt_feature records at p, the sets of set_size
+// rays made from them; cam0 holds the HEMI_CAM_* words too.  cam0 fills FrameParams::cam, which no camera kernel reads.
 struct SampleSource {
-    bool rays;
+    bool rays, hemi;
     const void *p;
     size_t n;
     uint32_t set_size;
@@ -2279,7 +2459,7 @@ struct SampleSource {
 // it lies (the caller copied it there on the stream), and the accumulator is not touched.  The facts carry moments = 0.
 static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
                          const BlockMask *mask, float *m2, float4 *ring) {
-    const bool sets = src.set_size != 0u;
+    const bool sets = src.set_size != 0u && !src.hemi;
     if (!src.rays) {
         if (!src.p || count < 1u || count > RT_SPP_PER_LAUNCH) return fail(ctx, RT_EINVAL, "a camera launch takes 1 .. %u blocks", RT_SPP_PER_LAUNCH);
     } else {
@@ -2294,7 +2474,7 @@ static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t firs
                               : frame_params(ctx, src.cam0, first, count, glog2);
     apply_mask(fp, mask);
     fp.m2 = m2;
-    if (src.rays) fp.rays = reinterpret_cast<const float4 *>(src.p);
+    if (src.rays) fp.rays = reinterpret_cast<const float4 *>(src.p);   // (a hemisphere source: fp.feats, the same bytes)
     else fp.cams = reinterpret_cast<const float *>(src.p);
     const DeviceScene sc = device_scene(ctx);
     if (ring) {
@@ -2313,12 +2493,15 @@ static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t firs
         if (plan.family == RT_CAMERA_PLAN_QUEUE) {
             const QueueRow *r = find_queue_row(ctx, src.rays ? "ray" : "camera", plan.accel, plan.geom, plan.waves);
             if (!r) return RT_ESTATE;
-            hipLaunchKernelGGL(!src.rays ? r->cams[ring != nullptr] : sets ? r->ray_sets : r->rays, grid, block, plan.lds_bytes, ctx->stream,
+            const QueueKernel kernel = !src.rays ? r->cams[ring != nullptr] : src.hemi ? gather_kernels().queue(plan.accel, plan.geom, plan.waves)
+                                       : sets ? r->ray_sets : r->rays;
+            if (!kernel) return fail(ctx, RT_ESTATE, "no pt_samples_q_hemi for the plan (accel %u, geom %u, %u waves)", plan.accel, plan.geom, plan.waves);
+            hipLaunchKernelGGL(kernel, grid, block, plan.lds_bytes, ctx->stream,
                                sc, fp, (const PixelRec *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, accum,
                                ctx->counters.p, plan.pixels_per_wave);
         } else if (src.rays) {
-            hipLaunchKernelGGL(ray_render_kernel(plan.count != 0u, plan.accel != 0u, sets), grid, block, 0, ctx->stream, sc, fp, accum,
-                               ctx->counters.p);
+            hipLaunchKernelGGL(src.hemi ? gather_kernels().fixed(plan.count != 0u, plan.accel != 0u) : ray_render_kernel(plan.count != 0u, plan.accel != 0u, sets),
+                               grid, block, 0, ctx->stream, sc, fp, accum, ctx->counters.p);
         } else {
             hipLaunchKernelGGL(camera_render_kernel(plan.count != 0u, plan.accel != 0u), grid, block, 0, ctx->stream, sc, fp, accum,
                                ctx->image.p, ctx->counters.p);
@@ -2332,7 +2515,7 @@ static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t firs
 // rt_render_spp_cameras, rt_render_adaptive_cameras, rt_render_again_cameras: `count` blocks at d_cams, cam0 the first of them
 int launch_cameras(rt_context *ctx, const float *d_cams, const float cam0[12], uint32_t first, uint32_t count, uint32_t glog2,
                    float4 *accum, const BlockMask *mask, float *m2, float4 *ring) {
-    return launch_source(ctx, {false, d_cams, 0u, 0u, cam0}, first, count, glog2, accum, mask, m2, ring);
+    return launch_source(ctx, {false, false, d_cams, 0u, 0u, cam0}, first, count, glog2, accum, mask, m2, ring);
 }
 // rt_render_rays (set_size 0: one record per ray), rt_render_ray_sets (1 .. RT_RAY_SET_MAX) and their adaptive forms
 int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size, uint32_t first, uint32_t count, uint32_t glog2,
@@ -2342,7 +2525,18 @@ int launch_rays(rt_context *ctx, const void *d_rays, size_t n, uint32_t set_size
         memcpy(&cam0[0], &set_size, sizeof(uint32_t));
         cam0[1] = 1.0f / (float)set_size;
     }
-    return launch_source(ctx, {true, d_rays, n, set_size, cam0}, first, count, glog2, accum, mask, m2, nullptr);
+    return launch_source(ctx, {true, false, d_rays, n, set_size, cam0}, first, count, glog2, accum, mask, m2, nullptr);
+}
+// rt_render_hemispheres: the p.k hemisphere rays of each of the n feature records as the record's ray set, never stored
+int launch_hemispheres(rt_context *ctx, const rt_feature *d_features, size_t n, const rt_hemisphere_params &p, uint32_t first,
+                       uint32_t count, uint32_t glog2, float4 *accum, float *m2) {
+    if (p.k < 1u) return fail(ctx, RT_EINVAL, "a hemisphere launch takes sets of 1 .. %u rays", RT_RAY_SET_MAX);
+    const uint32_t words[6] = {p.k, 0u, (uint32_t)p.seed, (uint32_t)(p.seed >> 32), 0u, p.flags};
+    float cam0[12] = {};
+    memcpy(cam0, words, sizeof words);
+    cam0[1] = 1.0f / (float)p.k;
+    cam0[HEMI_CAM_OFFSET] = p.offset;
+    return launch_source(ctx, {true, true, d_features, n, p.k, cam0}, first, count, glog2, accum, nullptr, m2, nullptr);
 }
 
 // ---- policy-dependent precomputation and probes ---------------------------------------------------------------
@@ -2527,14 +2721,23 @@ const pt::KernelSet g_kernel_set = {
     launch_render, launch_fused, launch_lookahead, ks_launch_probe, ks_launch_features, ks_launch_debug_hit, ks_launch_debug_material, ks_launch_debug_div3,
     ks_launch_face_normals, ks_launch_debug_builtin, ks_launch_debug_queue_sums, ks_launch_features_chain,
     ks_queue_pixels, ks_queue_occupancy, plan_samples, launch_cameras, plan_camera_samples, ks_launch_features_cameras,
-    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, ks_launch_occluded, ks_launch_occluded_hemi};
+    ks_plan_feature_cameras, launch_rays, ks_launch_features_rays, ks_launch_occluded, ks_launch_occluded_hemi, launch_hemispheres};
 
 }  // namespace
+#endif   // PT_GATHER_UNIT
 
 }  // namespace PT_NS
 
 namespace pt {
+#if PT_GATHER_UNIT
 #if PT_ARITH == 0
+const GatherKernels *gather_kernels_a0() { return &pt_a0::g_gather_kernels; }
+#elif PT_ARITH == 1
+const GatherKernels *gather_kernels_a1() { return &pt_a1::g_gather_kernels; }
+#else
+const GatherKernels *gather_kernels_a2() { return &pt_a2::g_gather_kernels; }
+#endif
+#elif PT_ARITH == 0
 const KernelSet *kernel_set_a0() { return &pt_a0::g_kernel_set; }
 #elif PT_ARITH == 1
 const KernelSet *kernel_set_a1() { return &pt_a1::g_kernel_set; }

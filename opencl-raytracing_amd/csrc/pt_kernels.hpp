@@ -99,7 +99,26 @@ struct KernelSet {
     // NULL: not stored) — one of the two at least
     int (*launch_occluded_hemi)(rt_context *ctx, const DeviceScene &sc, const rt_feature *d_features, size_t n,
                                 const rt_hemisphere_params &p, uint32_t *d_counts, void *d_rays_out);
+    // rt_render_hemispheres: launch_rays with the sets made — samples first .. first+count-1 of the n feature records at
+    // d_features, sample s of record i along hemisphere ray s % p.k of rt_occluded_hemispheres' spawn form (never stored),
+    // the sum added to accum[i] (updating m2[i]); a record without a hemisphere is skipped.  pt_samples_q_hemi, or
+    // pt_render_hemi for fixed lanes (GatherKernels below); facts and plan go to rt_context::Rays
+    int (*launch_hemispheres)(rt_context *ctx, const rt_feature *d_features, size_t n, const rt_hemisphere_params &p,
+                              uint32_t first, uint32_t count, uint32_t glog2, float4 *accum, float *m2);
 };
+
+// The kernels of rt_render_hemispheres, which a policy keeps in a translation unit of their own (pt_gather.hip: the text of
+// pt_kernels.hip once more, with nothing instantiated but these): launch_hemispheres launches them through these pointers.
+struct GatherKernels {
+    using Queue = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *, uint32_t);
+    using Fixed = void (*)(DeviceScene, FrameParams, float4 *, unsigned long long *);
+    Queue (*queue)(uint32_t accel, uint32_t geom, uint32_t waves);   // pt_samples_q_hemi of the queue's geometry row; NULL: no such row
+    Fixed (*fixed)(bool count, bool accel);                          // pt_render_hemi<COUNT, ACCEL>
+};
+// defined by pt_gather.hip compiled with -DPT_ARITH=0 / 1 / 2
+const GatherKernels *gather_kernels_a0();
+const GatherKernels *gather_kernels_a1();
+const GatherKernels *gather_kernels_a2();
 
 // defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2
 const KernelSet *kernel_set_a0();

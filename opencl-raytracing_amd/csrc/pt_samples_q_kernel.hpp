@@ -6,15 +6,27 @@
 //      the ray indices, the staged record holds the ray itself, and a refill gathers no camera block and normalises nothing
 //   3  pt_samples_q_raysets<ACCEL, GEOM, WAVES>: the ray form with a SET of records per ray (SETS; rt_render_ray_sets) —
 //      nothing of a ray is staged but its index, and a refill loads the record of its own sample from global memory
+//   4  pt_samples_q_hemi<ACCEL, GEOM, WAVES>: the ray-set form with the sets MADE from feature records (HEMI;
+//      rt_render_hemispheres) — a slot is a record index and belongs to a wave only where the record has a hemisphere, its
+//      frame is staged, and a refill makes the ray of its own sample in registers
 // No include guard: it is meant to be read once per form.
-#if PT_Q_LOOKAHEAD_FORM == 3
+#if PT_Q_LOOKAHEAD_FORM == 4
+template <bool ACCEL, int GEOM, int WAVES>
+__global__ __launch_bounds__(64, WAVES) void pt_samples_q_hemi(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
+                                                         const uint32_t *__restrict__ live,
+                                                         const uint32_t *__restrict__ live_count,
+                                                         float4 *__restrict__ accum, unsigned long long *counters,
+                                                         uint32_t pixels_per_wave) {
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = false, HEMI = true;
+    constexpr int COUNT_LOG2 = -1;
+#elif PT_Q_LOOKAHEAD_FORM == 3
 template <bool ACCEL, int GEOM, int WAVES>
 __global__ __launch_bounds__(64, WAVES) void pt_samples_q_raysets(DeviceScene sc, FrameParams fp, const PixelRec *__restrict__ recs,
                                                             const uint32_t *__restrict__ live,
                                                             const uint32_t *__restrict__ live_count,
                                                             float4 *__restrict__ accum, unsigned long long *counters,
                                                             uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = true;
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = true, HEMI = false;
     constexpr int COUNT_LOG2 = -1;
 #elif PT_Q_LOOKAHEAD_FORM == 2
 template <bool ACCEL, int GEOM, int WAVES>
@@ -23,7 +35,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q_rays(DeviceScene sc, F
                                                          const uint32_t *__restrict__ live_count,
                                                          float4 *__restrict__ accum, unsigned long long *counters,
                                                          uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = false;
+    constexpr bool COUNT = false, MOMENTS = false, CAM = true, CAM_LA = false, RAYS = true, SETS = false, HEMI = false;
     constexpr int COUNT_LOG2 = -1;
 #elif PT_Q_LOOKAHEAD_FORM == 1
 template <int GEOM, int WAVES>
@@ -32,7 +44,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q_la(DeviceScene sc, Fra
                                                        const uint32_t *__restrict__ live_count,
                                                        float4 *__restrict__ accum, unsigned long long *counters,
                                                        uint32_t pixels_per_wave) {
-    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true, RAYS = false, SETS = false;
+    constexpr bool COUNT = false, ACCEL = true, MOMENTS = false, CAM = true, CAM_LA = true, RAYS = false, SETS = false, HEMI = false;
     constexpr int COUNT_LOG2 = -1;
 #else
 template <bool COUNT, bool ACCEL, int GEOM, int WAVES, bool MOMENTS = false, int COUNT_LOG2 = -1, bool CAM = false>
@@ -41,7 +53,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
                                                     const uint32_t *__restrict__ live_count,
                                                     float4 *__restrict__ accum, unsigned long long *counters,
                                                     uint32_t pixels_per_wave) {
-    constexpr bool CAM_LA = false, RAYS = false, SETS = false;
+    constexpr bool CAM_LA = false, RAYS = false, SETS = false, HEMI = false;
 #endif
     extern __shared__ float4 s_dyn[];  // 16-byte aligned: no static LDS in this kernel
     // The tagged forms of sqrt and normalize (pt_arith.hpp) and the sphere scan that compares inside the root block
@@ -74,7 +86,9 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     unsigned long long cam_owners = 0;
     if (RAYS) {   // (slot = ray index: no tiles; cam_x carries it.  An adaptive round's mask is tested here: ray_active)
         cam_x = fp.slot_begin + blockIdx.x * pixels_per_wave + threadIdx.x;
-        cam_owns = threadIdx.x < pixels_per_wave && cam_x < fp.slot_end && ray_active(fp, cam_x);
+        // (HEMI: slot = record index, owned where the record has a hemisphere; a gather launch has no mask)
+        cam_owns = threadIdx.x < pixels_per_wave && cam_x < fp.slot_end &&
+                   (HEMI ? hemisphere_valid(fp.feats + 5u * (size_t)cam_x) : ray_active(fp, cam_x));
         cam_owners = __ballot(cam_owns);
         npix = (uint32_t)__popcll(cam_owners);
     } else if (CAM) {
@@ -100,7 +114,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
         c.lfaces = lds_ptr(s_faces);
     }
 
-    const WaveQueue q = SETS ? queue_stage_raysets(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+    const WaveQueue q = HEMI ? queue_stage_hemi(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
+                      : SETS ? queue_stage_raysets(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                       : RAYS ? queue_stage_rays(sc, fp, cam_owns, cam_x, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                       : CAM ? queue_stage_cam(sc, fp, cam_owns, cam_x, cam_y, cam_owners, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u)
                             : queue_stage<COUNT_LOG2, !COUNT && !ACCEL>(sc, fp, recs, live, npix, pix0, pixels_per_wave, s_dyn, GEOM != 0 ? fp.lds_face_f4 : 0u);
@@ -136,7 +151,7 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
             if (CAM) {
                 if (need && cand < q.total) {
                     idx = cand;
-                    const CameraEntry e = SETS ? queue_fetch_raysets(q, fp, idx) : RAYS ? queue_fetch_rays(q, fp, idx) : queue_fetch_cam(q, fp, idx);
+                    const CameraEntry e = HEMI ? queue_fetch_hemi(q, fp, idx) : SETS ? queue_fetch_raysets(q, fp, idx) : RAYS ? queue_fetch_rays(q, fp, idx) : queue_fetch_cam(q, fp, idx);
                     bv = e.bv;
                     bu = e.bu;
                     depth = 0u;

@@ -188,11 +188,15 @@ struct FrameParams {
     // Caller-supplied rays (rt_render_rays): the launch's ray buffer, two float4 per rt_ray — (o.xyz, x bits), (d.xyz, y bits)
     // — shares the same eight bytes for the same reason: a ray launch (pt_samples_q_rays, pt_render_rays) reads neither
     // la_image nor cams, is never a look-ahead launch, and no other kernel reads `rays`.
+    // Hemisphere gathers (rt_render_hemispheres): the launch's rt_feature records, five float4 each, in the same eight bytes
+    // — a gather launch (pt_samples_q_hemi, pt_render_hemi) is a ray launch whose rays are made from `feats`, not read.  Its
+    // parameters travel in `cam` (HEMI_CAM_*, pt_kernels.hip), of which a ray launch reads only the first two words.
     float4 *la_ring;
     union {
         const float4 *la_image;
         const float *cams;
         const float4 *rays;
+        const float4 *feats;
     };
     // per-pixel sample moments (RT_OPT_MOMENTS; NULL = off): W x H floats beside the accumulator the launch adds to, the
     // centred second moment of each pixel's sample luminances (pt_moments.hpp).  Read in the kernels' epilogues only

@@ -1496,6 +1496,41 @@ int rt_occluded_hemispheres(rt_context *ctx, const void *d_features, size_t n, c
                                          static_cast<uint32_t *>(d_counts), d_rays_out);
 }
 
+// rt_render_hemispheres: rt_render_ray_sets over the rays the spawn form would write, made in registers instead
+// (pt_samples_q_hemi / pt_render_hemi); every check stands before the first launch
+int rt_render_hemispheres(rt_context *ctx, const void *d_features, size_t n, const rt_hemisphere_params *p, uint32_t first_sample,
+                          uint32_t n_samples, void *d_accum) {
+    const int rc = check_ready(ctx, k_no_camera);
+    if (rc) return rc;
+    if (!p) return fail(ctx, RT_EINVAL, "rt_render_hemispheres: the parameters are NULL");
+    size_t records = 0;
+    const int bad = check_ray_records(ctx, "rt_render_hemispheres", n, p->k, true, &records);
+    if (bad != RT_OK) return bad;
+    if ((uintptr_t)d_features % 16u) return fail(ctx, RT_EINVAL, "d_features is not 16-byte aligned");
+    if ((uintptr_t)d_accum % sizeof(float4)) return fail(ctx, RT_EINVAL, "d_accum is not 16-byte aligned");
+    if (p->flags & ~RT_HEMI_FACE_FORWARD) return fail(ctx, RT_EINVAL, "unknown hemisphere flags 0x%x", p->flags);
+    if (!std::isfinite(p->offset)) return fail(ctx, RT_EINVAL, "the hemisphere offset must be finite");
+    if (n_samples == 0 || (uint64_t)first_sample + n_samples - 1 > RT_MAX_SAMPLE)
+        return fail(ctx, RT_EINVAL, "samples %u..+%u: 1 or more, up to the limit %u", first_sample, n_samples, RT_MAX_SAMPLE);
+    const size_t frame = (size_t)ctx->width * ctx->height;
+    if (!d_accum && n != frame) return fail(ctx, RT_EINVAL, "%zu records into the accumulator of a %d x %d frame", n, ctx->width, ctx->height);
+    if (!d_features) {
+        if (n != frame) return fail(ctx, RT_EINVAL, "the context's feature records are %d x %d, not %zu", ctx->width, ctx->height, n);
+        if (!ctx->features.ready) return fail(ctx, RT_ESTATE, "no rt_render_features call since the frame was (re)allocated");
+        d_features = ctx->features.records.p;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float4 *accum = d_accum ? static_cast<float4 *>(d_accum) : ctx->accum.p;
+    // (a hemisphere ray is chosen by the absolute sample, so a later launch needs no offset)
+    return for_each_launch(n_samples, [&](uint32_t done, uint32_t c) {
+        float *m2 = d_accum ? nullptr : ctx->moments.target();
+        const int r = ctx->ks->launch_hemispheres(ctx, static_cast<const rt_feature *>(d_features), n, *p, first_sample + done, c,
+                                                  group_log2_for(c), accum, m2);
+        if (r == RT_OK && !d_accum) ctx->accum_count += c;
+        return r;
+    });
+}
+
 // ---- device memory for a host without a HIP runtime of its own (the buffers the ray queries write into) ----------------------
 int rt_device_alloc(rt_context *ctx, size_t bytes, void **d_out) {
     if (!ctx) return RT_EINVAL;

@@ -44,7 +44,7 @@ SYMBOLS = (
     "rt_render_ray_sets",
     "rt_render_adaptive_rays", "rt_render_adaptive_variance_rays",
     "rt_intersect_rays", "rt_occluded_rays", "rt_device_alloc", "rt_device_free", "rt_device_copy",
-    "rt_occluded_hemispheres",
+    "rt_occluded_hemispheres", "rt_render_hemispheres",
 )
 
 # rt_set_option: options and the arithmetic policies of RT_OPT_ARITH (include/rt_amd.h)
@@ -611,8 +611,46 @@ class RayTracer:
         self.sync()   # (the division runs on torch's stream)
         return (1.0 - counts.float() / float(int(k))).reshape(self.height, self.width)
 
+    def renderHemispheres(self, features=None, k=16, first_sample=0, n_samples=None, seed=0, offset=0.0, face_forward=False,
+                          out=None):
+        """Hemisphere gather (rt_render_hemispheres, asynchronous): radiance along the k cosine-weighted rays of every
+        record — spawnHemispheres' rays, made in registers and never stored — ADDED to `out` exactly as
+        renderRaySets(spawnHemispheres(...), k, first_sample, n_samples, out) adds it: sample s of record i follows hemisphere
+        ray s mod k.  `features` as occludedHemispheres; n_samples None: k, every ray once.  `out`: an (n, 4) float32 device
+        tensor of sums and counts, or None: the accumulator (the context's own frame of records: resolve, the denoisers and
+        the moments follow).  A record without a hemisphere adds nothing, its count included.  out.rgb / out.w is the mean
+        incoming radiance under the cosine density: irradiance is pi times it.  → out."""
+        n = self.width * self.height if features is None else (int(features.shape[0]) if hasattr(features, "shape") and len(features.shape) else 0)
+        k, flags, first, count = _abi.check_gather(features, n, k, _abi.HEMI_FACE_FORWARD if face_forward else 0, offset, first_sample,
+                                                   n_samples, out, self.width, self.height, getattr(self, "_world", 1))
+        p = _abi.HemisphereParams(k, flags, int(seed) & 0xFFFFFFFFFFFFFFFF, float(offset), float("inf"))
+        self._check(self._lib.rt_render_hemispheres(
+            self._ctx, C.c_void_p(features.data_ptr()) if features is not None else None, n, C.byref(p), first, count,
+            C.c_void_p(out.data_ptr()) if out is not None else None))
+        return out
+
+    def irradiance(self, k, spp_per_direction=1, seed=0, offset=1e-3):
+        """Irradiance at the context's feature records (renderFeatures & co. made them) → an (h, w, 3) float32 device tensor
+        pi * rgb / count of renderHemispheres(None, k, 0, k * spp_per_direction, seed, offset, True) into a zeroed target:
+        k directions per pixel about the normal turned to face the viewer, each followed spp_per_direction times; 0 where
+        the pixel missed."""
+        import torch
+        k, spp = int(k), int(spp_per_direction)
+        if spp < 1:
+            raise ValueError("spp_per_direction must be at least 1, not %d" % spp)
+        _abi.check_gather(None, self.width * self.height, k, _abi.HEMI_FACE_FORWARD, offset, 0, k * spp, None, self.width, self.height,
+                          getattr(self, "_world", 1))
+        acc = torch.zeros((self.width * self.height, 4), dtype=torch.float32, device="cuda:%d" % self._device)
+        torch.cuda.synchronize(acc.device)
+        self.renderHemispheres(None, k, 0, k * spp, seed, offset, True, acc)
+        self.sync()   # (the division runs on torch's stream)
+        count = acc[:, 3:4]
+        # the binary32 quotient, correctly rounded: formed in binary64 and rounded once more (53 >= 2 * 24 + 2 bits)
+        mean_pi = ((acc[:, :3] * float(np.float32(np.pi))).double() / count.double()).float()
+        return torch.where(count > 0, mean_pi, torch.zeros_like(mean_pi)).reshape(self.height, self.width, 3)
+
     def lastRayPlan(self):
-        """(facts, plan) dicts of the last renderRays / renderRaySets launch (rt_debug_last_ray_plan): the camera planner's, with
+        """(facts, plan) dicts of the last renderRays / renderRaySets / renderHemispheres launch (rt_debug_last_ray_plan): the camera planner's, with
         n = the rays of the launch's last range."""
         f, p = _abi.CameraFacts(), _abi.CameraPlan()
         self._check(self._lib.rt_debug_last_ray_plan(self._ctx, C.byref(f), C.byref(p)))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_variant.sh <name> [-DFLAG=..]...  → opencl-raytracing_amd/variants/<name>.so
-# (the three translation units of librt_amd.so, five compilations, with extra -D switches; __graft_entry__.build_hip does the work)
+# (the four translation units of librt_amd.so, eight compilations, with extra -D switches; __graft_entry__.build_hip does the work)
 ROOT=$(dirname $(dirname $(readlink -f $0)))
 NAME=$1; shift
 mkdir -p $ROOT/opencl-raytracing_amd/variants

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/isa_stats.py [--arith K] [--unit rt_amd | rt_denoise] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
+"""tools/isa_stats.py [--arith K] [--unit rt_amd | rt_denoise | pt_gather] [kernel-substring ...] — static ISA statistics of the shipped gfx950 kernels.
 
 Compiles csrc/pt_kernels.hip for the device only (-S, the flags of __graft_entry__ for arithmetic policy K = 0 | 1 | 2,
 default 2 = rocm-opencl, the policy bench.py times; ISA_ARITH in the environment does the same) and prints, per
@@ -7,7 +7,7 @@ kernel: VGPRs / SGPRs / scratch bytes / spilled VGPRs from the code-object metad
 histogram grouped into the issue-cost classes measured by tools/valu_microbench.hip
 (profiles/r02_valu_microbench.md).  --unit rt_denoise / --unit rt_amd read the policy-free kernels of csrc/rt_denoise.hip
 (pt_atrous, pt_dn_variance, pt_atrous_vg) / csrc/rt_amd.hip (pt_adaptive_merge, ...) instead: compiled once, with the
-IEEE divide.  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
+IEEE divide; --unit pt_gather the policy-compiled kernels of csrc/pt_gather.hip (rt_render_hemispheres).  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
 instructions); --listing prints the labels and instructions of the named kernels.  --diff A.json B.json [kernel-substring
 ...] compiles nothing: it compares two --json --digest dumps, prints the kernels present in one only and, for every kernel
 whose hash differs, VGPRs, waves per SIMD, scratch, spilled VGPRs and the VALU / SALU / VMEM / LDS instruction counts before
@@ -89,7 +89,7 @@ def device_asm(force=False, arith=None):
     srcs = g.hip_sources()
     by_name = {os.path.splitext(os.path.basename(s))[0]: s for s in srcs if s.endswith(".hip")}
     unit = sys.argv[sys.argv.index("--unit") + 1:][:1] if "--unit" in sys.argv else []
-    if unit and unit[0] != "pt_kernels":
+    if unit and unit[0] not in g.POLICY_UNITS:
         if unit[0] not in by_name:
             sys.exit("--unit %s: not one of %s" % (unit[0], ", ".join(sorted(by_name))))
         out = os.path.join(ROOT, "build", "%s_gfx950.s" % unit[0])
@@ -102,11 +102,12 @@ def device_asm(force=False, arith=None):
     arith = default_arith() if arith is None else int(arith)
     extra = os.environ.get("ISA_EXTRA_FLAGS", "").split()   # e.g. ISA_EXTRA_FLAGS="-DPT_Q_WAVES=5" for a variant
     tag = ("_" + "_".join(e.lstrip("-D").replace("=", "") for e in extra)) if extra else ""
-    out = os.path.join(ROOT, "build", "pt_kernels_a%d_gfx950%s.s" % (arith, tag))
+    name = unit[0] if unit else "pt_kernels"   # (--unit pt_gather: the policy's gather kernels, csrc/pt_gather.hip)
+    out = os.path.join(ROOT, "build", "%s_a%d_gfx950%s.s" % (name, arith, tag))
     os.makedirs(os.path.dirname(out), exist_ok=True)
     if force or not os.path.isfile(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in srcs):
         flags = [f for f in g.HIP_FLAGS if f not in ("-shared", "-fPIC")] + g.POLICY_FLAGS[arith]
-        subprocess.check_call([g.HIPCC] + flags + extra + ["--cuda-device-only", "-S", by_name["pt_kernels"], "-o", out],
+        subprocess.check_call([g.HIPCC] + flags + extra + ["--cuda-device-only", "-S", by_name[name], "-o", out],
                               stderr=subprocess.DEVNULL)
     return out
 

@@ -26,7 +26,17 @@ and, by the host's clock over --host-rounds rounds (default --rounds; seconds ea
 records as they lie on the host -> rays.hemisphere_sets -> upload -> rt_occluded_rays -> sync, which is what rt_cli --ao K and
 every user of hemisphere_sets ran before.  The fused counts are checked against occ_dumped's on the way.
 
+With the hemisphere gather (rt_render_hemispheres, DESIGN.md §5 "Hemisphere gather") --gather K is a mode of its own:
+nothing of the above runs, and over the same W x H first-hit records, K samples per record (every direction once),
+alternating inside every round:
+    fused        renderHemispheres into an external target: the rays made at the sample queue's refill, none stored
+    spawn_sets   spawnHemispheres, then renderRaySets over the rays it wrote: the two calls the fused one replaces
+    sets_only    renderRaySets alone over those rays, for orientation
+with the bytes the two-call sequence moves through memory for its rays (32 B x W x H x K written, then read once per
+sample).  The two targets are compared on the way: equal bytes on the records that have a hemisphere.
+
     python tools/queries_bench.py [--scenes c2,c4,c5] [--size 1920x1080] [--rounds 5] [--policy 2] [--ao 16] [--json out.json]
+    python tools/queries_bench.py --gather 64 [--scenes c2,c5] [--size 1920x1080] [--rounds 5] [--policy 2]
 """
 import argparse
 import json
@@ -128,6 +138,64 @@ def hemisphere_rows(t, stream, rec, k, rounds, host_rounds):
     return row
 
 
+def gather_rows(t, stream, rec, k, rounds):
+    """The rows of rt_render_hemispheres over the (n,) FEATURE records `rec`, k samples per record → {configuration: statistics}"""
+    import torch
+    n = len(rec)
+    feats = torch.from_numpy(np.ascontiguousarray(rec).view(np.float32).reshape(n, 20).copy()).cuda()
+    dumped = torch.empty((n * k, 8), dtype=torch.float32, device="cuda")
+    fused, twin = (torch.zeros((n, 4), dtype=torch.float32, device="cuda") for _ in range(2))
+    torch.cuda.synchronize()
+    kw = dict(k=k, seed=7, offset=1e-3, face_forward=True)
+
+    def spawn_sets():
+        t.spawnHemispheres(feats, out=dumped, **kw)
+        t.renderRaySets(dumped, k, 0, k, out=twin)
+
+    # the comparison first, on fresh targets: one call each
+    t.renderHemispheres(feats, first_sample=0, n_samples=k, out=fused, **kw)
+    spawn_sets()
+    t.sync()
+    valid = torch.from_numpy(((rec["flags"] & 1) != 0) & np.isfinite(rec["normal"]).all(1) & (rec["normal"] != 0).any(1)).cuda()
+    row = {"targets_equal": bool((fused[valid].view(torch.int32) == twin[valid].view(torch.int32)).all()) and not bool(fused[~valid].any()),
+           "valid_share": float(valid.float().mean()),
+           "mean_radiance": float((fused[valid][:, :3].sum(1) / (3.0 * fused[valid][:, 3])).mean()) if bool(valid.any()) else 0.0,
+           "ray_bytes_written": 32 * n * k, "ray_bytes_read": 32 * n * k}
+    configs = [("fused", lambda: t.renderHemispheres(feats, first_sample=0, n_samples=k, out=fused, **kw)),
+               ("spawn_sets", spawn_sets),
+               ("sets_only", lambda: t.renderRaySets(dumped, k, 0, k, out=twin))]
+    row.update(stats(timed(stream, configs, rounds)))
+    t.sync()
+    return row
+
+
+def gather_mode(a, w, h):
+    """--gather K: the fused gather against the two calls it replaces, per scene"""
+    import torch
+    result = {"size": [w, h], "policy": a.policy, "rounds": a.rounds, "gather": a.gather, "scenes": {}}
+    for name in [s for s in a.scenes.split(",") if s]:
+        wl = rt.workloads.get(name, width=w, height=h)
+        t = rt.RayTracer(w, h, scene=wl.scene, seed=rt.workloads.SEED)
+        t.setArith(a.policy)
+        stream = torch.cuda.Stream()
+        t.setStream(stream.cuda_stream)
+        t.renderFeatures(wl.camera)
+        r = gather_rows(t, stream, t.featureRecords().reshape(-1), a.gather, a.rounds)
+        r["walk_overflow"] = t.walkOverflow()
+        result["scenes"][name] = r
+        print("%s %dx%d, policy %d, %d rounds (ms: median, min .. max); gather of %d samples along %d directions from %.1f %% of the pixels" %
+              (name, w, h, a.policy, a.rounds, a.gather, a.gather, 100 * r["valid_share"]))
+        for c in ("fused", "spawn_sets", "sets_only"):
+            print("  gather%-4d %-10s %9.3f  (%.3f .. %.3f)" % (a.gather, c, r[c]["median"], r[c]["min"], r[c]["max"]))
+        print("  spawn_sets / fused %.3f, sets_only / fused %.3f; the sequence writes %.2f GB of rays and reads %.2f GB; targets equal: %s" %
+              (r["spawn_sets"]["median"] / r["fused"]["median"], r["sets_only"]["median"] / r["fused"]["median"],
+               r["ray_bytes_written"] / 1e9, r["ray_bytes_read"] / 1e9, r["targets_equal"]), flush=True)
+        t.close()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(result, f, indent=1)
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
@@ -137,11 +205,14 @@ def main():
     ap.add_argument("--policy", type=int, default=2)
     ap.add_argument("--ao", type=int, default=16)
     ap.add_argument("--host-rounds", type=int, default=None)
+    ap.add_argument("--gather", type=int, default=0)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     T = rt.RayTracer
     have = hasattr(T, "occludedRays")
     w, h = (int(v) for v in a.size.split("x"))
+    if a.gather:
+        return gather_mode(a, w, h)
     result = {"size": [w, h], "policy": a.policy, "rounds": a.rounds, "have_queries": have, "scenes": {}}
     for name in [s for s in a.scenes.split(",") if s]:
         wl = rt.workloads.get(name, width=w, height=h)
