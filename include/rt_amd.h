@@ -281,6 +281,12 @@ int rt_sample_counter(const rt_context *ctx, uint32_t *out);
  * 64 spp: rt_clear; rt_render_spp(cam, 0, 64); rt_resolve.
  * A call of more than 512 samples per pixel is executed as consecutive launches of 512 (the accumulator is the sum of
  * their sums; results within a launch are summed in a fixed order).
+ * WHEN the clear happens (RT_OPT_ACCUM_STORE 1, the default): rt_clear records it and returns.  The clear is ordered before
+ * the work of the next library call on this context and before rt_sync returns — never later, possibly not sooner: a fused
+ * rt_render_spp launch that writes every pixel of the frame stores its sums instead of adding them to zeros (the same bits),
+ * and every other call, rt_device_accum and rt_sync included, enqueues the memset first.  A caller that works on the
+ * accumulator through a pointer it obtained BEFORE the rt_clear, on the context's stream, calls rt_sync (or rt_device_accum
+ * again) after the rt_clear first.
  */
 int rt_clear(rt_context *ctx);
 int rt_render_spp(rt_context *ctx, const float camera[12], uint32_t first_sample, uint32_t n_samples);
@@ -973,6 +979,15 @@ int rt_device_accum(rt_context *ctx, void **d_rgba);
                                            while it is 1, give RT_EINVAL.  A change of value invalidates the moments until the next
                                            rt_clear / rt_render_adaptive.  rt_render_adaptive_variance(_cameras) need 1 and give
                                            RT_ESTATE otherwise.  Image and accumulator: the same bit for bit                  */
+#define RT_OPT_ACCUM_STORE 13           /* 1 (default): rt_clear records the clear instead of enqueuing it, and a fused rt_render_spp
+                                           launch that writes every pixel of the frame exactly once — 64 samples per pixel through the
+                                           sample queue without a BVH walk, an unsharded, unmasked frame in one slot range, no
+                                           counters, no moments — STORES its
+                                           sums (0 + sum, the words an add to a zeroed pixel leaves); whatever else reads, writes
+                                           or hands out the accumulator, and every wait for the stream, enqueues the memset first
+                                           (see rt_clear).  0: rt_clear enqueues the memset at once and every launch adds; a clear
+                                           recorded under 1 is enqueued by the change to 0.  Any other value: RT_EINVAL.  Same
+                                           result bit for bit                                                                   */
 #define RT_OPT_ARITH 6                  /* the ARITHMETIC POLICY of the trace kernels (csrc/pt_arith.hpp).  The reference's
                                            random numbers are table entries indexed by a hash of the ray direction
                                            (raytracer.cl:113-125): one ulp re-routes a path, so "the reference's
@@ -1083,6 +1098,10 @@ int rt_stage_ms_history(rt_context *ctx, float *first_ms, float *second_ms, size
  * per look-ahead batch, RT_OPT_LOOKAHEAD) of this context that reused the kept prefix (RT_OPT_PREFIX_CACHE) and that
  * traced it in full, since rt_create. */
 int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses);
+
+/* rt_clear calls of this context since rt_create whose clear was recorded (RT_OPT_ACCUM_STORE 1) and then ended by a fused
+ * launch that STORED its sums (`stored`), or by the memset, enqueued in front of whatever came next (`materialised`). */
+int rt_accum_store_stats(rt_context *ctx, uint64_t *stored, uint64_t *materialised);
 
 /* Look-ahead (RT_OPT_LOOKAHEAD) since rt_create: `batches` look-ahead launches; `served` rt_render_again calls whose image
  * came from a look-ahead frame (the launching call included); `direct` rt_render_again calls that ran the direct kernel;

@@ -202,6 +202,7 @@ def moments_prototypes(lib):
 def prefix_cache_prototypes(lib):
     """ctypes prototype of rt_prefix_cache_stats (RT_OPT_PREFIX_CACHE)."""
     lib.rt_prefix_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.rt_accum_store_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]   # (RT_OPT_ACCUM_STORE)
 
 
 def lookahead_prototypes(lib):

@@ -96,6 +96,20 @@ PT_DEV void accumulate(float4 *__restrict__ accum, size_t pix, V3 sum, uint32_t 
     a.w += (float)count;
     accum[pix] = a;
 }
+// A cleared frame is stored, not added to (FrameParams::store; DESIGN §5 "A cleared frame is stored"): the words accumulate
+// leaves in a pixel that holds zeros — the same operands in the same order, 0.0f + sum, so every word keeps its bits, a sum
+// of -0.0f included — without the load and without the wait for it.  The kernels that take it test fp.store wave-uniformly
+// (accumulate_any); everything else keeps accumulate.  PT_ACCUM_STORE 0: no kernel reads the field.
+#ifndef PT_ACCUM_STORE
+#define PT_ACCUM_STORE 1
+#endif
+PT_DEV void accumulate_store(float4 *__restrict__ accum, size_t pix, V3 sum, uint32_t count) {
+    accum[pix] = make_float4(0.0f + sum.x, 0.0f + sum.y, 0.0f + sum.z, 0.0f + (float)count);
+}
+PT_DEV void accumulate_any(const FrameParams &fp, float4 *__restrict__ accum, size_t pix, V3 sum, uint32_t count) {
+    if (PT_ACCUM_STORE && fp.store) accumulate_store(accum, pix, sum, count);
+    else accumulate(accum, pix, sum, count);
+}
 
 // ---- per-pixel sample moments (FrameParams::m2, RT_OPT_MOMENTS; pt_moments.hpp) --------------------------------------
 // A launch that adds `count` samples of sum `sum` to a pixel merges their centred second moment m2B — about the launch's
@@ -399,7 +413,9 @@ __global__ __launch_bounds__(256, TREES ? PT_PREFIX_WAVES : 1) void pt_prefix(De
             if (accum) {   // (every sample of a finished pixel is the same colour: the launch's own M2 is 0)
                 const V3 fsum = final_sum(xyz(rec.out), fp.count, fp.group_log2);
                 if (fp.m2) moments_update(accum, fp.m2, (size_t)y * fp.w + x, fsum, fp.count, 0.0f);
-                accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
+                // (a launch with counters or a BVH walk never stores: accum_store_qualifies)
+                if (COUNT || ACCEL) accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
+                else accumulate_any(fp, accum, (size_t)y * fp.w + x, fsum, fp.count);
             }
             if (COUNT) cn.c[CN_SAMPLES] += 1;  // scaled by count below
         } else {
@@ -527,7 +543,7 @@ __global__ __launch_bounds__(256) void pt_final_replay(FrameParams fp, const Fin
     if (!slot_to_pixel(fp, e.slot, x, y)) return;   // (never: pt_prefix stored the slots of valid pixels only)
     const V3 fsum = final_sum(mk(e.r, e.g, e.b), fp.count, fp.group_log2);
     if (fp.m2) moments_update(accum, fp.m2, (size_t)y * fp.w + x, fsum, fp.count, 0.0f);   // (as pt_prefix)
-    accumulate(accum, (size_t)y * fp.w + x, fsum, fp.count);
+    accumulate_any(fp, accum, (size_t)y * fp.w + x, fsum, fp.count);
 }
 #endif
 
@@ -914,22 +930,54 @@ PT_DEV V3 queue_lane_slot64(const WaveQueue &q, uint32_t p, uint32_t l) {
     }
     return sum;
 }
+// The sums' addresses once per half-wave (PT_SUMS_ADDR; queue_sums_tree<6, STORE> only, so that no other kernel changes): one LDS
+// address per lane, that of slot (half, i); the slots of (pb + half, i), (pb + 2 + half, i), (·, i + 32) and of the second
+// pass lie at constant distances from it, which the LDS reads take as immediate offsets.  Ownership is asked once per pixel,
+// not once per read, and both reads of a pixel stand under the one test: a pixel the wave does not own still gives
+// 0.0f + 0.0f = +0, the value the two guarded reads gave.  The accumulator index y · w + x stays below RT_MAX_DIM² and is
+// formed in 32 bits, then scaled and added to the base in one 64-bit step.
+#ifndef PT_SUMS_ADDR
+#define PT_SUMS_ADDR 1
+#endif
+static_assert((uint64_t)RT_MAX_DIM * RT_MAX_DIM <= 0xFFFFFFFFull, "a pixel index fits 32 bits (queue_sums_tree, PT_SUMS_ADDR)");
+// both slots of lane i of a pixel at `sl` (its slot i): (0.0f + slot i) + (0.0f + slot i + 32), or +0 for a pixel not owned
+PT_DEV V3 queue_lane_pair64(LdsF32 sl, bool owned) {
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    if (owned) {
+        sum = sum + mk(sl[0], sl[1], sl[2]);
+        sum = sum + (mk(0.0f, 0.0f, 0.0f) + mk(sl[96], sl[97], sl[98]));
+    }
+    return sum;
+}
 // CL = 6: a launch of 64 samples per pixel with 64 lanes per pixel (at most QUEUE_SLOTS / 64 = 8 pixels: two passes)
-template <int CL = -1>
+// STORE: the instantiation may be launched with fp.store set (pt_samples_q<false, false, 0 | 1, …, COUNT_LOG2 = 6>); every
+// other one never reads the field.
+template <int CL = -1, bool STORE = false>
 PT_DEV void queue_sums_tree(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
     if (CL == 6) {
         static_assert(QUEUE_SLOTS / 64u <= 8u, "two passes of four pixels");
         const uint32_t lane = threadIdx.x, half = lane >> 5, i = lane & 31u, row = lane >> 4;
+        const LdsF32 sl0 = q.slot + 3u * (half * 64u + i);   // (PT_SUMS_ADDR: slot i of pixel `half`)
 #pragma unroll
         for (uint32_t pb = 0; pb < 8u; pb += 4u) {
             if (pb >= q.npix) break;
-            V3 a = queue_lane_slot64(q, pb + half, i), b = queue_lane_slot64(q, pb + 2u + half, i);
-            a = a + queue_lane_slot64(q, pb + half, i + 32u);   // offset 32
-            b = b + queue_lane_slot64(q, pb + 2u + half, i + 32u);
+            V3 a, b;
+            if (STORE && PT_SUMS_ADDR) {
+                a = queue_lane_pair64(sl0 + 3u * 64u * pb, pb + half < q.npix);
+                b = queue_lane_pair64(sl0 + 3u * 64u * (pb + 2u), pb + 2u + half < q.npix);
+            } else {
+                a = queue_lane_slot64(q, pb + half, i), b = queue_lane_slot64(q, pb + 2u + half, i);
+                a = a + queue_lane_slot64(q, pb + half, i + 32u);   // offset 32
+                b = b + queue_lane_slot64(q, pb + 2u + half, i + 32u);
+            }
             V3 sum = mk(row_pair_add(a.x, b.x), row_pair_add(a.y, b.y), row_pair_add(a.z, b.z));   // offset 16
             sum = row_add<1>(row_add<2>(row_add<4>(row_add<8>(sum))));
             const uint32_t p = pb + ((row & 1u) << 1 | row >> 1);
-            if (p < q.npix && (lane & 15u) == 0u) accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, 64u);
+            if (p < q.npix && (lane & 15u) == 0u) {
+                if (STORE && PT_SUMS_ADDR) accumulate_any(fp, accum, q.xy[p].y * (uint32_t)fp.w + q.xy[p].x, sum, 64u);   // (32-bit index)
+                else if (STORE) accumulate_any(fp, accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, 64u);
+                else accumulate(accum, (size_t)q.xy[p].y * fp.w + q.xy[p].x, sum, 64u);
+            }
         }
         return;
     }
@@ -966,11 +1014,11 @@ PT_DEV void queue_sums_tree(const WaveQueue &q, const FrameParams &fp, float4 *_
 //   the kernels with a BVH walk (pt_samples_q<…, ACCEL = true>, pt_samples_w): their waves live for milliseconds, the
 //   epilogue is nothing to them, and with the tree C4 and C5 measured 1.2 % and 0.9 % SLOWER than the parent
 //   (profiles/r13_experiments.md) — the walk loops' code moved with the epilogue behind them.
-template <bool MOMENTS, bool BUTTERFLY = false, int CL = -1>
+template <bool MOMENTS, bool BUTTERFLY = false, int CL = -1, bool STORE = false>
 PT_DEV void queue_sums(const WaveQueue &q, const FrameParams &fp, float4 *__restrict__ accum) {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (PT_QUEUE_SUMS_TREE && !MOMENTS && !BUTTERFLY) return queue_sums_tree<CL>(q, fp, accum);   // (moments need the sum in all g lanes)
+    if (PT_QUEUE_SUMS_TREE && !MOMENTS && !BUTTERFLY) return queue_sums_tree<CL, STORE>(q, fp, accum);   // (moments need the sum in all g lanes)
     const uint32_t lane = threadIdx.x;
     const uint32_t g = 1u << fp.group_log2, ppp = 64u >> fp.group_log2;
     for (uint32_t pb = 0; pb < q.npix; pb += ppp) {
@@ -2081,6 +2129,7 @@ static int launch_ranges(rt_context *ctx, FrameParams &fp, uint32_t slots, Body 
 int launch_render(rt_context *ctx, int mode, const float cam[12], uint32_t first, uint32_t count, uint32_t glog2, float4 *accum,
                   const BlockMask *mask, float *m2) {
     if (mode < MODE_ACCUM || mode > MODE_RETRACE) return fail(ctx, RT_EINVAL, "unknown render mode %d", mode);
+    CLEAR_TRY(ctx);
     FrameParams fp = frame_params(ctx, cam, first, count, glog2);
     apply_mask(fp, mask);
     fp.m2 = mode == MODE_ACCUM ? m2 : nullptr;
@@ -2328,6 +2377,31 @@ static void refresh_stage_block(rt_context *ctx, const DeviceScene &sc) {
     ctx->stage_block.builds++;
 }
 
+// May this slot range of a fused launch STORE its sums (FrameParams::store)?  A clear is pending, the target is the context's
+// accumulator, and after the two stages every pixel of the frame has been written exactly once by a kernel with the store arm:
+//  * one slot range over an unsharded, unmasked frame: the slots 0 .. slot_end are the pixels of every tile, slot_to_pixel
+//    refuses exactly those beyond the frame's edge (and those of seg_cap's rounded-up tail, >= slot_end), so each pixel of
+//    the frame is `valid` in exactly one work-item of pt_prefix;
+//  * pt_prefix makes a valid pixel either finished — it writes the pixel's sum itself and lists it, and on a prefix-cache
+//    hit pt_final_replay writes the listed pixels — or live, appended once to the live list (a pixel with a decision tree
+//    is a live pixel whose record says so);
+//  * the queue family hands every live-list entry to exactly one wave (live_take; the exact grid launches the units that
+//    own one), and queue_sums_tree writes each of the wave's npix pixels once.  An empty grid means no live pixel;
+//  * no moments (moments_update reads the accumulator), no counters (the counting kernels keep the add), no BVH walk (their
+//    kernels keep the butterfly and the add), no look-ahead (no accumulator), and the COUNT_LOG2 = 6 kernel — 64 samples on
+//    64 lanes per pixel: the generic-count kernels keep the add too.
+// (in two steps: what the call itself says, known before anything is enqueued, and what the range's plan says)
+static bool accum_store_may_qualify(const rt_context *ctx, const FrameParams &fp, const float4 *accum, const BlockMask *mask,
+                                    const float4 *ring, const float *m2, bool one_range) {
+    return PT_ACCUM_STORE && ctx->accum_store && ctx->clear_pending && accum && accum == ctx->accum.p && !ring && !mask && !m2 &&
+           one_range && fp.world == 1u && !ctx->count_enabled && fp.count == 64u && fp.group_log2 == 6u;
+}
+static bool accum_store_qualifies(const rt_context *ctx, const FrameParams &fp, const SamplePlan &plan, const float4 *accum,
+                                  const BlockMask *mask, const float4 *ring, const float *m2, bool one_range) {
+    return accum_store_may_qualify(ctx, fp, accum, mask, ring, m2, one_range) && plan.family == RT_PLAN_QUEUE && !plan.accel &&
+           !plan.count && !plan.moments && plan.geom < 2u && plan.count_log2 == 6u && plan.waves == PT_Q_WAVES;   // (queue_kernel's k64 test)
+}
+
 // Fused path: pt_prefix (one work-item per pixel) + the planned sample kernel (g lanes per live pixel).  While camera and
 // scene rest the first stage is pt_final_replay over what the last pt_prefix left (rt_context::PrefixCache).
 // ring != NULL: a LOOK-AHEAD launch (rt_render_again, RT_OPT_LOOKAHEAD) — the same two stages over the same slot buffers and
@@ -2362,6 +2436,9 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
     bool exact = false;
     if ((rc = learn_live_counts(ctx, hit, live_count, &exact)) != RT_OK) return rc;
     rt_context::SampleGrid &sg = ctx->sample_grid;
+    // (a pending clear that this call cannot store over is enqueued here, in front of the call's first event as rt_clear's
+    // memset always was: the call's entry in the event history keeps timing the kernels alone)
+    if (!accum_store_may_qualify(ctx, fp, accum, mask, ring, m2, per >= slots) && (rc = materialise_clear(ctx)) != RT_OK) return rc;
     hipEvent_t *evp = ctx->ev[ctx->ev_count % rt_context::EV_RING];
     HIP_TRY(ctx, hipEventRecord(evp[0], ctx->stream));
     for (uint32_t b = 0; b < slots; b = fp.slot_end) {
@@ -2381,9 +2458,19 @@ static int launch_fused_any(rt_context *ctx, const float cam[12], uint32_t first
         const SampleFacts facts = sample_facts(ctx, sc, fp, exact);
         const SamplePlan plan = plan_samples(facts);
         fp.lds_face_f4 = plan.lds_face_f4;
+        // A cleared frame is stored, not added to (rt_context::clear_pending): this launch qualifies when its two stages write
+        // every pixel of the frame exactly once with kernels that have the store arm — see accum_store_qualifies.  The first
+        // launch of a call only: it ends the pending state, the later ones add.
+        const bool store = accum_store_qualifies(ctx, fp, plan, accum, mask, ring, m2, per >= slots);
+        if (store) fp.store = 1u;
+        else if ((rc = materialise_clear(ctx)) != RT_OK) return rc;
         launch_first_stage(ctx, sc, fp, hit, ring != nullptr, accum, live_count);
         HIP_TRY(ctx, hipEventRecord(evp[2], ctx->stream));  // (the last slot range's; one range is the normal case)
         if ((rc = launch_plan(ctx, plan, sc, fp, accum, live_count)) != RT_OK) return rc;
+        // (the frame now holds this launch's sums.  Had the sample kernel not been launched, the clear would still be pending and
+        // the memset that ends it would wipe what the first stage stored: a failed call leaves a cleared frame)
+        if (store) ctx->clear_pending = false, ctx->clears_stored++;
+        fp.store = 0u;
         sg.last_facts = facts, sg.last_plan = plan;
         sg.launches++;
         sg.workgroups += plan.grid_units;   // (what rt_sample_grid_stats reports)
@@ -2470,6 +2557,7 @@ static int launch_source(rt_context *ctx, const SampleSource &src, uint32_t firs
         if (mask && src.n != (size_t)ctx->width * ctx->height)   // (ray_active reads the block of pixel i: i must be one)
             return fail(ctx, RT_EINVAL, "a masked ray launch takes one ray per pixel of the %d x %d frame", ctx->width, ctx->height);
     }
+    CLEAR_TRY(ctx);   // (these launches add, and a look-ahead launch starts from the image)
     FrameParams fp = src.rays ? frame_params(ctx, src.cam0, first, count, glog2, 0, 1)   // (unsharded: slot = ray index)
                               : frame_params(ctx, src.cam0, first, count, glog2);
     apply_mask(fp, mask);

@@ -293,6 +293,8 @@ __global__ __launch_bounds__(64, WAVES) void pt_samples_q(DeviceScene sc, FrameP
     // (wave-uniform: a look-ahead launch; never a counting one, never with moments; of the camera rows those without a BVH walk)
     constexpr bool LA_BRANCH = CAM ? !ACCEL : !COUNT && !MOMENTS;
     if (CAM_LA || (!RAYS && LA_BRANCH && fp.la_ring)) queue_replay<CAM>(q, fp);   // (a ray launch is never a look-ahead launch)
-    else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2>(q, fp, accum);
+    // (the two COUNT_LOG2 = 6 kernels may be launched on a cleared frame: FrameParams::store.  The generic-count kernels keep
+    // the add: with the second arm behind its loop C3's kernel at 256 samples measured 0.5 % slower, profiles/r32_experiments.md)
+    else queue_sums<MOMENTS, COUNT || ACCEL, COUNT_LOG2, PT_Q_LOOKAHEAD_FORM == 0 && !COUNT && !ACCEL && !MOMENTS && !CAM && COUNT_LOG2 == 6>(q, fp, accum);
     flush_counters<COUNT>(cn, counters, 1);
 }

@@ -4,6 +4,7 @@
 // pt_kernels.hip) in namespaces of their own, and all of them share these layouts.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/rt_amd.h"
@@ -163,7 +164,12 @@ struct FrameParams {
     uint32_t group_log2;            // lanes per pixel = 1 << group_log2 (<= 64)
     uint32_t seg_cap;               // live list: its capacity in entries (whole pt_prefix workgroups; the heavy pixels fill it from the end)
     float inv_count;                // 1 / count, the IEEE quotient computed on the host: a scalar operand of the queue kernels
-    PixelTree *trees;               // shared decision trees of this launch (pt_prefix writes, the sample kernels read)
+    // 1: the accumulator is logically zero (a pending rt_clear) and this launch writes every pixel of the frame exactly once,
+    // so the fused kernels STORE their sums instead of adding them (accumulate_store, pt_kernels.hip; PT_ACCUM_STORE).  Read
+    // in the epilogues of pt_prefix, pt_final_replay and pt_samples_q<false, false, 0 | 1, …> only.  The word lies in the four
+    // bytes of padding in front of `trees`: the struct keeps its size and every other field its place.
+    uint32_t store;
+    PixelTree *trees;              // shared decision trees of this launch (pt_prefix writes, the sample kernels read)
     PixelRec *tree_wait;            // glass vertices waiting for the next level of their tree (PT_TREE_WAITS per tree)
     uint32_t *tree_count;           // how many trees pt_prefix's workgroups reserved
     uint32_t tree_cap;              // capacity of `trees` (0: trees off — RT_OPT_PREFIX_TREE, counting builds)
@@ -202,6 +208,7 @@ struct FrameParams {
     // centred second moment of each pixel's sample luminances (pt_moments.hpp).  Read in the kernels' epilogues only
     float *m2;
 };
+static_assert(sizeof(FrameParams) == 192 && offsetof(FrameParams, trees) == 112, "FrameParams::store fills padding: no field moves");
 
 // the decision-block mask of an adaptive round, as the launchers take it (NULL = every pixel)
 struct BlockMask {

@@ -332,6 +332,7 @@ int alloc_frame(rt_context *ctx, int w, int h) {
     ctx->width = w;
     ctx->height = h;
     ctx->accum_count = 0;
+    ctx->clear_pending = false;   // (the new accumulator IS zero)
     ctx->sample_counter = 0;
     return RT_OK;
 }
@@ -354,8 +355,9 @@ int read_back(rt_context *ctx, void *dst, size_t bytes, const void *src, size_t 
     if (!dst || bytes != need) return fail(ctx, RT_EINVAL, "%s buffer must be %zu bytes", what, need);
     if (!ready) return fail(ctx, RT_ESTATE, "no %s call since the frame was (re)allocated", producer);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CLEAR_TRY(ctx);   // (src may be the accumulator or made from it)
     HIP_TRY(ctx, hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 }  // namespace rtamd
@@ -392,7 +394,7 @@ int apply_arith(rt_context *ctx) {
         int rc = ctx->ks->launch_face_normals(ctx, ctx->faces.p, (uint32_t)(ctx->h_faces.size() / 3));
         if (rc == RT_OK) rc = ctx->ks->launch_face_normals(ctx, ctx->mbvh_faces.p, (uint32_t)(ctx->h_mbvh_faces.size() / 3));
         if (rc != RT_OK) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        SYNC_TRY(ctx);
     }
     return RT_OK;
 }
@@ -491,14 +493,14 @@ int rt_resize(rt_context *ctx, int width, int height) {
     if (width < 1 || height < 1 || width > RT_MAX_DIM || height > RT_MAX_DIM)
         return fail(ctx, RT_EINVAL, "frame size %dx%d outside 1..%d", width, height, RT_MAX_DIM);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return alloc_frame(ctx, width, height);
 }
 
 int rt_set_stream(rt_context *ctx, void *hip_stream) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     ctx->prefix_changed();
     ctx->ev_count = 0;
@@ -514,7 +516,7 @@ int rt_set_scene(rt_context *ctx, const rt_scene_desc *d) {
         std::string err;
         if (int rc = prepare_scene(*d, ps, err)) return fail(ctx, rc, "%s", err.c_str());
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        SYNC_TRY(ctx);
         ctx->have_scene = false;
         // (behind the materials: room for the staged scene block, rt_context::StageBlock)
         HIP_TRY(ctx, ctx->materials.upload(d->materials, d->material_count,
@@ -566,7 +568,7 @@ int rt_set_textures(rt_context *ctx, const float *rgba, int w, int h, int layers
     if (!ctx) return RT_EINVAL;
     ctx->prefix_changed();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     if (layers == 0) {
         float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         HIP_TRY(ctx, ctx->tex.upload(&zero, 1));
@@ -588,7 +590,7 @@ int rt_set_random_table(rt_context *ctx, const float *table, size_t n) {
     if (!table || n != RT_RANDOM_TABLE_FLOATS) return fail(ctx, RT_EINVAL, "table must hold %d floats", RT_RANDOM_TABLE_FLOATS);
     ctx->prefix_changed();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     // 2 floats of slack: getVec reads idx..idx+2 with idx < 100000 — inside the table already
     HIP_TRY(ctx, ctx->table.upload(table, n));
     return RT_OK;
@@ -605,7 +607,7 @@ int rt_get_random_table(rt_context *ctx, float *out, size_t n) {
     if (!ctx) return RT_EINVAL;
     if (!out || n != RT_RANDOM_TABLE_FLOATS) return fail(ctx, RT_EINVAL, "table must hold %d floats", RT_RANDOM_TABLE_FLOATS);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     HIP_TRY(ctx, hipMemcpy(out, ctx->table.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -719,7 +721,7 @@ int lookahead_hand_out(rt_context *ctx, bool timed) {
     la.next_sample++;
     la.served++;
     ctx->sample_counter++;  // src/raytracer.cpp:147
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -761,7 +763,7 @@ int rt_render(rt_context *ctx, const float camera[12]) {
     remember_camera(ctx, camera);
     ctx->sample_counter = 0;  // src/raytracer.cpp:128
     if ((rc = ctx->ks->launch_render(ctx, MODE_TRACE, camera, 0, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // queue.finish(), src/raytracer.cpp:140
+    SYNC_TRY(ctx);  // queue.finish(), src/raytracer.cpp:140
     return RT_OK;
 }
 
@@ -794,7 +796,7 @@ int rt_render_again(rt_context *ctx, const float camera[12]) {
     la.direct++;
     ctx->sample_counter++;  // src/raytracer.cpp:147
     if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, camera, ctx->sample_counter, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -846,7 +848,12 @@ int for_each_launch(uint32_t n_samples, Launch launch) {
 int rt_clear(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
+    // RT_OPT_ACCUM_STORE 1: the clear is recorded, not enqueued — a fused launch that writes every pixel stores its sums into
+    // the frame as it lies (launch_fused_any), and whatever else comes next enqueues the memset first (materialise_clear).
+    // A clear that is still pending is enqueued before this one is recorded.
+    CLEAR_TRY(ctx);
+    if (ctx->accum_store) ctx->clear_pending = true;
+    else HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
     ctx->accum_count = 0;
     return moments_begin(ctx);
 }
@@ -1078,12 +1085,13 @@ int rt_render_again_cameras(rt_context *ctx, const float *cameras, uint32_t n_ca
     la.direct++;
     ctx->sample_counter++;
     if ((rc = ctx->ks->launch_render(ctx, MODE_RETRACE, cameras + 12u * (size_t)(s % n_cameras), ctx->sample_counter, 1, 0, ctx->accum.p, nullptr, nullptr)) != RT_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
 static int resolve_into(rt_context *ctx, int linear_only) {
     uint32_t n = (uint32_t)ctx->width * ctx->height;
+    CLEAR_TRY(ctx);
     hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->accum.p, ctx->image.p, n,
                        linear_only);
     HIP_TRY(ctx, hipGetLastError());
@@ -1181,6 +1189,7 @@ int adaptive_rounds(rt_context *ctx, AdaptiveRule rule, const rt_adaptive_params
     if (mom && !a.m2_scratch.p) HIP_TRY(ctx, a.m2_scratch.alloc(px));
     ctx->image_epoch++;   // (the call ends in a resolve)
     const size_t bytes = px * sizeof(float4);
+    ctx->clear_pending = false;   // (a pending rt_clear is this memset)
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, bytes, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.scratch.p, 0, bytes, ctx->stream));
     if (rule == RULE_DAMMERTZ) HIP_TRY(ctx, hipMemsetAsync(a.half.p, 0, bytes, ctx->stream));
@@ -1224,7 +1233,7 @@ int adaptive_rounds(rt_context *ctx, AdaptiveRule rule, const rt_adaptive_params
         rounds++;
         ctx->accum_count = first + c;
         HIP_TRY(ctx, hipMemcpyAsync(st.data(), a.stats.p, st_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        SYNC_TRY(ctx);
         uint64_t still = 0;
         for (uint32_t r = 0; r < PT_MERGE_REPLICAS; r++) {
             still += st[r * PT_MERGE_STRIDE];
@@ -1234,7 +1243,7 @@ int adaptive_rounds(rt_context *ctx, AdaptiveRule rule, const rt_adaptive_params
         if (still == 0) break;
     }
     if ((rc = resolve_into(ctx, 0)) != RT_OK) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     a.blocks = blocks;
     a.variance = rule == RULE_VARIANCE;
     out->rounds = rounds;
@@ -1337,8 +1346,9 @@ int rt_read_sample_counts(rt_context *ctx, uint32_t *counts, size_t bytes) {
     if (!counts || bytes != n * sizeof(uint32_t)) return fail(ctx, RT_EINVAL, "count buffer must be %zu bytes", n * sizeof(uint32_t));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<float4> h(n);
+    CLEAR_TRY(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->accum.p, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     for (size_t i = 0; i < n; i++) counts[i] = (uint32_t)h[i].w;
     return RT_OK;
 }
@@ -1559,7 +1569,7 @@ int rt_device_copy(rt_context *ctx, void *dst, const void *src, size_t bytes, in
     if (bytes == 0) return RT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -1668,7 +1678,7 @@ int rt_moments_merge(uint32_t nA, const float sumA[3], float m2A, uint32_t nB, c
 int rt_sync(rt_context *ctx) {
     if (!ctx) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -1692,7 +1702,7 @@ int rt_trace_samples(rt_context *ctx, const float camera[12], const uint32_t *x,
     const FrameParams fp = frame_params(ctx, camera, 0, 1, 0);
     if ((rc = ctx->ks->launch_probe(ctx, fp, device_scene(ctx), d_in.p, (uint32_t)n, d_out.p)) != RT_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, d_out.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -1708,10 +1718,11 @@ int rt_read_linear(rt_context *ctx, float *rgba, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<float4> tmp;
     HIP_TRY(ctx, tmp.alloc(n));
+    CLEAR_TRY(ctx);
     hipLaunchKernelGGL(pt_resolve, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->accum.p, tmp.p, (uint32_t)n, 1);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(rgba, tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -1723,6 +1734,8 @@ int rt_device_image(rt_context *ctx, void **d_rgba) {
 
 int rt_device_accum(rt_context *ctx, void **d_rgba) {
     if (!ctx || !d_rgba) return RT_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CLEAR_TRY(ctx);   // (the caller's own work on the stream may come next)
     *d_rgba = ctx->accum.p;
     return RT_OK;
 }
@@ -1757,7 +1770,7 @@ int debug_roundtrip(rt_context *ctx, const void *in, size_t bytes, void *out, si
     HIP_TRY(ctx, hipMemcpyAsync(d_in.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = launch(d_in.p, d_out.p)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 }  // namespace
@@ -1852,6 +1865,7 @@ int rt_pack_accum(rt_context *ctx, void *d_packed, size_t bytes) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float cam0[12] = {0};
     FrameParams fp = frame_params(ctx, cam0, 0, 0, 0);
+    CLEAR_TRY(ctx);
     hipLaunchKernelGGL(pt_pack, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, fp, ctx->accum.p, (float4 *)d_packed, n);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
@@ -1866,6 +1880,7 @@ int rt_unpack_accum(rt_context *ctx, const void *d_packed, size_t bytes, int src
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float cam0[12] = {0};
     FrameParams fp = frame_params(ctx, cam0, 0, 0, 0, src_rank, world);  // the SENDER's shard
+    CLEAR_TRY(ctx);
     if (fp.slot_end)
         hipLaunchKernelGGL(pt_unpack, dim3((fp.slot_end + 255) / 256), dim3(256), 0, ctx->stream, fp, (const float4 *)d_packed, ctx->accum.p);
     HIP_TRY(ctx, hipGetLastError());
@@ -1882,6 +1897,14 @@ int rt_set_option(rt_context *ctx, int option, int value) {
         case RT_OPT_WALK_SLICES: ctx->walk_slices = value != 0; return RT_OK;
         case RT_OPT_WAVE_FILL: ctx->wave_fill = value != 0; return RT_OK;
         case RT_OPT_EXACT_GRID: ctx->sample_grid.exact = value != 0; return RT_OK;
+        case RT_OPT_ACCUM_STORE:
+            if (value != 0 && value != 1) return fail(ctx, RT_EINVAL, "RT_OPT_ACCUM_STORE takes 0 or 1");
+            if (value == 0) {   // (eager from here on: a clear recorded under 1 is enqueued now)
+                HIP_TRY(ctx, hipSetDevice(ctx->device));
+                CLEAR_TRY(ctx);
+            }
+            ctx->accum_store = value != 0;
+            return RT_OK;
         case RT_OPT_MOMENTS:
             if (value != 0 && value != 1) return fail(ctx, RT_EINVAL, "RT_OPT_MOMENTS takes 0 or 1");
             if (value == 1 && ctx->world > 1)
@@ -1907,7 +1930,7 @@ int rt_set_option(rt_context *ctx, int option, int value) {
                                   : value == RT_ARITH_ROCM_OCL ? kernel_set_a2() : nullptr;
             if (!ks) return fail(ctx, RT_EINVAL, "RT_OPT_ARITH takes RT_ARITH_IEEE (0), RT_ARITH_ROCM_OCL_NOCONTRACT (1) or RT_ARITH_ROCM_OCL (2)");
             HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            SYNC_TRY(ctx);
             ctx->arith = value;
             ctx->ks = ks;
             ctx->sample_counter = 0;
@@ -1919,6 +1942,13 @@ int rt_set_option(rt_context *ctx, int option, int value) {
             return RT_OK;
         default: return fail(ctx, RT_EINVAL, "unknown option %d", option);
     }
+}
+
+int rt_accum_store_stats(rt_context *ctx, uint64_t *stored, uint64_t *materialised) {
+    if (!ctx || !stored || !materialised) return RT_EINVAL;
+    *stored = ctx->clears_stored;
+    *materialised = ctx->clears_materialised;
+    return RT_OK;
 }
 
 int rt_prefix_cache_stats(rt_context *ctx, uint64_t *hits, uint64_t *misses) {
@@ -1957,7 +1987,7 @@ int rt_debug_live_list(rt_context *ctx, uint32_t out[4]) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint32_t h[LIVE_COUNT_STRIDE];
     HIP_TRY(ctx, hipMemcpyAsync(h, ss.live.p + ss.capacity + 256u, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     out[0] = ctx->sample_grid.last_facts.seg_cap;
     out[1] = ctx->sample_grid.last_plan.pixels_per_wave;
     out[2] = h[0];
@@ -2033,7 +2063,7 @@ int rt_debug_stage_block(rt_context *ctx, float *out, size_t capacity_float4, ui
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(out, reinterpret_cast<const char *>(ctx->materials.p) + stage_block_offset((uint32_t)ctx->materials.n),
                                 n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 
@@ -2050,7 +2080,7 @@ int rt_get_counters(rt_context *ctx, rt_counters *out) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h(COUNTER_REPLICAS * COUNTER_STRIDE);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->counters.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     uint64_t *o = (uint64_t *)out;
     for (int i = 0; i < 14; i++) {
         o[i] = 0;
@@ -2064,7 +2094,7 @@ int rt_get_debug_counters(rt_context *ctx, uint64_t out[2]) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h(COUNTER_REPLICAS * COUNTER_STRIDE);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->counters.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     out[0] = out[1] = 0;
     for (int r = 0; r < COUNTER_REPLICAS; r++) {
         out[0] += h[(size_t)r * COUNTER_STRIDE + 14];
@@ -2099,7 +2129,7 @@ int rt_walk_overflow(rt_context *ctx, uint32_t *flags_out) {
     if (!ctx || !flags_out) return RT_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpyAsync(flags_out, ctx->d_walk_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SYNC_TRY(ctx);
     return RT_OK;
 }
 

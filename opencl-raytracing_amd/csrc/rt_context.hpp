@@ -239,6 +239,13 @@ struct rt_context {
                                      // every one of them has a BVH (pt_samples_w)
     bool walk_slices = true;         // RT_OPT_WALK_SLICES
     uint32_t accum_count = 0;
+    // rt_clear under RT_OPT_ACCUM_STORE 1 records the clear instead of enqueuing it: the accumulator is LOGICALLY zero while
+    // clear_pending is set, and its bytes are whatever they were.  A qualifying fused launch (launch_fused_any, pt_kernels.hip)
+    // stores its sums and ends the state; everything else that reads, writes or hands out the accumulator, and every wait
+    // for the stream, calls materialise_clear first.
+    bool accum_store = true;         // RT_OPT_ACCUM_STORE
+    bool clear_pending = false;
+    uint64_t clears_stored = 0, clears_materialised = 0;   // how the recorded clears ended (rt_accum_store_stats)
     uint32_t sample_counter = 0;
     bool count_enabled = false;
 
@@ -338,6 +345,33 @@ int read_back(rt_context *ctx, void *dst, size_t bytes, const void *src, size_t 
         if (e_ != hipSuccess) return fail(ctx, RT_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The pending rt_clear, enqueued now (rt_context::clear_pending): the memset rt_clear enqueues under RT_OPT_ACCUM_STORE 0, on
+// the context's stream, in front of whatever the caller is about to enqueue or wait for.
+inline int materialise_clear(rt_context *ctx) {
+    if (!ctx->clear_pending) return RT_OK;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->accum.p, 0, (size_t)ctx->width * ctx->height * sizeof(float4), ctx->stream));
+    ctx->clear_pending = false;
+    ctx->clears_materialised++;
+    return RT_OK;
+}
+// every wait for the context's stream: a pending clear is ordered before it returns
+inline int sync_stream(rt_context *ctx) {
+    const int rc = materialise_clear(ctx);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+#define SYNC_TRY(ctx)                         \
+    do {                                      \
+        const int rc_ = sync_stream(ctx);     \
+        if (rc_ != RT_OK) return rc_;         \
+    } while (0)
+#define CLEAR_TRY(ctx)                        \
+    do {                                      \
+        const int rc_ = materialise_clear(ctx); \
+        if (rc_ != RT_OK) return rc_;         \
+    } while (0)
+
 inline DeviceScene device_scene(const rt_context *ctx) {
     DeviceScene s;
     s.materials = ctx->materials.p;
@@ -416,6 +450,7 @@ inline FrameParams frame_params(const rt_context *ctx, const float cam[12], uint
     fp.count = count;
     fp.group_log2 = glog2;
     fp.seg_cap = 0;
+    fp.store = 0;
     fp.trees = nullptr;
     fp.tree_wait = nullptr;
     fp.tree_count = nullptr;

@@ -387,6 +387,7 @@ int denoise_variance(rt_context *ctx, const rt_denoise_variance_params *vp, bool
         return fail(ctx, RT_ESTATE, "the sample moments are not valid: set RT_OPT_MOMENTS to 1, then rt_clear or rt_render_adaptive");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_buffers(ctx, true)) != RT_OK) return rc;
+    CLEAR_TRY(ctx);   // (the filters read the accumulator)
     rt_context::Denoise &d = ctx->denoise;
     const uint32_t w = (uint32_t)ctx->width, h = (uint32_t)ctx->height;
     DenoiseVariance dv;
@@ -432,6 +433,7 @@ int rt_denoise(rt_context *ctx, const rt_denoise_params *dp) {
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_buffers(ctx, false)) != RT_OK) return rc;
+    CLEAR_TRY(ctx);   // (the filter reads the accumulator)
     for (uint32_t i = 0; i < p.iterations; i++) {
         StepPlan sp = plan_step(ctx, p, i);
         sp.ds.inv_c = inv_sq(p.sigma_own, (int)i);

@@ -33,7 +33,7 @@ SYMBOLS = (
     "rt_denoise", "rt_read_denoised", "rt_device_denoised",
     "rt_denoise_variance", "rt_read_variance", "rt_device_variance",
     "rt_read_moments", "rt_device_moments", "rt_moments_merge", "rt_denoise_moments",
-    "rt_prefix_cache_stats", "rt_lookahead_stats", "rt_lookahead_plan",
+    "rt_prefix_cache_stats", "rt_accum_store_stats", "rt_lookahead_stats", "rt_lookahead_plan",
     "rt_sample_units", "rt_sample_grid_stats", "rt_debug_live_list", "rt_debug_wave_fixed", "rt_debug_stage_block", "rt_debug_queue_pixels", "rt_debug_queue_occupancy", "rt_debug_queue_sums",
     "rt_debug_plan_samples", "rt_debug_last_sample_plan",
     "rt_render_spp_cameras", "rt_debug_plan_camera_samples", "rt_debug_last_camera_plan",
@@ -53,6 +53,7 @@ OPT_PREFIX_CACHE = 9
 OPT_LOOKAHEAD = 10
 OPT_EXACT_GRID = 11
 OPT_MOMENTS = 12
+OPT_ACCUM_STORE = 13
 ARITH_IEEE, ARITH_ROCM_OCL_NOCONTRACT, ARITH_ROCM_OCL = 0, 1, 2
 # rt_render_features_chain: the material types a chain is followed through
 FOLLOW_REFLECTIVE, FOLLOW_REFRACTIVE, FOLLOW_DIELECTRIC = _abi.FOLLOW_REFLECTIVE, _abi.FOLLOW_REFRACTIVE, _abi.FOLLOW_DIELECTRIC
@@ -364,6 +365,7 @@ class RayTracer:
     OPT_LOOKAHEAD = 10
     OPT_EXACT_GRID = 11
     OPT_MOMENTS = 12
+    OPT_ACCUM_STORE = 13
 
     def setOption(self, option, value):
         self._check(self._lib.rt_set_option(self._ctx, option, int(value)))
@@ -1018,6 +1020,13 @@ class RayTracer:
         hits, misses = C.c_uint64(), C.c_uint64()
         self._check(self._lib.rt_prefix_cache_stats(self._ctx, C.byref(hits), C.byref(misses)))
         return int(hits.value), int(misses.value)
+
+    def accumStoreStats(self):
+        """(stored, materialised): clear() calls recorded under OPT_ACCUM_STORE 1 that a fused launch ended by storing its
+        sums / that ended in the memset, enqueued in front of whatever came next."""
+        stored, mat = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rt_accum_store_stats(self._ctx, C.byref(stored), C.byref(mat)))
+        return int(stored.value), int(mat.value)
 
     def lookaheadStats(self):
         """(batches, served, direct, discarded) of renderAgain since the context was made (OPT_LOOKAHEAD): look-ahead
