@@ -49,15 +49,17 @@
 #ifndef PT_ARITH
 #define PT_ARITH 0
 #endif
-#if PT_ARITH == 0
-#define PT_NS pt_a0
-#elif PT_ARITH == 1
-#define PT_NS pt_a1
-#elif PT_ARITH == 2
-#define PT_NS pt_a2
-#else
+#if PT_ARITH != 0 && PT_ARITH != 1 && PT_ARITH != 2
 #error "PT_ARITH must be 0 (IEEE), 1 (ROCm OpenCL builtins, no contraction) or 2 (ROCm OpenCL default build)"
 #endif
+// The policy's suffix, formed once: PT_POLICY(name) is name0 / name1 / name2 (PT_ARITH must be given as the bare digit).
+// The namespace and the two accessors a policy's translation units define (pt_kernels.hpp) are named by it.
+#define PT_PASTE_(a, b) a##b
+#define PT_PASTE(a, b) PT_PASTE_(a, b)
+#define PT_POLICY(name) PT_PASTE(name, PT_ARITH)
+#define PT_NS PT_POLICY(pt_a)                          // pt_a0, pt_a1, pt_a2
+#define PT_KERNEL_SET PT_POLICY(kernel_set_a)          // pt::kernel_set_a0 …      (pt_kernels.hip defines it)
+#define PT_GATHER_KERNELS PT_POLICY(gather_kernels_a)  // pt::gather_kernels_a0 …  (pt_gather.hip defines it)
 #define PT_OCL (PT_ARITH != 0)        // ROCm's OpenCL builtin library
 #define PT_CONTRACT (PT_ARITH == 2)   // clang's -ffp-contract=on at the reference's expression sites
 
@@ -253,7 +255,7 @@ PT_DEV V3 normalize(V3 v) {
 // and the translation unit is compiled without fast math.)  The asm is not volatile and touches no memory: it may
 // be moved, merged and dropped like the call it stands for.  tools/isa_stats.py is the proof, tests/test_mixcol_host.py
 // keeps it.  Contract: identical to __ocml_min_f32 for every pair of operands that holds no signalling NaN; a
-// signalling NaN in a colour is outside it, as a NaN radiance already is (pt_kernels.hip, queue_sums_tree).
+// signalling NaN in a colour is outside it, as a NaN radiance already is (pt_queue.hpp, queue_sums_tree).
 // -DPT_MIXCOL_FAST=0: the sample queue asks for the untagged min (the switch is read where the tag is set,
 // pt_samples_q_kernel.hpp, so that rt_debug_builtin's probe of the tagged form is the same code in both builds).
 #ifndef PT_MIXCOL_FAST

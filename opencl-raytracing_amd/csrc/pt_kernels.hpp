@@ -107,20 +107,21 @@ struct KernelSet {
                               uint32_t first, uint32_t count, uint32_t glog2, float4 *accum, float *m2);
 };
 
-// The kernels of rt_render_hemispheres, which a policy keeps in a translation unit of their own (pt_gather.hip: the text of
-// pt_kernels.hip once more, with nothing instantiated but these): launch_hemispheres launches them through these pointers.
+// The kernels of rt_render_hemispheres, which a policy keeps in a translation unit of their own (pt_gather.hip: made of the
+// headers pt_kernels.hip's sample kernels are made of — pt_sample.hpp, pt_queue.hpp, pt_samples_q_kernel.hpp — with nothing
+// instantiated but these): launch_hemispheres launches them through these pointers.
 struct GatherKernels {
     using Queue = void (*)(DeviceScene, FrameParams, const PixelRec *, const uint32_t *, const uint32_t *, float4 *, unsigned long long *, uint32_t);
     using Fixed = void (*)(DeviceScene, FrameParams, float4 *, unsigned long long *);
     Queue (*queue)(uint32_t accel, uint32_t geom, uint32_t waves);   // pt_samples_q_hemi of the queue's geometry row; NULL: no such row
     Fixed (*fixed)(bool count, bool accel);                          // pt_render_hemi<COUNT, ACCEL>
 };
-// defined by pt_gather.hip compiled with -DPT_ARITH=0 / 1 / 2
+// defined by pt_gather.hip compiled with -DPT_ARITH=0 / 1 / 2 (as PT_GATHER_KERNELS, pt_arith.hpp)
 const GatherKernels *gather_kernels_a0();
 const GatherKernels *gather_kernels_a1();
 const GatherKernels *gather_kernels_a2();
 
-// defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2
+// defined by pt_kernels.hip compiled with -DPT_ARITH=0 / 1 / 2 (as PT_KERNEL_SET, pt_arith.hpp)
 const KernelSet *kernel_set_a0();
 const KernelSet *kernel_set_a1();
 const KernelSet *kernel_set_a2();

@@ -1,5 +1,6 @@
-// pt_samples_q_kernel.hpp — the text of the sample-queue kernel, included by pt_kernels.hip (and by nothing else) once per
-// FORM of the kernel, inside the policy's namespace, with PT_Q_LOOKAHEAD_FORM defined:
+// pt_samples_q_kernel.hpp — the text of the sample-queue kernel, included once per FORM of the kernel, inside the policy's
+// namespace, after pt_queue.hpp and with PT_Q_LOOKAHEAD_FORM defined — forms 0 – 3 by pt_kernels.hip, form 4 by pt_gather.hip
+// (and by nothing else):
 //   0  pt_samples_q<COUNT, ACCEL, GEOM, WAVES, MOMENTS, COUNT_LOG2, CAM>, every instantiation there was
 //   1  pt_samples_q_la<GEOM, WAVES>: the look-ahead form of the camera entry's ACCEL rows (CAM_LA; see pt_kernels.hip)
 //   2  pt_samples_q_rays<ACCEL, GEOM, WAVES>: the camera entry fed from a ray buffer (RAYS; rt_render_rays) — the slots ARE

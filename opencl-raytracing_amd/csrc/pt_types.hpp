@@ -150,7 +150,7 @@ struct PixelTree {      // 8 x 16 + 8 x 80 = 768 bytes at 3 levels
 enum RenderMode { MODE_ACCUM = 0, MODE_TRACE = 1, MODE_RETRACE = 2 };
 
 #ifndef PT_RING_PIXEL_MAJOR
-#define PT_RING_PIXEL_MAJOR 0   // layout of the look-ahead ring: 0 frame-major (shipped), 1 pixel-major (A/B variant; pt_kernels.hip ring_at)
+#define PT_RING_PIXEL_MAJOR 0   // layout of the look-ahead ring: 0 frame-major (shipped), 1 pixel-major (A/B variant; pt_sample.hpp ring_at)
 #endif
 
 struct FrameParams {
@@ -165,7 +165,7 @@ struct FrameParams {
     uint32_t seg_cap;               // live list: its capacity in entries (whole pt_prefix workgroups; the heavy pixels fill it from the end)
     float inv_count;                // 1 / count, the IEEE quotient computed on the host: a scalar operand of the queue kernels
     // 1: the accumulator is logically zero (a pending rt_clear) and this launch writes every pixel of the frame exactly once,
-    // so the fused kernels STORE their sums instead of adding them (accumulate_store, pt_kernels.hip; PT_ACCUM_STORE).  Read
+    // so the fused kernels STORE their sums instead of adding them (accumulate_store, pt_sample.hpp; PT_ACCUM_STORE).  Read
     // in the epilogues of pt_prefix, pt_final_replay and pt_samples_q<false, false, 0 | 1, …> only.  The word lies in the four
     // bytes of padding in front of `trees`: the struct keeps its size and every other field its place.
     uint32_t store;
@@ -196,7 +196,7 @@ struct FrameParams {
     // la_image nor cams, is never a look-ahead launch, and no other kernel reads `rays`.
     // Hemisphere gathers (rt_render_hemispheres): the launch's rt_feature records, five float4 each, in the same eight bytes
     // — a gather launch (pt_samples_q_hemi, pt_render_hemi) is a ray launch whose rays are made from `feats`, not read.  Its
-    // parameters travel in `cam` (HEMI_CAM_*, pt_kernels.hip), of which a ray launch reads only the first two words.
+    // parameters travel in `cam` (HEMI_CAM_*, pt_sample.hpp), of which a ray launch reads only the first two words.
     float4 *la_ring;
     union {
         const float4 *la_image;

@@ -59,7 +59,26 @@ struct DevBuf {
 namespace pt { struct KernelSet; }
 
 #define ACCEL_MIN_SPHERES 64
-#define RT_SPP_PER_LAUNCH 512u   // samples per pixel of one trace launch (rt_render_spp splits larger calls); = QUEUE_SLOTS of pt_kernels.hip
+#define RT_SPP_PER_LAUNCH 512u   // samples per pixel of one trace launch (rt_render_spp splits larger calls); = QUEUE_SLOTS below
+// The sample queue's launch constants (the queue itself: pt_queue.hpp): what the planners (plan_samples, plan_camera_samples,
+// pt_kernels.hip) size a launch by and the kernels of both policy units (pt_kernels.hip, pt_gather.hip) are compiled for.
+#ifndef QUEUE_SLOTS
+#define QUEUE_SLOTS 512   // upper bound of samples a wave owns; the launch picks pixels_per_wave
+#endif
+#ifndef QUEUE_MAX_PIXELS
+#define QUEUE_MAX_PIXELS 16
+#endif
+#ifndef PT_Q_WAVES
+#define PT_Q_WAVES 6  // waves per SIMD the register allocator must leave room for: 6 = 80 VGPRs (A/B on C2: 5 → 2.62 ms, 6 → 2.48)
+#endif
+#ifndef PT_Q_WAVES_ACCEL
+#define PT_Q_WAVES_ACCEL 5  // scenes that mix BVH meshes with small ones (every other mesh scene runs pt_samples_w), and scenes with a sphere BVH
+                            // next to lenses / small meshes: 96 VGPRs (at 6 waves per SIMD = 80 VGPRs these instantiations spill 21 registers)
+#endif
+#ifndef PT_Q_WAVES_SPHERE_BVH
+#define PT_Q_WAVES_SPHERE_BVH 6  // scenes whose only BVH is the sphere BVH (C4 at 8 spp, r02: 5 → 76.9 ms, 6 → 71.8 ms)
+#endif
+static_assert(QUEUE_SLOTS >= RT_SPP_PER_LAUNCH, "rt_render_spp's launches must fit a wave's sample queue");
 #define RT_LOOKAHEAD_MAX 64                     // largest RT_OPT_LOOKAHEAD: frames of one look-ahead batch
 #define RT_LOOKAHEAD_MAX_BYTES (1ull << 30)     // budget of a context's look-ahead ring: a batch holds as many frames as fit
 #ifndef MESH_BVH_MIN_FACES

@@ -1,4 +1,4 @@
-"""numpy statements of the sample queue's per-pixel summation (csrc/pt_kernels.hip queue_sums), float32 throughout.
+"""numpy statements of the sample queue's per-pixel summation (csrc/pt_queue.hpp queue_sums), float32 throughout.
 
 butterfly_lane0  the CONTRACT: lane l of a pixel's g = 1 << group_log2 lanes starts from 0.0f and adds its slots
                  l, l + g, … in that order; then for off = g/2 … 1 every lane adds lane l ^ off's value to its own;
@@ -14,7 +14,7 @@ import numpy as np
 f32 = np.float32
 LANES = np.arange(64)
 COUNTS = (1, 2, 3, 5, 8, 16, 17, 24, 32, 33, 63, 64, 65, 128, 200, 512)
-QUEUE_SLOTS, QUEUE_MAX_PIXELS = 512, 16     # csrc/pt_kernels.hip
+QUEUE_SLOTS, QUEUE_MAX_PIXELS = 512, 16     # csrc/rt_context.hpp
 
 
 def max_pixels(count):

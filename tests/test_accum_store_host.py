@@ -1,4 +1,4 @@
-"""CPU: the two switches of the stored frame (csrc/pt_kernels.hip PT_ACCUM_STORE, PT_SUMS_ADDR; DESIGN §5 "A cleared frame is
+"""CPU: the two switches of the stored frame (csrc/pt_sample.hpp PT_ACCUM_STORE, csrc/pt_queue.hpp PT_SUMS_ADDR; DESIGN §5 "A cleared frame is
 stored") are live and confined — read from the compiler's listings (tools/isa_stats.py), not from the source text.  Policy 2
 is compiled as shipped, with either switch off and with both off, policy 0 as shipped and with both off; the builds are
 compared kernel by kernel through the digest of their instructions.

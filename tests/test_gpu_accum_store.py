@@ -1,5 +1,5 @@
-"""GPU (-m gpu): a cleared frame is stored, not added to (RT_OPT_ACCUM_STORE, include/rt_amd.h; csrc/pt_kernels.hip
-accumulate_store, launch_fused_any).  Under RT_OPT_ACCUM_STORE 1 rt_clear records the clear, a qualifying fused
+"""GPU (-m gpu): a cleared frame is stored, not added to (RT_OPT_ACCUM_STORE, include/rt_amd.h; csrc/pt_sample.hpp
+accumulate_store, csrc/pt_kernels.hip launch_fused_any).  Under RT_OPT_ACCUM_STORE 1 rt_clear records the clear, a qualifying fused
 launch stores 0 + sum over whatever the frame held, and everything else enqueues the memset first.  Every result here is
 compared word for word (uint32, ==) with the SAME library under RT_OPT_ACCUM_STORE 0, where rt_clear enqueues the memset at
 once and every launch adds — the parent's behaviour.

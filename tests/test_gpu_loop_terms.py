@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the sample queue reads its staged scene tables from LDS wherever they are staged (csrc/pt_kernels.hip
+"""GPU (-m gpu): the sample queue reads its staged scene tables from LDS wherever they are staged (csrc/pt_queue.hpp
 PT_TABLES_BY_COUNT: presence asked of the scene's counts — the pointer calls a table at LDS address 0 absent) and changes no bit.
 
 Frames of the fused path against the direct path pt_render — which this does not touch — with == as uint32: C2, C3, the

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the sample queue's per-pixel sums without LDS permutes (csrc/pt_kernels.hip queue_sums_tree).
+"""GPU (-m gpu): the sample queue's per-pixel sums without LDS permutes (csrc/pt_queue.hpp queue_sums_tree).
 
 1. rt_debug_queue_sums — one wave, its slots filled from an array — against the numpy butterfly (tests/queue_sums_ref.py),
    as uint32: every group size, the counts of the host test, one pixel / the most a wave may own / one number in between,

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the sample queue's mesh-free kernels gather only the random-table entries an interaction reads
-(csrc/pt_kernels.hip PT_RND_BY_USE, pt_device.hpp fetch_rnd_by_use: randomVec's entry at a diffuse or textured vertex, random's
+(csrc/pt_queue.hpp PT_RND_BY_USE, pt_device.hpp fetch_rnd_by_use: randomVec's entry at a diffuse or textured vertex, random's
 at a dielectric one, nothing at a mirror or a refractive one) and change no bit.
 
 Frames of the fused path against the direct path pt_render — which this does not touch — with == as uint32, at 61 x 37 and

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the fixed cost a wave of the sample queue pays around its sample loop (csrc/pt_kernels.hip: the instantiation
+"""GPU (-m gpu): the fixed cost a wave of the sample queue pays around its sample loop (csrc/pt_queue.hpp: the instantiation
 for exactly 64 samples per pixel, the scene's LDS tables copied from the context's staged block, the texel set-up kept in
 its branch, queue_stage's coordinates without the division) changes no bit.
 

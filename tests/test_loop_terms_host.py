@@ -1,4 +1,4 @@
-"""CPU: the switch that makes the sample queue ask "is the table staged?" of the scene's counts (csrc/pt_kernels.hip
+"""CPU: the switch that makes the sample queue ask "is the table staged?" of the scene's counts (csrc/pt_queue.hpp
 PT_TABLES_BY_COUNT, DESIGN §8, profiles/r20_experiments.md) is live and confined — read from the compiler's listing, not from
 the source text: the device code of arithmetic policy 2 is compiled as shipped and with the switch off (tools/isa_stats.py,
 two compilations side by side), and the two are compared kernel by kernel.  Were the tag to fall back to the pointer test,

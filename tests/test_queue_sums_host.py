@@ -1,4 +1,4 @@
-"""Host-only: the sample queue's per-pixel sums (csrc/pt_kernels.hip queue_sums), in float32 numpy.
+"""Host-only: the sample queue's per-pixel sums (csrc/pt_queue.hpp queue_sums), in float32 numpy.
 
 The contract is the xor butterfly's lane 0 (pt_render's order).  queue_sums_tree forms lane 0's tree alone — no lane but
 the first of a pixel's group is stored — with several pixels packed into one register as the tree narrows.  Both, and the

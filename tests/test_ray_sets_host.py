@@ -136,7 +136,7 @@ def test_check_ray_sets_rejects_bad_inputs_without_a_device():
 
 
 def test_the_kernels_remainder_rule():
-    """ray_set_member (csrc/pt_kernels.hip): s mod k as s - uint(float(s) + 0.5f) * (1.0f / k)) * k, every operation in
+    """ray_set_member (csrc/pt_sample.hpp): s mod k as s - uint(float(s) + 0.5f) * (1.0f / k)) * k, every operation in
     float32, over the whole domain the library admits: samples 0 .. RT_MAX_SAMPLE, set sizes 1 .. RT_RAY_SET_MAX."""
     s = np.arange(0, 65536, dtype=np.uint32)
     sf = s.astype(np.float32) + np.float32(0.5)

@@ -1,5 +1,5 @@
 """CPU: the switch that makes an interaction of the sample queue gather only the random-table entries its material reads
-(csrc/pt_kernels.hip PT_RND_BY_USE, pt_device.hpp fetch_rnd_by_use, profiles/r22_experiments.md) is live and confined — read
+(csrc/pt_queue.hpp PT_RND_BY_USE, pt_device.hpp fetch_rnd_by_use, profiles/r22_experiments.md) is live and confined — read
 from the compiler's listing, not from the source text: the device code of arithmetic policy 2 is compiled as shipped and with
 the switch off (tools/isa_stats.py, two compilations side by side), and the two are compared kernel by kernel.  Were the
 kernel to fall back to the two unconditional gathers, no kernel would differ and this fails; were the change to leak into

@@ -1,4 +1,4 @@
-"""Host-only: rt_sample_units, the launcher's restatement of the sample kernels' live_take (csrc/pt_kernels.hip), against
+"""Host-only: rt_sample_units, the launcher's restatement of the sample kernels' live_take (csrc/pt_sample.hpp), against
 a Python restatement of that device function.  For every capacity, pixels per unit and pair of raw counters — counters
 past the capacity included, which the kernels clamp — every unit below the returned number takes at least one pixel,
 every unit from it on takes none, and the takes add up to the clamped counts."""
@@ -10,7 +10,7 @@ rt = cases.rt
 
 
 def live_take(cap, count_light, count_heavy, unit, want):
-    """→ (first entry, entries) of `unit`: live_take of csrc/pt_kernels.hip, line by line."""
+    """→ (first entry, entries) of `unit`: live_take of csrc/pt_sample.hpp, line by line."""
     cnt_l = min(count_light, cap)
     cnt_h = min(count_heavy, cap - cnt_l)
     units_h = (cnt_h + want - 1) // want if want else 0

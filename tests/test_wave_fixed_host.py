@@ -35,7 +35,7 @@ def test_the_layout_helper_has_the_kernels_caps():
     types = open(os.path.join(CSRC, "pt_types.hpp")).read()
     assert (A.LDS_MATERIALS, A.LDS_WINNERS, A.LDS_PLANES) == tuple(
         int(_define(types, n)) for n in ("PT_LDS_MATERIALS", "PT_LDS_WINNERS", "PT_LDS_PLANES"))
-    kernels = open(os.path.join(CSRC, "pt_kernels.hip")).read()
+    kernels = "".join(open(os.path.join(CSRC, f)).read() for f in ("pt_kernels.hip", "pt_queue.hpp"))
     assert 1 << int(re.search(r"#define PT_XY_FAST_MAX_TILES \(1u << (\d+)\)", kernels).group(1)) == W.XY_FAST_MAX_TILES
     # the block follows the materials in their allocation, 16-byte aligned: a material is 48 bytes
     assert A.MATERIAL.itemsize == 48 and A.MATERIAL.itemsize % 16 == 0

@@ -1,4 +1,4 @@
-"""Host restatements for the wave's fixed cost (csrc/pt_kernels.hip stage_xy, csrc/pt_device.hpp stage_tables): the staged
+"""Host restatements for the wave's fixed cost (csrc/pt_queue.hpp stage_xy, csrc/pt_device.hpp stage_tables): the staged
 scene block from a scene's arrays, and queue_stage's division-free tile quotient in float32."""
 import numpy as np
 

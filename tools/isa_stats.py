@@ -7,7 +7,8 @@ kernel: VGPRs / SGPRs / scratch bytes / spilled VGPRs from the code-object metad
 histogram grouped into the issue-cost classes measured by tools/valu_microbench.hip
 (profiles/r02_valu_microbench.md).  --unit rt_denoise / --unit rt_amd read the policy-free kernels of csrc/rt_denoise.hip
 (pt_atrous, pt_dn_variance, pt_atrous_vg) / csrc/rt_amd.hip (pt_adaptive_merge, ...) instead: compiled once, with the
-IEEE divide; --unit pt_gather the policy-compiled kernels of csrc/pt_gather.hip (rt_render_hemispheres).  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
+IEEE divide; --unit pt_gather the policy-compiled kernels of csrc/pt_gather.hip (rt_render_hemispheres), made of the same headers
+(csrc/pt_sample.hpp, pt_queue.hpp, pt_samples_q_kernel.hpp) as the sample kernels of csrc/pt_kernels.hip.  --json dumps everything for bench.py / profile summaries (--digest: with a hash of each kernel's
 instructions); --listing prints the labels and instructions of the named kernels.  --diff A.json B.json [kernel-substring
 ...] compiles nothing: it compares two --json --digest dumps, prints the kernels present in one only and, for every kernel
 whose hash differs, VGPRs, waves per SIMD, scratch, spilled VGPRs and the VALU / SALU / VMEM / LDS instruction counts before
